@@ -19,7 +19,10 @@ The timed loop ALTERNATES two realisations of the field (same analytic field, tw
 same array, so what a context carries over from its previous call (kernel forms, the code book it speculates with) is what a
 series of similar arrays gives it, not what a repeated array gives it. `identical_input` reports the repeated-array figure beside it.
 
-Printed JSON line (rank 0): the driver contract + "roofline" (the path's algorithmic bytes per launch — input +
+Printed JSON line (rank 0): the driver contract — metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of one timed
+step), ratio, config. A plain run does only what that needs: set-up, --warmup steps, --steps timed steps, --dump-outputs DIR (the last
+step's payload, see dump_outputs), the line. Everything else below is measured with --full only (the --no-* options trim it):
+"roofline" (the path's algorithmic bytes per launch — input +
 payload — over the dominant kernel's duration, live HIP-event timing; `frac_kernel_compulsory` prices the kernel's own bytes;
 "roofline_path" = the same bytes over the whole step; "roofline_decompress" the decode) + "ms_per_step_median" (every step timed on
 its own) + "value_deterministic" / "value_cold" + "cpu_baseline" (the
@@ -64,7 +67,53 @@ def parse_args():
     ap.add_argument("--no-cold", action="store_true", help="skip the cold / hint-miss timings")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not run the two rocprofv3 --pmc child passes that measure roofline.traffic in this run")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)  # (the child of those passes: warm-up + steps, nothing else, no line)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-step medians, stage times, decode check and timing, rooflines (live PMC "
+                         "passes), cold / identical-input / two-context legs, host end-to-end, extra configs, CPU baseline. The --no-* options "
+                         "apply to this mode; a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result (rank 0's payload bytes as float32, a fixed seeded sample of "
+                         "them when it is long, with their positions, and its size) to DIR/*.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def field3d_fast(shape, dtype=np.float32, sigma=2e-3, seed=20260928, scale=1.0):
+    """tests/fields.py's field3d bit for bit (tests/test_bench_cpu.py) in a third of its time: the separable product and the diagonal
+    wave are evaluated on their 1-D arguments and broadcast instead of on three meshgrids; the noise is the same generator's one draw"""
+    nz, ny, nx = shape
+    az, ay, ax = (np.arange(n, dtype=np.float64) for n in (nz, ny, nx))
+    f = np.sin(2 * np.pi * ax / 64)[None, None, :] * np.cos(2 * np.pi * ay / 96)[None, :, None]
+    f = f * np.sin(2 * np.pi * az / 128)[:, None, None]
+    wave = 0.25 * np.sin(2 * np.pi * np.arange(nx + 2 * ny + 3 * nz, dtype=np.float64) / 37)  # (x + 2y + 3z is an integer)
+    base = np.arange(nx)[None, :] + 2 * np.arange(ny)[:, None]
+    for z in range(nz):
+        f[z] += wave[base + 3 * z]
+    f += np.random.default_rng(seed).normal(0.0, sigma, size=f.shape)
+    return (scale * f).astype(dtype)
+
+
+DUMP_MAX_POSITIONS = 4 << 20  # payload bytes written by --dump-outputs: 16 MB of float32 values + 32 MB of float64 positions at most
+DUMP_HEAD = 1 << 16           # (the payload's first bytes — header, code book — are always among them)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(w, psize, out_dir):
+    """--dump-outputs: what the timed path hands its caller after the last step — the payload in device memory and its size. The bytes
+    go out as float32 values with their positions (float64); a payload longer than DUMP_MAX_POSITIONS is sampled: its head plus
+    positions drawn with a fixed seed"""
+    os.makedirs(out_dir, exist_ok=True)
+    data = w.d_payload[:psize].cpu().numpy()
+    if psize <= DUMP_MAX_POSITIONS:
+        idx = np.arange(psize, dtype=np.int64)
+    else:
+        drawn = np.random.default_rng(DUMP_SEED).integers(0, psize, DUMP_MAX_POSITIONS - DUMP_HEAD)
+        idx = np.union1d(np.arange(DUMP_HEAD, dtype=np.int64), drawn)
+    np.save(os.path.join(out_dir, "payload.npy"), data[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "payload_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "payload_size.npy"), np.array([psize], dtype=np.float64))
 
 
 def relaunch_as_ranks(n):
@@ -84,7 +133,11 @@ class Workload:
     """one configuration, device resident: input tensor, context, payload buffer; step() = one pass of the hot path"""
 
     def __init__(self, torch, sz3_amd, dev, local_rank, rank, shape, dtype, algo, eb, comm=None, dist=None, field="default"):
-        from fields import field3d, field_c4a
+        # (tests/fields.py's field3d and field_c4a, computed faster: the same arrays)
+        field3d = field3d_fast
+
+        def field_c4a(shape, seed):
+            return field3d_fast(shape, np.float64, sigma=2e-3, seed=seed, scale=3.3e-5)
         self.torch, self.sz = torch, sz3_amd
         self.shape, self.algo, self.eb, self.dtype = shape, algo, eb, dtype
         self.npdt = np.float32 if dtype == "f32" else np.float64
@@ -728,21 +781,19 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * raw_bytes / (elapsed / args.steps) / 1e9
     ratio = world * raw_bytes / float(total_payload)
-    h_spec, m_spec = w.dc.spec_stats()
-    per_step = w.per_step(max(20, args.steps))  # (every rank: a step of a multi-rank run holds a collective)
-    acc = w.stage_profile()
-    stats = w.dc.stats()
-    max_err, dec_ms = w.verify_and_time_decode(psize)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(w, psize, args.dump_outputs)
+
+    def close():
+        if comm is not None:
+            comm.close()
+        if dist is not None:
+            dist.destroy_process_group()
 
     out = None
+    is_c2 = args.algo == "lorenzo" and args.dtype == "f32" and tuple(shape) == (512, 512, 512) and args.eb == 1e-3
+    is_c3 = args.algo == "interp" and args.dtype == "f32" and tuple(shape) == (512, 512, 512) and args.eb == 1e-4
     if rank == 0:
-        is_c2 = args.algo == "lorenzo" and args.dtype == "f32" and tuple(shape) == (512, 512, 512) and args.eb == 1e-3
-        is_c3 = args.algo == "interp" and args.dtype == "f32" and tuple(shape) == (512, 512, 512) and args.eb == 1e-4
-        # (the PMC passes of tools/pmc_blk.sh were taken on the benchmark field, where the selection hands the array to the plain path)
-        is_c4c = (args.algo == "composed" and args.dtype == "f64" and tuple(shape) == (128, 1024, 1024) and args.eb == 1e-6 and args.field == "default"
-                  and w.stream_predictor() == 0)
-        is_c4a = (args.algo == "composed" and args.dtype == "f64" and tuple(shape) == (128, 1024, 1024) and args.eb == 1e-6 and args.field == "c4a"
-                  and w.stream_predictor() == 2)  # (tools/pmc_blk.sh with FIELD=c4a: profiles/r03_pmc_blk_c4a.txt)
         out = {
             "metric": "compression throughput GB/s + ratio at fixed abs errBound, 512^3 f32",
             "value": round(value, 3), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -756,8 +807,28 @@ def main():
                                        "interp-notune": "interpolation (ALGO_INTERP)", "composed": "Lorenzo + regression per block"}[args.algo], args.eb),
                        "parallelism": "slab%d" % world, "algo": "HIP_LORENZO(16)" if args.algo in ("lorenzo", "composed") else "HIP_INTERP(17)", "eb": args.eb,
                        "exchange": exchange},
-            "ratio": round(ratio, 4), "max_abs_err": max_err, "err_bound_ok": bool(max_err <= args.eb),
-            "payload_bytes_rank0": int(psize),
+            "ratio": round(ratio, 4), "payload_bytes_rank0": int(psize),
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        close()
+        return
+
+    h_spec, m_spec = w.dc.spec_stats()
+    per_step = w.per_step(max(20, args.steps))  # (every rank: a step of a multi-rank run holds a collective)
+    acc = w.stage_profile()
+    stats = w.dc.stats()
+    max_err, dec_ms = w.verify_and_time_decode(psize)
+
+    if rank == 0:
+        # (the PMC passes of tools/pmc_blk.sh were taken on the benchmark field, where the selection hands the array to the plain path)
+        is_c4c = (args.algo == "composed" and args.dtype == "f64" and tuple(shape) == (128, 1024, 1024) and args.eb == 1e-6 and args.field == "default"
+                  and w.stream_predictor() == 0)
+        is_c4a = (args.algo == "composed" and args.dtype == "f64" and tuple(shape) == (128, 1024, 1024) and args.eb == 1e-6 and args.field == "c4a"
+                  and w.stream_predictor() == 2)  # (tools/pmc_blk.sh with FIELD=c4a: profiles/r03_pmc_blk_c4a.txt)
+        out.update({
+            "max_abs_err": max_err, "err_bound_ok": bool(max_err <= args.eb),
             "ms_per_step_median": per_step,
             "decompress_device": {"ms": round(dec_ms, 4), "gbps": round(raw_bytes / (dec_ms * 1e-3) / 1e9, 2)},
             # SURVEY.md 8(d), decompression: read sizeof(T) / ratio, write sizeof(T) per element — the whole decode (all its kernels) against the peak
@@ -774,7 +845,7 @@ def main():
                                              "inside stage 1's own launch (a function of the input alone): nothing is speculated, nothing verified, hits = misses = 0, "
                                              "and `value`, `value_deterministic` and a context's second call are the same path. Other streams (wide alphabets: C3, the C4 "
                                              "slab) still pack with the previous call's book while this call's is built beside the encoder; a miss repeats the encoder"},
-        }
+        })
         if args.algo == "composed":
             pid = w.stream_predictor()
             out["block_selection"] = {"stream_predictor": pid,
@@ -953,10 +1024,7 @@ def main():
         out["cpu_baseline"] = cpu_baseline(w)
     if rank == 0:
         print(json.dumps(out), flush=True)
-    if comm is not None:
-        comm.close()
-    if dist is not None:
-        dist.destroy_process_group()
+    close()
 
 
 if __name__ == "__main__":

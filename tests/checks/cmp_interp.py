@@ -1,5 +1,5 @@
 import sys, os
-R=os.environ.get("GRAFT_REPO_ROOT","/root/repo"); sys.path.insert(0,R); sys.path.insert(0,R+"/tests")
+R=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0,R); sys.path.insert(0,R+"/tests")
 import numpy as np, torch, sz3_amd
 from fields import field3d
 from oracle_binding import *

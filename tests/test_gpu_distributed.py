@@ -97,7 +97,7 @@ def test_bench_relaunches_itself_as_two_ranks_and_prints_one_line():
     """The driver's multi-GPU run is the first time bench.py --gpus N > 1 executes on real hardware. Its plumbing — the relaunch as N
     ranks under torch.distributed.run on 127.0.0.1, the barrier + max-over-ranks timing, the summed payload, ONE line from rank 0 — is
     run here with both ranks on the one GPU (SZ3_BENCH_ONE_GPU=1: the histogram then travels through gloo; RCCL wants a GPU per rank)."""
-    d = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "128", "--no-extra", "--no-cold", "--no-host-e2e", "--no-cpu-baseline",
+    d = _bench(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "128", "--no-extra", "--no-cold", "--no-host-e2e", "--no-cpu-baseline",
                 "--no-live-traffic"], {"SZ3_BENCH_ONE_GPU": "1"})
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["scaling"] == "weak" and d["unit"] == "GB/s"
     assert "gloo" in d["config"]["exchange"] and d["config"]["parallelism"] == "slab2"
@@ -109,7 +109,7 @@ def test_bench_two_ranks_print_the_multi_gpu_configs():
     """with N > 1 the line also carries BASELINE.json's configs[3] (1024^3 f64, Lorenzo + regression, 8 slabs: both
     fields) and configs[4] (100 x 500^3 f32, REL 1e-3 of the all-reduced range, 8 slabs of time steps) — here at reduced sizes
     (SZ3_BENCH_EXTRA_SCALE=small), two ranks on the one GPU. api/impl/SZImplOMP.hpp:48-107 is the split they mirror."""
-    d = _bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--size", "128", "--no-cold", "--no-host-e2e", "--no-cpu-baseline", "--no-live-traffic"],
+    d = _bench(["--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--size", "128", "--no-cold", "--no-host-e2e", "--no-cpu-baseline", "--no-live-traffic"],
                {"SZ3_BENCH_ONE_GPU": "1", "SZ3_BENCH_EXTRA_SCALE": "small"})
     assert d["n_gpus"] == 2 and d["err_bound_ok"] and "roofline" in d
     ex = d["extra_configs"]
@@ -128,7 +128,7 @@ def test_bench_eight_ranks_on_the_one_gpu():
     GPU (SZ3_BENCH_ONE_GPU=1: gloo carries the histogram) and the multi-GPU legs at reduced sizes: eight ranks rendezvous, the line says
     n_gpus 8 / slab8, C4's fields are coded as eight slabs, C5's 100 time steps are cut 12, 13, 12, 13, ... as the reference cuts them
     (api/impl/SZImplOMP.hpp:48-50) and every leg decodes within its bound."""
-    d = _bench(["--gpus", "8", "--steps", "2", "--warmup", "1", "--size", "96", "--no-cold", "--no-host-e2e", "--no-cpu-baseline", "--no-live-traffic"],
+    d = _bench(["--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--size", "96", "--no-cold", "--no-host-e2e", "--no-cpu-baseline", "--no-live-traffic"],
                {"SZ3_BENCH_ONE_GPU": "1", "SZ3_BENCH_EXTRA_SCALE": "small"}, timeout=1500)
     assert d["n_gpus"] == 8 and d["config"]["parallelism"] == "slab8" and d["scaling"] == "weak" and d["err_bound_ok"]
     ex = d["extra_configs"]
@@ -144,7 +144,7 @@ def test_bench_on_every_visible_gpu_over_rccl():
     """with more than one GPU on the box: the real thing at N = 2 (RCCL all-reduce of the histogram inside the library, one rank per GPU)"""
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU on this box")
-    d = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "256", "--no-extra", "--no-cold", "--no-host-e2e", "--no-cpu-baseline",
+    d = _bench(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "256", "--no-extra", "--no-cold", "--no-host-e2e", "--no-cpu-baseline",
                 "--no-live-traffic"], {})
     assert d["n_gpus"] == 2 and "RCCL" in d["config"]["exchange"] and d["err_bound_ok"]
 

@@ -8,7 +8,7 @@ import os, sys, runpy
 sys.path.insert(0, "$R")
 import sz3_amd
 sz3_amd.lib().sz3hip_debug_flags(int(os.environ["F"]))
-sys.argv = ["bench.py"] + "--algo composed --field c4a --dtype f64 --shape 128,1024,1024 --eb 1e-6 --steps 10 --warmup 2 --no-cpu-baseline --no-host-e2e --no-cold --no-live-traffic".split()
+sys.argv = ["bench.py"] + "--algo composed --field c4a --dtype f64 --shape 128,1024,1024 --eb 1e-6 --steps 10 --warmup 2 --no-cpu-baseline --no-host-e2e --no-cold --no-live-traffic --full".split()
 runpy.run_path("$R/bench.py", run_name="__main__")
 PY
   grep '^{' /tmp/ab.log | tail -1 | python3 -c "

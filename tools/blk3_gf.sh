@@ -8,7 +8,7 @@ cd /tmp
 for lib in ${VARIANTS:-product}; do
   rm -rf /tmp/pb
   if [ "$lib" = product ]; then unset SZ3HIP_LIB; else export SZ3HIP_LIB=$R/sz3_amd/lab/libsz3hip_$lib.so; fi
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -o r -- python $R/bench.py --algo composed --field c4a --dtype f64 --shape 128,1024,1024 --eb 1e-6 --steps 3 --warmup 1 --no-cpu-baseline --no-host-e2e --no-cold --no-live-traffic > /tmp/pb.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/pb -o r -- python $R/bench.py --full --algo composed --field c4a --dtype f64 --shape 128,1024,1024 --eb 1e-6 --steps 3 --warmup 1 --no-cpu-baseline --no-host-e2e --no-cold --no-live-traffic > $TMPDIR/pb.log 2>&1
   echo "== $lib"
   tail -1 /tmp/pb.log | python3 -c "
 import sys, json

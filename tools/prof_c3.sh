@@ -2,7 +2,7 @@
 # rocprofv3 kernel trace of the C3 bench (interpolation, abs 1e-4) -> gpurun_out/prof_c3/kernel_stats.csv; extra bench args: "$@"
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-B="python $R/bench.py --algo interp --eb 1e-4 --steps 10 --warmup 3 --no-cpu-baseline --no-host-e2e --no-extra $@"
+B="python $R/bench.py --full --algo interp --eb 1e-4 --steps 10 --warmup 3 --no-cpu-baseline --no-host-e2e --no-extra $@"
 rm -rf $R/gpurun_out/prof_c3; mkdir -p $R/gpurun_out/prof_c3
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_c3/raw -o r -- $B > $R/gpurun_out/prof_c3/bench.log 2>&1
 cp $R/gpurun_out/prof_c3/raw/*kernel_stats.csv $R/gpurun_out/prof_c3/kernel_stats.csv 2>/dev/null

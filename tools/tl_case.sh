@@ -3,7 +3,7 @@
 # the step is cut between two launches of the kernel named in $LASTK (default k_publish)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-B="python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-e2e --no-extra --no-cold --no-live-traffic $@"
+B="python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-e2e --no-extra --no-cold --no-live-traffic $@"
 rm -rf /tmp/tlc; mkdir -p /tmp/tlc
 rocprofv3 --kernel-trace --output-format csv -d /tmp/tlc/raw -o r -- $B > /tmp/tlc/bench.log 2>&1
 python - <<PY
