@@ -414,6 +414,11 @@ void *szi_histogram_for_exchange(sz3hip_ctx *ctx) {
     ctx->hist_reduced = true;
     return ctx->d_hist;
 }
+// The host API's own exchanges (conf.openmp's exchange_histograms, sz3hip_compress_rank) on its pooled slots: the context is marked as
+// one whose histogram is exchanged for ONE call — from before its stage 1, which then keeps the forms that leave the histogram whole
+// and final, to the end of its finish() — and unmarked afterwards: the slot's next plain call is a fresh slot's (the sampled book among
+// its forms). Marked, the context behaves as after sz3hip_histogram_ptr.
+void szi_exchange_call(sz3hip_ctx *ctx, bool on) { ctx->hist_exposed = on; }
 extern "C" size_t sz3hip_histogram_len(const sz3hip_ctx *) { return SZH_HIST_BINS; }
 extern "C" int sz3hip_ctx_set_histogram(sz3hip_ctx *ctx, void *d_hist) {
     ctx->d_hist = d_hist ? (uint64_t *)d_hist : ctx->d_hist_own;
@@ -825,11 +830,13 @@ static int blk_all_lorenzo(sz3hip_ctx *ctx, const sz3hip_config *conf, const voi
     // same configuration made it from a count assumes the same outcome and goes on without the count's round trip to the host (a copy,
     // a synchronisation and the relaunch latency: ~65 us of an idle GPU at C4's slab); the count travels with the state block at the
     // call's end (k_publish) and finish() repeats the call in this waiting form when it decides otherwise.
+    // (a context whose histogram is exchanged between the stages — multi-GPU — decides in the waiting form: finish()'s repeat of stage 1
+    // could not redo that exchange, and would code the slab with a book of its own histogram)
     const sz3hip_config &k = ctx->blk_dec_conf;
     bool same = ctx->blk_dec_valid && k.N == conf->N && k.blockSize == conf->blockSize && k.absErrorBound == conf->absErrorBound && k.quantbinCnt == conf->quantbinCnt &&
                 k.lorenzo == conf->lorenzo && k.lorenzo2 == conf->lorenzo2 && k.regression == conf->regression;
     for (int i = 0; same && i < conf->N; i++) same = k.dims[i] == conf->dims[i];
-    if (same && ctx->spec_off != 1 && !(szk_dbg_flags & 1073741824)) {
+    if (same && ctx->spec_off != 1 && !ctx->hist_exposed && !ctx->hist_reduced && !(szk_dbg_flags & 1073741824)) {
         ctx->blk_spec = true;
         ctx->blk_spec_all = ctx->blk_dec_all;
         ctx->blk_spec_nblocks = nblocks;

@@ -687,6 +687,7 @@ struct SlabJob {
     size_t out_cap = 0, out_size = 0;
     std::vector<unsigned char> own_out;  // multi-slab: the blob is staged here, then copied into the container
     bool lossless = false, staged = false;
+    bool exchange = false;       // the call sums this slab's histogram with the other slabs' between the stages (szi_exchange_call)
     size_t frame = zs::FRAME;    // bytes of payload per zstd frame (the pieces of a pipelined call take smaller ones: a piece's last frame is the call's tail)
     int asked_algo = -1;         // the caller's cmprAlgo (conf.cmprAlgo is rewritten to what was written)
     double mn = 0, mx = 0;
@@ -796,6 +797,7 @@ int job_stage1(SlabJob &j) {
         return 0;
     }
     // ALGO_LORENZO_REG / NOPRED -> HIP Lorenzo stream (16); ALGO_INTERP / ALGO_INTERP_LORENZO -> HIP interpolation (17)
+    if (j.exchange) szi_exchange_call(s->ctx, true);  // (cleared by the caller when the call is over)
     if (sz3hip_compress_stage1(s->ctx, &j.conf, s->dev_in, s->stream)) return j.failed(sz3hip_last_error_code());
     j.staged = true;
     return 0;
@@ -2068,11 +2070,11 @@ int exchange_histograms(std::vector<SlabJob> &jobs, const std::vector<int> &devi
             continue;
         }
         SlabJob *l = per[d][0];
-        bufs[d] = sz3hip_histogram_ptr(l->slot->ctx);
+        bufs[d] = l->slot->ctx->d_hist;
         streams[d] = l->slot->stream;
         for (size_t k = 1; k < per[d].size(); k++) {
             HIPCHK(hipStreamSynchronize(per[d][k]->slot->stream));  // (its stage 1 wrote the histogram being added)
-            if (szk_launch_hist_add((uint64_t *)bufs[d], (const uint64_t *)sz3hip_histogram_ptr(per[d][k]->slot->ctx), SZH_HIST_BINS,
+            if (szk_launch_hist_add((uint64_t *)bufs[d], (const uint64_t *)per[d][k]->slot->ctx->d_hist, SZH_HIST_BINS,
                                     (hipStream_t)streams[d]))
                 return fail(SZ3HIP_EHIP, "histogram add kernel failed");
         }
@@ -2091,7 +2093,7 @@ int exchange_histograms(std::vector<SlabJob> &jobs, const std::vector<int> &devi
         }
         HIPCHK(hipSetDevice(devices[d]));
         for (size_t k = 1; k < per[d].size(); k++)
-            HIPCHK(hipMemcpyAsync(sz3hip_histogram_ptr(per[d][k]->slot->ctx), bufs[d], SZH_HIST_BINS * 8, hipMemcpyDeviceToDevice,
+            HIPCHK(hipMemcpyAsync(per[d][k]->slot->ctx->d_hist, bufs[d], SZH_HIST_BINS * 8, hipMemcpyDeviceToDevice,
                                   (hipStream_t)streams[d]));
         HIPCHK(hipStreamSynchronize((hipStream_t)streams[d]));
     }
@@ -2144,6 +2146,7 @@ size_t compress_slabs(sz3hip_config &conf, int dataType, const void *data, unsig
         ct.blockSize = geo.blockSize;
         job_init(jobs[g], ct, dataType, (const unsigned char *)data + lo * base * es, g);
         jobs[g].slot = get_slot(devices[g % ndev], cdt, g / ndev);
+        jobs[g].exchange = G > 1 || g_comm != nullptr;  // (exchange_histograms: the slabs' histograms are summed whenever there are several)
         jobs[g].own_out.resize(zs::bound_frames(jobs[g].raw_bytes) + 64);
         jobs[g].out = jobs[g].own_out.data();
         jobs[g].out_cap = jobs[g].own_out.size();
@@ -2190,6 +2193,8 @@ size_t compress_slabs(sz3hip_config &conf, int dataType, const void *data, unsig
     for (int t = 1; t < ndev; t++) th.emplace_back(worker, t);
     worker(0);
     for (auto &t : th) t.join();
+    for (auto &j : jobs)  // the slots go back to the pool as they were: the next call exchanges nothing unless it says so
+        if (j.exchange && j.slot->ctx) szi_exchange_call(j.slot->ctx, false);
     if (shared_rc) {
         fail(shared_rc, "%s", shared_err.c_str());
         return 0;
@@ -2511,6 +2516,13 @@ extern "C" size_t sz3hip_compress_rank(sz3hip_comm *comm, const sz3hip_config *g
     SlabJob j;
     job_init(j, ct, dataType, slab_data, g);
     j.slot = get_slot(sz3hip_comm_device(comm, 0), cdt, 0);
+    j.exchange = conf.cmprAlgo != SZ3HIP_ALGO_LOSSLESS;  // (= `exchanges` below)
+    struct Unmark {  // whichever way the call ends, the pooled slot leaves it without the exchange mark
+        SlabJob &j;
+        ~Unmark() {
+            if (j.exchange && j.slot->ctx) szi_exchange_call(j.slot->ctx, false);
+        }
+    } unmark{j};
     j.out = reinterpret_cast<unsigned char *>(blob);
     j.out_cap = cap;
     if (cap < zs::bound_frames(j.raw_bytes) + 8) {
@@ -2576,7 +2588,7 @@ extern "C" size_t sz3hip_compress_rank(sz3hip_comm *comm, const sz3hip_config *g
         }
         void *hb = sc + 16;
         if (j.staged) {
-            hb = sz3hip_histogram_ptr(j.slot->ctx);
+            hb = j.slot->ctx->d_hist;
         } else if (hipMemsetAsync(hb, 0, SZH_HIST_BINS * 8, (hipStream_t)stream) != hipSuccess) {
             fail(SZ3HIP_EHIP, "hipMemsetAsync failed");
             return 0;

@@ -45,6 +45,7 @@ int szi_tuner_took_lorenzo(sz3hip_ctx *ctx, int *quantbinCnt);  // the default a
 void szi_run_parallel(int n, const std::function<void(int)> &f);  // f(0 .. n - 1) over the host API's pool of threads (sz3hip_host.cpp), f(0) on the caller
 size_t szi_zstd_size(const void *src, size_t n);  // ZSTD_compress(level 3)'s size of a buffer (sz3hip_host.cpp: libzstd lives there); 0 on error
 void *szi_histogram_for_exchange(sz3hip_ctx *ctx);  // the histogram, for the library's own all-reduce between the stages (sz3hip_api.cpp)
+void szi_exchange_call(sz3hip_ctx *ctx, bool on);    // the host API's slots: the histogram is exchanged in this call only (sz3hip_api.cpp)
 
 struct Writer {
     unsigned char *p;

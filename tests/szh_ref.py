@@ -156,6 +156,33 @@ def kraft(lens):
     return float(np.sum(2.0 ** (-lens[lens > 0].astype(np.float64))))
 
 
+def huffman_cost(freq):
+    """-> (total bits, tree height) of an unlimited Huffman code over the non-zero counts of `freq` (heapq: independent of the kernels)"""
+    import heapq
+    heap = [(int(f), i, 0) for i, f in enumerate(freq) if f]   # (freq, tiebreak, height)
+    heapq.heapify(heap)
+    cost = 0
+    cnt = len(freq)
+    while len(heap) > 1:
+        f1, _, h1 = heapq.heappop(heap)
+        f2, _, h2 = heapq.heappop(heap)
+        cost += f1 + f2
+        cnt += 1
+        heapq.heappush(heap, (f1 + f2, cnt, max(h1, h2) + 1))
+    return cost, heap[0][2]
+
+
+def assert_book_optimal(freq, lens, limit):
+    """the book's total bits over `freq` equal an unlimited Huffman code's when that code respects the length limit (16 bits up to
+    512 symbols, else 24), otherwise lie within 0.2 % of it (length-limited code)"""
+    cost, height = huffman_cost(freq)
+    gpu_cost = int((np.asarray(freq, dtype=np.int64) * np.asarray(lens).astype(np.int64)).sum())
+    if height <= limit:
+        assert gpu_cost == cost, "code is not optimal"
+    else:
+        assert cost <= gpu_cost <= cost * 1.002, "length-limited code too far from optimal"
+
+
 def huffman_decode(h, sec):
     """slow reference decoder of the chunked bit-stream -> uint16 codes"""
     n = h["n"]

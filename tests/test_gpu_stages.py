@@ -94,22 +94,7 @@ def test_stages(name, gen, eb):
         if filled:
             assert h["sym_min"] == min(book) and h["sym_count"] == len(book)
             freq = np.maximum(freq, 1)
-        import heapq
-        heap = [(int(f), i, 0) for i, f in enumerate(freq) if f]   # (freq, tiebreak, height)
-        heapq.heapify(heap)
-        cost = 0
-        cnt = len(freq)
-        while len(heap) > 1:
-            f1, _, h1 = heapq.heappop(heap)
-            f2, _, h2 = heapq.heappop(heap)
-            cost += f1 + f2
-            cnt += 1
-            heapq.heappush(heap, (f1 + f2, cnt, max(h1, h2) + 1))
-        gpu_cost = int((freq * lens.astype(np.int64)).sum())
-        if heap[0][2] <= limit:
-            assert gpu_cost == cost, "code is not optimal"
-        else:
-            assert cost <= gpu_cost <= cost * 1.002, "length-limited code too far from optimal"
+        szh_ref.assert_book_optimal(freq, lens, limit)
     # K6: python decoder reads the bit-stream back to the same codes
     if a.size <= 120000:
         assert np.array_equal(szh_ref.huffman_decode(h, sec), exp_codes.reshape(-1))
