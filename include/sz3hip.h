@@ -139,6 +139,31 @@ size_t sz3hip_compress(const sz3hip_config *conf, int dataType, const void *data
  * the slabs are unpacked and decoded side by side and copied out in order. Arrays of 32 MB and more leave the device through a ring
  * of pinned staging buffers whose chunks host threads copy on into decData (a fresh array's pages are faulted in by those threads). */
 int sz3hip_decompress(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, void *decData);
+/* The two calls above for an array that lives in device memory: the container sz3hip_compress writes for the same array, byte for byte,
+ * read from d_data; what sz3hip_decompress writes, bit for bit, written to d_out (conf is overwritten from the trailer). The array does not
+ * cross the host link: only the payload does (zstd, header and trailer stay host stages; cmpData is host memory, its capacity rule
+ * sz3hip_compress_bound). Everything between the copy in and the copy out is the host API's code: dispatcher policies (range-based bounds,
+ * eb == 0, the ratio < 3 lossless check, the length_error fallback), stock format, conf->openmp slabs and the pipelined pieces (all coded
+ * on the array's own device), the ten element types (integers on the f64 route, 64-bit values beyond 2^53 lossless), the tuner's decisions
+ * (run in stage 1 with the host API's settings — exact pricing, deterministic — instead of beside the copy in).
+ *  - d_data / d_out: device memory (hipPointerGetAttributes); the call runs on the device that owns it, not on SZ3HIP_DEVICE. Anything
+ *    else is SZ3HIP_EINVAL before any launch.
+ *  - strides: element strides, slowest first, one per conf->N extent (the extents left after size-1 ones are dropped); NULL: contiguous.
+ *    Strides are >= 0; an output whose strides make two elements overlap is SZ3HIP_EINVAL. A contiguous f32 / f64 input is read in place
+ *    (never written); integer or strided inputs are gathered into the library's buffer by a strided kernel; a contiguous f32 / f64 output
+ *    of the library's own streams is decoded in place, other outputs are scattered into the view.
+ *  - stream (may be NULL): compression — the library's streams wait for an event recorded on it before the array is first read, so a
+ *    producer's pending kernels need no host synchronisation; decompression — what is queued on it is waited for before d_out is written.
+ *    Both calls are synchronous: on return the container is written, d_data is no longer read and d_out is complete.
+ * The array reaches the host only where the host API's code reads it there: the lossless stream and its fallbacks, the ratio < 3
+ * comparison, the stock 1-D ALGO_LORENZO_REG chain (and, decoding, a lossless stream or that chain is decoded on the host and copied in). */
+size_t sz3hip_compress_from_device(const sz3hip_config *conf, int dataType, const void *d_data, const int64_t *strides, char *cmpData, size_t cmpCap,
+                                   void *stream);
+int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, void *d_out, const int64_t *strides,
+                                void *stream);
+/* (test and measurement hook) the strided gather alone: the view (N extents, element strides) of d_in into the contiguous d_out on stream,
+ * integers widened to f64 as the compress call does; asynchronous */
+int sz3hip_debug_gather(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream);
 /* One algorithm of the reference's dispatcher (SZ_compress_LorenzoReg / SZ_compress_Interp / ..., SZDispatcher.hpp:28-42 and
  * their SZ_decompress_* counterparts :89-99): only the bytes between the container's 16-byte header and its Config trailer.
  * compress: returns their number (0 on error); *conf is updated like the reference updates it (absolute bound resolved,

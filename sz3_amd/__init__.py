@@ -144,6 +144,10 @@ def lib():
     L.sz3hip_decompress.restype = C.c_int
     L.sz3hip_decompress.argtypes = [P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.sz3hip_peek_config.restype = C.c_int
+    L.sz3hip_compress_from_device.restype = C.c_size_t
+    L.sz3hip_compress_from_device.argtypes = [P(_CConfig), C.c_int, C.c_void_p, P(C.c_int64), C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sz3hip_decompress_to_device.restype = C.c_int
+    L.sz3hip_decompress_to_device.argtypes = [P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(C.c_int64), C.c_void_p]
     L.sz3hip_peek_config.argtypes = [P(_CConfig), C.c_void_p, C.c_size_t]
     L.sz3hip_ctx_create.restype = C.c_void_p
     L.sz3hip_ctx_create.argtypes = [C.c_int, C.c_uint64, C.c_int]
@@ -320,34 +324,105 @@ def compress_bound(conf, dtype):
     return int(lib().sz3hip_compress_bound(C.byref(conf._c), _dtype_id(dtype)))
 
 
-def compress(data, conf, out=None):
+def _gpu_tensor(x):
+    """x is a torch tensor on a HIP device (without importing torch when the caller never did)"""
+    import sys
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(x, torch.Tensor) and x.device.type == "cuda"
+
+
+def _np_dtype(dtype):
+    """a NumPy dtype, also from a torch dtype (torch.float32 -> float32)"""
+    import sys
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(dtype, torch.dtype):
+        return np.dtype(str(dtype).replace("torch.", ""))
+    return np.dtype(dtype)
+
+
+def _view_strides(t, conf):
+    """element strides of a tensor for the Config's extents: size-1 dimensions dropped the way Config drops them"""
+    dims = [int(d) for d in t.shape if int(d) != 1]
+    strides = [int(st) for d, st in zip(t.shape, t.stride()) if int(d) != 1]
+    if tuple(dims or [1]) != tuple(conf.dims):
+        raise ValueError("config dims %s do not match the tensor's shape %s" % (conf.dims, tuple(t.shape)))
+    if not strides:
+        strides = [1]
+    return (C.c_int64 * len(strides))(*strides)
+
+
+def _stream_handle(device, stream):
+    if stream is not None:
+        return int(getattr(stream, "cuda_stream", stream))
+    import torch
+    return int(torch.cuda.current_stream(device).cuda_stream)
+
+
+def compress(data, conf, out=None, stream=None):
     """sz.compress (sz.pyx:185-272): returns (uint8 ndarray, ratio). `out`: a caller's uint8 buffer of at least
     compress_bound(conf, dtype) bytes — the pre-allocated form, SZ_compress(conf, data, cmpData, cmpCap) (api/sz.hpp:43-62); a buffer
-    used before costs no first-touch page faults."""
-    a = np.ascontiguousarray(data)
-    dt = _dtype_id(a.dtype)
-    if int(conf.num) != a.size:
-        raise ValueError("config dims do not match the array")
-    cap = compress_bound(conf, a.dtype)
+    used before costs no first-touch page faults.
+    `data` may be a torch tensor on a HIP device, also a strided view: it is compressed where it lies (sz3hip_compress_from_device, the
+    same container as for its host copy); `stream` (a torch stream or a raw handle; default: the device's current stream) is what the
+    library waits for before it reads the tensor."""
+    gpu = _gpu_tensor(data)
+    if gpu:
+        a = data
+        npdt = _np_dtype(a.dtype)
+        if int(conf.num) != a.numel():
+            raise ValueError("config dims do not match the array")
+    else:
+        a = np.ascontiguousarray(data)
+        npdt = a.dtype
+        if int(conf.num) != a.size:
+            raise ValueError("config dims do not match the array")
+    dt = _dtype_id(npdt)
+    cap = compress_bound(conf, npdt)
     if out is None:
         out = np.empty(cap, dtype=np.uint8)
     elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < cap:
         raise ValueError("out must be a contiguous uint8 array of at least compress_bound(conf, dtype) = %d bytes" % cap)
     else:
         cap = out.size
-    n = lib().sz3hip_compress(C.byref(conf._c), dt, a.ctypes.data, out.ctypes.data, cap)
+    if gpu:
+        n = lib().sz3hip_compress_from_device(C.byref(conf._c), dt, a.data_ptr(), _view_strides(a, conf), out.ctypes.data, cap,
+                                              _stream_handle(a.device, stream))
+        nbytes = a.numel() * npdt.itemsize
+    else:
+        n = lib().sz3hip_compress(C.byref(conf._c), dt, a.ctypes.data, out.ctypes.data, cap)
+        nbytes = a.nbytes
     if n == 0:
         raise SZ3HipError(-1, lib().sz3hip_last_error().decode())
     blob = out[:n]  # a view, like pysz (sz.pyx:230-272): the untouched rest of the bound-sized buffer is never resident
-    return blob, a.nbytes / float(n)
+    return blob, nbytes / float(n)
 
 
-def decompress(blob, dtype, shape=None, out=None):
+def decompress(blob, dtype, shape=None, out=None, device=None, stream=None):
     """sz.decompress (sz.pyx:276-365): returns (ndarray, Config). `out`: a caller's array of the stream's element count and `dtype`
-    — the pre-allocated form, SZ_decompress(conf, cmpData, cmpSize, decData) (api/sz.hpp:84-110)."""
+    — the pre-allocated form, SZ_decompress(conf, cmpData, cmpSize, decData) (api/sz.hpp:84-110). `dtype` may be a torch dtype.
+    `out` may be a torch tensor on a HIP device, also a view (a sub-box of a larger tensor): the array is decoded into it
+    (sz3hip_decompress_to_device) and (out, Config) returned. `device=`: a tensor allocated there, returned as (tensor, Config).
+    `stream`: what is waited for before the tensor is written (default: the device's current stream)."""
     blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
     conf = Config(1)
     _check(lib().sz3hip_peek_config(C.byref(conf._c), blob.ctypes.data, blob.size))
+    npdt = _np_dtype(dtype)
+    if device is not None or _gpu_tensor(out):
+        import torch
+        if out is None:
+            out = torch.empty(conf.dims, dtype=getattr(torch, npdt.name), device=device)
+            if shape is not None:
+                shape = tuple(shape)
+        else:
+            shape = None
+        if not _gpu_tensor(out):
+            raise ValueError("out must be a tensor on a HIP device")
+        if _np_dtype(out.dtype) != npdt or out.numel() != int(conf.num):
+            raise ValueError("out must be a %s tensor of %d elements" % (npdt, int(conf.num)))
+        _check(lib().sz3hip_decompress_to_device(C.byref(conf._c), _dtype_id(npdt), blob.ctypes.data, blob.size, out.data_ptr(),
+                                                 _view_strides(out, conf), _stream_handle(out.device, stream)))
+        return (out.reshape(shape) if shape is not None else out), conf
+    dtype = npdt
     if out is None:
         dec = np.empty(int(conf.num), dtype=dtype)
     else:

@@ -682,6 +682,14 @@ struct SlabJob {
     size_t es = 0, raw_bytes = 0;
     sz3hip_config conf;          // this slab's Config; cmprAlgo becomes the id of the stream that was written
     const void *data = nullptr;  // host pointer of the slab
+    // sz3hip_compress_from_device: the slab as a view of the caller's device array (data stays null), what stage 1 reads (that array
+    // itself when it is a contiguous f32 / f64 one, else the slot's buffer), the event the slot's stream waits for before reading it,
+    // and the host copy made only where the host API's code reads the array on the host (host_array)
+    const void *dsrc = nullptr;
+    szk_view dview{};
+    const void *din = nullptr;
+    hipEvent_t ready = nullptr;
+    std::vector<uint8_t> host_copy;
     HostSlot *slot = nullptr;
     unsigned char *out = nullptr;  // receives the dispatcher's output ([u64 rawLen][zstd frames])
     size_t out_cap = 0, out_size = 0;
@@ -703,6 +711,27 @@ struct SlabJob {
     }
 };
 
+// The caller's array of a device call (sz3hip_compress_from_device / sz3hip_decompress_to_device): its first element, its view (the
+// Config's N extents in the last N places, element strides), the device that holds it, and — compression — the event the slots' streams
+// wait for before reading it.
+struct DevArray {
+    char *ptr = nullptr;
+    szk_view view{};
+    int N = 0, device = 0;
+    hipEvent_t ready = nullptr;
+    // slab [lo, hi) along dims[0]: its first element and its view
+    char *slab(uint64_t lo, uint64_t hi, size_t es, szk_view *v) const {
+        *v = view;
+        v->dims[4 - N] = hi - lo;
+        return ptr + (int64_t)lo * view.str[4 - N] * (int64_t)es;
+    }
+};
+void job_device_source(SlabJob &j, const DevArray *dev, uint64_t lo, uint64_t hi) {
+    if (!dev) return;
+    j.dsrc = dev->slab(lo, hi, j.es, &j.dview);
+    j.ready = dev->ready;
+}
+
 // utils/Statistic.hpp:32-56 with the range from the device min/max kernel; data_range computes max - min in T (:12-21)
 int abs_eb_from_range(sz3hip_config &conf, int cdt, double mn, double mx) {
     if (conf.errorBoundMode == SZ3HIP_EB_ABS) return 0;
@@ -723,6 +752,8 @@ int abs_eb_from_range(sz3hip_config &conf, int cdt, double mn, double mx) {
     return 0;
 }
 
+std::atomic<int> g_stock_format{-1};  // (sz3hip_set_stock_format; -1: SZ3HIP_STOCK_FORMAT decides at the first call)
+
 // phase 1: input into HBM (SZDispatcher.hpp:27 makes a copy too), local value range when the bound needs it
 int job_upload(SlabJob &j) {
     if (j.conf.cmprAlgo == SZ3HIP_ALGO_LOSSLESS) {
@@ -738,16 +769,46 @@ int job_upload(SlabJob &j) {
     sz3hip_ctx *ctx = s->ctx;
     szi_pretune_cancel(ctx);
     const size_t cbytes = (size_t)j.conf.num * (j.cdt == SZ3HIP_FLOAT ? 4 : 8);
-    if (ensure_dev(&s->dev_in, &s->dev_in_bytes, cbytes)) return j.failed(SZ3HIP_EHIP);
+    // (a device call reads a contiguous f32 / f64 array where it lies; the stock writers use the slot's buffer as scratch: a copy for them)
+    const bool in_place = j.dsrc && !j.is_int && j.dview.contig && g_stock_format.load() <= 0;
+    if (!in_place && ensure_dev(&s->dev_in, &s->dev_in_bytes, cbytes)) return j.failed(SZ3HIP_EHIP);
     const size_t pb = sz3hip_payload_bound_conf(ctx, &j.conf, 0);
     if (ensure_dev(&s->dev_payload, &s->dev_payload_bytes, pb)) return j.failed(SZ3HIP_EHIP);
     if (j.tm) j.tm->lap("setup");
-    if (!j.is_int) {
+    j.din = s->dev_in;
+    if (j.dsrc) {
+        if (j.ready && hipStreamWaitEvent(s->stream, j.ready, 0) != hipSuccess) {
+            fail(SZ3HIP_EHIP, "waiting for the caller's stream failed");
+            return j.failed(SZ3HIP_EHIP);
+        }
+        if (in_place) {
+            j.din = j.dsrc;
+        } else {
+            if (j.is_int && hipMemsetAsync(ctx->d_counters + 5, 0, 8, s->stream) != hipSuccess) {
+                fail(SZ3HIP_EHIP, "hipMemsetAsync failed");
+                return j.failed(SZ3HIP_EHIP);
+            }
+            if (szk_launch_gather(j.dataType, 1, j.dsrc, &j.dview, s->dev_in, reinterpret_cast<uint32_t *>(ctx->d_counters + 5), s->stream)) {
+                fail(SZ3HIP_EHIP, "gather kernel failed");
+                return j.failed(SZ3HIP_EHIP);
+            }
+            if (j.is_int) {
+                uint32_t big = 0;
+                if (hipMemcpyAsync(&big, ctx->d_counters + 5, 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                    hipStreamSynchronize(s->stream) != hipSuccess) {
+                    fail(SZ3HIP_EHIP, "device->host copy failed");
+                    return j.failed(SZ3HIP_EHIP);
+                }
+                if (big) j.lossless = true;
+            }
+        }
+        if (j.tm) j.tm->lap("device gather");
+    } else if (!j.is_int) {
         // the default algorithm's tuner from the host's copy of the array, beside its copy in (a thread of its own: the copy below blocks this
         // one; the tuner's launches, round trips and — host API default — its trials priced the reference's way vanish behind 9 ms of copy at
         // 512^3). Absolute bounds only: the others need the array's range first. A tuner that fails here runs in stage 1 as before.
         std::thread pre;
-        if (j.conf.cmprAlgo == SZ3HIP_ALGO_INTERP_LORENZO && j.conf.errorBoundMode == SZ3HIP_EB_ABS && j.raw_bytes >= (16u << 20) && !env_int("SZ3HIP_NO_PRETUNE", 0))
+        if (j.data && j.conf.cmprAlgo == SZ3HIP_ALGO_INTERP_LORENZO && j.conf.errorBoundMode == SZ3HIP_EB_ABS && j.raw_bytes >= (16u << 20) && !env_int("SZ3HIP_NO_PRETUNE", 0))
             pre = std::thread([ctx, &j] { (void)szi_pretune_host(ctx, &j.conf, j.data); });
         const hipError_t ec = hipMemcpy(s->dev_in, j.data, j.raw_bytes, hipMemcpyHostToDevice);
         if (pre.joinable()) pre.join();
@@ -778,7 +839,7 @@ int job_upload(SlabJob &j) {
         if (big) j.lossless = true;  // |x| > 2^53 is not exact in f64: keep such arrays lossless
     }
     if (!j.lossless && j.conf.errorBoundMode != SZ3HIP_EB_ABS && j.conf.errorBoundMode != SZ3HIP_EB_L2NORM)
-        if (sz3hip_minmax_device(ctx, s->dev_in, j.conf.num, &j.mn, &j.mx, s->stream)) return j.failed(sz3hip_last_error_code());
+        if (sz3hip_minmax_device(ctx, j.din, j.conf.num, &j.mn, &j.mx, s->stream)) return j.failed(sz3hip_last_error_code());
     return 0;
 }
 
@@ -798,7 +859,7 @@ int job_stage1(SlabJob &j) {
     }
     // ALGO_LORENZO_REG / NOPRED -> HIP Lorenzo stream (16); ALGO_INTERP / ALGO_INTERP_LORENZO -> HIP interpolation (17)
     if (j.exchange) szi_exchange_call(s->ctx, true);  // (cleared by the caller when the call is over)
-    if (sz3hip_compress_stage1(s->ctx, &j.conf, s->dev_in, s->stream)) return j.failed(sz3hip_last_error_code());
+    if (sz3hip_compress_stage1(s->ctx, &j.conf, j.din, s->stream)) return j.failed(sz3hip_last_error_code());
     j.staged = true;
     return 0;
 }
@@ -999,7 +1060,25 @@ static hipError_t d2h_staged(void *dst, const void *src, size_t bytes) {
     return e != hipSuccess ? e : f;
 }
 static bool d2h_staging_wanted(size_t bytes) { return bytes >= (32u << 20) && env_int("SZ3HIP_D2H_STAGED", 1) != 0; }
+// sz3hip_decompress_to_device: where the blob being decoded by this thread goes — a view of the caller's device array. The decoders hand
+// their result to d2h_out as they do for the host API, and it lands in the view instead (nothing when a decoder wrote it in place);
+// a blob decoded on the host (ALGO_LOSSLESS, the stock 1-D chain) never reaches d2h_out and is copied in afterwards (decode_blob_to).
+struct DevOut {
+    char *ptr = nullptr;
+    szk_view view{};
+    int dataType = 0;
+    hipStream_t stream = nullptr;
+    bool delivered = false;
+};
+static thread_local DevOut *t_devout = nullptr;
+static hipError_t devout_from_device(DevOut &o, const void *src) {  // (src: the decoded array, dataType elements, complete)
+    o.delivered = true;
+    if (src == o.ptr) return hipSuccess;
+    if (szk_launch_scatter(o.dataType, 0, src, o.ptr, &o.view, o.stream)) return hipErrorLaunchFailure;
+    return hipStreamSynchronize(o.stream);
+}
 static hipError_t d2h_out(void *dst, const void *src, size_t bytes) {
+    if (t_devout) return devout_from_device(*t_devout, src);
     if (t_gate && !t_gate->passed) {  // (a piece of a pipelined read: the calling thread copies, in piece order)
         t_gate->hand_over(dst, src, bytes);
         return hipSuccess;
@@ -1011,7 +1090,6 @@ static hipError_t d2h_out(void *dst, const void *src, size_t bytes) {
     if (t_prefault) t_prefault->wait();
     return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
 }
-std::atomic<int> g_stock_format{-1};
 // the slot's payload buffer, carved up for the stock path's kernels: sizes are asked for first, then the buffer is grown once
 struct DevArena {
     std::vector<std::pair<void **, size_t>> want;
@@ -1052,6 +1130,40 @@ static int stock_zstd_failed(SlabJob &j) {
     if (code != SZ3HIP_ECAPACITY) return code;
     j.lossless = true;
     return SZ3HIP_EUNSUPPORTED;
+}
+// The slab's array on the host: the host API's own, or — a device call — a copy made the first time a fallback asks for it (the lossless
+// stream, the ratio < 3 comparison, the stock 1-D chain). nullptr: the copy failed (the message is recorded).
+static const uint8_t *host_array(SlabJob &j) {
+    if (j.data) return (const uint8_t *)j.data;
+    if (!j.dsrc) {
+        fail(SZ3HIP_EHIP, "internal: no source array");
+        return nullptr;
+    }
+    if (j.host_copy.size() == j.raw_bytes) return j.host_copy.data();
+    HostSlot *s = j.slot;
+    if (hipSetDevice(s->device) != hipSuccess || (!s->stream && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess)) {
+        fail(SZ3HIP_EHIP, "no usable HIP device");
+        return nullptr;
+    }
+    if (j.ready) (void)hipStreamWaitEvent(s->stream, j.ready, 0);  // (a lossless call reaches here without job_upload)
+    j.host_copy.resize(j.raw_bytes);
+    void *tmp = nullptr;
+    hipError_t e = hipSuccess;
+    if (j.dview.contig) {
+        e = hipMemcpyAsync(j.host_copy.data(), j.dsrc, j.raw_bytes, hipMemcpyDeviceToHost, s->stream);
+    } else {
+        e = hipMalloc(&tmp, j.raw_bytes);
+        if (e == hipSuccess && szk_launch_gather(j.dataType, 0, j.dsrc, &j.dview, tmp, nullptr, s->stream)) e = hipErrorLaunchFailure;
+        if (e == hipSuccess) e = hipMemcpyAsync(j.host_copy.data(), tmp, j.raw_bytes, hipMemcpyDeviceToHost, s->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (tmp) (void)hipFree(tmp);
+    if (e != hipSuccess) {
+        j.host_copy.clear();
+        fail(SZ3HIP_EHIP, "device->host copy of the array failed: %s", hipGetErrorString(e));
+        return nullptr;
+    }
+    return j.host_copy.data();
 }
 // 0: j.out holds [u64 rawLen][zstd frames] of a stock stream and j.conf names it; SZ3HIP_EUNSUPPORTED: stage 1 took another predictor
 int stock_encode_interp(SlabJob &j) {
@@ -1146,8 +1258,10 @@ int stock_encode_interp(SlabJob &j) {
     j.conf.interpAlpha = sp.alpha;
     j.conf.interpBeta = sp.beta;
     if ((double)j.raw_bytes / (double)j.out_size < 3) {  // SZDispatcher.hpp:62-74
+        const uint8_t *ha = host_array(j);
+        if (!ha) return sz3hip_last_error_code();
         std::vector<uint8_t> z(zs::bound_frames(j.raw_bytes) + 8);
-        size_t zsz = zs::compress_frames((const uint8_t *)j.data, j.raw_bytes, z.data(), z.size(), nullptr, stock_frame(j.raw_bytes));
+        size_t zsz = zs::compress_frames(ha, j.raw_bytes, z.data(), z.size(), nullptr, stock_frame(j.raw_bytes));
         if (zsz && zsz < j.out_size && zsz <= j.out_cap) {
             memcpy(j.out, z.data(), zsz);
             j.out_size = zsz;
@@ -1330,8 +1444,10 @@ int stock_encode_nopred(SlabJob &j) {
     if (!j.out_size) return stock_zstd_failed(j);
     j.conf.cmprAlgo = SZ3HIP_ALGO_NOPRED;
     if ((double)j.raw_bytes / (double)j.out_size < 3) {  // SZDispatcher.hpp:62-74
+        const uint8_t *ha = host_array(j);
+        if (!ha) return sz3hip_last_error_code();
         std::vector<uint8_t> z(zs::bound_frames(j.raw_bytes) + 8);
-        size_t zsz = zs::compress_frames((const uint8_t *)j.data, j.raw_bytes, z.data(), z.size(), nullptr, stock_frame(j.raw_bytes));
+        size_t zsz = zs::compress_frames(ha, j.raw_bytes, z.data(), z.size(), nullptr, stock_frame(j.raw_bytes));
         if (zsz && zsz < j.out_size && zsz <= j.out_cap) {
             memcpy(j.out, z.data(), zsz);
             j.out_size = zsz;
@@ -1357,13 +1473,15 @@ static int stock_encode_lorenzo_reg_1d(SlabJob &j) {
     uint64_t n_unpred = 0;
     std::vector<float> ui32, ul32;
     std::vector<double> ui64, ul64;
+    const uint8_t *ha = host_array(j);
+    if (!ha) return sz3hip_last_error_code();
     if (j.cdt == SZ3HIP_FLOAT) {
-        std::vector<float> data((const float *)j.data, (const float *)j.data + n), unpred;
+        std::vector<float> data((const float *)ha, (const float *)ha + n), unpred;
         stock::lorenzo_reg_write_1d<float>(n, B, cf.absErrorBound, radius, set_mask, data.data(), codes, unpred, selection, coef_codes, ui32, ul32);
         n_unpred = unpred.size();
         un.assign((const uint8_t *)unpred.data(), (const uint8_t *)unpred.data() + n_unpred * 4);
     } else {
-        std::vector<double> data((const double *)j.data, (const double *)j.data + n), unpred;
+        std::vector<double> data((const double *)ha, (const double *)ha + n), unpred;
         stock::lorenzo_reg_write_1d<double>(n, B, cf.absErrorBound, radius, set_mask, data.data(), codes, unpred, selection, coef_codes, ui64, ul64);
         n_unpred = unpred.size();
         un.assign((const uint8_t *)unpred.data(), (const uint8_t *)unpred.data() + n_unpred * 8);
@@ -1380,8 +1498,10 @@ static int stock_encode_lorenzo_reg_1d(SlabJob &j) {
     if (!j.out_size) return stock_zstd_failed(j);
     j.conf.cmprAlgo = SZ3HIP_ALGO_LORENZO_REG;
     if ((double)j.raw_bytes / (double)j.out_size < 3) {  // SZDispatcher.hpp:62-74
+        const uint8_t *ha = host_array(j);
+        if (!ha) return sz3hip_last_error_code();
         std::vector<uint8_t> z(zs::bound_frames(j.raw_bytes) + 8);
-        size_t zsz = zs::compress_frames((const uint8_t *)j.data, j.raw_bytes, z.data(), z.size(), nullptr, stock_frame(j.raw_bytes));
+        size_t zsz = zs::compress_frames(ha, j.raw_bytes, z.data(), z.size(), nullptr, stock_frame(j.raw_bytes));
         if (zsz && zsz < j.out_size && zsz <= j.out_cap) {
             memcpy(j.out, z.data(), zsz);
             j.out_size = zsz;
@@ -1582,8 +1702,10 @@ int stock_encode_lorenzo_reg(SlabJob &j) {
     if (j.tm) j.tm->lap("zstd");
     j.conf.cmprAlgo = SZ3HIP_ALGO_LORENZO_REG;
     if ((double)j.raw_bytes / (double)j.out_size < 3) {  // SZDispatcher.hpp:62-74
+        const uint8_t *ha = host_array(j);
+        if (!ha) return sz3hip_last_error_code();
         std::vector<uint8_t> z(zs::bound_frames(j.raw_bytes) + 8);
-        size_t zsz = zs::compress_frames((const uint8_t *)j.data, j.raw_bytes, z.data(), z.size(), nullptr, stock_frame(j.raw_bytes));
+        size_t zsz = zs::compress_frames(ha, j.raw_bytes, z.data(), z.size(), nullptr, stock_frame(j.raw_bytes));
         if (zsz && zsz < j.out_size && zsz <= j.out_cap) {
             memcpy(j.out, z.data(), zsz);
             j.out_size = zsz;
@@ -1955,7 +2077,7 @@ int job_encode(SlabJob &j) {
             // itself (the device call grows the lists to what the input needs; a slab that took this turn is coded with its
             // own code book — every blob carries its code lengths, so the container does not care)
             if (ensure_dev(&s->dev_payload, &s->dev_payload_bytes, sz3hip_payload_bound_conf(ctx, &j.conf, 1))) return j.failed(SZ3HIP_EHIP);
-            rc = sz3hip_compress_device(ctx, &j.conf, s->dev_in, s->dev_payload, s->dev_payload_bytes, &dsize, s->stream);
+            rc = sz3hip_compress_device(ctx, &j.conf, j.din, s->dev_payload, s->dev_payload_bytes, &dsize, s->stream);
         }
         if (j.lossless) {
         } else if (rc == SZ3HIP_EOUTLIERS) {
@@ -2005,8 +2127,10 @@ int job_encode(SlabJob &j) {
                 j.conf.blockSize = (int)ctx->h_state->hdr.interp_id;
             }
             if ((double)j.raw_bytes / (double)j.out_size < 3) {  // SZDispatcher.hpp:62-74
+                const uint8_t *ha = host_array(j);
+                if (!ha) return j.failed(sz3hip_last_error_code());
                 std::vector<uint8_t> z(zs::bound_frames(j.raw_bytes) + 8);
-                size_t zsz = zs::compress_frames((const uint8_t *)j.data, j.raw_bytes, z.data(), z.size());
+                size_t zsz = zs::compress_frames(ha, j.raw_bytes, z.data(), z.size());
                 if (zsz && zsz < j.out_size && zsz <= j.out_cap) {
                     memcpy(j.out, z.data(), zsz);
                     j.out_size = zsz;
@@ -2018,8 +2142,14 @@ int job_encode(SlabJob &j) {
     if (j.lossless) {
         j.conf.cmprAlgo = SZ3HIP_ALGO_LOSSLESS;
         // (a stock container's lossless stream: one frame when the lossy ones are, SZ3HIP_STOCK_ONE_FRAME: the reference's bytes)
-        j.out_size = zs::compress_frames((const uint8_t *)j.data, j.raw_bytes, j.out, j.out_cap, nullptr, g_stock_format.load() > 0 ? stock_frame(j.raw_bytes) : zs::FRAME);
+        const uint8_t *ha = host_array(j);
+        if (!ha) return j.failed(sz3hip_last_error_code());
+        j.out_size = zs::compress_frames(ha, j.raw_bytes, j.out, j.out_cap, nullptr, g_stock_format.load() > 0 ? stock_frame(j.raw_bytes) : zs::FRAME);
         if (!j.out_size) return j.failed(sz3hip_last_error_code());
+    }
+    if (j.dsrc && s->stream && hipStreamSynchronize(s->stream) != hipSuccess) {  // (a device call: nothing reads the caller's array after the call)
+        fail(SZ3HIP_EHIP, "hipStreamSynchronize failed");
+        return j.failed(SZ3HIP_EHIP);
     }
     return 0;
 }
@@ -2040,7 +2170,7 @@ void job_init(SlabJob &j, const sz3hip_config &conf, int dataType, const void *d
 // The histogram exchange of a multi-slab call (the calling thread drives every GPU, as a single-process RCCL program
 // does): per GPU the histograms of its slabs are summed into the first one's, the per-GPU sums are all-reduced over
 // xGMI, the result is handed back to every slab's context. Slabs that never reached stage 1 (lossless) take no part.
-int exchange_histograms(std::vector<SlabJob> &jobs, const std::vector<int> &devices) {
+int exchange_histograms(std::vector<SlabJob> &jobs, const std::vector<int> &devices, sz3hip_comm *comm) {
     const size_t nd = devices.size();
     std::vector<std::vector<SlabJob *>> per(nd);
     for (auto &j : jobs)
@@ -2049,14 +2179,14 @@ int exchange_histograms(std::vector<SlabJob> &jobs, const std::vector<int> &devi
                 if (j.slot->device == devices[d]) per[d].push_back(&j);
     size_t total = 0;
     for (auto &p : per) total += p.size();
-    if (total <= 1 && !g_comm) return 0;
+    if (total <= 1 && !comm) return 0;
     std::vector<sz3hip_ctx *> lead(nd, nullptr);
     std::vector<void *> bufs(nd, nullptr), streams(nd, nullptr);
     static std::vector<std::pair<int, void *>> zero_hist;  // per device: what a GPU without a coded slab contributes
     for (size_t d = 0; d < nd; d++) {
         HIPCHK(hipSetDevice(devices[d]));
         if (per[d].empty()) {
-            if (!g_comm) continue;
+            if (!comm) continue;
             void *z = nullptr;
             for (auto &zh : zero_hist)
                 if (zh.first == devices[d]) z = zh.second;
@@ -2079,13 +2209,13 @@ int exchange_histograms(std::vector<SlabJob> &jobs, const std::vector<int> &devi
                 return fail(SZ3HIP_EHIP, "histogram add kernel failed");
         }
     }
-    if (g_comm) {
-        int rc = sz3hip_comm_allreduce_u64(g_comm, bufs.data(), SZH_HIST_BINS, streams.data());
+    if (comm) {
+        int rc = sz3hip_comm_allreduce_u64(comm, bufs.data(), SZH_HIST_BINS, streams.data());
         if (rc) return rc;
     }
     for (size_t d = 0; d < nd; d++) {
         if (per[d].empty()) {
-            if (g_comm) {
+            if (comm) {
                 HIPCHK(hipSetDevice(devices[d]));
                 HIPCHK(hipStreamSynchronize(nullptr));
             }
@@ -2101,12 +2231,13 @@ int exchange_histograms(std::vector<SlabJob> &jobs, const std::vector<int> &devi
 }
 
 // SZ_compress_OMP (api/impl/SZImplOMP.hpp:16-117) over GPUs: returns the size of the container body written at `out`
-size_t compress_slabs(sz3hip_config &conf, int dataType, const void *data, unsigned char *out, size_t cap) {
-    const int ndev = multi_devices();
+// (dev: a device call — every slab on the array's own device, no communicator)
+size_t compress_slabs(sz3hip_config &conf, int dataType, const void *data, const DevArray *dev, unsigned char *out, size_t cap) {
+    const int ndev = dev ? 1 : multi_devices();
     const int G = multi_slabs(conf);
     const int cdt = dtype_compute(dataType);
     const size_t es = dtype_size(dataType);
-    if (conf.cmprAlgo != SZ3HIP_ALGO_LOSSLESS) {
+    if (conf.cmprAlgo != SZ3HIP_ALGO_LOSSLESS && !dev) {
         int have = 0;
         if (hipGetDeviceCount(&have) != hipSuccess || have < 1) {
             (void)hipGetLastError();
@@ -2126,8 +2257,9 @@ size_t compress_slabs(sz3hip_config &conf, int dataType, const void *data, unsig
             if (!g_comm) return 0;
         }
     }
+    sz3hip_comm *const comm = dev ? nullptr : g_comm;
     std::vector<int> devices;
-    for (int d = 0; d < ndev; d++) devices.push_back(ndev == 1 ? host_device() : d);
+    for (int d = 0; d < ndev; d++) devices.push_back(dev ? dev->device : ndev == 1 ? host_device() : d);
     const uint64_t base = conf.num / conf.dims[0];
     std::vector<SlabJob> jobs(G);
     for (int g = 0; g < G; g++) {
@@ -2144,9 +2276,10 @@ size_t compress_slabs(sz3hip_config &conf, int dataType, const void *data, unsig
         ct.num = geo.num;
         ct.predDim = geo.predDim;
         ct.blockSize = geo.blockSize;
-        job_init(jobs[g], ct, dataType, (const unsigned char *)data + lo * base * es, g);
+        job_init(jobs[g], ct, dataType, data ? (const unsigned char *)data + lo * base * es : nullptr, g);
+        job_device_source(jobs[g], dev, lo, hi);
         jobs[g].slot = get_slot(devices[g % ndev], cdt, g / ndev);
-        jobs[g].exchange = G > 1 || g_comm != nullptr;  // (exchange_histograms: the slabs' histograms are summed whenever there are several)
+        jobs[g].exchange = G > 1 || comm != nullptr;  // (exchange_histograms: the slabs' histograms are summed whenever there are several)
         jobs[g].own_out.resize(zs::bound_frames(jobs[g].raw_bytes) + 64);
         jobs[g].out = jobs[g].own_out.data();
         jobs[g].out_cap = jobs[g].own_out.size();
@@ -2181,7 +2314,7 @@ size_t compress_slabs(sz3hip_config &conf, int dataType, const void *data, unsig
         if (!shared_rc)
             for (int g = t; g < G; g += ndev) job_stage1(jobs[g]);
         bar.wait();
-        if (t == 0 && !shared_rc && exchange_histograms(jobs, devices)) {
+        if (t == 0 && !shared_rc && exchange_histograms(jobs, devices, comm)) {
             shared_rc = sz3hip_last_error_code();
             shared_err = sz3hip_last_error();
         }
@@ -2236,10 +2369,10 @@ int ensure_host(HostSlot *s, size_t want) {
 // the pipelined form of a plain call (piece_count above): one host thread per piece; the copies in take turns in piece order (the link
 // carries one at a time at full rate), everything behind them — stage 1, code book, packer, copy out, zstd — runs as soon as its piece
 // has arrived, beside the next pieces' copies; the blobs go to their places in piece order as their sizes become known
-size_t compress_pieces(sz3hip_config &conf, int dataType, const void *data, unsigned char *out, size_t cap, int G, HostTimer *tm) {
+size_t compress_pieces(sz3hip_config &conf, int dataType, const void *data, const DevArray *darr, unsigned char *out, size_t cap, int G, HostTimer *tm) {
     const int cdt = dtype_compute(dataType);
     const size_t es = dtype_size(dataType);
-    const int dev = host_device();
+    const int dev = darr ? darr->device : host_device();
     int have = 0;
     if (hipGetDeviceCount(&have) != hipSuccess || have < 1) {
         (void)hipGetLastError();
@@ -2265,7 +2398,8 @@ size_t compress_pieces(sz3hip_config &conf, int dataType, const void *data, unsi
         ct.num = geo.num;
         ct.predDim = geo.predDim;
         ct.openmp = 0;  // (the caller's blockSize stands: this is a plain call's array, not SZ_compress_OMP's setDims)
-        job_init(jobs[g], ct, dataType, (const unsigned char *)data + lo * base * es, g);
+        job_init(jobs[g], ct, dataType, data ? (const unsigned char *)data + lo * base * es : nullptr, g);
+        job_device_source(jobs[g], darr, lo, hi);
         jobs[g].slot = get_slot(dev, cdt, g);
         jobs[g].frame = PIECE_FRAME;
         if (ensure_host(jobs[g].slot, zs::bound_frames(jobs[g].raw_bytes, PIECE_FRAME) + 64)) return 0;
@@ -2362,30 +2496,40 @@ size_t compress_pieces(sz3hip_config &conf, int dataType, const void *data, unsi
 // on anything but some 1-D arrays; other outcomes keep this library's own ids. Default: the environment's SZ3HIP_STOCK_FORMAT (else 0).
 extern "C" void sz3hip_set_stock_format(int on) { g_stock_format.store(on ? 1 : 0); }
 extern "C" int sz3hip_get_stock_format(void) { return g_stock_format.load() > 0 ? 1 : 0; }
-extern "C" size_t sz3hip_compress(const sz3hip_config *config, int dataType, const void *data, char *cmpData,
-                                  size_t cmpCap) {
-    HostTimer tm;
-    if (g_stock_format.load() < 0) g_stock_format.store(env_int("SZ3HIP_STOCK_FORMAT", 0) ? 1 : 0);
+namespace {
+// the argument checks of both compress calls
+sz3hip_config checked_config(const sz3hip_config *config, int dataType, size_t cmpCap, bool *ok) {
+    *ok = false;
+    sz3hip_config conf = *config;  // sz.hpp:45
     if (!dtype_ok(dataType)) {
         fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
-        return 0;
+        return conf;
     }
-    sz3hip_config conf = *config;  // sz.hpp:45
     if (conf.N < 1 || conf.N > 4) {
         fail(SZ3HIP_EINVAL, "Data dimension higher than 4 is not supported.");
-        return 0;
+        return conf;
     }
     uint64_t num = 1;
     for (int i = 0; i < conf.N; i++) num *= conf.dims[i];
     if (num != conf.num || num == 0) {
         fail(SZ3HIP_EINVAL, "conf.num does not match conf.dims");
-        return 0;
+        return conf;
     }
-    if (zs::load()) return 0;
+    if (zs::load()) return conf;
     if (cmpCap < sz3hip_compress_bound(&conf, dataType)) {  // sz.hpp:47-49
         fail(SZ3HIP_ECAPACITY, "The buffer for compressed data is not large enough.");
-        return 0;
+        return conf;
     }
+    *ok = true;
+    return conf;
+}
+// sz3hip_compress (data: host) and sz3hip_compress_from_device (dev): everything between the copy in and the copy out is the same code
+size_t compress_impl(const sz3hip_config *config, int dataType, const void *data, const DevArray *dev, char *cmpData, size_t cmpCap) {
+    HostTimer tm;
+    if (g_stock_format.load() < 0) g_stock_format.store(env_int("SZ3HIP_STOCK_FORMAT", 0) ? 1 : 0);
+    bool ok = false;
+    sz3hip_config conf = checked_config(config, dataType, cmpCap, &ok);
+    if (!ok) return 0;
     unsigned char *out = reinterpret_cast<unsigned char *>(cmpData);
     const uint8_t caller_dtype = conf.dataType;
     Writer w{out};
@@ -2404,15 +2548,16 @@ extern "C" size_t sz3hip_compress(const sz3hip_config *config, int dataType, con
     else some.lock();
     DeviceGuard guard;
     if (conf.openmp) {  // SZ_compress_impl, api/impl/SZImpl.hpp:10-20
-        payload_size = compress_slabs(conf, dataType, data, w.p, payload_cap);
+        payload_size = compress_slabs(conf, dataType, data, dev, w.p, payload_cap);
         if (!payload_size) return 0;
     } else if (pieces) {
-        payload_size = compress_pieces(conf, dataType, data, w.p, payload_cap, pieces, &tm);
+        payload_size = compress_pieces(conf, dataType, data, dev, w.p, payload_cap, pieces, &tm);
         if (!payload_size) return 0;
     } else {
         SlabJob j;
         job_init(j, conf, dataType, data, 0);
-        SlotLease lease(host_device(), j.cdt);
+        if (dev) job_device_source(j, dev, 0, conf.dims[0]);
+        SlotLease lease(dev ? dev->device : host_device(), j.cdt);
         j.slot = lease.s;
         j.out = w.p;
         j.out_cap = payload_cap;
@@ -2435,6 +2580,95 @@ extern "C" size_t sz3hip_compress(const sz3hip_config *config, int dataType, con
     else conf.dataType = (uint8_t)dataType;
     w.p += sz3hip_config_save(&conf, w.p);
     return (size_t)(w.p - out);
+}
+}  // namespace
+extern "C" size_t sz3hip_compress(const sz3hip_config *config, int dataType, const void *data, char *cmpData, size_t cmpCap) {
+    return compress_impl(config, dataType, data, nullptr, cmpData, cmpCap);
+}
+
+namespace {
+// The caller's array of a device call: view from the Config's extents and the element strides (NULL: contiguous), then the device that
+// owns the memory. An output view whose elements overlap is refused (sufficient test: each extent's stride, in increasing order, passes
+// beyond everything the smaller strides reach).
+int dev_array(const sz3hip_config *c, const int64_t *strides, const void *ptr, bool output, DevArray *d) {
+    const int N = c->N;
+    d->N = N;
+    d->ptr = (char *)ptr;
+    szk_view &v = d->view;
+    v = szk_view{};
+    for (int i = 0; i < 4; i++) v.dims[i] = 1;
+    int64_t run = 1;
+    v.contig = 1;
+    for (int i = N - 1; i >= 0; i--) {
+        const int k = 4 - N + i;
+        v.dims[k] = c->dims[i];
+        v.str[k] = strides ? strides[i] : run;
+        if (v.str[k] < 0) return fail(SZ3HIP_EINVAL, "stride %d is negative (%lld)", i, (long long)v.str[k]);
+        if (c->dims[i] > 1 && v.str[k] != run) v.contig = 0;
+        run *= (int64_t)c->dims[i];
+    }
+    if (v.contig)
+        for (int i = 4 - N; i < 4; i++) v.str[i] = i == 3 ? 1 : v.str[i];
+    if (output && !v.contig) {
+        std::vector<std::pair<int64_t, uint64_t>> sd;
+        for (int i = 4 - N; i < 4; i++)
+            if (v.dims[i] > 1) sd.push_back({v.str[i], v.dims[i]});
+        std::sort(sd.begin(), sd.end());
+        int64_t reach = 0;  // the largest offset the dimensions so far address
+        for (auto &e : sd) {
+            if (e.first <= reach) return fail(SZ3HIP_EINVAL, "the output strides make elements overlap");
+            reach += e.first * (int64_t)(e.second - 1);
+        }
+    }
+    if (!ptr) return fail(SZ3HIP_EINVAL, "the device array is NULL");
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof(a));
+    const hipError_t e = hipPointerGetAttributes(&a, ptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SZ3HIP_EINVAL, "the array is not device memory the HIP runtime knows (hipPointerGetAttributes: %s)", hipGetErrorString(e));
+    }
+    if (a.type != hipMemoryTypeDevice) return fail(SZ3HIP_EINVAL, "the array is not device memory (memory type %d)", (int)a.type);
+    d->device = a.device;
+    return 0;
+}
+}  // namespace
+
+extern "C" int sz3hip_debug_gather(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream) {
+    if (!dtype_ok(dataType) || N < 1 || N > 4) return fail(SZ3HIP_EINVAL, "bad arguments");
+    sz3hip_config c;
+    memset(&c, 0, sizeof(c));
+    c.N = N;
+    for (int i = 0; i < N; i++) c.dims[i] = dims[i];
+    DevArray d;
+    int rc = dev_array(&c, strides, d_in, false, &d);
+    if (rc) return rc;
+    if (szk_launch_gather(dataType, 1, d_in, &d.view, d_out, nullptr, (hipStream_t)stream)) return fail(SZ3HIP_EHIP, "gather kernel failed");
+    return 0;
+}
+
+extern "C" size_t sz3hip_compress_from_device(const sz3hip_config *config, int dataType, const void *d_data, const int64_t *strides, char *cmpData,
+                                              size_t cmpCap, void *stream) {
+    bool ok = false;
+    const sz3hip_config conf = checked_config(config, dataType, cmpCap, &ok);
+    if (!ok) return 0;
+    DevArray dev;
+    if (dev_array(&conf, strides, d_data, false, &dev)) return 0;
+    DeviceGuard guard;
+    if (hipSetDevice(dev.device) != hipSuccess) {
+        fail(SZ3HIP_EHIP, "hipSetDevice(%d) failed", dev.device);
+        return 0;
+    }
+    // the slots' streams wait for what the caller's stream has queued (a producer's kernels) before they read the array
+    if (hipEventCreateWithFlags(&dev.ready, hipEventDisableTiming) != hipSuccess) {
+        fail(SZ3HIP_EHIP, "hipEventCreate failed");
+        return 0;
+    }
+    size_t n = 0;
+    if (hipEventRecord(dev.ready, (hipStream_t)stream) != hipSuccess) fail(SZ3HIP_EHIP, "hipEventRecord on the caller's stream failed");
+    else n = compress_impl(config, dataType, nullptr, &dev, cmpData, cmpCap);
+    (void)hipEventDestroy(dev.ready);
+    return n;
 }
 
 namespace {
@@ -2713,16 +2947,25 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
                     is_int ? "integer" : "floating-point");
     if ((rc = slot_ctx(s, conf->num))) return rc;
     const size_t cbytes = (size_t)conf->num * (cdt == SZ3HIP_FLOAT ? 4 : 8);
-    if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, cbytes))) return rc;
+    // (a device call's contiguous f32 / f64 array is decoded where it lies)
+    void *dst = t_devout && t_devout->view.contig && !is_int ? (void *)t_devout->ptr : nullptr;
+    if (!dst) {
+        if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, cbytes))) return rc;
+        dst = s->dev_in;
+    }
     if ((rc = ensure_dev(&s->dev_payload, &s->dev_payload_bytes, std::max<size_t>(raw_len + 64, is_int ? raw_bytes : 0)))) return rc;
     HIPCHK(hipMemcpy(s->dev_payload, s->pin, raw_len, hipMemcpyHostToDevice));
     stamp(1);
-    rc = sz3hip_decompress_device(s->ctx, s->dev_payload, raw_len, s->dev_in, s->stream);
+    rc = sz3hip_decompress_device(s->ctx, s->dev_payload, raw_len, dst, s->stream);
     if (rc) return rc;
     if (!is_int) {
         HIPCHK(hipStreamSynchronize(s->stream));
         stamp(2);
-        HIPCHK(d2h_out(decData, s->dev_in, raw_bytes));
+        HIPCHK(d2h_out(decData, dst, raw_bytes));
+    } else if (t_devout) {  // (narrowed straight into the caller's view)
+        t_devout->delivered = true;
+        if (szk_launch_scatter(dataType, 1, s->dev_in, t_devout->ptr, &t_devout->view, s->stream)) return fail(SZ3HIP_EHIP, "integer narrowing kernel failed");
+        HIPCHK(hipStreamSynchronize(s->stream));
     } else {
         rc = szk_launch_f64_to_int(dataType, (const double *)s->dev_in, conf->num, s->dev_payload, s->stream);
         if (rc) return fail(SZ3HIP_EHIP, "integer narrowing kernel failed");
@@ -2732,9 +2975,39 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
     return 0;
 }
 
+// One blob to the host array at host_dst, or (dev) to rows [lo, hi) of the caller's device array
+int decode_blob_to(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, void *host_dst, const DevArray *dev, uint64_t lo,
+                   uint64_t hi) {
+    if (!dev) return decompress_blob(s, conf, dataType, p, payload, host_dst);
+    HIPCHK(hipSetDevice(s->device));
+    if (!s->stream) HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    const size_t bytes = (size_t)conf->num * dtype_size(dataType);
+    DevOut o;
+    o.ptr = dev->slab(lo, hi, dtype_size(dataType), &o.view);
+    o.dataType = dataType;
+    o.stream = s->stream;
+    // the paths that write the array on the host write it here (malloc: pages nobody touches cost nothing)
+    std::unique_ptr<uint8_t, void (*)(void *)> h((uint8_t *)malloc(std::max<size_t>(bytes, 1)), free);
+    if (!h) return fail(SZ3HIP_EHIP, "out of host memory (%zu bytes)", bytes);
+    t_devout = &o;
+    int rc = decompress_blob(s, conf, dataType, p, payload, h.get());
+    t_devout = nullptr;
+    if (rc || o.delivered) return rc;
+    if (o.view.contig) {
+        HIPCHK(hipMemcpyAsync(o.ptr, h.get(), bytes, hipMemcpyHostToDevice, s->stream));
+    } else {
+        if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, bytes))) return rc;
+        HIPCHK(hipMemcpyAsync(s->dev_in, h.get(), bytes, hipMemcpyHostToDevice, s->stream));
+        if (szk_launch_scatter(dataType, 0, s->dev_in, o.ptr, &o.view, s->stream)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
 // SZ_decompress_OMP (api/impl/SZImplOMP.hpp:120-186): [i32 G][Config x G][u64 size x G][blob x G], slab g of the array
 // described by the outer Config goes to GPU g % (visible GPUs), one host thread per GPU
-int decompress_slabs(const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, void *decData) {
+// (dev: a device call — every slab on the array's own device, into its rows of the caller's array)
+int decompress_slabs(const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, void *decData, const DevArray *dev) {
     const unsigned char *end = p + payload;
     if (payload < 4) return fail(SZ3HIP_EFORMAT, "truncated multi-slab container");
     Reader r{p};
@@ -2764,7 +3037,8 @@ int decompress_slabs(const sz3hip_config *conf, int dataType, const unsigned cha
         if (ct[g].num != (hi - lo) * base) return fail(SZ3HIP_EFORMAT, "slab %d does not have the extent the outer Config implies", g);
         if (ct[g].cmprAlgo != SZ3HIP_ALGO_LOSSLESS) need_gpu = true;
     }
-    const int ndev = need_gpu ? multi_devices() : 1;
+    const int ndev = need_gpu && !dev ? multi_devices() : 1;
+    const int dev0 = dev ? dev->device : host_device();
     const int cdt = dtype_compute(dataType);
     // G comes from the container (a reference OMP file of a many-core host, or a hostile stream): the pipelined reader below keeps a
     // host thread, a slot and a device context per piece alive at once, so it takes containers of at most MAX_PIPE pieces (what
@@ -2772,7 +3046,7 @@ int decompress_slabs(const sz3hip_config *conf, int dataType, const unsigned cha
     constexpr int MAX_PIPE = 16;
     const bool pipelined = ndev == 1 && G >= 2 && G <= MAX_PIPE && need_gpu && (size_t)conf->num * es >= (64u << 20) && env_int("SZ3HIP_PIECES", -1) != 0;
     std::vector<HostSlot *> slots(G);
-    for (int g = 0; g < G; g++) slots[g] = pipelined ? get_slot(host_device(), cdt, g) : get_slot(ndev == 1 ? host_device() : g % ndev, cdt, 0);
+    for (int g = 0; g < G; g++) slots[g] = pipelined ? get_slot(dev0, cdt, g) : get_slot(ndev == 1 ? dev0 : g % ndev, cdt, 0);
     std::vector<int> rcs(G, 0);
     std::vector<std::string> errs(G);
     if (pipelined) {
@@ -2790,14 +3064,14 @@ int decompress_slabs(const sz3hip_config *conf, int dataType, const unsigned cha
             gt.cv = &cv;
         }
         auto piece = [&](int g) {
-            t_gate = &gates[g];
+            t_gate = dev ? nullptr : &gates[g];  // (a device call's pieces write their own rows: nothing for this thread to copy)
             if (timing) {
                 t_stamps = &stamps[(size_t)g * 5];
                 t_stamp0 = t_call;
             }
             uint64_t lo, hi;
             slab_range(*conf, G, g, &lo, &hi);
-            rcs[g] = decompress_blob(slots[g], &ct[g], dataType, blobs + start[g], (size_t)size[g], (unsigned char *)decData + lo * base * es);
+            rcs[g] = decode_blob_to(slots[g], &ct[g], dataType, blobs + start[g], (size_t)size[g], decData ? (unsigned char *)decData + lo * base * es : nullptr, dev, lo, hi);
             if (rcs[g]) errs[g] = sz3hip_last_error();
             t_gate = nullptr;
             t_stamps = nullptr;
@@ -2851,7 +3125,7 @@ int decompress_slabs(const sz3hip_config *conf, int dataType, const unsigned cha
         for (int g = t; g < G; g += ndev) {
             uint64_t lo, hi;
             slab_range(*conf, G, g, &lo, &hi);
-            rcs[g] = decompress_blob(slots[g], &ct[g], dataType, blobs + start[g], (size_t)size[g], (unsigned char *)decData + lo * base * es);
+            rcs[g] = decode_blob_to(slots[g], &ct[g], dataType, blobs + start[g], (size_t)size[g], decData ? (unsigned char *)decData + lo * base * es : nullptr, dev, lo, hi);
             if (rcs[g]) errs[g] = sz3hip_last_error();
         }
     };
@@ -2888,7 +3162,7 @@ extern "C" int sz3hip_decompress(sz3hip_config *conf, int dataType, const char *
     if (conf->openmp) all.lock();
     else some.lock();
     DeviceGuard guard;
-    if (conf->openmp) return decompress_slabs(conf, dataType, p, (size_t)payload, decData);  // SZ_decompress_impl, SZImpl.hpp:22-32
+    if (conf->openmp) return decompress_slabs(conf, dataType, p, (size_t)payload, decData, nullptr);  // SZ_decompress_impl, SZImpl.hpp:22-32
     Prefault pf;  // (the output array's pages, populated beside the work below — when the copy out will not go through the staging ring)
     if (!d2h_staging_wanted((size_t)conf->num * dtype_size(dataType))) pf.start(decData, (size_t)conf->num * dtype_size(dataType));
     t_prefault = &pf;
@@ -2898,6 +3172,30 @@ extern "C" int sz3hip_decompress(sz3hip_config *conf, int dataType, const char *
     return rcd;
 }
 
+extern "C" int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, void *d_out, const int64_t *strides,
+                                           void *stream) {
+    if (!dtype_ok(dataType))
+        return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
+    int rc = sz3hip_peek_config(conf, cmpData, cmpSize);
+    if (rc) return rc;
+    if (zs::load()) return SZ3HIP_EZSTD;
+    DevArray dev;
+    if ((rc = dev_array(conf, strides, d_out, true, &dev))) return rc;
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(cmpData) + 8;
+    uint64_t payload;
+    memcpy(&payload, p, 8);
+    p += 8;
+    DeviceGuard guard;
+    HIPCHK(hipSetDevice(dev.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (what the caller queued on d_out comes first)
+    std::unique_lock<std::shared_mutex> all(g_host_mu, std::defer_lock);
+    std::shared_lock<std::shared_mutex> some(g_host_mu, std::defer_lock);
+    if (conf->openmp) all.lock();
+    else some.lock();
+    if (conf->openmp) return decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &dev);
+    SlotLease lease(dev.device, dtype_compute(dataType));
+    return decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &dev, 0, conf->dims[0]);
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // the reference's C ABI (tools/sz3c/include/sz3c.h:52-59, tools/sz3c/src/sz3c.cpp:11-94)

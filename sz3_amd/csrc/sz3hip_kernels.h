@@ -374,6 +374,16 @@ int szk_launch_interp_trials(int dtype, const szk_interp_params *ips, uint32_t n
 int szk_launch_code_cost(const uint64_t *hist, const uint64_t *counters, uint64_t *d_res, uint32_t n_books, uint64_t total,
                          int unpred_is_code0, hipStream_t s);
 
+// a strided view of rank <= 4 (dims slowest first, element strides; a lower rank is padded in front with extent 1); contig: unit strides
+struct szk_view {
+    uint64_t dims[4];
+    int64_t str[4];
+    int contig;
+};
+// gather: view -> contiguous buffer; widen: integers (sz_type 2 .. 9) become f64 and d_flag (if not null) gets 1 for |x| > 2^53; else a copy
+int szk_launch_gather(int sz_type /* SZ_FLOAT = 0 .. SZ_INT64 = 9 */, int widen, const void *d_in, const szk_view *v, void *d_out, uint32_t *d_flag, hipStream_t s);
+// scatter: contiguous buffer -> view; narrow: f64 -> the integer type (rounded, clamped to its range); else a copy
+int szk_launch_scatter(int sz_type, int narrow, const void *d_in, void *d_out, const szk_view *v, hipStream_t s);
 int szk_launch_int_to_f64(int sz_type /* SZ_UINT8 = 2 .. SZ_INT64 = 9 */, const void *d_in, uint64_t n, double *d_out, uint32_t *d_flag, hipStream_t s);
 int szk_launch_f64_to_int(int sz_type, const double *d_in, uint64_t n, void *d_out, hipStream_t s);
 int szk_launch_hist_add(uint64_t *d_dst, const uint64_t *d_src, uint32_t n, hipStream_t s);  // dst[i] += src[i]

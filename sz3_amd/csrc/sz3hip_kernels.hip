@@ -6031,71 +6031,185 @@ static inline uint32_t grid_for(uint64_t n, uint32_t block, uint32_t cap) {
 }
 
 // ---- integer inputs ride the f64 pipeline: every element type of the reference's HDF5 filter (tools/H5Z-SZ3/src/H5Z_SZ3.cpp:195-227 —
-// 8 / 16 / 32 / 64-bit, signed and unsigned) widened on the device; exact up to 2^53 in magnitude (beyond: the array stays lossless)
-template <typename I>
-__global__ __launch_bounds__(256) void k_int_to_f64(const I *__restrict__ in, uint64_t n, double *__restrict__ out, uint32_t *too_big) {
-    bool big = false;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        const I v = in[i];
-        if (sizeof(I) == 8) {
-            if (std::is_signed<I>::value) {
+// 8 / 16 / 32 / 64-bit, signed and unsigned) widened on the device; exact up to 2^53 in magnitude (beyond: the array stays lossless).
+// One kernel family moves an array between a strided view (rank <= 4, element strides) and a contiguous buffer: the gather reads the view
+// (integers widened to f64, or copied), the scatter writes it (f64 narrowed to the integer type, or copied). The host API calls them with
+// unit strides (a plain grid-stride loop, as before); the device-container calls (sz3hip_compress_from_device ...) with the caller's strides.
+template <typename Tin, typename Tout>
+__device__ __forceinline__ Tout szk_cvt(Tin v, bool &big) {
+    if constexpr (std::is_same<Tin, Tout>::value) {
+        return v;
+    } else if constexpr (std::is_floating_point<Tout>::value) {  // integer -> f64
+        if constexpr (sizeof(Tin) == 8) {
+            if constexpr (std::is_signed<Tin>::value) {
                 const long long a = (long long)v;
                 big |= a > (1ll << 53) || a < -(1ll << 53);
             } else {
                 big |= (unsigned long long)v > (1ull << 53);
             }
         }
-        out[i] = (double)v;
-    }
-    if (__ballot(big) && (threadIdx.x & 63) == 0) atomicOr(too_big, 1u);
-}
-template <typename I>
-__global__ __launch_bounds__(256) void k_f64_to_int(const double *__restrict__ in, uint64_t n, I *__restrict__ out) {
-    // (the reconstruction of an in-range integer within a bound >= 1 may leave the type's range by the bound: clamped, like a cast would not)
-    constexpr double lo = std::is_signed<I>::value ? -(double)(1ull << (8 * sizeof(I) - 1)) : 0.0;
-    constexpr double hi = sizeof(I) == 8 ? (std::is_signed<I>::value ? 9223372036854774784.0 : 18446744073709549568.0)  // largest doubles below 2^63 / 2^64
-                                         : (double)((1ull << (8 * sizeof(I) - (std::is_signed<I>::value ? 1 : 0))) - 1ull);
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        const double v = fmin(fmax(rint(in[i]), lo), hi);
-        out[i] = std::is_signed<I>::value ? (I)(long long)v : (I)(unsigned long long)v;
+        return (Tout)v;
+    } else {  // f64 -> integer
+        // (the reconstruction of an in-range integer within a bound >= 1 may leave the type's range by the bound: clamped, like a cast would not)
+        constexpr double lo = std::is_signed<Tout>::value ? -(double)(1ull << (8 * sizeof(Tout) - 1)) : 0.0;
+        constexpr double hi = sizeof(Tout) == 8 ? (std::is_signed<Tout>::value ? 9223372036854774784.0 : 18446744073709549568.0)  // largest doubles below 2^63 / 2^64
+                                                : (double)(~0ull >> (64 - 8 * sizeof(Tout) + (std::is_signed<Tout>::value ? 1 : 0)));
+        const double r = fmin(fmax(rint(v), lo), hi);
+        return std::is_signed<Tout>::value ? (Tout)(long long)r : (Tout)(unsigned long long)r;
     }
 }
-// sz_type: SZ_UINT8 = 2, SZ_INT8 = 3, SZ_UINT16 = 4, SZ_INT16 = 5, SZ_UINT32 = 6, SZ_INT32 = 7, SZ_UINT64 = 8, SZ_INT64 = 9 (include/SZ3/def.hpp:27-36)
-int szk_launch_int_to_f64(int sz_type, const void *d_in, uint64_t n, double *d_out, uint32_t *d_flag, hipStream_t s) {
-    const uint32_t g = grid_for(n, 256, 65536);
-#define SZK_W(T) hipLaunchKernelGGL((k_int_to_f64<T>), dim3(g), dim3(256), 0, s, (const T *)d_in, n, d_out, d_flag)
+// SCATTER = false: out[i] = in[view(i)]; true: out[view(i)] = in[i] (i: the row-major index over v.dims). Strided views: lanes run along
+// the innermost index, one wave per row (rows of fewer than 32 elements: 64 / inner rows per wave), four elements per lane in flight; a
+// row's offset is computed once per row, in 64 bits.
+template <typename Tin, typename Tout, bool SCATTER>
+__global__ __launch_bounds__(256) void k_strided(const Tin *__restrict__ in, Tout *__restrict__ out, szk_view v, uint64_t n, uint32_t *too_big) {
+    bool big = false;
+    if (v.contig) {
+        for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) out[i] = szk_cvt<Tin, Tout>(in[i], big);
+    } else {
+        const uint64_t inner = v.dims[3], rows = n / inner;
+        const int64_t s3 = v.str[3];
+        const uint32_t lane = threadIdx.x & 63;
+        const uint32_t rpw = inner < 32 ? (uint32_t)(64 / inner) : 1;  // rows per wave
+        const uint32_t sub = rpw > 1 ? lane / (uint32_t)inner : 0, x0 = rpw > 1 ? lane % (uint32_t)inner : lane;
+        const uint64_t xstep = rpw > 1 ? inner : 64;  // (rpw > 1: one element per lane and row)
+        const uint64_t nwaves = (uint64_t)gridDim.x * 4;
+        for (uint64_t r = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * rpw + sub; sub < rpw && r < rows; r += nwaves * rpw) {
+            const uint64_t q = r / v.dims[2];
+            const uint64_t i2 = r - q * v.dims[2];
+            const uint64_t i0 = q / v.dims[1], i1 = q - i0 * v.dims[1];
+            const int64_t sb = (int64_t)i0 * v.str[0] + (int64_t)i1 * v.str[1] + (int64_t)i2 * v.str[2];
+            const uint64_t cb = r * inner;
+            for (uint64_t x = x0; x < inner; x += 4 * xstep) {
+                Tin t[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const uint64_t xk = x + (uint64_t)k * xstep;
+                    if (xk < inner) t[k] = SCATTER ? in[cb + xk] : in[sb + (int64_t)xk * s3];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const uint64_t xk = x + (uint64_t)k * xstep;
+                    if (xk < inner) {
+                        if (SCATTER) out[sb + (int64_t)xk * s3] = szk_cvt<Tin, Tout>(t[k], big);
+                        else out[cb + xk] = szk_cvt<Tin, Tout>(t[k], big);
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (!std::is_same<Tin, Tout>::value && std::is_floating_point<Tout>::value && sizeof(Tin) == 8)
+        if (__ballot(big) && (threadIdx.x & 63) == 0) atomicOr(too_big, 1u);
+}
+static inline uint32_t strided_grid(const szk_view &v, uint64_t n) {
+    if (v.contig) return grid_for(n, 256, 65536);
+    const uint64_t inner = v.dims[3], rows = n / inner, rpw = inner < 32 ? 64 / inner : 1;
+    return grid_for((rows + rpw - 1) / rpw * 64, 256, 4096);
+}
+// A copy whose innermost stride is 1 and whose rows and bases are 16- (8-) byte aligned moves 16 (8) bytes per lane: the same view in
+// units of that width.
+static bool view_in_units(const szk_view &v, const void *strided_base, const void *dense_base, size_t es, size_t unit, szk_view *u) {
+    if (es >= unit || v.str[3] != 1 || (uintptr_t)strided_base % unit || (uintptr_t)dense_base % unit) return false;
+    if ((v.dims[3] * es) % unit) return false;
+    for (int d = 0; d < 3; d++)
+        if (v.dims[d] > 1 && ((uint64_t)v.str[d] * es) % unit) return false;
+    *u = v;
+    u->dims[3] = v.dims[3] * es / unit;
+    for (int d = 0; d < 3; d++) u->str[d] = v.dims[d] > 1 ? (int64_t)((uint64_t)v.str[d] * es / unit) : 0;
+    return true;
+}
+template <typename T, bool SCATTER>
+static void launch_copy(const void *in, void *out, const szk_view &v, uint64_t n, hipStream_t s) {
+    const void *sb = SCATTER ? out : in, *db = SCATTER ? in : out;
+    szk_view u;
+    if (!v.contig && view_in_units(v, sb, db, sizeof(T), 16, &u)) {
+        const uint64_t m = n * sizeof(T) / 16;
+        hipLaunchKernelGGL((k_strided<uint4, uint4, SCATTER>), dim3(strided_grid(u, m)), dim3(256), 0, s, (const uint4 *)in, (uint4 *)out, u, m, nullptr);
+    } else if (!v.contig && view_in_units(v, sb, db, sizeof(T), 8, &u)) {
+        const uint64_t m = n * sizeof(T) / 8;
+        hipLaunchKernelGGL((k_strided<uint2, uint2, SCATTER>), dim3(strided_grid(u, m)), dim3(256), 0, s, (const uint2 *)in, (uint2 *)out, u, m, nullptr);
+    } else {
+        hipLaunchKernelGGL((k_strided<T, T, SCATTER>), dim3(strided_grid(v, n)), dim3(256), 0, s, (const T *)in, (T *)out, v, n, nullptr);
+    }
+}
+static szk_view contiguous_view(uint64_t n) {
+    szk_view v{};
+    v.dims[0] = v.dims[1] = v.dims[2] = 1;
+    v.dims[3] = n;
+    v.str[3] = 1;
+    v.contig = 1;
+    return v;
+}
+// sz_type: SZ_FLOAT = 0, SZ_DOUBLE = 1, SZ_UINT8 = 2, SZ_INT8 = 3, SZ_UINT16 = 4, SZ_INT16 = 5, SZ_UINT32 = 6, SZ_INT32 = 7, SZ_UINT64 = 8,
+// SZ_INT64 = 9 (include/SZ3/def.hpp:27-36)
+int szk_launch_gather(int sz_type, int widen, const void *d_in, const szk_view *v, void *d_out, uint32_t *d_flag, hipStream_t s) {
+    uint64_t n = 1;
+    for (int d = 0; d < 4; d++) n *= v->dims[d];
+    if (n == 0) return 0;
+    const bool w = widen && sz_type >= 2;
+#define SZK_G(T)                                                                                                                                      \
+    do {                                                                                                                                              \
+        if (w)                                                                                                                                        \
+            hipLaunchKernelGGL((k_strided<T, double, false>), dim3(strided_grid(*v, n)), dim3(256), 0, s, (const T *)d_in, (double *)d_out, *v, n, d_flag); \
+        else                                                                                                                                          \
+            launch_copy<T, false>(d_in, d_out, *v, n, s);                                                                                             \
+    } while (0)
     switch (sz_type) {
-        case 2: SZK_W(uint8_t); break;
-        case 3: SZK_W(int8_t); break;
-        case 4: SZK_W(uint16_t); break;
-        case 5: SZK_W(int16_t); break;
-        case 6: SZK_W(uint32_t); break;
-        case 7: SZK_W(int32_t); break;
-        case 8: SZK_W(uint64_t); break;
-        case 9: SZK_W(int64_t); break;
+        case 0: launch_copy<float, false>(d_in, d_out, *v, n, s); break;
+        case 1: launch_copy<double, false>(d_in, d_out, *v, n, s); break;
+        case 2: SZK_G(uint8_t); break;
+        case 3: SZK_G(int8_t); break;
+        case 4: SZK_G(uint16_t); break;
+        case 5: SZK_G(int16_t); break;
+        case 6: SZK_G(uint32_t); break;
+        case 7: SZK_G(int32_t); break;
+        case 8: SZK_G(uint64_t); break;
+        case 9: SZK_G(int64_t); break;
         default: return -1;
     }
-#undef SZK_W
+#undef SZK_G
     SZK_CHECK_LAUNCH();
     return 0;
+}
+int szk_launch_scatter(int sz_type, int narrow, const void *d_in, void *d_out, const szk_view *v, hipStream_t s) {
+    uint64_t n = 1;
+    for (int d = 0; d < 4; d++) n *= v->dims[d];
+    if (n == 0) return 0;
+    const bool w = narrow && sz_type >= 2;
+#define SZK_S(T)                                                                                                                                      \
+    do {                                                                                                                                              \
+        if (w)                                                                                                                                        \
+            hipLaunchKernelGGL((k_strided<double, T, true>), dim3(strided_grid(*v, n)), dim3(256), 0, s, (const double *)d_in, (T *)d_out, *v, n, nullptr); \
+        else                                                                                                                                          \
+            launch_copy<T, true>(d_in, d_out, *v, n, s);                                                                                              \
+    } while (0)
+    switch (sz_type) {
+        case 0: launch_copy<float, true>(d_in, d_out, *v, n, s); break;
+        case 1: launch_copy<double, true>(d_in, d_out, *v, n, s); break;
+        case 2: SZK_S(uint8_t); break;
+        case 3: SZK_S(int8_t); break;
+        case 4: SZK_S(uint16_t); break;
+        case 5: SZK_S(int16_t); break;
+        case 6: SZK_S(uint32_t); break;
+        case 7: SZK_S(int32_t); break;
+        case 8: SZK_S(uint64_t); break;
+        case 9: SZK_S(int64_t); break;
+        default: return -1;
+    }
+#undef SZK_S
+    SZK_CHECK_LAUNCH();
+    return 0;
+}
+// the host API's contiguous forms
+int szk_launch_int_to_f64(int sz_type, const void *d_in, uint64_t n, double *d_out, uint32_t *d_flag, hipStream_t s) {
+    if (sz_type < 2 || sz_type > 9) return -1;
+    const szk_view v = contiguous_view(n);
+    return szk_launch_gather(sz_type, 1, d_in, &v, d_out, d_flag, s);
 }
 int szk_launch_f64_to_int(int sz_type, const double *d_in, uint64_t n, void *d_out, hipStream_t s) {
-    const uint32_t g = grid_for(n, 256, 65536);
-#define SZK_N(T) hipLaunchKernelGGL((k_f64_to_int<T>), dim3(g), dim3(256), 0, s, d_in, n, (T *)d_out)
-    switch (sz_type) {
-        case 2: SZK_N(uint8_t); break;
-        case 3: SZK_N(int8_t); break;
-        case 4: SZK_N(uint16_t); break;
-        case 5: SZK_N(int16_t); break;
-        case 6: SZK_N(uint32_t); break;
-        case 7: SZK_N(int32_t); break;
-        case 8: SZK_N(uint64_t); break;
-        case 9: SZK_N(int64_t); break;
-        default: return -1;
-    }
-#undef SZK_N
-    SZK_CHECK_LAUNCH();
-    return 0;
+    if (sz_type < 2 || sz_type > 9) return -1;
+    const szk_view v = contiguous_view(n);
+    return szk_launch_scatter(sz_type, 1, d_in, d_out, &v, s);
 }
 
 // ---- several slabs on one GPU: their code histograms are summed before / instead of the RCCL exchange ------------------
