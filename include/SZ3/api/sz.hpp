@@ -455,6 +455,18 @@ inline int dtype_of() {
 }
 }  // namespace hipdetail
 
+// (libsz3hip) the numbers of verify() above for two contiguous arrays of n elements in DEVICE memory, reduced on the device that holds
+// them (sz3hip_verify_device: each array read once, nothing printed); bound >= 0: n_over / first_over count |dec - ori| > bound.
+// stream: what is waited for before the arrays are read. Errors are the exceptions of the entry points below.
+template <class T>
+inline sz3hip_verify_stats hip_verify_device(const T *d_ori, const T *d_dec, size_t n, double bound = -1, void *stream = nullptr) {
+    const uint64_t dims[1] = {(uint64_t)n};
+    sz3hip_verify_stats st;
+    const int rc = sz3hip_verify_device(hipdetail::dtype_of<T>(), 1, dims, d_ori, nullptr, d_dec, nullptr, bound, &st, stream);
+    if (rc) hipdetail::raise_last(rc);
+    return st;
+}
+
 }  // namespace SZ3
 
 // ---- the four entry points (global namespace, as in the reference) --------------------------------------------

@@ -164,6 +164,43 @@ int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, const char *c
 /* (test and measurement hook) the strided gather alone: the view (N extents, element strides) of d_in into the contiguous d_out on stream,
  * integers widened to f64 as the compress call does; asynchronous */
 int sz3hip_debug_gather(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream);
+/* The question that follows a round trip in device memory — is the decoded array within the bound, what PSNR did it get — answered where
+ * the arrays lie: the numbers of the reference's verify<T> (utils/Statistic.hpp:79-137: Min, Max, range, max absolute error, max point-wise
+ * relative error, PSNR, NRMSE, normError, normErr_norm, acEff) for two arrays in device memory, each read once by one reduction kernel
+ * (sz3hip_verify.hip); 152 bytes cross the host link. Nothing falls back to a host loop.
+ *  - dims: the caller's own N = 1 .. 4 extents, slowest first (extents of 1 are allowed; no Config is involved). strides_ori / strides_dec:
+ *    element strides of each array, one per extent; NULL: contiguous. Strides are >= 0; the views may overlap and a stride of 0 is a
+ *    broadcast (both arrays are only read). The two arrays share the extents, not the strides.
+ *  - d_ori / d_dec: device memory of ONE device, aligned to the element size (hipPointerGetAttributes); the call runs on that device.
+ *    Anything else is SZ3HIP_EINVAL before any launch, and *out is left as it was.
+ *  - stream (may be NULL): the library's stream waits for an event recorded on it before the arrays are read; the call is synchronous:
+ *    on return *out is filled. Calls on one device serialise on a workspace that is made by the first of them and kept for the process
+ *    (after the first call on a device, a call allocates nothing).
+ *  - per element a = ori, b = dec: float types e = |(double)b - (double)a|; integer types the exact difference (the unsigned magnitude at
+ *    the type's width, then converted: an int64 pair beyond 2^53 that differs by 1 reports 1.0), a and b enter the sums as (double).
+ *    Every accumulator is f64.
+ *  - NON-FINITE positions: a position where a or b is NaN or +-Inf is counted in n_nonfinite and left out of every other statistic; it is
+ *    also counted in n_nonfinite_mismatch when the two are not of the same kind (one NaN and the other not, an infinity against anything
+ *    but the same infinity). With n_nonfinite == 0 every number means what the reference's verify means; the reference's own NaN
+ *    behaviour depends on the element order (Max = ori_data[0], then "<") and is not reproduced. Nothing finite at all: min = max = NaN,
+ *    max_diff = 0, argmax = n.
+ *  - bound: n_over counts the finite positions with e > bound (strictly), first_over is the smallest row-major index of them (n: none);
+ *    a bound that is negative or NaN means "no bound given" (n_over = 0, first_over = n).
+ *  - argmax: the smallest row-major index, over the extents, at which max_diff is reached. max_pw_rel: max of e / |a| over a != 0.
+ *  - derived fields, the reference's formulas in IEEE double with m = n - n_nonfinite, nothing special-cased (identical arrays: psnr = +inf,
+ *    a constant ori: what IEEE gives): mse = sum_sq_err / m, range = max - min, psnr = 20 log10(range) - 10 log10(mse),
+ *    nrmse = sqrt(mse) / range, l2_err = sqrt(sum_sq_err), l2_err_norm = l2_err / sqrt(sum_sq_dec), acEff = the Pearson coefficient
+ *    (second moments accumulated about a value of the data and merged pairwise: DESIGN.md, "Verify on the device").
+ * Errors: unknown dataType SZ3HIP_EUNSUPPORTED; N outside 1 .. 4, an extent of 0, a negative stride, out == NULL, a host pointer, no device,
+ * arrays of two devices: SZ3HIP_EINVAL. */
+typedef struct sz3hip_verify_stats {
+    uint64_t n, n_nonfinite, n_nonfinite_mismatch, n_over, first_over, argmax;
+    double min, max, max_diff, max_pw_rel;
+    double sum_ori, sum_dec, sum_sq_err, sum_sq_dec;
+    double psnr, nrmse, l2_err, l2_err_norm, acEff;
+} sz3hip_verify_stats;
+int sz3hip_verify_device(int dataType, int N, const uint64_t *dims, const void *d_ori, const int64_t *strides_ori, const void *d_dec,
+                         const int64_t *strides_dec, double bound, sz3hip_verify_stats *out, void *stream);
 /* One algorithm of the reference's dispatcher (SZ_compress_LorenzoReg / SZ_compress_Interp / ..., SZDispatcher.hpp:28-42 and
  * their SZ_decompress_* counterparts :89-99): only the bytes between the container's 16-byte header and its Config trailer.
  * compress: returns their number (0 on error); *conf is updated like the reference updates it (absolute bound resolved,

@@ -59,6 +59,13 @@ class _CStats(C.Structure):
                 ("narrow_codes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _CVerifyStats(C.Structure):
+    """sz3hip_verify_stats (include/sz3hip.h)"""
+    _fields_ = ([(k, C.c_uint64) for k in ("n", "n_nonfinite", "n_nonfinite_mismatch", "n_over", "first_over", "argmax")] +
+                [(k, C.c_double) for k in ("min", "max", "max_diff", "max_pw_rel", "sum_ori", "sum_dec", "sum_sq_err", "sum_sq_dec",
+                                           "psnr", "nrmse", "l2_err", "l2_err_norm", "acEff")])
+
+
 _lib = None
 
 
@@ -149,6 +156,9 @@ def lib():
     L.sz3hip_decompress_to_device.restype = C.c_int
     L.sz3hip_decompress_to_device.argtypes = [P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(C.c_int64), C.c_void_p]
     L.sz3hip_peek_config.argtypes = [P(_CConfig), C.c_void_p, C.c_size_t]
+    L.sz3hip_verify_device.restype = C.c_int
+    L.sz3hip_verify_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), C.c_void_p, P(C.c_int64), C.c_double,
+                                       P(_CVerifyStats), C.c_void_p]
     L.sz3hip_ctx_create.restype = C.c_void_p
     L.sz3hip_ctx_create.argtypes = [C.c_int, C.c_uint64, C.c_int]
     L.sz3hip_ctx_destroy.argtypes = [C.c_void_p]
@@ -435,8 +445,64 @@ def decompress(blob, dtype, shape=None, out=None, device=None, stream=None):
     return dec.reshape(shape), conf
 
 
+class VerifyStats(dict):
+    """the fields of sz3hip_verify_stats (include/sz3hip.h), as items and as attributes"""
+    __getattr__ = dict.__getitem__
+
+
+def _is_tensor(x):
+    import sys
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+def verify_stats(ori, dec, bound=None, stream=None):
+    """Error statistics of two torch tensors on the same HIP device with the same shape and dtype (one of the ten element types),
+    reduced on that device by one kernel that reads each tensor once (sz3hip_verify_device): the tensors do not cross the host link.
+    Views are welcome, each with its own strides (size-1 dimensions are dropped; at most 4 are left). `bound`: n_over / first_over count
+    the positions with |dec - ori| > bound (None: no bound). `stream` (a torch stream or a raw handle; default: the device's current
+    stream) is what the library waits for before it reads the tensors. Returns a VerifyStats: n, n_nonfinite, n_nonfinite_mismatch,
+    n_over, first_over, argmax, min, max, max_diff, max_pw_rel, sum_ori, sum_dec, sum_sq_err, sum_sq_dec, psnr, nrmse, l2_err,
+    l2_err_norm, acEff (include/sz3hip.h says what each means, also for positions that are not finite)."""
+    if not (_is_tensor(ori) and _is_tensor(dec)):
+        raise TypeError("verify_stats takes two torch tensors on a HIP device (got %s and %s)" % (type(ori).__name__, type(dec).__name__))
+    if not (_gpu_tensor(ori) and _gpu_tensor(dec)):
+        raise ValueError("verify_stats: both tensors must be on a HIP device (they are on %s and %s)" % (ori.device, dec.device))
+    if ori.device != dec.device:
+        raise ValueError("verify_stats: the tensors are on different devices (%s and %s)" % (ori.device, dec.device))
+    if tuple(ori.shape) != tuple(dec.shape):
+        raise ValueError("verify_stats: the shapes differ (%s and %s)" % (tuple(ori.shape), tuple(dec.shape)))
+    if ori.dtype != dec.dtype:
+        raise TypeError("verify_stats: the dtypes differ (%s and %s)" % (ori.dtype, dec.dtype))
+    name = str(ori.dtype).replace("torch.", "")
+    if name not in _SZ_TYPES:
+        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % ori.dtype)
+    if ori.numel() == 0:
+        raise ValueError("verify_stats: the tensors are empty")
+    keep = [i for i, d in enumerate(ori.shape) if int(d) != 1]
+    if len(keep) > 4:
+        raise ValueError("verify_stats: %d dimensions above size 1 (at most 4 are supported)" % len(keep))
+    dims = [int(ori.shape[i]) for i in keep] or [1]
+    so = [int(ori.stride(i)) for i in keep] or [1]
+    sd = [int(dec.stride(i)) for i in keep] or [1]
+    N = len(dims)
+    st = _CVerifyStats()
+    b = -1.0 if bound is None else float(bound)
+    _check(lib().sz3hip_verify_device(_SZ_TYPES[name], N, (C.c_uint64 * N)(*dims), ori.data_ptr(), (C.c_int64 * N)(*so), dec.data_ptr(),
+                                      (C.c_int64 * N)(*sd), b, C.byref(st), _stream_handle(ori.device, stream)))
+    return VerifyStats((k, getattr(st, k)) for k, _ in _CVerifyStats._fields_)
+
+
 def verify(ori, dec):
-    """sz.verify (sz.pyx:368-405, utils/Statistic.hpp:80-137): (max_diff, psnr, nrmse) in float64."""
+    """sz.verify (sz.pyx:368-405, utils/Statistic.hpp:80-137): (max_diff, psnr, nrmse) in float64. Two torch tensors on a HIP device
+    are compared where they lie (verify_stats), with the same conventions: the same triple whichever side the arrays are on."""
+    if _gpu_tensor(ori) and _gpu_tensor(dec):
+        st = verify_stats(ori, dec)
+        rng = st.max - st.min
+        mse = st.sum_sq_err / (st.n - st.n_nonfinite) if st.n > st.n_nonfinite else float("nan")
+        psnr = st.psnr if mse > 0 and rng > 0 else float("inf")
+        nrmse = st.nrmse if rng > 0 else 0.0
+        return float(st.max_diff), float(psnr), float(nrmse)
     o = np.asarray(ori, dtype=np.float64).ravel()
     d = np.asarray(dec, dtype=np.float64).ravel()
     err = np.abs(d - o)

@@ -29,6 +29,7 @@
 #include <condition_variable>
 #include <memory>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -2587,25 +2588,23 @@ extern "C" size_t sz3hip_compress(const sz3hip_config *config, int dataType, con
 }
 
 namespace {
-// The caller's array of a device call: view from the Config's extents and the element strides (NULL: contiguous), then the device that
-// owns the memory. An output view whose elements overlap is refused (sufficient test: each extent's stride, in increasing order, passes
-// beyond everything the smaller strides reach).
-int dev_array(const sz3hip_config *c, const int64_t *strides, const void *ptr, bool output, DevArray *d) {
-    const int N = c->N;
-    d->N = N;
-    d->ptr = (char *)ptr;
-    szk_view &v = d->view;
+// The caller's array of a device call, in two checks that sz3hip_compress_from_device / sz3hip_decompress_to_device (extents from a Config)
+// and sz3hip_verify_device (the caller's own extents) share.
+// dev_view: the view of N extents and their element strides (NULL: contiguous). An output view whose elements overlap is refused
+// (sufficient test: each extent's stride, in increasing order, passes beyond everything the smaller strides reach).
+int dev_view(int N, const uint64_t *dims, const int64_t *strides, bool output, szk_view *view) {
+    szk_view &v = *view;
     v = szk_view{};
     for (int i = 0; i < 4; i++) v.dims[i] = 1;
     int64_t run = 1;
     v.contig = 1;
     for (int i = N - 1; i >= 0; i--) {
         const int k = 4 - N + i;
-        v.dims[k] = c->dims[i];
+        v.dims[k] = dims[i];
         v.str[k] = strides ? strides[i] : run;
         if (v.str[k] < 0) return fail(SZ3HIP_EINVAL, "stride %d is negative (%lld)", i, (long long)v.str[k]);
-        if (c->dims[i] > 1 && v.str[k] != run) v.contig = 0;
-        run *= (int64_t)c->dims[i];
+        if (dims[i] > 1 && v.str[k] != run) v.contig = 0;
+        run *= (int64_t)dims[i];
     }
     if (v.contig)
         for (int i = 4 - N; i < 4; i++) v.str[i] = i == 3 ? 1 : v.str[i];
@@ -2620,6 +2619,10 @@ int dev_array(const sz3hip_config *c, const int64_t *strides, const void *ptr, b
             reach += e.first * (int64_t)(e.second - 1);
         }
     }
+    return 0;
+}
+// dev_pointer: the device that owns the memory; anything but device memory is refused
+int dev_pointer(const void *ptr, int *device) {
     if (!ptr) return fail(SZ3HIP_EINVAL, "the device array is NULL");
     hipPointerAttribute_t a;
     memset(&a, 0, sizeof(a));
@@ -2629,8 +2632,15 @@ int dev_array(const sz3hip_config *c, const int64_t *strides, const void *ptr, b
         return fail(SZ3HIP_EINVAL, "the array is not device memory the HIP runtime knows (hipPointerGetAttributes: %s)", hipGetErrorString(e));
     }
     if (a.type != hipMemoryTypeDevice) return fail(SZ3HIP_EINVAL, "the array is not device memory (memory type %d)", (int)a.type);
-    d->device = a.device;
+    *device = a.device;
     return 0;
+}
+int dev_array(const sz3hip_config *c, const int64_t *strides, const void *ptr, bool output, DevArray *d) {
+    d->N = c->N;
+    d->ptr = (char *)ptr;
+    int rc = dev_view(c->N, c->dims, strides, output, &d->view);
+    if (rc) return rc;
+    return dev_pointer(ptr, &d->device);
 }
 }  // namespace
 
@@ -3195,6 +3205,95 @@ extern "C" int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, co
     if (conf->openmp) return decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &dev);
     SlotLease lease(dev.device, dtype_compute(dataType));
     return decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &dev, 0, conf->dims[0]);
+}
+
+// ---- sz3hip_verify_device: the error statistics of two device arrays (kernels: sz3hip_verify.hip) ---------------------------------
+namespace {
+// One workspace per device, made on its first call and kept for the process: the library's stream for these launches, the event it waits
+// for, the per-workgroup records, the result and its pinned host copy. Calls on one device serialise on its mutex (a call is two short
+// launches and a 152-byte copy); after the first, a call allocates nothing.
+struct VerifyWs {
+    std::mutex mu;
+    bool ready = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t caller = nullptr;
+    szk_verify_rec *d_partials = nullptr, *d_result = nullptr, *h_result = nullptr;
+};
+std::mutex g_verify_mu;
+std::map<int, std::unique_ptr<VerifyWs>> g_verify_ws;
+VerifyWs *verify_ws(int device) {
+    std::lock_guard<std::mutex> l(g_verify_mu);
+    auto &p = g_verify_ws[device];
+    if (!p) p.reset(new VerifyWs);
+    return p.get();
+}
+int verify_ws_init(VerifyWs *w) {  // (under w->mu, on the workspace's device)
+    if (w->ready) return 0;
+    if (!w->stream) HIPCHK(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
+    if (!w->caller) HIPCHK(hipEventCreateWithFlags(&w->caller, hipEventDisableTiming));
+    if (!w->d_partials) HIPCHK(hipMalloc((void **)&w->d_partials, sizeof(szk_verify_rec) * (SZK_VERIFY_RECORDS + 1)));
+    w->d_result = w->d_partials + SZK_VERIFY_RECORDS;
+    if (!w->h_result) HIPCHK(hipHostMalloc((void **)&w->h_result, sizeof(szk_verify_rec)));
+    w->ready = true;
+    return 0;
+}
+}  // namespace
+
+extern "C" int sz3hip_verify_device(int dataType, int N, const uint64_t *dims, const void *d_ori, const int64_t *strides_ori, const void *d_dec,
+                                    const int64_t *strides_dec, double bound, sz3hip_verify_stats *out, void *stream) {
+    if (!dtype_ok(dataType)) return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
+    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++)
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+    if (!out) return fail(SZ3HIP_EINVAL, "the result pointer (out) is NULL");
+    szk_view vo, vd;
+    int rc;
+    if ((rc = dev_view(N, dims, strides_ori, false, &vo)) || (rc = dev_view(N, dims, strides_dec, false, &vd))) return rc;
+    int dev_o = 0, dev_d = 0;
+    if ((rc = dev_pointer(d_ori, &dev_o)) || (rc = dev_pointer(d_dec, &dev_d))) return rc;
+    if (dev_o != dev_d) return fail(SZ3HIP_EINVAL, "the two arrays are device memory of different devices (%d and %d)", dev_o, dev_d);
+    const size_t es = dtype_size(dataType);
+    if ((uintptr_t)d_ori % es || (uintptr_t)d_dec % es) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", es);
+    uint64_t n = 1;
+    for (int i = 0; i < N; i++) n *= dims[i];
+
+    DeviceGuard guard;
+    HIPCHK(hipSetDevice(dev_o));
+    VerifyWs *w = verify_ws(dev_o);
+    std::lock_guard<std::mutex> lock(w->mu);
+    if ((rc = verify_ws_init(w))) return rc;
+    // the library's stream waits for what the caller's stream has queued (a producer's kernels) before the arrays are read
+    HIPCHK(hipEventRecord(w->caller, (hipStream_t)stream));
+    HIPCHK(hipStreamWaitEvent(w->stream, w->caller, 0));
+    if (szk_launch_verify(dataType, d_ori, &vo, d_dec, &vd, bound, w->d_partials, w->d_result, w->stream)) return fail(SZ3HIP_EHIP, "the verify kernels failed to launch");
+    HIPCHK(hipMemcpyAsync(w->h_result, w->d_result, sizeof(szk_verify_rec), hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(hipStreamSynchronize(w->stream));
+    const szk_verify_rec r = *w->h_result;
+
+    sz3hip_verify_stats st;
+    st.n = n;
+    st.n_nonfinite = r.n_nonfinite;
+    st.n_nonfinite_mismatch = r.n_mismatch;
+    st.n_over = r.n_over;
+    st.first_over = r.first_over;
+    st.argmax = r.argmax;
+    st.min = r.mn;
+    st.max = r.mx;
+    st.max_diff = r.max_diff;
+    st.max_pw_rel = r.max_pw_rel;
+    st.sum_ori = r.sa;
+    st.sum_dec = r.sb;
+    st.sum_sq_err = r.see;
+    st.sum_sq_dec = r.sbb;
+    // utils/Statistic.hpp:119-136 in plain IEEE double, over the finite positions; nothing special-cased (identical arrays: psnr = +inf)
+    const double m = (double)(n - r.n_nonfinite), mse = st.sum_sq_err / m, range = st.max - st.min;
+    st.psnr = 20 * log10(range) - 10 * log10(mse);
+    st.nrmse = sqrt(mse) / range;
+    st.l2_err = sqrt(st.sum_sq_err);
+    st.l2_err_norm = st.l2_err / sqrt(st.sum_sq_dec);
+    st.acEff = r.cab / sqrt(r.m2a * r.m2b);  // Pearson: (sum3 / n) / (std1 * std2)
+    *out = st;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -388,6 +388,19 @@ int szk_launch_int_to_f64(int sz_type /* SZ_UINT8 = 2 .. SZ_INT64 = 9 */, const 
 int szk_launch_f64_to_int(int sz_type, const double *d_in, uint64_t n, void *d_out, hipStream_t s);
 int szk_launch_hist_add(uint64_t *d_dst, const uint64_t *d_src, uint32_t n, hipStream_t s);  // dst[i] += src[i]
 int szk_launch_minmax(int dtype, const void *d_in, uint64_t n, double *d_partial /*[2*1024]*/, double *d_out /*[2]*/, hipStream_t s);
+// error statistics of two views with the same extents (sz3hip_verify.hip): k_verify leaves one record per workgroup in d_partials
+// (SZK_VERIFY_RECORDS of them), k_verify_final folds them into *d_result. bound < 0 or NaN: none given (n_over stays 0).
+// The record: counts, extremes of ori, (max_diff, argmax) and first_over with row-major indices over the view's extents (n where there is
+// none), the four plain sums, and the second moments as a mergeable (n_fin, mean, M2, C) set: m2a = sum (a - mean_a)^2, cab = sum (a - mean_a)(b - mean_b).
+#define SZK_VERIFY_RECORDS 2048
+struct szk_verify_rec {
+    uint64_t n_fin, n_nonfinite, n_mismatch, n_over, first_over, argmax;
+    double mn, mx, max_diff, max_pw_rel;
+    double sa, sb, see, sbb;
+    double mean_a, mean_b, m2a, m2b, cab;
+};
+int szk_launch_verify(int sz_type /* SZ_FLOAT = 0 .. SZ_INT64 = 9 */, const void *d_ori, const szk_view *view_ori, const void *d_dec, const szk_view *view_dec,
+                      double bound, szk_verify_rec *d_partials, szk_verify_rec *d_result, hipStream_t s);
 int szk_launch_k1(int dtype, int ndim, const void *d_in, uint16_t *codes, szk_k1_params *p, hipStream_t s);
 int szk_launch_codebook(const uint64_t *d_hist, const szk_cb_params *p, hipStream_t s);
 int szk_launch_encode(const uint16_t *codes, uint64_t n, const uint32_t *d_enc, const szk_cb_info *info, int radius,
