@@ -29,6 +29,7 @@
 #define SZ3HIP_H
 #include <stddef.h>
 #include <stdint.h>
+#include "sz3hip_debug.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -347,7 +348,7 @@ int sz3hip_last_call_q16(const sz3hip_ctx *ctx);
  * MI355X it measured slower ("Round 4: the single-pass encoder"): the default stays the two-pass form. */
 void sz3hip_ctx_set_fused(sz3hip_ctx *ctx, int on);
 /* 1: this library carries the superseded forms kept for reference — the fused stage 1 above and the decoder's multi-symbol table
- * (sz3hip_debug_flags(2)) — i.e. it is the lab build (python -m sz3_amd.build --lab: sz3_amd/libsz3hip_lab.so). The product build
+ * (sz3hip_debug_flags(SZ3HIP_DBG_DEC_MULTI_SYM)) — i.e. it is the lab build (python -m sz3_amd.build --lab: sz3_amd/libsz3hip_lab.so). The product build
  * (libsz3hip.so) leaves them out: 0, and both switches do nothing. */
 int sz3hip_lab_build(void);
 /* test hooks: copy internal device arrays to host (quantisation codes as uint16, histogram as uint64) */
@@ -357,26 +358,7 @@ int sz3hip_debug_copy_codes(sz3hip_ctx *ctx, uint16_t *host_codes, uint64_t n);
 int sz3hip_debug_decode_info(sz3hip_ctx *ctx, uint32_t *out4);
 /* test hook: non-zero routes every shape through the generic (any-shape) stage-1 kernel instead of the tuned one */
 void sz3hip_debug_force_generic(int on);
-/* development switches (bit mask, process-wide; 0 = product behaviour). They force one of two equivalent paths, results unchanged (tests compare them):
- * 1 the wide code book compacts the histogram inside its own workgroup (round 5's default: k_cb_compact over the whole chip in front of it),
- * 2 Lorenzo decoder with the multi-symbol lookup table for small code books (round 5: up to three code words per 12-bit window; same output,
- * measured slower than the one-symbol table in its first form: opt-in),
- * 4 the one-launch block decoders' retry through the launch-per-front decoders, taken as if a flag poll had given up,
- * 8 no 16-bit form of the one-byte stage-1 kernel (round 5), 32 no marching kernel, 64 no one-byte codes, 128 interpolation pass by pass, one point per thread (no 8-wide level-1
- * kernels, no level kernels), 256 no stage-1 specialisation by code width, 512 decoder without the fused x prefix sum,
- * 1024 code book without the two-class construction, 4096 stage 1 without the XCD-aware task order, 8192 interpolation
- * histogram with the large tier and the windowed tail passes, 16384 predictor sets with Lorenzo-2 / regression fall back
- * to plain Lorenzo (no block path), 131072 contexts do not remember the previous call's code width / code-book form,
- * 262144 round-parallel Huffman merge for small alphabets, 2097152 Lorenzo decoder without half-width intermediates,
- * 4194304 interpolation level kernels whatever the array's size (normally from 256 blocks up), 536870912 the level kernels hand the grid of
- * stride 2 over in place (round 5's default: as a dense array — no partial-line stores at the level of stride 2, no strided gather at the finest). The 3-D block decoder (blocks of
- * 6^3; the product path is ONE launch for the chain of fronts, k_blk_wave3, after a local pass straight from the codes): 16 the
- * local pass a wave per block from an expanded copy of the deltas, 32768 groups of 3 x 3 x 3 blocks in closed form with a launch
- * per front (also what a one-launch decoder whose flag poll gave up falls back to), 8388608 a block per wave (65536 — round 3's groups
- * of 2 x 2 x 2 blocks inverted by line scans — exists in -DSZ3HIP_LAB builds only since round 5; in the product library it takes the block-per-wave form). The 2-D one (block edges
- * up to 16, no second-order member; product: k_blkn_wave2, one launch): 65536 groups of 4 x 4 blocks with a launch per front,
- * 8388608 a block per wave.
- * Experiments with WRONG or slower results (tools/dec_lab.py): 524288 decoder without stores, 1048576 decoder with direct stores. */
+/* development switches (bit mask, process-wide; 0 = product behaviour): an OR of enum sz3hip_dbg, sz3hip_debug.h, which says what each bit gates */
 void sz3hip_debug_flags(int flags);
 
 /* ---- (4) multi-GPU exchange over RCCL / xGMI ------------------------------------------------------------------- */

@@ -9,7 +9,9 @@ device-resident entry points used by bench.py and the multi-GPU driver.
 There is no CPU implementation here: importing works anywhere, but every call needs the built library and a HIP
 device and raises otherwise.
 """
+import contextlib
 import ctypes as C
+import enum
 import os
 
 import numpy as np
@@ -24,6 +26,58 @@ ALGO_HIP_LORENZO = 16
 ALGO_HIP_INTERP = 17
 INTERP_ALGO_LINEAR, INTERP_ALGO_CUBIC = 0, 1
 SZ_FLOAT, SZ_DOUBLE = 0, 1
+
+
+class Dbg(enum.IntFlag):
+    """The development switches of sz3hip_debug_flags: enum sz3hip_dbg of include/sz3hip_debug.h without the SZ3HIP_DBG_ prefix, same
+    values (tests/test_debug_flags_cpu.py keeps the two equal). Members of equal value are one bit with several meanings: setting it
+    switches all of them. The header says what each one gates."""
+    CB_COMPACT_IN_WG = 1
+    K1_LAB_NO_HIST = 1
+    DEC_MULTI_SYM = 2
+    K1_NO_CODE_STORES = 2
+    BLKDEC_FORCE_RETRY = 4
+    K1_V4_NO_STENCIL = 4
+    K1_NO_Q16 = 8
+    BLKDEC_LOCAL_EXPANDED = 16
+    K1_V4_NO_PREFETCH = 16
+    PACK_LAB_NO_STORES = 16
+    K1_NO_MARCH = 32
+    K1_NO_NARROW = 64
+    INTERP_NO_VEC = 128
+    K1_NO_WIDTH_SPEC = 256
+    DEC_NO_FUSED_X = 512
+    PACK_LAB_ONE_UNIT = 512
+    CB_ONE_CLASS = 1024
+    K1_NO_FUSED = 2048
+    BLK_RANK_3_LAUNCHES = 2048
+    BLK_SIDE_8_LAUNCHES = 2048
+    K1_NO_XCD_ORDER = 4096
+    CB_NO_SPEC_WIDE = 4096
+    INTERP_HIST_BIG = 8192
+    BLK_OFF = 16384
+    PACK_OLD = 32768
+    BLKDEC_GROUPS_3 = 32768
+    CB_NO_SAMPLED = 65536
+    BLKDEC_PER_FRONT = 65536
+    CTX_NO_MEMORY = 131072
+    CB_SERIAL_MERGE = 262144
+    DEC_NO_STORES = 524288
+    DEC_DIRECT_STORES = 1048576
+    DEC_NO_HALF = 2097152
+    INTERP_LEVELS_ANY_SIZE = 4194304
+    K1_NO_SAMP_IN_LAUNCH = 4194304
+    BLKDEC_BLOCK_PER_WAVE = 8388608
+    K1_Q16_PLAIN_STORES = 8388608
+    K1_NO_DEFER_FOLD = 16777216
+    PACK_NO_SEG_BITS = 33554432
+    BLK_FIT_TILES = 67108864
+    BLK_1D_WAVE_PER_BLOCK = 134217728
+    CTX_NO_PUBLISH_ZERO = 268435456
+    INTERP_HANDOVER_IN_PLACE = 536870912
+    DEC_CARRY_PASS = 536870912
+    BLK_NO_EXIT = 1073741824
+    BLK_NO_SELECT = 2147483648
 
 
 class SZ3HipError(RuntimeError):
@@ -251,6 +305,18 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise SZ3HipError(rc, lib().sz3hip_last_error().decode())
+
+
+@contextlib.contextmanager
+def debug_flags(flags):
+    """``with sz3_amd.debug_flags(Dbg.X | Dbg.Y):`` sets the process-wide development switches (sz3hip_debug_flags) for the body and
+    sets them back to 0 on the way out, also when the body raises. Not for nesting: the inner block's exit leaves 0, not the outer flags."""
+    L = lib()
+    L.sz3hip_debug_flags(int(flags))
+    try:
+        yield
+    finally:
+        L.sz3hip_debug_flags(0)
 
 
 _SZ_TYPES = {"float32": 0, "float64": 1, "uint8": 2, "int8": 3, "uint16": 4, "int16": 5, "uint32": 6, "int32": 7, "uint64": 8, "int64": 9}

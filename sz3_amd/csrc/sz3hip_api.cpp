@@ -515,7 +515,7 @@ static void cb_params_from(sz3hip_ctx *ctx, szk_cb_params &cb, uint64_t out_cap,
     cb.info = ctx->bk[slot].info;
     cb.n_books = 1;
     cb.range_ready = ctx->range_ready && !ctx->hist_exposed && !ctx->hist_reduced;
-    cb.part_hint = (szk_dbg_flags & 131072) ? -1 : ctx->cb_part;
+    cb.part_hint = (szk_dbg_flags & SZ3HIP_DBG_CTX_NO_MEMORY) ? -1 : ctx->cb_part;
     cb.mispredict = reinterpret_cast<uint32_t *>(ctx->d_counters + 7);  // (zeroed with the counters)
 }
 
@@ -523,7 +523,7 @@ static void cb_params_from(sz3hip_ctx *ctx, szk_cb_params &cb, uint64_t out_cap,
 static void dense2_for(sz3hip_ctx *ctx, szk_interp_params &ip) {
     ip.dense2 = nullptr;
     ip.dense2_elems = 0;
-    if (ip.N != 3 || !szk_interp_levels_ok(&ip) || (szk_dbg_flags & 536870912)) return;
+    if (ip.N != 3 || !szk_interp_levels_ok(&ip) || (szk_dbg_flags & SZ3HIP_DBG_INTERP_HANDOVER_IN_PLACE)) return;
     const size_t need = (size_t)(((ip.dims[0] - 1) / 2 + 1) * ((ip.dims[1] - 1) / 2 + 1) * ((ip.dims[2] - 1) / 2 + 1));
     if (ctx->dense2_elems < need) {
         if (ctx->d_dense2) (void)hipFree(ctx->d_dense2);
@@ -547,8 +547,8 @@ static int stage1_interp(sz3hip_ctx *ctx, const sz3hip_config *conf, const void 
     ip.vout_val = ctx->d_vout_val;
     ip.out_cap = ctx->cur_out_cap;
     ip.hist_big = (uint32_t)ctx->hist_big;
-    ip.hist_tail = ctx->hist_tail > 0 || (szk_dbg_flags & 8192) ? 1u : 0u;
-    if (szk_dbg_flags & 8192) ip.hist_big = 1;  // (test hook: large tier + tail passes whatever the history)
+    ip.hist_tail = ctx->hist_tail > 0 || (szk_dbg_flags & SZ3HIP_DBG_INTERP_HIST_BIG) ? 1u : 0u;
+    if (szk_dbg_flags & SZ3HIP_DBG_INTERP_HIST_BIG) ip.hist_big = 1;  // (test hook: large tier + tail passes whatever the history)
     ip.far_cnt = reinterpret_cast<uint32_t *>(ctx->d_counters + 6);  // (zeroed with the counters, fetched with the probe words)
     if (!ctx->copy_ahead) dense2_for(ctx, ip);
     prof_begin(ctx, ST_K1, s);
@@ -587,7 +587,7 @@ static int stage1_interp(sz3hip_ctx *ctx, const sz3hip_config *conf, const void 
 static bool book_spec_ok(const sz3hip_ctx *ctx, uint32_t predictor, uint32_t radius) {
     // (spec_skip: calls left to sit out after a miss — a series whose books keep changing pays for one failed attempt in
     // 2, 4, 8 calls, not in every call; spec_off == 2 switches the back-off off for tests)
-    return ctx->book_idx >= 0 && ctx->spec_off != 1 && (ctx->spec_skip == 0 || ctx->spec_off == 2) && !(szk_dbg_flags & 131072) &&
+    return ctx->book_idx >= 0 && ctx->spec_off != 1 && (ctx->spec_skip == 0 || ctx->spec_off == 2) && !(szk_dbg_flags & SZ3HIP_DBG_CTX_NO_MEMORY) &&
            ctx->book_pred == predictor && ctx->book_radius == radius;
 }
 // ---- stage 1, integer Lorenzo on the prequantised lattice ----
@@ -628,7 +628,7 @@ static int lorenzo_k1(sz3hip_ctx *ctx, int N, const uint64_t *dims, const void *
     // function of the input alone, whatever this context coded before and whichever form of stage 1 it takes. Not for contexts whose
     // histogram is exchanged between the stages (multi-GPU: the ranks share one book made from the summed histogram).
     const bool samp = allow_narrow && radius >= 128 && N <= 3 && p.d[3] % 256 == 0 && num >= SZK_SAMP_MIN_ELEMS && !ctx->hist_exposed && !ctx->hist_reduced &&
-                      !(szk_dbg_flags & 65536);
+                      !(szk_dbg_flags & SZ3HIP_DBG_CB_NO_SAMPLED);
     if (samp) {
         const int fresh = ctx->book_idx < 0 ? 0 : 1 - ctx->book_idx;  // (stage2_launch's slot for this call's book)
         p.samp.words = reinterpret_cast<uint32_t *>(ctx->d_counters + 16);  // zeroed with the counters
@@ -644,7 +644,7 @@ static int lorenzo_k1(sz3hip_ctx *ctx, int N, const uint64_t *dims, const void *
         p.spec_lens = ctx->bk[ctx->book_idx].lens;
         p.seg_bits = ctx->d_seg_bits;
         p.seg_made = reinterpret_cast<uint32_t *>(ctx->d_counters + 10) + 1;  // zeroed with the counters
-        p.defer_fold = ctx->hist_exposed || ctx->hist_reduced || (szk_dbg_flags & 16777216) ? 0 : 1;  // (whoever exchanges the histogram wants it complete after stage 1)
+        p.defer_fold = ctx->hist_exposed || ctx->hist_reduced || (szk_dbg_flags & SZ3HIP_DBG_K1_NO_DEFER_FOLD) ? 0 : 1;  // (whoever exchanges the histogram wants it complete after stage 1)
         // Round 4: stage 1 may code with that book itself (the fused form, k_lorenzo_quant_march3f: the launcher takes it for the
         // one-launch form on rows of whole segments when the scratch — the code array's memory — holds a slot per task). A verdict
         // miss then costs the whole call once more: a context that wants its payloads bit-identical to a fresh context's
@@ -692,7 +692,7 @@ static int stage1_lorenzo(sz3hip_ctx *ctx, const sz3hip_config *conf, const void
     ctx->s1_assumed_narrow = p.assumed_narrow != 0;
     ctx->s1_q16 = p.assumed_q16 != 0;
     ctx->s1_spec = p.spec_lens != nullptr;
-    ctx->seg_expected = p.seg_expected != 0 && !(szk_dbg_flags & 33554432);
+    ctx->seg_expected = p.seg_expected != 0 && !(szk_dbg_flags & SZ3HIP_DBG_PACK_NO_SEG_BITS);
     ctx->fold_rows = p.defer_fold ? p.fold_rows : 0;
     ctx->fold_range = p.range;
     ctx->s1_fused = p.fused != 0;
@@ -801,7 +801,7 @@ static int blk_all_lorenzo(sz3hip_ctx *ctx, const sz3hip_config *conf, const voi
     *all = false;
     ctx->blk_sel_given = false;
     ctx->blk_spec = false;
-    if (szk_dbg_flags & 2147483648u) return 0;  // (development: no selection pass, the fit pass chooses by its own wave sums)
+    if (szk_dbg_flags & SZ3HIP_DBG_BLK_NO_SELECT) return 0;  // (development: no selection pass, the fit pass chooses by its own wave sums)
     // (1-D: the fit pass chooses — the estimate looks at a block's two ends only and a line through 128 values wins there on every
     // field with noise above the bound, as in the reference: a selection pass of its own found no field to hand over and cost a
     // launch and a synchronisation, 2^27 values 1.97 -> 2.22 ms, C1 0.235 -> 0.27 ms)
@@ -836,7 +836,7 @@ static int blk_all_lorenzo(sz3hip_ctx *ctx, const sz3hip_config *conf, const voi
     bool same = ctx->blk_dec_valid && k.N == conf->N && k.blockSize == conf->blockSize && k.absErrorBound == conf->absErrorBound && k.quantbinCnt == conf->quantbinCnt &&
                 k.lorenzo == conf->lorenzo && k.lorenzo2 == conf->lorenzo2 && k.regression == conf->regression;
     for (int i = 0; same && i < conf->N; i++) same = k.dims[i] == conf->dims[i];
-    if (same && ctx->spec_off != 1 && !ctx->hist_exposed && !ctx->hist_reduced && !(szk_dbg_flags & 1073741824)) {
+    if (same && ctx->spec_off != 1 && !ctx->hist_exposed && !ctx->hist_reduced && !(szk_dbg_flags & SZ3HIP_DBG_BLK_NO_EXIT)) {
         ctx->blk_spec = true;
         ctx->blk_spec_all = ctx->blk_dec_all;
         ctx->blk_spec_nblocks = nblocks;
@@ -849,8 +849,8 @@ static int blk_all_lorenzo(sz3hip_ctx *ctx, const sz3hip_config *conf, const voi
     uint64_t others;
     memcpy(&others, ctx->h_blk_side_hdr, 8);
     ctx->blk_others = others;
-    *all = (mask & 1u) && !(szk_dbg_flags & 1073741824) && (others << BLK_EXIT_SHIFT) < nblocks;
-    ctx->blk_dec_valid = !(szk_dbg_flags & 1073741824);
+    *all = (mask & 1u) && !(szk_dbg_flags & SZ3HIP_DBG_BLK_NO_EXIT) && (others << BLK_EXIT_SHIFT) < nblocks;
+    ctx->blk_dec_valid = !(szk_dbg_flags & SZ3HIP_DBG_BLK_NO_EXIT);
     ctx->blk_dec_all = *all;
     ctx->blk_dec_conf = *conf;
     return 0;
@@ -1569,7 +1569,7 @@ extern "C" int sz3hip_compress_stage1(sz3hip_ctx *ctx, const sz3hip_config *conf
         shape.N = conf->N;
         for (int i = 0; i < conf->N && i < 4; i++) shape.dims[i] = conf->dims[i];
         // (speculation, below: stage 1 itself runs beside the tuner; not for 1-D arrays, whose tuner shares the histogram with it)
-        bool spec = ctx->spec_valid && !(szk_dbg_flags & 131072) && conf->N >= 2 && ctx->spec_conf.N == conf->N;
+        bool spec = ctx->spec_valid && !(szk_dbg_flags & SZ3HIP_DBG_CTX_NO_MEMORY) && conf->N >= 2 && ctx->spec_conf.N == conf->N;
         for (int i = 0; spec && i < conf->N; i++) spec = ctx->spec_conf.dims[i] == conf->dims[i];
         const bool ahead = !szk_interp_levels_ok(&shape) && !spec;
         if (!ctx->d_work) HIPCHK(hipMalloc(&ctx->d_work, ctx->max_n * (ctx->dtype == SZ3HIP_FLOAT ? 4 : 8)));
@@ -1659,7 +1659,7 @@ extern "C" int sz3hip_compress_stage1(sz3hip_ctx *ctx, const sz3hip_config *conf
         const uint32_t mask = (conf->lorenzo ? 1u : 0u) | (conf->lorenzo2 ? 2u : 0u) | (conf->regression ? 4u : 0u);
         if (mask == 0) return fail(SZ3HIP_EINVAL, "All lorenzo and regression methods are disabled.");
         if (mask != 1u) {
-            if (blk_shape_ok(conf) && (conf->N != 4 || !(mask & 2u)) && !(szk_dbg_flags & 16384)) {  // (the reference has no second-order Lorenzo for N = 4: LorenzoPredictor.hpp:92)
+            if (blk_shape_ok(conf) && (conf->N != 4 || !(mask & 2u)) && !(szk_dbg_flags & SZ3HIP_DBG_BLK_OFF)) {  // (the reference has no second-order Lorenzo for N = 4: LorenzoPredictor.hpp:92)
                 bool all_lorenzo = false;
                 const int rcs = blk_all_lorenzo(ctx, conf, d_in, eb, radius, mask, s, &all_lorenzo);
                 if (rcs) return rcs;
@@ -1714,7 +1714,7 @@ extern "C" int sz3hip_compress_stage2(sz3hip_ctx *ctx, void *d_payload, size_t c
     // encoder: C3 1.253 against 1.247 ms without, 1.33 with alternating fields. Not taken.)
     // (Not for block streams: their side section is copied by the assembly's list workgroups, which the sort roles replace.)
     const bool spec_wide = !spec && book_spec_ok(ctx, ctx->proto.predictor, ctx->proto.radius) && ctx->cb_part == 1 && !ctx->lists_long &&
-                           ctx->proto.predictor != 2 && !(szk_dbg_flags & 4096);
+                           ctx->proto.predictor != 2 && !(szk_dbg_flags & SZ3HIP_DBG_CB_NO_SPEC_WIDE);
     if (ctx->s1_fused && !spec) {
         // (cannot happen: the fused stage 1 is taken under the conditions of this stage's one-stream form; should they ever drift apart,
         // there is no code array to encode from — stage 1 once more, in the two-pass form)
@@ -1875,7 +1875,7 @@ static int stage2_launch(sz3hip_ctx *ctx, void *d_payload, size_t cap, hipStream
     prof_end(ctx, ST_SPAN, s);
     // the state block to the host, and — when the call turns out to need no repeat — the next call's histogram and counters zeroed,
     // in one small launch behind the packer's (k_publish); finish() polls the sequence word
-    ctx->pub_zero = ctx->d_hist == ctx->d_hist_own && !ctx->hist_exposed && !(szk_dbg_flags & 268435456);
+    ctx->pub_zero = ctx->d_hist == ctx->d_hist_own && !ctx->hist_exposed && !(szk_dbg_flags & SZ3HIP_DBG_CTX_NO_PUBLISH_ZERO);
     ctx->pub_seq++;
     ctx->pub_blk_zero = ctx->pub_zero && ctx->d_blk_counters && ctx->d_blk_stats5;
     if (szk_launch_publish(ctx->d_state, ctx->h_state, ctx->h_pub_seq, ctx->pub_seq, ctx->pub_zero ? (void *)ctx->d_hist : nullptr,
@@ -2004,7 +2004,7 @@ extern "C" int sz3hip_compress_finish(sz3hip_ctx *ctx, size_t *payload_size, voi
         ctx->pre_stream = ctx->pub_stream;
         ctx->blk_pre_cleared = ctx->pub_blk_zero;
         ctx->blk_pre_stream = ctx->pub_stream;
-    } else if (ctx->d_hist == ctx->d_hist_own && !ctx->hist_exposed && !(szk_dbg_flags & 268435456)) {
+    } else if (ctx->d_hist == ctx->d_hist_own && !ctx->hist_exposed && !(szk_dbg_flags & SZ3HIP_DBG_CTX_NO_PUBLISH_ZERO)) {
         if (hipMemsetAsync(ctx->d_hist, 0, SZH_HIST_BINS * 8 + SZ_COUNTER_BYTES, s) == hipSuccess) {
             ctx->pre_cleared = true;
             ctx->pre_stream = s;
@@ -2244,7 +2244,7 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
 extern "C" int sz3hip_last_call_fused(const sz3hip_ctx *ctx) { return ctx->last_fused ? 1 : 0; }
 extern "C" int sz3hip_last_call_q16(const sz3hip_ctx *ctx) { return ctx->last_q16 ? 1 : 0; }
 // 1: the library was built with the superseded forms (python -m sz3_amd.build --lab): the fused stage 1 (sz3hip_ctx_set_fused) and the
-// decoder's multi-symbol table (sz3hip_debug_flags(2)); the product build leaves them out and both switches do nothing
+// decoder's multi-symbol table (SZ3HIP_DBG_DEC_MULTI_SYM); the product build leaves them out and both switches do nothing
 extern "C" int sz3hip_lab_build(void) {
 #ifdef SZ3HIP_LAB
     return 1;
@@ -2259,8 +2259,8 @@ extern "C" void sz3hip_get_spec_stats(const sz3hip_ctx *ctx, uint32_t *hits, uin
 }
 extern "C" void sz3hip_debug_flags(int flags) {
     szk_dbg_flags = flags;
-    szk_interp_novec = (flags & 128) != 0;  // 128: interpolation without the 8-wide level-1 kernels and without the level kernels
-    szk_interp_min_blocks = (flags & 4194304) ? 1 : 256;  // 4194304: level kernels whatever the array's size
+    szk_interp_novec = (flags & SZ3HIP_DBG_INTERP_NO_VEC) != 0;  // interpolation without the 8-wide level-1 kernels and without the level kernels
+    szk_interp_min_blocks = (flags & SZ3HIP_DBG_INTERP_LEVELS_ANY_SIZE) ? 1 : 256;  // level kernels whatever the array's size
 }
 extern "C" int sz3hip_debug_codebook_info(sz3hip_ctx *ctx, uint64_t *out16) {
     HIPCHK(hipSetDevice(ctx->device));
@@ -2387,7 +2387,7 @@ extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, 
     }
     prof_begin(ctx, ST_DEC_HUFF, s);
     // (a Lorenzo stream's small book — code words up to 16 bits, at most 1024 symbols: the tables' launch also makes the multi-symbol table)
-    const bool ms_book = h.predictor == 0 && h.qbytes == 4 && h.max_len >= 1 && h.max_len <= 16 && h.sym_count <= 1024 && (szk_dbg_flags & 2) && sz3hip_lab_build();
+    const bool ms_book = h.predictor == 0 && h.qbytes == 4 && h.max_len >= 1 && h.max_len <= 16 && h.sym_count <= 1024 && (szk_dbg_flags & SZ3HIP_DBG_DEC_MULTI_SYM) && sz3hip_lab_build();
     // (a Lorenzo stream's header names the symbol that stands for a listed delta in its anchor_stride field: 0 = symbol 0 itself)
     const uint32_t esc_sym = h.predictor == 0 ? (uint32_t)h.anchor_stride : 0u;
     if (h.predictor == 0 && h.anchor_stride && (h.anchor_stride < h.sym_min || h.anchor_stride >= (uint64_t)h.sym_min + h.sym_count))
@@ -2407,11 +2407,11 @@ extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, 
     dp.single_sym = h.sym_min;
     // Lorenzo stream, rows of at most one chunk, a sorted delta-outlier list: the decoder also does the x prefix sum
     const uint64_t row = h.dims[3];
-    const bool fuse_x = h.predictor == 0 && h.n_dout <= 32768 && row >= 1 && row <= SZH_CHUNK_SYMS && !(szk_dbg_flags & 512);  // (lists that long are sorted)
+    const bool fuse_x = h.predictor == 0 && h.n_dout <= 32768 && row >= 1 && row <= SZH_CHUNK_SYMS && !(szk_dbg_flags & SZ3HIP_DBG_DEC_NO_FUSED_X);  // (lists that long are sorted)
     dp.scan_row = fuse_x ? (uint32_t)row : 0u;
     dp.radius = h.radius;
     dp.q_bytes = h.qbytes;
-    dp.reserved = ((szk_dbg_flags & 524288) ? 1u : 0u) | ((szk_dbg_flags & 1048576) ? 2u : 0u);  // (experiments: no stores / direct stores)
+    dp.reserved = ((szk_dbg_flags & SZ3HIP_DBG_DEC_NO_STORES) ? SZK_DEC_DBG_NO_STORES : 0u) | ((szk_dbg_flags & SZ3HIP_DBG_DEC_DIRECT_STORES) ? SZK_DEC_DBG_DIRECT_STORES : 0u);  // (experiments: no stores / direct stores)
     dp.q_out = d_out;
     dp.dout_idx = reinterpret_cast<const uint64_t *>(pl + o.dout_idx);
     dp.dout_val = pl + o.dout_val;
@@ -2426,7 +2426,7 @@ extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, 
     if (fuse_x && (SZH_UNIT_SYMS % row) != 0) {
         if (!ctx->d_carry) HIPCHK(hipMalloc(&ctx->d_carry, (ctx->max_chunks * SZH_SUBS + 8) * 8));
         dp.carry = ctx->d_carry;
-        if (row % SZH_UNIT_SYMS == 0 && h.n > row && !(szk_dbg_flags & 536870912)) carry_in_scan = ctx->d_carry;
+        if (row % SZH_UNIT_SYMS == 0 && h.n > row && !(szk_dbg_flags & SZ3HIP_DBG_DEC_CARRY_PASS)) carry_in_scan = ctx->d_carry;
         else dp.carry_pass = 1;
     }
     dp.half = 0;
@@ -2437,7 +2437,7 @@ extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, 
     // follow then move half the bytes (the code array, idle in the fused mode, holds them). The decoder and the scans raise a
     // flag on a value that does not fit; the full-width chain is enqueued right behind with that flag as its gate (its kernels
     // return at once while it is clear), so the call stays asynchronous and correct either way.
-    const bool half = fuse_x && szk_half_scans_ok(&h) && ctx->half_skip == 0 && !(szk_dbg_flags & 2097152);
+    const bool half = fuse_x && szk_half_scans_ok(&h) && ctx->half_skip == 0 && !(szk_dbg_flags & SZ3HIP_DBG_DEC_NO_HALF);
     ctx->last_half = half ? 1u : 0u;
     ctx->last_carry = dp.carry ? (dp.carry_pass ? 1u : 2u) : 0u;
     void *d_half = ctx->d_codes;  // f32 data: int16 values in the code array (2 bytes per element, idle in the fused mode)

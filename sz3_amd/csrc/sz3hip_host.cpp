@@ -249,7 +249,8 @@ static void parallel_copy(uint8_t *dst, const uint8_t *src, size_t n) {  // (lar
 // every part of its copy how many bytes have landed; a frame's task is handed to the pool when its input is complete (the payload's
 // trip from the device overlaps its compression). It returns non-zero on failure.
 typedef std::function<int(const std::function<void(size_t)> &)> Feeder;
-// SZ3HIP_TIMING: the frame tasks' time in the queue and at work, summed over the process (printed by the pipelined call)
+// SZ3HIP_TIMING (read once, when the library is loaded): the host API's wall-clock breakdowns on stderr (HostTimer, the pipelined calls);
+// here the frame tasks' time in the queue and at work, summed over the process (printed by the pipelined call)
 static const bool lab_timing = getenv("SZ3HIP_TIMING") != nullptr;
 static std::atomic<uint64_t> lab_queue_us{0}, lab_run_us{0}, lab_tasks{0};
 struct Arena {  // the frames' private buffers, kept by whoever calls again and again (a host slot): no mapping, no first touch per call
@@ -648,7 +649,7 @@ struct DeviceGuard {
 struct HostTimer {
     bool on;
     std::chrono::steady_clock::time_point t0;
-    HostTimer() : on(getenv("SZ3HIP_TIMING") != nullptr), t0(std::chrono::steady_clock::now()) {}
+    HostTimer() : on(zs::lab_timing), t0(std::chrono::steady_clock::now()) {}
     void lap(const char *what) {
         if (!on) return;
         auto t1 = std::chrono::steady_clock::now();
@@ -3065,7 +3066,7 @@ int decompress_slabs(const sz3hip_config *conf, int dataType, const unsigned cha
         // back through the staging ring (d2h_staged above), each as soon as its piece has handed it over
         std::mutex mu;
         std::condition_variable cv;
-        const bool timing = getenv("SZ3HIP_TIMING") != nullptr;
+        const bool timing = zs::lab_timing;
         const auto t_call = std::chrono::steady_clock::now();
         std::vector<double> stamps((size_t)G * 5, 0.0);
         std::vector<D2hGate> gates(G);

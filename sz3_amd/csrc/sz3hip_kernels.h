@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sz3hip_format.h"
+#include "../../include/sz3hip_debug.h"
 
 // lattice constants derived from the absolute error bound (identical on the encode and the decode side)
 struct szk_lattice {
@@ -63,7 +64,7 @@ struct szk_k1_params {
     uint64_t d[4];  // extents slowest first, left-padded with 1: [w][z][y][x]
     szk_lattice lat;
     uint32_t radius;
-    uint32_t dbg;      // ablation switches for tools/k1_lab.py (0 in production)
+    uint32_t dbg;      // the debug flags in force (enum sz3hip_dbg; 0 in production): szk_launch_k1 copies the whole word, the kernels test its K1 switches
     szk_mode mode;
     uint64_t out_cap;  // capacity of each outlier list
     uint64_t *hist;    // [SZH_HIST_BINS]
@@ -123,6 +124,9 @@ struct szk_cb_info {
     uint64_t ts[12];  // phase timestamps (wall_clock64, 100 MHz) for tools/cb_lab.py
     uint32_t first_code[SZH_MAX_LEN + 2];  // (round 5) first code word of every length: what k_cb_assign needs of the book's workgroup (reserved == 0x5A5A while the code words are its to make)
 };
+// szk_cb_params::dbg, the code book's private copy of two debug flags
+#define SZK_CB_DBG_ONE_CLASS 1u     // SZ3HIP_DBG_CB_ONE_CLASS: codebook_wide takes the one-class construction
+#define SZK_CB_DBG_SERIAL_MERGE 2u  // SZ3HIP_DBG_CB_SERIAL_MERGE: cb_small merges by one wave, pick by pick
 struct szk_cb_params {
     uint32_t *enc;   // [65536] (code << 5) | len
     uint8_t *lens;   // [65536]
@@ -139,7 +143,7 @@ struct szk_cb_params {
     int t_is_32bit, q_is_32bit;
     szk_cb_info *info;
     uint32_t n_books;  // 0/1: one code book (+ the outlier sorts); 2..SZK_MAX_BOOKS: a batch, tables sliced per book
-    uint32_t dbg;      // development switches, filled by the launcher from the debug flags (1: force the one-class fallback)
+    uint32_t dbg;      // SZK_CB_DBG_*: filled by szk_launch_codebook from the debug flags
     int range_ready;   // the range words are already filled (stage 1 kept them with the histogram): no k_hist_range launch
     int part_hint;     // -1: both forms of k_codebook are launched; 0 / 1: only that form (small / wide alphabets), see mispredict
     uint32_t *mispredict;  // set to 1 by a form launched alone that meets the other form's alphabet
@@ -221,6 +225,10 @@ struct szk_encode_roles {
     uint64_t *fold_hist;
     uint32_t *fold_range;
 };
+// k_pack_b's last argument (szk_launch_encode: `beside`)
+#define SZK_PACKB_ONLY_SAMPLED 1u    // launched beside k_pack: it works only when the call codes with its sampled book
+#define SZK_PACKB_LAB_NO_STORES 8u   // SZ3HIP_DBG_PACK_LAB_NO_STORES (lab build)
+#define SZK_PACKB_LAB_ONE_UNIT 16u   // SZ3HIP_DBG_PACK_LAB_ONE_UNIT (lab build)
 
 #define DEC_LUT_BITS 12u
 struct szk_dec_tables {
@@ -234,6 +242,9 @@ struct szk_dec_tables {
     // complement; with fewer than three code words the later sums repeat the last one: the running sum is always "+ s2 + d3")
     uint32_t mlut[1u << DEC_LUT_BITS];
 };
+// szk_dec_params::reserved, the decoder's private copy of two debug flags (experiments of tools/dec_lab.py, WRONG results)
+#define SZK_DEC_DBG_NO_STORES 1u      // SZ3HIP_DBG_DEC_NO_STORES
+#define SZK_DEC_DBG_DIRECT_STORES 2u  // SZ3HIP_DBG_DEC_DIRECT_STORES
 struct szk_dec_params {
     uint64_t n, n_chunks;
     uint64_t bitstream_off, total_words;  // the bit-stream section of the payload and its length in 32-bit words
@@ -247,7 +258,7 @@ struct szk_dec_params {
     // that starts in an earlier unit misses those units' running sums: every unit leaves its own in carry[] and k_scan_carry
     // (or the first strided scan, rows that are multiples of the unit) adds them afterwards (not needed when the row length
     // divides the unit).
-    uint32_t scan_row, radius, q_bytes, reserved;  // q_bytes: 4 = int32 lattice (f32 data), 8 = int64 (f64 data)
+    uint32_t scan_row, radius, q_bytes, reserved;  // q_bytes: 4 = int32 lattice (f32 data), 8 = int64 (f64 data); reserved: SZK_DEC_DBG_*
     void *q_out;  // lattice deltas summed along x: int32 (f32 data) / int64 (f64 data), n elements
     void *carry;  // [units] running sum at the end of every unit (same type), nullptr when rows start on unit boundaries
     uint32_t carry_pass;  // 1: k_scan_carry adds them behind the decoder; 0: the first strided scan does (szk_launch_reconstruct*)

@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256, (NDIM == 3 ? 3 : 2)) void k_lorenzo_quant_v4(c
         int x0, y0, z0;
         uint32_t w;
         decode(tile, x0, y0, z0, w);
-        if ((p.dbg & 16) && tile != blockIdx.x) fetch(tile, R);
+        if ((p.dbg & SZ3HIP_DBG_K1_V4_NO_PREFETCH) && tile != blockIdx.x) fetch(tile, R);
         __syncthreads();  // previous tile's stencil reads are done before the slab is overwritten
 
         // ---- prequantise the fetched registers into the LDS slab ----
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256, (NDIM == 3 ? 3 : 2)) void k_lorenzo_quant_v4(c
             }
         }
         // ---- next tile's loads go out now and stay in flight across the barrier and the stencil ----
-        if (!(p.dbg & 16) && tile + gridDim.x < ntiles) fetch(tile + gridDim.x, R);
+        if (!(p.dbg & SZ3HIP_DBG_K1_V4_NO_PREFETCH) && tile + gridDim.x < ntiles) fetch(tile + gridDim.x, R);
         __syncthreads();
 
         uint16_t *ctile = codes + (uint64_t)w * vol + ((uint64_t)z0 * plane + (uint64_t)y0 * d0 + x0);
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(256, (NDIM == 3 ? 3 : 2)) void k_lorenzo_quant_v4(c
                 } else {
                     lds_ld4(L + c, cur);
                 }
-                if (p.dbg & 4) {
+                if (p.dbg & SZ3HIP_DBG_K1_V4_NO_STENCIL) {
 #pragma unroll
                     for (int i = 0; i < 4; i++) ra[i] = rb[i] = rd[i] = cur[i];
                 } else {
@@ -499,8 +499,8 @@ __global__ __launch_bounds__(256, (NDIM == 3 ? 3 : 2)) void k_lorenzo_quant_v4(c
                 const bool ctr = code[i] == (uint32_t)radius;
                 center_count += ctr;
                 slow |= !inr | !inwin;
-#ifdef LAB_ABLATE  // (lab builds: bit 1 of the debug flags switches the histogram off; in the product library the bit belongs to the code book)
-                if (!(p.dbg & 1))
+#ifdef LAB_ABLATE  // (lab builds: SZ3HIP_DBG_K1_LAB_NO_HIST switches the histogram off; in the product library the bit is the code book's alone)
+                if (!(p.dbg & SZ3HIP_DBG_K1_LAB_NO_HIST))
 #endif
                 atomicAdd(&myh[(ctr | !inwin) ? dummy_bin : bin], 1u);
             }
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(256, (NDIM == 3 ? 3 : 2)) void k_lorenzo_quant_v4(c
             uint2 pk;
             pk.x = code[0] | (code[1] << 16);
             pk.y = code[2] | (code[3] << 16);
-            if (!(p.dbg & 2)) *reinterpret_cast<uint2 *>(ctile + off) = pk;
+            if (!(p.dbg & SZ3HIP_DBG_K1_NO_CODE_STORES)) *reinterpret_cast<uint2 *>(ctile + off) = pk;
             if (slow) {  // rare: delta outliers, value outliers, codes outside the LDS histogram window
                 const uint64_t gi = (uint64_t)w * vol + (uint64_t)gz * plane + (uint64_t)gy * d0 + gx;
 #pragma unroll
@@ -740,7 +740,7 @@ __device__ __forceinline__ void march_body(const T *__restrict__ in, uint16_t *_
     // the shared lines from HBM
     // (grids that are not a multiple of 8 keep the plain order: the remapped sequence would have holes)
     const uint32_t per_xcd = gridDim.x / 8u;
-    const uint32_t wg_seq = gridDim.x % 8u == 0 && !(p.dbg & 4096u) ? (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u : blockIdx.x;
+    const uint32_t wg_seq = gridDim.x % 8u == 0 && !(p.dbg & SZ3HIP_DBG_K1_NO_XCD_ORDER) ? (blockIdx.x % 8u) * per_xcd + blockIdx.x / 8u : blockIdx.x;
     const uint32_t wave_gid = wg_seq * 4 + threadIdx.x / WAVE, nwaves = gridDim.x * 4u;
     for (uint32_t task = wave_gid; task < ntasks; task += nwaves) {
         uint32_t b = task;
@@ -1313,7 +1313,7 @@ __device__ __forceinline__ void narrow_task(NarrowCtx<T> &c, const Lattice<T> &l
             if (EDGE) rare &= xok;
             if (!EDGE || xok) {
 #ifdef LAB_ABLATE
-                if (!(c.p->dbg & 1u))
+                if (!(c.p->dbg & SZ3HIP_DBG_K1_LAB_NO_HIST))
 #endif
                 if (!SAMP)  // (a sampled book needs no histogram)
 #pragma unroll
@@ -1334,7 +1334,7 @@ __device__ __forceinline__ void narrow_task(NarrowCtx<T> &c, const Lattice<T> &l
                     // book_rejected walks this call's complete histogram — finds it missing from the book and voids the call)
                 } else {
 #ifdef LAB_ABLATE
-                if (!(c.p->dbg & 2u))
+                if (!(c.p->dbg & SZ3HIP_DBG_K1_NO_CODE_STORES))
 #endif
                 // (streaming store: the codes are next read by another launch; what stays dirty in the L2s is written back at the kernel's end)
 #ifdef LAB_PLAIN_STORE
@@ -1604,7 +1604,7 @@ __device__ __forceinline__ void march_narrow(const T *__restrict__ in, uint16_t 
     const uint32_t ntx = (c.d0 + MARCH_TX - 1) / MARCH_TX, nty = (c.d1 + TY - 1) / TY, ntz = (c.d2 + MARCH_TZ - 1) / MARCH_TZ;
     // XCD-aware task order (see march_body)
     const uint32_t per_xcd = grid / 8u;
-    const uint32_t wg_seq = grid % 8u == 0 && !(p.dbg & 4096u) ? (bid % 8u) * per_xcd + bid / 8u : bid;
+    const uint32_t wg_seq = grid % 8u == 0 && !(p.dbg & SZ3HIP_DBG_K1_NO_XCD_ORDER) ? (bid % 8u) * per_xcd + bid / 8u : bid;
     const uint32_t nwaves = grid * 4u;
     for (uint32_t task = wg_seq * 4 + wv; task < ntasks; task += nwaves) {
         uint32_t b = task;
@@ -1803,7 +1803,7 @@ __device__ __forceinline__ void narrow16_task(NarrowCtx<float> &c, const Lattice
 #elif defined(LAB_ST) && LAB_ST == 3
                 __hip_atomic_store(reinterpret_cast<uint32_t *>(c.codes8 + grow + x), tA | (tB << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #else
-                if (c.p->dbg & 8388608u) *reinterpret_cast<uint32_t *>(c.codes8 + grow + x) = tA | (tB << 8);  // (lab: plain stores — the codes stay in the caches for the packer)
+                if (c.p->dbg & SZ3HIP_DBG_K1_Q16_PLAIN_STORES) *reinterpret_cast<uint32_t *>(c.codes8 + grow + x) = tA | (tB << 8);  // (lab: plain stores — the codes stay in the caches for the packer)
                 else __builtin_nontemporal_store(tA | (tB << 8), reinterpret_cast<uint32_t *>(c.codes8 + grow + x));
 #endif
             }
@@ -1978,7 +1978,7 @@ __device__ __forceinline__ void march_narrow16(const float *__restrict__ in, uin
     __syncthreads();
     const uint32_t ntx = (c.d0 + MARCH_TX - 1) / MARCH_TX, nty = (c.d1 + TY - 1) / TY;
     const uint32_t per_xcd = grid / 8u;
-    const uint32_t wg_seq = grid % 8u == 0 && !(p.dbg & 4096u) ? (bid % 8u) * per_xcd + bid / 8u : bid;
+    const uint32_t wg_seq = grid % 8u == 0 && !(p.dbg & SZ3HIP_DBG_K1_NO_XCD_ORDER) ? (bid % 8u) * per_xcd + bid / 8u : bid;
     const uint32_t nwaves = grid * 4u;
     for (uint32_t task = wg_seq * 4 + wv; task < ntasks; task += nwaves) {
         uint32_t b = task;
@@ -2950,7 +2950,7 @@ __device__ void codebook_wide(const uint64_t *__restrict__ hist, const szk_cb_pa
     __syncthreads();
     if (cls) {  // every rare symbol: the class's code word + a fixed-length index
         const uint32_t len_cls = p.lens[pseudo_sym], len_rare = len_cls + rare_bits;
-        if (len_rare > L || (p.dbg & 1u)) {  // (the weight floor above makes this all but impossible) one-class construction instead
+        if (len_rare > L || (p.dbg & SZK_CB_DBG_ONE_CLASS)) {  // (the weight floor above makes this all but impossible) one-class construction instead
             __syncthreads();
             if (t < SZH_MAX_LEN + 2) s_cnt[t] = 0;
             for (uint32_t q = t; q < range; q += NT) p.lens[lo + q] = 0;
@@ -3126,7 +3126,7 @@ __device__ void cb_small(const uint64_t *__restrict__ hist, const szk_cb_params 
         // single symbol: zero-length code, empty bit-stream (as encoder/HuffmanEncoder.hpp:233-237)
     } else {
         // 3. merge: one wave out of registers (32-bit counts), or thread 0 (64-bit counts)
-        if (s_total < 0xFFFFFFFFull && !(p.dbg & 2u)) {  // (the rounds by one wave; debug flag 262144: the serial wave merge — C2-like 145 symbols 33 us, C1's 398 87 us)
+        if (s_total < 0xFFFFFFFFull && !(p.dbg & SZK_CB_DBG_SERIAL_MERGE)) {  // (the rounds by one wave; SZ3HIP_DBG_CB_SERIAL_MERGE: the serial wave merge — C2-like 145 symbols 33 us, C1's 398 87 us)
             // round-parallel merge on the 256 live threads (every round pairs ALL pending items below the smallest possible
             // new node, cb_merge_rounds): ~a dozen rounds for a smooth field's 128 symbols instead of 127 dependent picks of
             // one wave (28 us of the kernel's 38 at C2)
@@ -4691,7 +4691,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     __shared__ __align__(8) uint64_t s_stage[PB_WAVES][STAGE_WORDS / 2];
     // (launched beside k_pack behind the two-launch form of stage 1 — only_sampled: this kernel then packs, sorts and assembles only
     // when the call codes with its sampled book, k_pack otherwise)
-    if ((only_sampled & 1u) && !(ap.samp_words && ap.samp_words[SZK_SAMP_READY] && szk_is_narrow(mode))) return;
+    if ((only_sampled & SZK_PACKB_ONLY_SAMPLED) && !(ap.samp_words && ap.samp_words[SZK_SAMP_READY] && szk_is_narrow(mode))) return;
     const uint32_t roles = rp.on ? ROLE_BLOCKS : 0u;
     if (blockIdx.x < roles) {  // (the pair table's memory serves as their scratch; they are 256-thread bodies: the other waves leave)
         if (threadIdx.x >= 256u) return;
@@ -4729,8 +4729,8 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     // once per chunk in k_pack's loop (whose wave then idles through the store acknowledgement of its previous chunk).
     constexpr uint32_t PB_BATCH = 4;
     const uint64_t n_units = (n_full + PB_BATCH - 1) / PB_BATCH;
-#ifdef SZ3HIP_LAB  // (lab build: what the launch's time is made of — only_sampled bits 8: no stores of the stream, 16: every unit reads the first unit's codes)
-    const bool lab_nost = (only_sampled & 8u) != 0, lab_nold = (only_sampled & 16u) != 0;
+#ifdef SZ3HIP_LAB  // (lab build: what the launch's time is made of — only_sampled bits SZK_PACKB_LAB_NO_STORES: no stores of the stream, SZK_PACKB_LAB_ONE_UNIT: every unit reads the first unit's codes)
+    const bool lab_nost = (only_sampled & SZK_PACKB_LAB_NO_STORES) != 0, lab_nold = (only_sampled & SZK_PACKB_LAB_ONE_UNIT) != 0;
 #else
     constexpr bool lab_nost = false, lab_nold = false;
 #endif
@@ -5157,7 +5157,7 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t *__restrict__ payl
     uint16_t *out = codes + s0;
     QO *qout = QB ? reinterpret_cast<QO *>(p.q_out) + s0 : nullptr;
     // (wave-uniform: all 64 lanes decode full units — everywhere but in the array's last wave)
-    const bool coop = !(p.reserved & 2u) && __ballot(nsym == UNIT) == ~0ull;
+    const bool coop = !(p.reserved & SZK_DEC_DBG_DIRECT_STORES) && __ballot(nsym == UNIT) == ~0ull;
     uint4 *stage = s_out[threadIdx.x / WAVE];
     uint8_t *wave_out = QB ? reinterpret_cast<uint8_t *>(p.q_out) + (s0 - (uint64_t)lane_id() * UNIT) * ELT
                            : reinterpret_cast<uint8_t *>(codes + (s0 - (uint64_t)lane_id() * UNIT));
@@ -5500,7 +5500,7 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t *__restrict__ payl
                     }
                 }
             }
-            if (p.reserved & 1u) {  // (experiment: no output traffic; the sum keeps the work alive)
+            if (p.reserved & SZK_DEC_DBG_NO_STORES) {  // (experiment: no output traffic; the sum keeps the work alive)
                 QO sx = 0;
 #pragma unroll
                 for (int k = 0; k < 16; k++) sx += qv[k];
@@ -6233,7 +6233,7 @@ int szk_launch_minmax(int dtype, const void *d_in, uint64_t n, double *d_partial
 }
 
 int szk_force_generic = 0;  // test hook: route every shape through the generic kernel
-int szk_dbg_flags = 0;     // ablation switches (tools/k1_lab.py)
+int szk_dbg_flags = 0;     // sz3hip_debug_flags(): an OR of enum sz3hip_dbg
 
 // persistent grid = resident workgroups of the kernel on this device (occupancy API x CU count), capped by the
 // number of hist_partial rows and by the tile count
@@ -6271,15 +6271,21 @@ static uint32_t k1_grid(const void *kernel, uint64_t ntiles) {
     return (uint32_t)gb;
 }
 
-// the marching kernel + histogram fold. When one-byte codes are possible both specialisations are launched with the same
-// grid (= rows of the fold); the one the probe did not choose returns at once.
+// the tasks of the marching forms: MARCH_TX x ty x MARCH_TZ elements each (ty = 1 for 1-D arrays, else LAB_MTY)
+static uint64_t march_tasks(const uint64_t d[4], uint64_t ty) {
+    return ((d[3] + MARCH_TX - 1) / MARCH_TX) * ((d[2] + ty - 1) / ty) * ((d[1] + MARCH_TZ - 1) / MARCH_TZ) * d[0];
+}
+// the marching kernel + histogram fold, in the form launch_k1 decided on (one_launch). When one-byte codes are possible and the form
+// is not the one-launch one, both specialisations are launched with the same grid (= rows of the fold); the one the probe did not
+// choose returns at once.
 template <typename T, int NDIM, int TY, bool WIN16>
-static void launch_march_w(const void *d_in, uint16_t *codes, szk_k1_params &p, uint64_t nb, hipStream_t s) {
+static void launch_march_w(const void *d_in, uint16_t *codes, szk_k1_params &p, uint64_t nb, bool one_launch, hipStream_t s) {
     uint32_t grid = 0;
     p.seg_expected = 0;
     p.assumed_q16 = 0;
+    const bool by_width = p.mode.allow && !(szk_dbg_flags & SZ3HIP_DBG_K1_NO_WIDTH_SPEC);  // (the kernels are specialised by code width)
     if (p.prof_ev0) (void)hipEventRecord((hipEvent_t)p.prof_ev0, s);
-    if (p.mode.allow && !(szk_dbg_flags & 256) && p.hint_narrow > 0 && !(szk_dbg_flags & 131072)) {
+    if (one_launch) {
         // the context's previous call took one-byte codes: one launch of the form built around them (it decides the width from
         // THIS call's probe and handles either). After a two-byte call the two specialisations below are launched as on a first
         // call: the run-time-width form is a third slower on two-byte codes (574 vs 363 us at C4's slab) than the specialised one
@@ -6288,7 +6294,7 @@ static void launch_march_w(const void *d_in, uint16_t *codes, szk_k1_params &p, 
         // the fused form: NDIM 3 bodies (1-D ... 3-D arrays), rows cut into whole segments, and a scratch that holds a slot per task
         const uint32_t slot_words = fuse_slot_words(TY, p.d[2], p.d[1]);
         const bool fuse = NDIM == 3 && p.fuse && p.seg_expected && p.fuse_enc && p.fuse_info && p.fuse_slots && p.seg_base && p.fuse_flag &&
-                          nb * (uint64_t)slot_words + 2 <= p.fuse_cap_words && nb * (uint64_t)slot_words < (1ull << 32) && !(szk_dbg_flags & 2048);
+                          nb * (uint64_t)slot_words + 2 <= p.fuse_cap_words && nb * (uint64_t)slot_words < (1ull << 32) && !(szk_dbg_flags & SZ3HIP_DBG_K1_NO_FUSED);
 #ifndef SZ3HIP_LAB  // (the fused form — round 4, slower than two passes on this chip — is part of the lab build only: python -m sz3_amd.build --lab)
         const bool fuse_built = false;
 #else
@@ -6303,11 +6309,11 @@ static void launch_march_w(const void *d_in, uint16_t *codes, szk_k1_params &p, 
                 hipLaunchKernelGGL((k_lorenzo_quant_march3f<T, 3, TY>), dim3(grid), dim3(256), 0, s, (const T *)d_in, codes, p, (uint32_t)nb, grid);
             }
 #endif
-        } else if (NDIM == 3 && sizeof(T) == 4 && p.hint_q16 > 0 && p.q16_flag && p.d[0] == 1 && !(szk_dbg_flags & 8)) {
-            // the 16-bit form: the previous call's probe saw lattice values within +-Q16_LIM / 2 only (debug flag 8 keeps the form below)
+        } else if (NDIM == 3 && sizeof(T) == 4 && p.hint_q16 > 0 && p.q16_flag && p.d[0] == 1 && !(szk_dbg_flags & SZ3HIP_DBG_K1_NO_Q16)) {
+            // the 16-bit form: the previous call's probe saw lattice values within +-Q16_LIM / 2 only (SZ3HIP_DBG_K1_NO_Q16 keeps the form below)
             if constexpr (NDIM == 3 && sizeof(T) == 4) {
                 p.assumed_q16 = 1;
-                if (p.samp.words && !(szk_dbg_flags & 4194304)) {
+                if (p.samp.words && !(szk_dbg_flags & SZ3HIP_DBG_K1_NO_SAMP_IN_LAUNCH)) {
                     // the sampled book inside the launch: SZK_SAMP_ROLES workgroups in front of the workers take the sample and build the book,
                     // the workers sum the segments' bits with it (and keep no histogram: nothing to fold)
                     p.samp_in_launch = 1;
@@ -6320,7 +6326,7 @@ static void launch_march_w(const void *d_in, uint16_t *codes, szk_k1_params &p, 
                     hipLaunchKernelGGL((k_lorenzo_quant_march3q<TY, false>), dim3(grid), dim3(256), 0, s, (const float *)d_in, codes, p, (uint32_t)nb, grid);
                 }
             }
-        } else if (NDIM == 3 && sizeof(T) == 4 && p.samp.words && p.d[0] == 1 && !(szk_dbg_flags & 4194304)) {
+        } else if (NDIM == 3 && sizeof(T) == 4 && p.samp.words && p.d[0] == 1 && !(szk_dbg_flags & SZ3HIP_DBG_K1_NO_SAMP_IN_LAUNCH)) {
             // (f32 only: the f64 kernel with the sampling code inlined needs a stack — 20 bytes a lane, paid by every wave — and runs at
             // three waves per SIMD as it is; f64 streams get their sampled book from k_sample behind the launch)
             if constexpr (NDIM == 3 && sizeof(T) == 4) {  // the one-byte kernel with the sampling workgroups in front (as the 16-bit form above)
@@ -6334,7 +6340,7 @@ static void launch_march_w(const void *d_in, uint16_t *codes, szk_k1_params &p, 
             grid = k1_grid((const void *)k_lorenzo_quant_march3<T, NDIM, TY>, (nb + 3) / 4);
             hipLaunchKernelGGL((k_lorenzo_quant_march3<T, NDIM, TY>), dim3(grid), dim3(256), 0, s, (const T *)d_in, codes, p, (uint32_t)nb, grid);
         }
-    } else if (p.mode.allow && !(szk_dbg_flags & 256)) {
+    } else if (by_width) {
         // (first call of a context) each specialisation gets the grid its own occupancy allows (all workgroups resident: the tasks are dealt by stride;
         // the two-byte kernel holds 38-72 KB of LDS); the fold reads the larger number of rows, the two-byte kernel leaves
         // them all empty
@@ -6358,19 +6364,33 @@ static void launch_march_w(const void *d_in, uint16_t *codes, szk_k1_params &p, 
     // of two-byte codes leaves the words untouched and the classic code book is built)
     if (p.samp.words && !p.samp_in_launch) {
         if constexpr (NDIM == 3) {
-            if (p.mode.allow && !(szk_dbg_flags & 256)) hipLaunchKernelGGL((k_sample<T>), dim3(SZK_SAMP_ROLES), dim3(256), 0, s, (const T *)d_in, p);
+            if (by_width) hipLaunchKernelGGL((k_sample<T>), dim3(SZK_SAMP_ROLES), dim3(256), 0, s, (const T *)d_in, p);
             else p.samp.words = nullptr;
         } else {
             p.samp.words = nullptr;
         }
     }
 }
-// the marching kernel + histogram fold. When one-byte codes are possible both specialisations are launched (the one the
-// probe did not choose returns at once); the two-byte one with the LDS window the context asks for (szk_k1_params::wide16)
+template <typename T, int NDIM>
+static void launch_probe(const void *d_in, const szk_k1_params &p, hipStream_t s) {
+    const uint64_t nsamp_threads = ((p.mode.n_total + SZK_PROBE_STRIDE - 1) / SZK_PROBE_STRIDE) * 64;
+    hipLaunchKernelGGL((k_probe<T, NDIM>), dim3((uint32_t)std::min<uint64_t>((nsamp_threads + 255) / 256, 1024)), dim3(256), 0, s, (const T *)d_in, p, p.mode.n_total, p.mode.probe_big);
+}
+// the marching forms: the probe in front (the one-launch form runs it itself), then the marching kernel + histogram fold; the two-byte
+// kernel with the LDS window the context asks for (szk_k1_params::wide16)
 template <typename T, int NDIM, int TY>
-static void launch_march(const void *d_in, uint16_t *codes, szk_k1_params &p, uint64_t nb, hipStream_t s) {
-    if (p.wide16) launch_march_w<T, NDIM, TY, true>(d_in, codes, p, nb, s);
-    else launch_march_w<T, NDIM, TY, false>(d_in, codes, p, nb, s);
+static void launch_march(const void *d_in, uint16_t *codes, szk_k1_params &p, bool one_launch, hipStream_t s) {
+    if (p.mode.allow && !one_launch) launch_probe<T, NDIM>(d_in, p, s);
+    const uint64_t nb = march_tasks(p.d, TY);  // wave tasks
+    if (p.wide16) launch_march_w<T, NDIM, TY, true>(d_in, codes, p, nb, one_launch, s);
+    else launch_march_w<T, NDIM, TY, false>(d_in, codes, p, nb, one_launch, s);
+}
+// the tiled kernel (x extents the marching forms do not take) + its histogram fold
+template <typename T, int NDIM, int FTZ>
+static void launch_v4(const void *d_in, uint16_t *codes, const szk_k1_params &p, uint64_t nb, hipStream_t s) {
+    const uint32_t grid = k1_grid((const void *)k_lorenzo_quant_v4<T, NDIM, FTZ>, nb);
+    hipLaunchKernelGGL((k_lorenzo_quant_v4<T, NDIM, FTZ>), dim3(grid), dim3(256), 0, s, (const T *)d_in, codes, p, (uint32_t)nb);
+    hipLaunchKernelGGL(k_hist_reduce, dim3(HIST_WIN / 256, 64), dim3(256), 0, s, p.hist_partial, grid, (int)p.radius - HIST_WIN / 2, p.hist, (uint32_t *)nullptr);
 }
 
 template <typename T>
@@ -6388,30 +6408,26 @@ static int launch_k1(int ndim, const void *d_in, uint16_t *codes, szk_k1_params 
 #define LAB_MTY 4
 #endif
     constexpr int MTY = LAB_MTY;
-    const bool march = fast && !(szk_dbg_flags & 32) && d0 >= 128 && tiles(MARCH_TX, MTY, MARCH_TZ) < (1ull << 31) && (ndim == 3 || ndim == 4);
+    const bool march = fast && !(szk_dbg_flags & SZ3HIP_DBG_K1_NO_MARCH) && d0 >= 128 && tiles(MARCH_TX, MTY, MARCH_TZ) < (1ull << 31) && (ndim == 3 || ndim == 4);
     // 1-D and 2-D arrays are 3-D arrays with d2 = 1 (and d1 = 1): the register-marching kernel needs no plane-size limit
-    const bool march12 = !szk_force_generic && !(szk_dbg_flags & 32) && (ndim == 1 || ndim == 2) && d0 % 4 == 0 && d0 >= 128 &&
+    const bool march12 = !szk_force_generic && !(szk_dbg_flags & SZ3HIP_DBG_K1_NO_MARCH) && (ndim == 1 || ndim == 2) && d0 % 4 == 0 && d0 >= 128 &&
                          d0 < (1ull << 31) && d1 < (1ull << 31) && tiles(MARCH_TX, ndim == 1 ? 1 : MTY, MARCH_TZ) < (1ull << 31);
     if (!march && !march12) p.mode.allow = 0;
     if ((!march && !march12) || ndim > 3 || !p.mode.allow) p.samp.words = nullptr;  // (the sampled book is the one-byte marching forms')
     p.samp_in_launch = 0;
     p.fold_rows = 0;
     p.seg_expected = 0;
-    // (same condition as launch_march_w's first branch: the one-launch form runs the probe itself)
-    const bool one_launch = (march || march12) && p.mode.allow && !(szk_dbg_flags & 256) && p.hint_narrow > 0 && !(szk_dbg_flags & 131072);
+    // stage 1's form, decided here once: the context's previous call took one-byte codes -> one launch of the marching form built around
+    // them, which runs the probe itself (launch_march_w's first branch) and is the only form that keeps the range words
+    const bool one_launch = (march || march12) && p.mode.allow && !(szk_dbg_flags & SZ3HIP_DBG_K1_NO_WIDTH_SPEC) && p.hint_narrow > 0 &&
+                            !(szk_dbg_flags & SZ3HIP_DBG_CTX_NO_MEMORY);
     p.assumed_narrow = one_launch ? 1 : 0;
-    // (the range words are kept by the one-launch form only: launch_march_w's first branch, same condition)
-    p.range_kept = (march || march12) && p.range && p.mode.allow && !(szk_dbg_flags & 256) && p.hint_narrow > 0 && !(szk_dbg_flags & 131072) ? 1 : 0;
+    p.range_kept = one_launch && p.range ? 1 : 0;
     if (!p.range_kept) p.range = nullptr;
     switch (ndim) {
         case 1:
             if (march12) {
-                if (p.mode.allow && !one_launch) {
-                    const uint64_t nsamp_threads = ((p.mode.n_total + SZK_PROBE_STRIDE - 1) / SZK_PROBE_STRIDE) * 64;
-                    hipLaunchKernelGGL((k_probe<T, 3>), dim3((uint32_t)std::min<uint64_t>((nsamp_threads + 255) / 256, 1024)), dim3(256), 0, s, (const T *)d_in, p, p.mode.n_total, p.mode.probe_big);
-                }
-                nb = tiles(MARCH_TX, 1, MARCH_TZ);
-                launch_march<T, 3, 1>(d_in, codes, p, nb, s);
+                launch_march<T, 3, 1>(d_in, codes, p, one_launch, s);
                 break;
             }
             nb = tiles(4096, 1, 1);
@@ -6420,12 +6436,7 @@ static int launch_k1(int ndim, const void *d_in, uint16_t *codes, szk_k1_params 
             break;
         case 2:
             if (march12) {
-                if (p.mode.allow && !one_launch) {
-                    const uint64_t nsamp_threads = ((p.mode.n_total + SZK_PROBE_STRIDE - 1) / SZK_PROBE_STRIDE) * 64;
-                    hipLaunchKernelGGL((k_probe<T, 3>), dim3((uint32_t)std::min<uint64_t>((nsamp_threads + 255) / 256, 1024)), dim3(256), 0, s, (const T *)d_in, p, p.mode.n_total, p.mode.probe_big);
-                }
-                nb = tiles(MARCH_TX, MTY, MARCH_TZ);
-                launch_march<T, 3, MTY>(d_in, codes, p, nb, s);
+                launch_march<T, 3, MTY>(d_in, codes, p, one_launch, s);
                 break;
             }
             nb = tiles(128, 32, 1);
@@ -6434,19 +6445,11 @@ static int launch_k1(int ndim, const void *d_in, uint16_t *codes, szk_k1_params 
             break;
         case 3:
             if (march) {
-                if (p.mode.allow && !one_launch) {
-                    const uint64_t nsamp_threads = ((p.mode.n_total + SZK_PROBE_STRIDE - 1) / SZK_PROBE_STRIDE) * 64;
-                    hipLaunchKernelGGL((k_probe<T, 3>), dim3((uint32_t)std::min<uint64_t>((nsamp_threads + 255) / 256, 1024)), dim3(256), 0, s, (const T *)d_in, p, p.mode.n_total, p.mode.probe_big);
-                }
-                nb = tiles(MARCH_TX, MTY, MARCH_TZ);  // wave tasks
-                launch_march<T, 3, MTY>(d_in, codes, p, nb, s);
+                launch_march<T, 3, MTY>(d_in, codes, p, one_launch, s);
                 break;
             }
             if (fast) {
-                nb = tiles(64, 8, FTZ);
-                const uint32_t grid = k1_grid((const void *)k_lorenzo_quant_v4<T, 3, FTZ>, nb);
-                hipLaunchKernelGGL((k_lorenzo_quant_v4<T, 3, FTZ>), dim3(grid), dim3(256), 0, s, (const T *)d_in, codes, p, (uint32_t)nb);
-                hipLaunchKernelGGL(k_hist_reduce, dim3(HIST_WIN / 256, 64), dim3(256), 0, s, p.hist_partial, grid, (int)p.radius - HIST_WIN / 2, p.hist, (uint32_t *)nullptr);
+                launch_v4<T, 3, FTZ>(d_in, codes, p, tiles(64, 8, FTZ), s);
                 break;
             }
             nb = tiles(64, 8, 8);
@@ -6455,19 +6458,11 @@ static int launch_k1(int ndim, const void *d_in, uint16_t *codes, szk_k1_params 
             break;
         default:
             if (march) {
-                if (p.mode.allow && !one_launch) {
-                    const uint64_t nsamp_threads = ((p.mode.n_total + SZK_PROBE_STRIDE - 1) / SZK_PROBE_STRIDE) * 64;
-                    hipLaunchKernelGGL((k_probe<T, 4>), dim3((uint32_t)std::min<uint64_t>((nsamp_threads + 255) / 256, 1024)), dim3(256), 0, s, (const T *)d_in, p, p.mode.n_total, p.mode.probe_big);
-                }
-                nb = tiles(MARCH_TX, MTY, MARCH_TZ);  // wave tasks
-                launch_march<T, 4, MTY>(d_in, codes, p, nb, s);
+                launch_march<T, 4, MTY>(d_in, codes, p, one_launch, s);
                 break;
             }
             if (fast) {
-                nb = tiles(64, 8, FTZ);
-                const uint32_t grid = k1_grid((const void *)k_lorenzo_quant_v4<T, 4, FTZ>, nb);
-                hipLaunchKernelGGL((k_lorenzo_quant_v4<T, 4, FTZ>), dim3(grid), dim3(256), 0, s, (const T *)d_in, codes, p, (uint32_t)nb);
-                hipLaunchKernelGGL(k_hist_reduce, dim3(HIST_WIN / 256, 64), dim3(256), 0, s, p.hist_partial, grid, (int)p.radius - HIST_WIN / 2, p.hist, (uint32_t *)nullptr);
+                launch_v4<T, 4, FTZ>(d_in, codes, p, tiles(64, 8, FTZ), s);
                 break;
             }
             nb = tiles(64, 8, 4);
@@ -6481,13 +6476,12 @@ static int launch_k1(int ndim, const void *d_in, uint16_t *codes, szk_k1_params 
 uint64_t szk_fuse_scratch_words(int ndim, const uint64_t d[4]) {  // (the tasks of launch_k1's marching forms: 256 x TY x MARCH_TZ, TY = 1 for 1-D arrays)
     if (ndim < 1 || ndim > 3 || d[3] % MARCH_TX != 0 || d[3] >= (1ull << 31) || d[2] >= (1ull << 31) || d[1] >= (1ull << 31)) return 0;
     const uint32_t ty = ndim == 1 ? 1u : (uint32_t)LAB_MTY;
-    const uint64_t nb = (d[3] / MARCH_TX) * ((d[2] + ty - 1) / ty) * ((d[1] + MARCH_TZ - 1) / MARCH_TZ) * d[0];
-    return nb * fuse_slot_words(ty, d[2], d[1]) + 2;
+    return march_tasks(d, ty) * fuse_slot_words(ty, d[2], d[1]) + 2;
 }
 int szk_launch_k1(int dtype, int ndim, const void *d_in, uint16_t *codes, szk_k1_params *p, hipStream_t s) {
     szk_k1_params &pp = *p;  // mode.allow is cleared when the chosen kernel has no one-byte store path
     pp.dbg = (uint32_t)szk_dbg_flags;
-    if (szk_dbg_flags & 64) pp.mode.allow = 0;
+    if (szk_dbg_flags & SZ3HIP_DBG_K1_NO_NARROW) pp.mode.allow = 0;
     return dtype == 0 ? launch_k1<float>(ndim, d_in, codes, pp, s) : launch_k1<double>(ndim, d_in, codes, pp, s);
 }
 
@@ -6495,7 +6489,7 @@ int szk_launch_codebook(const uint64_t *d_hist, const szk_cb_params *p, hipStrea
     const uint32_t nb = p->n_books ? p->n_books : 1;  // > 1: batch of independent code books (tuner trials), no outlier sort
     szk_cb_params q = *p;
     q.n_books = nb;
-    q.dbg = ((szk_dbg_flags & 1024) ? 1u : 0u) | ((szk_dbg_flags & 262144) ? 2u : 0u);  // (262144: the small path with the round-parallel merge)
+    q.dbg = ((szk_dbg_flags & SZ3HIP_DBG_CB_ONE_CLASS) ? SZK_CB_DBG_ONE_CLASS : 0u) | ((szk_dbg_flags & SZ3HIP_DBG_CB_SERIAL_MERGE) ? SZK_CB_DBG_SERIAL_MERGE : 0u);
     if (nb > 1) {  // (a single book's range words are zeroed by the caller together with its counters)
         hipError_t e = hipMemsetAsync(q.range, 0, 16 * nb, s);
         if (e != hipSuccess) return (int)e;
@@ -6503,8 +6497,8 @@ int szk_launch_codebook(const uint64_t *d_hist, const szk_cb_params *p, hipStrea
     if (!p->range_ready) hipLaunchKernelGGL(k_hist_range, dim3(SZH_HIST_BINS / 256, nb), dim3(256), 0, s, d_hist, q.range);
     // which of the two forms applies is known on the device only; a context that remembers the previous call's alphabet
     // launches that form alone (solo): the kernel raises `mispredict` when it is the wrong one and the host repeats stage 2
-    // (a single book that may be a wide one: its compaction over the whole chip first, sz3hip_debug_flags(1): inside the book's workgroup as before)
-    q.keys_ready = nb == 1 && p->part_hint != 0 && !(szk_dbg_flags & 1) ? 1 : 0;
+    // (a single book that may be a wide one: its compaction over the whole chip first, SZ3HIP_DBG_CB_COMPACT_IN_WG: inside the book's workgroup as before)
+    q.keys_ready = nb == 1 && p->part_hint != 0 && !(szk_dbg_flags & SZ3HIP_DBG_CB_COMPACT_IN_WG) ? 1 : 0;
     if (q.keys_ready) hipLaunchKernelGGL(k_cb_compact, dim3(CBC_BLOCKS), dim3(1024), 0, s, d_hist, q.keys, q.syms, q.ifreq);
     if (p->part_hint != 1) hipLaunchKernelGGL(k_codebook<0>, dim3(nb == 1 ? 3 : nb), dim3(CB_LAUNCH), 0, s, d_hist, q);
     q.assign_later = q.keys_ready;  // (the same cases: a single book that may be a wide one)
@@ -6609,9 +6603,9 @@ int szk_launch_encode(const uint16_t *codes, uint64_t n, const uint32_t *d_enc, 
 #else
     if (mg) return -2;  // (no fused stage 1 in this build: nothing hands a merge over)
 #endif
-    if (asmp && !(rp.on && !rp.no_book) && n_chunks >= 4096 && ((asmp->assumed_narrow && !(szk_dbg_flags & 32768)) || asmp->samp_words)) {
+    if (asmp && !(rp.on && !rp.no_book) && n_chunks >= 4096 && ((asmp->assumed_narrow && !(szk_dbg_flags & SZ3HIP_DBG_PACK_OLD)) || asmp->samp_words)) {
         // one-byte codes (stage 1's one-launch form assumed them; a probe that says otherwise voids the call) and no book built beside the
-        // packer: the pair-table packer, one 1024-thread workgroup per CU (sz3hip_debug_flags(32768): k_pack as before)
+        // packer: the pair-table packer, one 1024-thread workgroup per CU (SZ3HIP_DBG_PACK_OLD: k_pack as before)
         static int n_cu = 0;
         if (!n_cu) {
             int dev = 0;
@@ -6624,14 +6618,14 @@ int szk_launch_encode(const uint16_t *codes, uint64_t n, const uint32_t *d_enc, 
         // (a call that may code with its sampled book is this kernel's whatever the debug flag says: k_pack's one-byte path takes code words
         // up to 16 bits. Behind the two-launch form of stage 1 — a context's first call — whether it does is known on the device only:
         // both packers are launched and the one whose case it is not returns at once)
-        uint32_t beside = asmp->samp_words && !asmp->assumed_narrow ? 1u : 0u;
+        uint32_t beside = asmp->samp_words && !asmp->assumed_narrow ? SZK_PACKB_ONLY_SAMPLED : 0u;
 #ifdef SZ3HIP_LAB
-        beside |= (szk_dbg_flags & 16) ? 8u : 0u;   // (lab switches of k_pack_b: see the kernel)
-        beside |= (szk_dbg_flags & 512) ? 16u : 0u;
+        beside |= (szk_dbg_flags & SZ3HIP_DBG_PACK_LAB_NO_STORES) ? SZK_PACKB_LAB_NO_STORES : 0u;   // (lab switches of k_pack_b: see the kernel)
+        beside |= (szk_dbg_flags & SZ3HIP_DBG_PACK_LAB_ONE_UNIT) ? SZK_PACKB_LAB_ONE_UNIT : 0u;
 #endif
         hipLaunchKernelGGL(k_pack_b, dim3(rb + PB_ASM_BLOCKS + pb), dim3(PB_THREADS), 0, s, codes, n, d_enc, chunk_words, group_off, mode, sym_add, state,
                            payload, apv, pb, split, rp, beside);
-        if (beside & 1u) {
+        if (beside & SZK_PACKB_ONLY_SAMPLED) {
             const uint32_t pb2 = pgrid < 1280 - extra ? pgrid : 1280 - extra;
             hipLaunchKernelGGL((k_pack<ENC_WIN>), dim3(rb + pb2 + (asmp ? ASM_BLOCKS : 0)), dim3(256), 0, s, codes, n, d_enc, info, chunk_words, group_off, mode,
                                sym_add, state, payload, apv, pb2, rp);

@@ -1043,7 +1043,7 @@ __global__ __launch_bounds__(1024) void k_blk_rank_small(const uint8_t *__restri
     if (threadIdx.x == 0) *n_reg_out = s_carry;
 }
 static void launch_blk_rank(const uint8_t *sel, uint32_t nblocks, uint32_t *rank, uint32_t *comp, uint32_t *run_scratch, uint64_t *n_reg, hipStream_t s) {
-    if (nblocks <= RANK_SMALL && !(szk_dbg_flags & 2048)) {  // (debug flag 2048: the three launches whatever the block count)
+    if (nblocks <= RANK_SMALL && !(szk_dbg_flags & SZ3HIP_DBG_BLK_RANK_3_LAUNCHES)) {  // (SZ3HIP_DBG_BLK_RANK_3_LAUNCHES: the three launches whatever the block count)
         hipLaunchKernelGGL(k_blk_rank_small, dim3(1), dim3(1024), 0, s, sel, nblocks, rank, comp, n_reg);
         return;
     }
@@ -5392,7 +5392,7 @@ static int launch_blk_side_build(const szk_blk_params *p, const szk_blk_scratch 
 static int launch_blkn_compress(int dtype, const void *d_in, uint16_t *codes, const szk_blk_params *p, const szk_blk_scratch *sc, hipStream_t s) {
     const uint32_t nblocks = blk_count_blocks(p);
     const uint64_t n = p->d[1] * p->d[2];
-    if (p->ndim == 1 && (p->mask & 2u) && !(p->mask & 4u) && !p->sel_given && !(szk_dbg_flags & 134217728)) {
+    if (p->ndim == 1 && (p->mask & 2u) && !(p->mask & 4u) && !p->sel_given && !(szk_dbg_flags & SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK)) {
         // Lorenzo members only (debug flag 134217728: the general fit pass): choices by k_blkn_sel12, codes straight from the array
         szk_blk_params q = *p;
         q.sel_given = 1;
@@ -5419,13 +5419,13 @@ static int launch_blkn_compress(int dtype, const void *d_in, uint16_t *codes, co
     do {                                                                                                                        \
         const uint32_t gfit = (uint32_t)std::min<uint64_t>(BLK_GRID_ENC * 4 / NW, ((uint64_t)nblocks + NW - 1) / NW);                 \
         const uint32_t glor = (uint32_t)std::min<uint64_t>(BLK_GRID_ENC * 8 / NW, (n + NW * 64 - 1) / (NW * 64));                     \
-        if (!TWO && !p->sel_given && !(p->mask & 2u) && !(szk_dbg_flags & 134217728)) { /* 1-D: four blocks per wave (debug flag 134217728: a wave per block) */ \
+        if (!TWO && !p->sel_given && !(p->mask & 2u) && !(szk_dbg_flags & SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK)) { /* 1-D: four blocks per wave (SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK: a wave per block) */ \
             const uint32_t grow = (uint32_t)std::min<uint64_t>(BLK_GRID_ENC * 4 / NW, ((uint64_t)nblocks + NW * 4 - 1) / (NW * 4));    \
             hipLaunchKernelGGL((k_blkn_fit_rows<T, HW, NW>), dim3(grow), dim3(NW * 64), 0, s, (const T *)d_in, codes, *p, nblocks); \
         } else                                                                                                                  \
         hipLaunchKernelGGL((k_blkn_fit<T, HW, NW, TWO, false>), dim3(gfit), dim3(NW * 64), 0, s, (const T *)d_in, codes, *p, nblocks, \
                            (unsigned long long *)nullptr);                                                                          \
-        if (!TWO && !p->sel_given && !(p->mask & 2u) && !(szk_dbg_flags & 134217728)) { /* 1-D, q~ of everything in the work array: four codes per thread */ \
+        if (!TWO && !p->sel_given && !(p->mask & 2u) && !(szk_dbg_flags & SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK)) { /* 1-D, q~ of everything in the work array: four codes per thread */ \
             const uint32_t g4 = (uint32_t)std::min<uint64_t>(BLK_GRID_ENC * 8 / NW, (n + NW * 256 - 1) / (NW * 256));                  \
             hipLaunchKernelGGL((k_blkn_lorenzo1v<T, HW, NW * 64>), dim3(g4), dim3(NW * 64), 0, s, codes, *p, n);                   \
         } else                                                                                                                  \
@@ -5440,7 +5440,7 @@ static int launch_blkn_compress(int dtype, const void *d_in, uint16_t *codes, co
     // device-scope atomic per non-empty bin, ~400 addresses that EVERY workgroup hits: they are performed one after another at the memory
     // side, ~20 ns each, and C1's 1024 workgroups of four waves spent 21 of the stencil pass's 27 us and 7 of the fit pass's 20 queueing
     // there (measured with the flush switched off). A quarter of the workgroups, a quarter of the queue.
-    const bool wg16 = p->ndim == 1 && !(szk_dbg_flags & 134217728);
+    const bool wg16 = p->ndim == 1 && !(szk_dbg_flags & SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK);
     if (dtype == 0) {
         if (sc->wide_hist) BLKN_ENC(float, BLK_HWIN_WIDE, 16);
         else if (wg16) BLKN_ENC1(float, BLK_HWIN, 16, false);
@@ -5484,10 +5484,10 @@ int szk_launch_blk_compress(int dtype, const void *d_in, uint16_t *codes, const 
     // With the selection pass's choices: the fit pass codes the regression blocks (and leaves their lattice values), the stencil
     // pass every other element straight from the array. Without (development switch): fit and selection by the fit pass, the
     // lattice values of everything through qwork, Lorenzo blocks from tiles.
-    const bool by_element = p->sel_given && !(p->mask & 2u) && !(szk_dbg_flags & 67108864);  // (k_blk_rows: first-order Lorenzo only)
+    const bool by_element = p->sel_given && !(p->mask & 2u) && !(szk_dbg_flags & SZ3HIP_DBG_BLK_FIT_TILES);  // (k_blk_rows: first-order Lorenzo only)
     const uint64_t nrows = p->d[0] * p->d[1];
     // the regression blocks' list before the fit pass walks it (the side section wants the same ranks afterwards: made once)
-    const bool rank_first = p->sel_given && !(szk_dbg_flags & 1073741824);
+    const bool rank_first = p->sel_given && !(szk_dbg_flags & SZ3HIP_DBG_BLK_NO_EXIT);
     if (rank_first) launch_blk_rank(p->sel, nblocks, sc->rank, sc->comp, sc->run_scratch, sc->counters + 0, s);
     if (p->sel_given && !by_element) {
         const dim3 g((uint32_t)((p->d[2] + 255) / 256), (uint32_t)std::min<uint64_t>(nrows, 32768));
@@ -5532,7 +5532,7 @@ static int launch_blk_side_build(const szk_blk_params *p, const szk_blk_scratch 
     // the group sizes are staged in the rank array, which the encoder needs no more once comp is written)
     double *stats = reinterpret_cast<double *>(sc->counters + 4);
     uint32_t *group_bits = sc->rank;
-    if (nblocks <= SIDE_SMALL_BLOCKS && !(szk_dbg_flags & 2048)) {  // (debug flag 2048: the eight launches whatever the block count)
+    if (nblocks <= SIDE_SMALL_BLOCKS && !(szk_dbg_flags & SZ3HIP_DBG_BLK_SIDE_8_LAUNCHES)) {  // (SZ3HIP_DBG_BLK_SIDE_8_LAUNCHES: the eight launches whatever the block count)
         double *st = p->ndim == 4 ? sc->stats5 : stats;
 #define SIDE_SMALL(NC, RK) hipLaunchKernelGGL((k_blk_side_small<NC, RK>), dim3(sc->range ? 1 + SZH_HIST_BINS / 1024 : 1), dim3(1024), 0, s, (const uint8_t *)p->sel, nblocks, sc->rank, sc->comp, sc->counters + 0, (const int64_t *)p->coef, st, group_bits, sc->side, sc->counters + 2, sc->range_hist, sc->range)
         if (p->ndim == 4) {
@@ -5566,7 +5566,7 @@ static int launch_blk_side_build(const szk_blk_params *p, const szk_blk_scratch 
     return 0;
 }
 
-int szk_blk_side_small(uint64_t nblocks) { return nblocks <= SIDE_SMALL_BLOCKS && !(szk_dbg_flags & 2048) ? 1 : 0; }
+int szk_blk_side_small(uint64_t nblocks) { return nblocks <= SIDE_SMALL_BLOCKS && !(szk_dbg_flags & SZ3HIP_DBG_BLK_SIDE_8_LAUNCHES) ? 1 : 0; }
 int szk_launch_blk_select(int dtype, const void *d_in, const szk_blk_params *p, uint64_t *n_other, hipStream_t s) {
     const uint32_t nblocks = blk_count_blocks(p);
     const dim3 g((nblocks + 255) / 256), b(256);
@@ -5642,10 +5642,10 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
                                hipEvent_t side_done, const int dbg, uint32_t **ctl_out) {
     *ctl_out = nullptr;
     const uint32_t nblocks = blk_count_blocks(p);
-    // (k_blk_local3v reads the codes themselves: the far deltas alone go to the work array; debug flag 16: the expanded copy and the
+    // (k_blk_local3v reads the codes themselves: the far deltas alone go to the work array; SZ3HIP_DBG_BLKDEC_LOCAL_EXPANDED: the expanded copy and the
     // wave-per-block pass)
-    const bool fusedv = p->ndim == 3 && p->B == 6 && p->carry && !(dbg & (32768 | 65536 | 8388608 | 16));
-    const bool wave2 = p->ndim == 2 && !(p->mask & 2u) && p->B <= 16 && p->carry && !(dbg & (8388608 | 65536));  // (k_blkn_wave2 reads the codes too)
+    const bool fusedv = p->ndim == 3 && p->B == 6 && p->carry && !(dbg & (SZ3HIP_DBG_BLKDEC_GROUPS_3 | SZ3HIP_DBG_BLKDEC_PER_FRONT | SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE | SZ3HIP_DBG_BLKDEC_LOCAL_EXPANDED));
+    const bool wave2 = p->ndim == 2 && !(p->mask & 2u) && p->B <= 16 && p->carry && !(dbg & (SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE | SZ3HIP_DBG_BLKDEC_PER_FRONT));  // (k_blkn_wave2 reads the codes too)
     if (p->ndim == 1 || fusedv || wave2) {
         if (szk_launch_scatter_deltas(dtype, h->n, payload, o, h->n_dout, p->qwork, s)) return -1;
     } else if (szk_launch_expand_deltas(dtype, codes, h->n, (int)h->radius, payload, o, h->n_dout, p->qwork, s)) return -1;
@@ -5670,8 +5670,8 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
     if (p->ndim == 1 && (p->mask & 2u)) {  // second-order Lorenzo in the set: the scan of affine maps (k_blkn2_*)
         const uint32_t gpre = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 3) / 4);
         const uint32_t ntiles = (nblocks + BLKN_TILE - 1) / BLKN_TILE;
-        // blocks of up to 128 values, a multiple of 8: four blocks per wave (debug flag 134217728: a wave per block)
-        const bool rows = p->B <= 128 && p->B % 8 == 0 && !(dbg & 134217728);
+        // blocks of up to 128 values, a multiple of 8: four blocks per wave (SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK: a wave per block)
+        const bool rows = p->B <= 128 && p->B % 8 == 0 && !(dbg & SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK);
         const uint32_t grow = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 15) / 16);
 #define BLKN2_DEC(T, QT)                                                                                                                          \
     do {                                                                                                                                          \
@@ -5687,8 +5687,8 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
 #undef BLKN2_DEC
     } else
     if (wave2) {
-        // 2-D, first-order Lorenzo + regression, block edges up to 16: ONE launch for the chain of fronts (k_blkn_wave2; debug flag
-        // 65536: groups of 4 x 4 blocks with a launch per front, k_blkn_decode2g)
+        // 2-D, first-order Lorenzo + regression, block edges up to 16: ONE launch for the chain of fronts (k_blkn_wave2;
+        // SZ3HIP_DBG_BLKDEC_PER_FRONT: groups of 4 x 4 blocks with a launch per front, k_blkn_decode2g)
         const uint32_t gpre = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 3) / 4);
         const uint32_t ng1 = (p->nb[1] + BLKN_G - 1) / BLKN_G, ng2 = (p->nb[2] + BLKN_G - 1) / BLKN_G;
         const uint64_t nslots = (uint64_t)ng1 * ng2;
@@ -5710,8 +5710,8 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
     } else
     if (p->ndim < 3) {
         const uint32_t gpre = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 3) / 4);
-        // 1-D, blocks of up to 128 values, a multiple of 8: four blocks per wave (debug flag 134217728: a wave per block)
-        const bool rows1 = p->ndim == 1 && p->B <= 128 && p->B % 8 == 0 && !(dbg & 134217728);
+        // 1-D, blocks of up to 128 values, a multiple of 8: four blocks per wave (SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK: a wave per block)
+        const bool rows1 = p->ndim == 1 && p->B <= 128 && p->B % 8 == 0 && !(dbg & SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK);
         const uint32_t grow1 = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 15) / 16);
         if (rows1) {
             if (dtype == 0) hipLaunchKernelGGL(k_blkn_pre1_rows<float>, dim3(grow1), dim3(256), 0, s, codes, p->qwork, d_out, *p, nblocks, sc->rank, coef_by_rank);
@@ -5721,8 +5721,8 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
         else hipLaunchKernelGGL(k_blkn_pre<double>, dim3(gpre), dim3(256), 0, s, codes, p->qwork, d_out, *p, nblocks, sc->rank, coef_by_rank);
         if (p->ndim == 1) {
             const uint32_t ntiles = (nblocks + BLKN_TILE - 1) / BLKN_TILE;
-            // blocks of up to 128 values, a multiple of 8: four blocks per wave (debug flag 134217728: a wave per block)
-            const bool rows = p->B <= 128 && p->B % 8 == 0 && !(dbg & 134217728);
+            // blocks of up to 128 values, a multiple of 8: four blocks per wave (SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK: a wave per block)
+            const bool rows = p->B <= 128 && p->B % 8 == 0 && !(dbg & SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK);
             const uint32_t grow = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 15) / 16);
             if (dtype == 0) {
                 hipLaunchKernelGGL(k_blkn_scan_tile<int32_t>, dim3(ntiles), dim3(1024), 0, s, p->sel, nblocks, p->carry);
@@ -5743,7 +5743,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
                 if (dtype == 0) hipLaunchKernelGGL(k_blkn_decode2s<float>, dim3((nfront + 3) / 4), dim3(256), 0, s, p->qwork, d_out, *p, d, by_lo, nfront);
                 else hipLaunchKernelGGL(k_blkn_decode2s<double>, dim3((nfront + 3) / 4), dim3(256), 0, s, p->qwork, d_out, *p, d, by_lo, nfront);
             }
-        } else if (p->B <= 16 && !(dbg & 8388608)) {  // groups of 4 x 4 blocks per workgroup, a launch per front (debug flag 65536; 8388608: a block per wave)
+        } else if (p->B <= 16 && !(dbg & SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE)) {  // groups of 4 x 4 blocks per workgroup, a launch per front (SZ3HIP_DBG_BLKDEC_PER_FRONT; SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE: a block per wave)
             const uint32_t ng1 = (p->nb[1] + BLKN_G - 1) / BLKN_G, ng2 = (p->nb[2] + BLKN_G - 1) / BLKN_G;
             for (uint32_t d = 0; d < ng1 + ng2 - 1; d++) {
                 const uint32_t gy_lo = d >= ng2 ? d - (ng2 - 1) : 0, gy_hi = d < ng1 - 1 ? d : ng1 - 1;
@@ -5760,7 +5760,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
             }
         }
     } else
-    if (p->B == 6 && p->carry && !(dbg & (32768 | 65536 | 8388608))) {  // one launch for the chain of fronts (k_blk_wave3)
+    if (p->B == 6 && p->carry && !(dbg & (SZ3HIP_DBG_BLKDEC_GROUPS_3 | SZ3HIP_DBG_BLKDEC_PER_FRONT | SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE))) {  // one launch for the chain of fronts (k_blk_wave3)
         constexpr uint32_t G = 3;
         const uint32_t ng0 = (p->nb[0] + G - 1) / G, ng1 = (p->nb[1] + G - 1) / G, ng2 = (p->nb[2] + G - 1) / G;
         const uint32_t ngd = ng0 + ng1 + ng2 - 2;
@@ -5793,7 +5793,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
         SZK_CHECK_LAUNCH();
         return 0;
     } else
-    if (p->B == 6 && (dbg & 32768)) {  // debug flag 32768: groups of 3 x 3 x 3 blocks per workgroup, closed form, a launch per front (k_blk_decode_gf)
+    if (p->B == 6 && (dbg & SZ3HIP_DBG_BLKDEC_GROUPS_3)) {  // groups of 3 x 3 x 3 blocks per workgroup, closed form, a launch per front (k_blk_decode_gf)
         constexpr uint32_t G = 3;
         const uint32_t ng0 = (p->nb[0] + G - 1) / G, ng1 = (p->nb[1] + G - 1) / G, ng2 = (p->nb[2] + G - 1) / G;
         const uint32_t ngd = ng0 + ng1 + ng2 - 2;
@@ -5812,7 +5812,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
         }
     } else
 #ifdef SZ3HIP_LAB
-    if (p->B == 6 && !(dbg & 8388608)) {  // round 3's form (lab builds, debug flag 65536): groups of 2 x 2 x 2 blocks, line scans (debug flag 8388608: a block per wave)
+    if (p->B == 6 && !(dbg & SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE)) {  // round 3's form (lab builds, SZ3HIP_DBG_BLKDEC_PER_FRONT): groups of 2 x 2 x 2 blocks, line scans (SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE: a block per wave)
         const uint32_t ng0 = (p->nb[0] + 1) / 2, ng1 = (p->nb[1] + 1) / 2, ng2 = (p->nb[2] + 1) / 2;
         const uint32_t ngd = ng0 + ng1 + ng2 - 2;
         {
@@ -5884,8 +5884,8 @@ int szk_launch_blk_decompress(int dtype, const uint16_t *codes, void *d_out, con
     if (rc || !ctl) return rc;
     uint32_t gave_up = 0;
     if (hipMemcpyAsync(&gave_up, ctl + 1, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -1;
-    if (!gave_up && !(szk_dbg_flags & 4)) return 0;  // (debug flag 4: take the retry as if a poll had given up — tests)
-    return blk_decompress_impl(dtype, codes, d_out, p, sc, payload, h, o, coef_by_rank, s, nullptr, szk_dbg_flags | 32768 | 65536, &ctl);
+    if (!gave_up && !(szk_dbg_flags & SZ3HIP_DBG_BLKDEC_FORCE_RETRY)) return 0;  // (take the retry as if a poll had given up — tests)
+    return blk_decompress_impl(dtype, codes, d_out, p, sc, payload, h, o, coef_by_rank, s, nullptr, szk_dbg_flags | SZ3HIP_DBG_BLKDEC_GROUPS_3 | SZ3HIP_DBG_BLKDEC_PER_FRONT, &ctl);
 }
 
 int szk_launch_trial_lorenzo12(int dtype, const void *d_samples, uint64_t per, uint64_t nsb, double eb, int radius, uint64_t *hist, uint64_t *counters,

@@ -41,7 +41,6 @@ def test_fused_stage1_writes_the_unfused_encoders_bytes(shape, dtype):
     n = a.size
     eb = 1e-3
     conf = _conf(shape, eb)
-    L = sz3_amd.lib()
     ctxs = [sz3_amd.DeviceCompressor(n, dtype), sz3_amd.DeviceCompressor(n, dtype)]
     for d in ctxs:
         d.set_fused(True)  # (opt-in: the default is the two-pass form)
@@ -50,11 +49,8 @@ def test_fused_stage1_writes_the_unfused_encoders_bytes(shape, dtype):
     def run(dc, arr, flags=0):
         t = torch.from_numpy(arr).to(dev)
         pl = torch.empty(cap, dtype=torch.uint8, device=dev)
-        L.sz3hip_debug_flags(flags)
-        try:
+        with sz3_amd.debug_flags(flags):
             size = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, 0)
-        finally:
-            L.sz3hip_debug_flags(0)
         fused = dc.fused
         dec = torch.empty_like(t)
         dc.decompress(pl.data_ptr(), size, dec.data_ptr(), 0)
@@ -64,7 +60,7 @@ def test_fused_stage1_writes_the_unfused_encoders_bytes(shape, dtype):
 
     for k, arr in enumerate([a, a, b, c3, b]):
         got, fused = run(ctxs[0], arr)
-        ref, fused_ref = run(ctxs[1], arr, flags=2048)  # (2048: no fused stage 1)
+        ref, fused_ref = run(ctxs[1], arr, flags=sz3_amd.Dbg.K1_NO_FUSED)
         assert not fused_ref
         assert fused == (k > 0), (k, fused)
         assert got == ref, "call %d: the fused stage 1 and the unfused encoder disagree" % k
@@ -142,15 +138,11 @@ def test_multi_symbol_decoder_matches_the_one_symbol_decoder(shape, eb):
     pl = torch.empty(cap, dtype=torch.uint8, device=dev)
     size = dc.compress(_conf(shape, eb), t.data_ptr(), pl.data_ptr(), cap, 0)
     outs = []
-    L = sz3_amd.lib()
-    for flag in (0, 2, 2097152):   # one-symbol table, multi-symbol table (opt-in), no half-width chain at all
-        L.sz3hip_debug_flags(flag)
-        try:
+    for flag in (0, sz3_amd.Dbg.DEC_MULTI_SYM, sz3_amd.Dbg.DEC_NO_HALF):   # one-symbol table, multi-symbol table (opt-in), no half-width chain at all
+        with sz3_amd.debug_flags(flag):
             o = torch.empty_like(t)
             dc.decompress(pl.data_ptr(), size, o.data_ptr(), 0)
             torch.cuda.synchronize()
-        finally:
-            L.sz3hip_debug_flags(0)
         outs.append(o.cpu().numpy())
     assert np.array_equal(outs[0], outs[1], equal_nan=True) and np.array_equal(outs[0], outs[2], equal_nan=True)
     fin = np.isfinite(a)

@@ -45,8 +45,7 @@ def _try(dc, blob, n, dtype):
 @pytest.mark.parametrize("kind", ["plain-3d", "block-1d", "block-3d", "block-4d"])
 def test_tampered_headers_are_refused(kind):
     L = sz3_amd.lib()
-    try:
-        L.sz3hip_debug_flags(NO_EXIT)
+    with sz3_amd.debug_flags(NO_EXIT):
         if kind == "block-1d":
             a = field1d(40000, np.float32)
         elif kind == "block-4d":
@@ -55,8 +54,6 @@ def test_tampered_headers_are_refused(kind):
         else:
             a = field3d((24, 40, 56), np.float32)
         dc, blob, d_in = _device_payload(a, regression=kind != "plain-3d")
-    finally:
-        L.sz3hip_debug_flags(0)
     n = a.size
     h, o, sec = szh_ref.parse(bytes(blob))
     assert h["predictor"] == (0 if kind == "plain-3d" else 2)

@@ -128,19 +128,16 @@ LEVEL_CASES = [c for c in CASES if c[0].startswith("3d")] + [
 
 @pytest.mark.parametrize("name,gen,eb,kw", LEVEL_CASES, ids=[c[0] for c in LEVEL_CASES])
 def test_level_kernels_bit_exact_with_oracle(name, gen, eb, kw):
-    """debug flag 4194304 sends every level of every 3-D array through the level kernels (one launch per level, a block's three
+    """Dbg.INTERP_LEVELS_ANY_SIZE sends every level of every 3-D array through the level kernels (one launch per level, a block's three
     passes in LDS; normally taken from 256 blocks up): codes, unpredictable set and reconstruction against the oracle."""
-    try:
-        sz3_amd.lib().sz3hip_debug_flags(4194304)
+    with sz3_amd.debug_flags(sz3_amd.Dbg.INTERP_LEVELS_ANY_SIZE):
         test_interp_bit_exact_with_oracle(name, gen, eb, kw)
-    finally:
-        sz3_amd.lib().sz3hip_debug_flags(0)
 
 
 @pytest.mark.parametrize("kw", [dict(interpAlgo=1), dict(interpAlgo=1, interpDirection=5), dict(interpAlgo=0)], ids=["cubic", "cubic-dir5", "linear"])
 def test_level_kernels_at_their_natural_size(kw):
     """231 x 200 x 193: 8 x 7 x 7 blocks at the finest level (the level kernels' own routing: fine levels in the level kernel, coarse
-    ones pass by pass on the same work array), against the oracle; and the same bytes as the per-pass path (flag 128)"""
+    ones pass by pass on the same work array), against the oracle; and the same bytes as the per-pass path (Dbg.INTERP_NO_VEC)"""
     a = field3d((231, 200, 193))
     a[100, 50, 60] = np.nan
     a[7, 199, 192] = 1e30
@@ -155,15 +152,12 @@ def test_level_kernels_at_their_natural_size(kw):
     for k, v in kw.items():
         setattr(conf, k, v)
     res = []
-    try:
-        for flag in (0, 128):
-            sz3_amd.lib().sz3hip_debug_flags(flag)
+    for flag in (0, sz3_amd.Dbg.INTERP_NO_VEC):
+        with sz3_amd.debug_flags(flag):
             pl = torch.empty(cap, dtype=torch.uint8, device=dev)
             n = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, 0)
             torch.cuda.synchronize()
             res.append(pl[:n].clone())
-    finally:
-        sz3_amd.lib().sz3hip_debug_flags(0)
     assert res[0].numel() == res[1].numel() and torch.equal(res[0], res[1])
 
 
@@ -190,7 +184,7 @@ def test_interp_host_api_and_ratio():
 
 @pytest.mark.parametrize("VEC_SHAPE", [(48, 56, 128), (40, 33, 100), (17, 24, 36), (65, 33, 96), (34, 66, 132), (70, 40, 20), (200, 136), (67, 36), (40004,)])
 def test_vector_and_scalar_level1_kernels_agree(VEC_SHAPE):
-    """debug flag 128 forces the one-point-per-thread kernels: same payload, byte for byte"""
+    """Dbg.INTERP_NO_VEC forces the one-point-per-thread kernels: same payload, byte for byte"""
     a = {1: field1d, 2: field2d, 3: field3d}[len(VEC_SHAPE)](VEC_SHAPE if len(VEC_SHAPE) > 1 else VEC_SHAPE[0])
     a.flat[a.size // 3 + 7] = np.nan
     dev = torch.device("cuda:0")
@@ -202,16 +196,13 @@ def test_vector_and_scalar_level1_kernels_agree(VEC_SHAPE):
     conf.cmprAlgo = sz3_amd.ALGO_INTERP
     conf.absErrorBound = 1e-3
     sizes, outs = [], []
-    try:
-        for k, flag in enumerate((0, 128)):
-            sz3_amd.lib().sz3hip_debug_flags(flag)
+    for k, flag in enumerate((0, sz3_amd.Dbg.INTERP_NO_VEC)):
+        with sz3_amd.debug_flags(flag):
             sizes.append(dc.compress(conf, t.data_ptr(), pl[k].data_ptr(), cap, 0))
             o = torch.empty_like(t)
             dc.decompress(pl[k].data_ptr(), sizes[-1], o.data_ptr(), 0)
             torch.cuda.synchronize()
             outs.append(o)
-    finally:
-        sz3_amd.lib().sz3hip_debug_flags(0)
     for k in (1,):
         assert sizes[0] == sizes[k] and torch.equal(pl[0][:sizes[0]], pl[k][:sizes[k]])
         assert bool(((outs[0] == outs[k]) | (outs[0].isnan() & outs[k].isnan())).all())
@@ -219,7 +210,7 @@ def test_vector_and_scalar_level1_kernels_agree(VEC_SHAPE):
 
 @pytest.mark.parametrize("dtype,eb", [(np.float32, 1e-6), (np.float64, 1e-6)])
 def test_histogram_tail_passes_change_nothing(dtype, eb):
-    """tight bound: the interpolation codes spread over the whole alphabet. Debug flag 8192 forces the histogram pass with
+    """tight bound: the interpolation codes spread over the whole alphabet. Dbg.INTERP_HIST_BIG forces the histogram pass with
     the 16384-bin tier plus the three windowed tail passes (normally a per-context choice from the previous call's counts):
     the payload must be the same bytes as with the plain pass. (Noise of 5000 quantisation steps: a tenth of the codes lie
     beyond +-8192, none beyond the quantiser's range - lists of more than 32768 unpredictable values are not sorted.)"""
@@ -230,17 +221,14 @@ def test_histogram_tail_passes_change_nothing(dtype, eb):
     conf.cmprAlgo = sz3_amd.ALGO_INTERP
     conf.absErrorBound = eb
     res = []
-    try:
-        for flag in (0, 8192):
-            sz3_amd.lib().sz3hip_debug_flags(flag)
+    for flag in (0, sz3_amd.Dbg.INTERP_HIST_BIG):
+        with sz3_amd.debug_flags(flag):
             dc = sz3_amd.DeviceCompressor(a.size, a.dtype)
             cap = dc.payload_bound(a.size, worst_case=True)
             pl = torch.empty(cap, dtype=torch.uint8, device=dev)
             size = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, 0)
             torch.cuda.synchronize()
             res.append(pl[:size].clone())
-    finally:
-        sz3_amd.lib().sz3hip_debug_flags(0)
     assert res[0].numel() == res[1].numel() and torch.equal(res[0], res[1])
     st = dc.stats()
     assert st["n_value_outliers"] < 32768 and st["max_code_len"] > 12  # (the spread is real: thousands of distinct symbols)
@@ -250,7 +238,7 @@ def test_histogram_tail_passes_change_nothing(dtype, eb):
 def test_dense_hand_over_between_the_two_finest_levels_changes_nothing(shape, dtype, algo):
     """round 5: when the levels of stride 2 and 1 both run as level launches, the coarser one leaves its grid in a dense array and the
     finest reads its coarse points from there (no partial-line stores, no strided gather). Same payload, byte for byte, as the
-    hand-over in place (debug flag 536870912); level launches forced on these small arrays (flag 4194304); every direction order that
+    hand-over in place (Dbg.INTERP_HANDOVER_IN_PLACE); level launches forced on these small arrays (Dbg.INTERP_LEVELS_ANY_SIZE); every direction order that
     puts another axis last, linear and cubic, ragged extents, f64"""
     import torch
     dev = torch.device("cuda:0")
@@ -265,19 +253,17 @@ def test_dense_hand_over_between_the_two_finest_levels_changes_nothing(shape, dt
         conf.interpAlgo = algo
         conf.interpDirection = direction
         outs = {}
-        for flag in (4194304 | 536870912, 4194304):
+        LEVELS, IN_PLACE = sz3_amd.Dbg.INTERP_LEVELS_ANY_SIZE, sz3_amd.Dbg.INTERP_HANDOVER_IN_PLACE
+        for flag in (LEVELS | IN_PLACE, LEVELS):
             dc = sz3_amd.DeviceCompressor(a.size, a.dtype, device=0)
             dc.set_deterministic(True)
             cap = dc.payload_bound(a.size, worst_case=True)
             d_pl = torch.empty(cap, dtype=torch.uint8, device=dev)
-            sz3_amd.lib().sz3hip_debug_flags(flag)
-            try:
+            with sz3_amd.debug_flags(flag):
                 size = dc.compress(conf, d_in.data_ptr(), d_pl.data_ptr(), cap, st)
-            finally:
-                sz3_amd.lib().sz3hip_debug_flags(0)
             torch.cuda.synchronize()
             outs[flag] = d_pl[:size].cpu().numpy().copy()
-        assert np.array_equal(outs[4194304], outs[4194304 | 536870912]), "the dense hand-over changed the payload (direction %d)" % direction
+        assert np.array_equal(outs[LEVELS], outs[LEVELS | IN_PLACE]), "the dense hand-over changed the payload (direction %d)" % direction
 
 
 def test_a_one_dimensional_array_takes_any_interp_direction():

@@ -11,8 +11,8 @@ from fields import field3d
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-OLD_PACKER = 32768  # sz3hip_debug_flags: k_pack for one-byte codes as before round 6
-NO_SAMPLE = 65536   # ... the exact histogram's book (code words up to 16 bits, which both packers take; a call with a sampled book is k_pack_b's alone)
+OLD_PACKER = sz3_amd.Dbg.PACK_OLD  # sz3hip_debug_flags: k_pack for one-byte codes as before round 6
+NO_SAMPLE = sz3_amd.Dbg.CB_NO_SAMPLED  # ... the exact histogram's book (code words up to 16 bits, which both packers take; a call with a sampled book is k_pack_b's alone)
 
 
 def _conf(shape, eb):
@@ -55,7 +55,6 @@ def test_pair_table_packer_writes_the_old_packers_bytes(name, gen, eb):
     a = gen()
     n = a.size
     conf = _conf(a.shape, eb)
-    L = sz3_amd.lib()
     t = torch.from_numpy(a).to(dev)
 
     def run(flags, spec):
@@ -64,13 +63,10 @@ def test_pair_table_packer_writes_the_old_packers_bytes(name, gen, eb):
         cap = dc.payload_bound(n, worst_case=True)
         pl = torch.empty(cap, dtype=torch.uint8, device=dev)
         outs = []
-        L.sz3hip_debug_flags(flags)
-        try:
+        with sz3_amd.debug_flags(flags):
             for _ in range(3):  # (the first call of a context waits for the probe: the one-launch form — and with it k_pack_b — from the second call on)
                 size = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, 0)
                 outs.append(pl[:size].cpu().numpy().tobytes())
-        finally:
-            L.sz3hip_debug_flags(0)
         dec = torch.empty_like(t)
         dc.decompress(pl.data_ptr(), size, dec.data_ptr(), 0)
         torch.cuda.synchronize()

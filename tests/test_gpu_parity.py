@@ -457,17 +457,15 @@ def test_half_width_decoder_intermediates_and_their_overflow_path(shape, carry, 
         assert modes[2] == ((0 if overflows else 1), carry)
         assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[1], outs[2])
         assert float(np.max(np.abs(outs[0].astype(np.float64) - a.astype(np.float64)))) <= eb
-        for flags, want in ((2097152, (0, carry)), (536870912, None), (2097152 | 536870912, (0, 1 if carry else 0))):
-            L.sz3hip_debug_flags(flags)  # 2097152: full-width chain only; 536870912: the carries by their own pass
-            try:
+        NO_HALF, CARRY_PASS = sz3_amd.Dbg.DEC_NO_HALF, sz3_amd.Dbg.DEC_CARRY_PASS  # full-width chain only; the carries by their own pass
+        for flags, want in ((NO_HALF, (0, carry)), (CARRY_PASS, None), (NO_HALF | CARRY_PASS, (0, 1 if carry else 0))):
+            with sz3_amd.debug_flags(flags):
                 ref = torch.empty_like(t)
                 dc.decompress(pl.data_ptr(), n, ref.data_ptr(), 0)
                 torch.cuda.synchronize()
                 L.sz3hip_debug_decode_info(dc._h, info)
                 if want is not None:
                     assert (info[0], info[1]) == want
-            finally:
-                L.sz3hip_debug_flags(0)
             assert np.array_equal(ref.cpu().numpy(), outs[0])
 
 

@@ -46,7 +46,6 @@ def test_q16_stage1_writes_the_one_byte_kernels_bytes(shape):
     n = arrs[0].size
     eb = 1e-3
     conf = _conf(shape, eb)
-    L = sz3_amd.lib()
     ctxs = [sz3_amd.DeviceCompressor(n, np.float32), sz3_amd.DeviceCompressor(n, np.float32)]
     for d in ctxs:
         d.set_deterministic(True)
@@ -55,12 +54,9 @@ def test_q16_stage1_writes_the_one_byte_kernels_bytes(shape):
     def run(dc, arr, flags):
         t = torch.from_numpy(arr).to(dev)
         pl = torch.empty(cap, dtype=torch.uint8, device=dev)
-        L.sz3hip_debug_flags(flags)
-        try:
+        with sz3_amd.debug_flags(flags):
             size = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, 0)
             codes = dc.debug_codes(n)
-        finally:
-            L.sz3hip_debug_flags(0)
         q16 = dc.q16
         dec = torch.empty_like(t)
         dc.decompress(pl.data_ptr(), size, dec.data_ptr(), 0)
@@ -70,7 +66,7 @@ def test_q16_stage1_writes_the_one_byte_kernels_bytes(shape):
 
     for k, arr in enumerate(arrs):
         got, codes, q16 = run(ctxs[0], arr, 0)
-        ref, codes_ref, q16_ref = run(ctxs[1], arr, 8)
+        ref, codes_ref, q16_ref = run(ctxs[1], arr, sz3_amd.Dbg.K1_NO_Q16)
         assert not q16_ref
         assert q16 == (k > 0), (k, q16)
         assert np.array_equal(codes, codes_ref), "call %d: codes differ at %s" % (k, np.flatnonzero(codes != codes_ref)[:8])
@@ -97,20 +93,16 @@ def test_q16_stage1_with_listed_deltas_and_values():
     n = a.size
     eb = 1e-3
     conf = _conf(shape, eb)
-    L = sz3_amd.lib()
     out = []
-    for flags in (0, 8):
+    for flags in (0, sz3_amd.Dbg.K1_NO_Q16):
         dc = sz3_amd.DeviceCompressor(n, np.float32)
         dc.set_deterministic(True)
         cap = dc.payload_bound(n, worst_case=True)
         t = torch.from_numpy(a).to(dev)
         pl = torch.empty(cap, dtype=torch.uint8, device=dev)
-        L.sz3hip_debug_flags(flags)
-        try:
+        with sz3_amd.debug_flags(flags):
             for _ in range(2):
                 size = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, 0)
-        finally:
-            L.sz3hip_debug_flags(0)
         assert dc.q16 == (flags == 0)
         st = dc.stats()
         assert st["n_delta_outliers"] > 300

@@ -18,7 +18,8 @@ from fields import field3d, field_c4a  # noqa: E402
 from oracle_binding import make_config, oracle, oracle_compress, oracle_selection  # noqa: E402
 
 
-NO_EXIT = 1073741824  # sz3hip_debug_flags: the block stream even where the selection would hand the array to the plain Lorenzo path
+Dbg = sz3_amd.Dbg
+NO_EXIT = Dbg.BLK_NO_EXIT  # sz3hip_debug_flags: the block stream even where the selection would hand the array to the plain Lorenzo path
 
 
 @pytest.fixture(autouse=True)
@@ -213,8 +214,8 @@ def test_predictor_sets_outside_the_block_path():
 @pytest.mark.parametrize("shape", [(37, 50, 66), (12, 13, 100), (6, 6, 6), (19, 7, 40), (54, 36, 18)], ids=["ragged", "thin", "one-block", "ragged-2", "whole-groups"])
 def test_grouped_and_per_block_decoders_agree(shape):
     """blocks of 6^3 are decoded in groups of 3 x 3 x 3 per workgroup in closed form (k_blk_local3 + k_blk_decode_gf: a block inverted
-    with a zero halo, then 7 / 26 halo terms per element); debug flag 65536 takes round 3's groups of 2 x 2 x 2 with line scans through
-    a shared LDS tile, 8388608 the block-per-wave fronts: same array, bit for bit, on shapes with ragged and missing blocks in the
+    with a zero halo, then 7 / 26 halo terms per element); Dbg.BLKDEC_PER_FRONT takes round 3's groups of 2 x 2 x 2 with line scans through
+    a shared LDS tile, Dbg.BLKDEC_BLOCK_PER_WAVE the block-per-wave fronts: same array, bit for bit, on shapes with ragged and missing blocks in the
     last groups"""
     for dtype in (np.float32, np.float64):
         a = field3d(shape, dtype)
@@ -222,13 +223,11 @@ def test_grouped_and_per_block_decoders_agree(shape):
         for mask in ("L1+R", "L1+L2+R"):
             blob, _ = sz3_amd.compress(a, _conf(shape, 1e-3, *MASKS[mask]))
             outs = []
-            try:
-                for flag in (0, 4, 16, 32768, 65536, 8388608):  # (4: the one-launch decoder, then the retry a poll that gave up takes)
-                    sz3_amd.lib().sz3hip_debug_flags(flag)
+            # (FORCE_RETRY: the one-launch decoder, then the retry a poll that gave up takes)
+            for flag in (0, Dbg.BLKDEC_FORCE_RETRY, Dbg.BLKDEC_LOCAL_EXPANDED, Dbg.BLKDEC_GROUPS_3, Dbg.BLKDEC_PER_FRONT, Dbg.BLKDEC_BLOCK_PER_WAVE):
+                with sz3_amd.debug_flags(flag):
                     dec, c2 = sz3_amd.decompress(blob, dtype, shape)
                     outs.append(dec)
-            finally:
-                sz3_amd.lib().sz3hip_debug_flags(0)
             assert all(np.array_equal(outs[0], o) for o in outs[1:])
             assert float(np.max(np.abs(outs[0].astype(np.float64) - a.astype(np.float64)))) <= 1e-3
 
@@ -245,7 +244,6 @@ def test_fields_where_only_lorenzo_is_chosen_become_the_plain_stream(dtype):
     shape, eb = (60, 96, 132), 1e-3
     smooth = field3d(shape, dtype)                     # noise above the bound: regression never wins
     ramps = field_c4a(shape, seed=5).astype(dtype)     # C4a: regression wins in a share of the blocks
-    L = sz3_amd.lib()
     for a, ebx, want in ((smooth, eb, 0), (ramps, 1e-6, 2)):
         t = torch.from_numpy(a).to(dev)
         dc = sz3_amd.DeviceCompressor(a.size, dtype)
@@ -263,12 +261,9 @@ def test_fields_where_only_lorenzo_is_chosen_become_the_plain_stream(dtype):
         torch.cuda.synchronize()
         if want == 0:
             assert n1 == n2 and torch.equal(pl[0][:n1], pl[1][:n2]), "the hand-over is the plain stream itself"
-        L.sz3hip_debug_flags(NO_EXIT)
-        try:
+        with sz3_amd.debug_flags(NO_EXIT):
             n3 = dc.compress(conf, t.data_ptr(), pl[2].data_ptr(), cap, 0)
             torch.cuda.synchronize()
-        finally:
-            L.sz3hip_debug_flags(0)
         h3, _, sec3 = szh_ref.parse(pl[2][:n3].cpu().numpy().tobytes())
         assert h3["predictor"] == 2
         sel, _ = szh_ref.parse_side(h3, sec3)
@@ -304,11 +299,9 @@ def test_block_stream_with_a_wide_alphabet_on_a_reused_context():
     shape, eb = (30, 96, 256), 1e-6
     a = field3d(shape, np.float64, sigma=2e-6)
     t = torch.from_numpy(a).to(dev)
-    L = sz3_amd.lib()
     payloads = {}
-    for name, flags in (("rows", NO_EXIT), ("tiles", NO_EXIT | 67108864)):
-        L.sz3hip_debug_flags(flags)
-        try:
+    for name, flags in (("rows", NO_EXIT), ("tiles", NO_EXIT | Dbg.BLK_FIT_TILES)):
+        with sz3_amd.debug_flags(flags):
             dc = sz3_amd.DeviceCompressor(a.size, np.float64)
             conf = _conf(shape, eb, 1, 0, 1)
             cap = dc.payload_bound_conf(conf, worst_case=True)
@@ -323,8 +316,6 @@ def test_block_stream_with_a_wide_alphabet_on_a_reused_context():
                 got.append(pl[:n].cpu().numpy().tobytes())
             assert got[0] == got[1] == got[2], "the payload depends on the context's history"
             payloads[name] = got[0]
-        finally:
-            L.sz3hip_debug_flags(0)
     h, _, sec = szh_ref.parse(payloads["rows"])
     assert h["predictor"] == 2 and h["sym_count"] > 3000
     assert payloads["rows"] == payloads["tiles"]

@@ -14,7 +14,7 @@ import sz3_amd  # noqa: E402
 import szh_ref  # noqa: E402
 from fields import field1d, field2d  # noqa: E402
 from oracle_binding import make_config, oracle_compress, oracle_selection  # noqa: E402
-from test_gpu_regression import MASKS, NO_EXIT, _block_streams_wanted, _conf, _payload_of  # noqa: E402,F401  (the autouse fixture: block streams wanted)
+from test_gpu_regression import MASKS, NO_EXIT, Dbg, _block_streams_wanted, _conf, _payload_of  # noqa: E402,F401  (the autouse fixture: block streams wanted)
 
 
 def _field(shape, dtype):
@@ -46,10 +46,10 @@ def test_low_dimensional_block_stream_against_the_numpy_model(mask, dtype, shape
     assert set(np.unique(sel)) <= {0, 2}
     if mask == "L1+R":
         print(shape, "regression blocks: %.3f" % float((np.asarray(sel) == 2).mean()))
-    # the encoder without the selection pass in front (development switch 2147483648: the fit pass chooses and leaves q~ of every
+    # the encoder without the selection pass in front (development switch Dbg.BLK_NO_SELECT: the fit pass chooses and leaves q~ of every
     # element in the work array, the code pass reads it back) writes the same stream
     try:
-        sz3_amd.lib().sz3hip_debug_flags(NO_EXIT | 2147483648)
+        sz3_amd.lib().sz3hip_debug_flags(NO_EXIT | Dbg.BLK_NO_SELECT)
         blob2, _ = sz3_amd.compress(a, conf)
     finally:
         sz3_amd.lib().sz3hip_debug_flags(NO_EXIT)
@@ -120,21 +120,19 @@ def test_full_size_round_trip_of_a_long_series():
 @pytest.mark.parametrize("shape,block,eb", [((300, 517), None, 0.15), ((130, 70), 8, 0.15), ((17, 1000), 16, 1e-3), ((64, 64), 16, 0.2), ((1000, 1300), 12, 0.15)])
 def test_grouped_and_per_block_2d_decoders_agree(shape, block, eb):
     """2-D blocks of up to 16 x 16 are decoded in groups of 4 x 4 per workgroup, the whole chain of fronts in one launch
-    (k_blkn_wave2: tickets in the fronts' order, flags, closed form); debug flag 65536 takes round 3's launch per front (inner fronts
-    through a shared LDS tile, DPP row scans), 8388608 the block-per-wave fronts: same array, bit for bit, with ragged and missing
+    (k_blkn_wave2: tickets in the fronts' order, flags, closed form); Dbg.BLKDEC_PER_FRONT takes round 3's launch per front (inner fronts
+    through a shared LDS tile, DPP row scans), Dbg.BLKDEC_BLOCK_PER_WAVE the block-per-wave fronts: same array, bit for bit, with ragged and missing
     blocks in the last groups, on fields where regression blocks sit among the Lorenzo blocks"""
     for dtype in (np.float32, np.float64):
         a = field2d(shape, dtype)
         a[shape[0] // 2:, :] += 3.0
         blob, _ = sz3_amd.compress(a, _conf(shape, eb, 1, 0, 1, block=block))
         outs = []
-        try:
-            for flag in (NO_EXIT, NO_EXIT | 4, NO_EXIT | 65536, NO_EXIT | 8388608):  # (4: the retry a flag poll that gave up takes)
-                sz3_amd.lib().sz3hip_debug_flags(flag)
+        # (FORCE_RETRY: the retry a flag poll that gave up takes)
+        for flag in (NO_EXIT, NO_EXIT | Dbg.BLKDEC_FORCE_RETRY, NO_EXIT | Dbg.BLKDEC_PER_FRONT, NO_EXIT | Dbg.BLKDEC_BLOCK_PER_WAVE):
+            with sz3_amd.debug_flags(flag):
                 dec, c2 = sz3_amd.decompress(blob, dtype, shape)
                 outs.append(dec)
-        finally:
-            sz3_amd.lib().sz3hip_debug_flags(0)
         assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2])
         assert float(np.max(np.abs(outs[0].astype(np.float64) - a.astype(np.float64)))) <= eb
         h, o, sec = szh_ref.parse(_payload_of(blob))
@@ -165,19 +163,16 @@ def test_low_dimensional_fields_where_only_lorenzo_is_chosen_become_the_plain_st
 
 @pytest.mark.parametrize("n,block,dtype", [(1 << 20, None, np.float32), (100003, 100, np.float32), (40000, 7, np.float64), (100003, 104, np.float64), (5001, 8, np.float32)])
 def test_1d_fit_by_rows_of_lanes_and_by_waves_agree(n, block, dtype):
-    """1-D: four blocks per wave (a block per DPP row of 16 lanes, k_blkn_fit_rows) against a wave per block (debug flag 134217728):
+    """1-D: four blocks per wave (a block per DPP row of 16 lanes, k_blkn_fit_rows) against a wave per block (Dbg.BLK_1D_WAVE_PER_BLOCK):
     the same choices and the same stream (the sums are taken in a different order: coefficients could differ in the last bit of a
     double, not on these fields)"""
     a = field1d(n, dtype)
     conf = _conf((n,), 1e-3, 1, 0, 1, block=block)
     blobs = []
-    try:
-        for flag in (NO_EXIT, NO_EXIT | 134217728):
-            sz3_amd.lib().sz3hip_debug_flags(flag)
+    for flag in (NO_EXIT, NO_EXIT | Dbg.BLK_1D_WAVE_PER_BLOCK):
+        with sz3_amd.debug_flags(flag):
             blob, _ = sz3_amd.compress(a, conf)
             blobs.append(_payload_of(blob))
-    finally:
-        sz3_amd.lib().sz3hip_debug_flags(0)
     h0, _, s0 = szh_ref.parse(blobs[0])
     h1, _, s1 = szh_ref.parse(blobs[1])
     sel0, sel1 = np.asarray(szh_ref.parse_side(h0, s0)[0]), np.asarray(szh_ref.parse_side(h1, s1)[0])
@@ -186,12 +181,9 @@ def test_1d_fit_by_rows_of_lanes_and_by_waves_agree(n, block, dtype):
     # ... and the decoder's Lorenzo pass: rows of lanes (blocks of up to 128 values, a multiple of 8) against a wave per block
     blob, _ = sz3_amd.compress(a, conf)
     outs = []
-    try:
-        for flag in (0, 134217728):
-            sz3_amd.lib().sz3hip_debug_flags(flag)
+    for flag in (0, Dbg.BLK_1D_WAVE_PER_BLOCK):
+        with sz3_amd.debug_flags(flag):
             outs.append(sz3_amd.decompress(blob, dtype, (n,))[0])
-    finally:
-        sz3_amd.lib().sz3hip_debug_flags(0)
     assert outs[0].tobytes() == outs[1].tobytes()
     assert float(np.max(np.abs(outs[0].astype(np.float64) - a.astype(np.float64)))) <= 1e-3
 
@@ -239,17 +231,17 @@ def test_1d_second_order_block_stream_against_the_numpy_model(mask, dtype, n, eb
     allowed = {i for i, b in enumerate(MASKS[mask]) if b} | {0}  # (0: the fallback of a regression that is not valid)
     assert set(np.unique(sel)) <= allowed
     print(n, mask, "ratio %.2f" % ratio, "shares L1 %.3f L2 %.3f R %.3f" % tuple(float((sel == k).mean()) for k in range(3)))
-    # sets of Lorenzo members only take a pass of their own for the choices (k_blkn_sel12) and code straight from the array; debug flag
-    # 134217728 sends them through the general fit pass (q~ of every element through the work array): same stream
+    # sets of Lorenzo members only take a pass of their own for the choices (k_blkn_sel12) and code straight from the array;
+    # Dbg.BLK_1D_WAVE_PER_BLOCK sends them through the general fit pass (q~ of every element through the work array): same stream
     try:
-        sz3_amd.lib().sz3hip_debug_flags(NO_EXIT | 134217728)
+        sz3_amd.lib().sz3hip_debug_flags(NO_EXIT | Dbg.BLK_1D_WAVE_PER_BLOCK)
         blob2, _ = sz3_amd.compress(a, conf)
     finally:
         sz3_amd.lib().sz3hip_debug_flags(NO_EXIT)
     assert _payload_of(blob2) == _payload_of(blob)
     # ... and the decoder by rows of lanes (blocks of up to 128 values, a multiple of 8) against a wave per block: the same array
     try:
-        sz3_amd.lib().sz3hip_debug_flags(NO_EXIT | 134217728)
+        sz3_amd.lib().sz3hip_debug_flags(NO_EXIT | Dbg.BLK_1D_WAVE_PER_BLOCK)
         dec2, _ = sz3_amd.decompress(blob, dtype, (n,))
     finally:
         sz3_amd.lib().sz3hip_debug_flags(NO_EXIT)
@@ -340,7 +332,7 @@ def test_2d_second_order_block_stream_against_the_numpy_model(mask, dtype, shape
     print(shape, mask, "ratio %.2f" % ratio, "shares L1 %.3f L2 %.3f R %.3f" % tuple(float((sel == k).mean()) for k in range(3)))
     # the encoder without the selection pass in front (the fit pass chooses, q~ of every element through the work array): same stream
     try:
-        sz3_amd.lib().sz3hip_debug_flags(NO_EXIT | 2147483648)
+        sz3_amd.lib().sz3hip_debug_flags(NO_EXIT | Dbg.BLK_NO_SELECT)
         blob2, _ = sz3_amd.compress(a, conf)
     finally:
         sz3_amd.lib().sz3hip_debug_flags(NO_EXIT)

@@ -12,9 +12,9 @@ import szh_ref
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-NO_SAMPLE = 65536      # sz3hip_debug_flags: no sampled book (the exact histogram's book, as before round 6)
-NO_Q16 = 8             # ... the one-byte kernel instead of its 16-bit form
-SAMPLE_APART = 4194304  # ... the 16-bit form without the sampling workgroups: the sample as a launch of its own
+NO_SAMPLE = sz3_amd.Dbg.CB_NO_SAMPLED  # sz3hip_debug_flags: no sampled book (the exact histogram's book, as before round 6)
+NO_Q16 = sz3_amd.Dbg.K1_NO_Q16  # ... the one-byte kernel instead of its 16-bit form
+SAMPLE_APART = sz3_amd.Dbg.K1_NO_SAMP_IN_LAUNCH  # ... the 16-bit form without the sampling workgroups: the sample as a launch of its own
 
 
 def _conf(shape, eb):
@@ -27,12 +27,8 @@ def _conf(shape, eb):
 
 
 def _run(dc, t, conf, cap, pl, flags=0):
-    L = sz3_amd.lib()
-    L.sz3hip_debug_flags(flags)
-    try:
+    with sz3_amd.debug_flags(flags):
         size = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, 0)
-    finally:
-        L.sz3hip_debug_flags(0)
     return pl[:size].cpu().numpy().tobytes()
 
 

@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of round 6's small-array forms: the side section of a block-composed stream built by ONE workgroup (k_blk_side_small, up to
-16384 blocks) against the eight launches it replaces (sz3hip_debug_flags(2048)), and the code book of a 257 .. 640-symbol alphabet built by
+16384 blocks) against the eight launches it replaces (Dbg.BLK_SIDE_8_LAUNCHES), and the code book of a 257 .. 640-symbol alphabet built by
 k_codebook<0> alone against the wide form (k_cb_compact + k_codebook<1> + k_cb_assign, which a first call launches beside it: part_hint -1) —
 byte for byte, on 1-D, 2-D, 3-D and 4-D arrays, with and without regression blocks."""
 import numpy as np
@@ -11,25 +11,24 @@ from fields import field1d, field2d, field3d, field4d
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-EIGHT_LAUNCHES = 2048  # sz3hip_debug_flags: the side section's kernels one by one whatever the block count
-BOTH_BOOKS = 131072    # ... both code book launches every call (the one whose alphabet it is builds the book)
+Dbg = sz3_amd.Dbg
+# sz3hip_debug_flags: the side section's kernels one by one whatever the block count (the bit is also BLK_RANK_3_LAUNCHES, which matters
+# here too: the rank pass in front of the side section then goes launch by launch as well)
+EIGHT_LAUNCHES = Dbg.BLK_SIDE_8_LAUNCHES | Dbg.BLK_RANK_3_LAUNCHES
+BOTH_BOOKS = Dbg.CTX_NO_MEMORY  # ... both code book launches every call (the one whose alphabet it is builds the book)
 
 
 def _payloads(a, conf, flags, calls=3):
     dev = torch.device("cuda:0")
-    L = sz3_amd.lib()
     t = torch.from_numpy(a).to(dev)
     dc = sz3_amd.DeviceCompressor(a.size, a.dtype)
     cap = max(dc.payload_bound(a.size, worst_case=True), dc.payload_bound_conf(conf))
     pl = torch.empty(cap, dtype=torch.uint8, device=dev)
     outs = []
-    L.sz3hip_debug_flags(flags)
-    try:
+    with sz3_amd.debug_flags(flags):
         for _ in range(calls):
             size = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, 0)
             outs.append(pl[:size].cpu().numpy().tobytes())
-    finally:
-        L.sz3hip_debug_flags(0)
     dec = torch.empty_like(t)
     dc.decompress(pl.data_ptr(), size, dec.data_ptr(), 0)
     torch.cuda.synchronize()

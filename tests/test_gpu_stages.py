@@ -128,15 +128,14 @@ def test_fast_kernel_equals_generic(shape, dtype):
     a = (field3d(shape, dtype) if len(shape) == 3 else field4d(shape, dtype))
     a[tuple(s // 2 for s in shape)] = np.nan
     a[tuple(s // 3 for s in shape)] = 4e4
-    try:
-        sz3_amd.lib().sz3hip_debug_flags(64)          # two-byte codes on both sides (the narrow mode has its own test)
-        sz3_amd.lib().sz3hip_debug_force_generic(1)
-        c0, p0, d0, s0 = _roundtrip_device(a, 1e-3)
-        sz3_amd.lib().sz3hip_debug_force_generic(0)
-        c1, p1, d1, s1 = _roundtrip_device(a, 1e-3)
-    finally:
-        sz3_amd.lib().sz3hip_debug_force_generic(0)
-        sz3_amd.lib().sz3hip_debug_flags(0)
+    with sz3_amd.debug_flags(sz3_amd.Dbg.K1_NO_NARROW):  # two-byte codes on both sides (the narrow mode has its own test)
+        try:
+            sz3_amd.lib().sz3hip_debug_force_generic(1)
+            c0, p0, d0, s0 = _roundtrip_device(a, 1e-3)
+            sz3_amd.lib().sz3hip_debug_force_generic(0)
+            c1, p1, d1, s1 = _roundtrip_device(a, 1e-3)
+        finally:
+            sz3_amd.lib().sz3hip_debug_force_generic(0)
     assert np.array_equal(c0, c1)
     assert s0["n_value_outliers"] == s1["n_value_outliers"] and s0["n_delta_outliers"] == s1["n_delta_outliers"]
     h0, _, sec0 = szh_ref.parse(p0)
@@ -150,11 +149,8 @@ def test_narrow_and_wide_code_paths_agree():
     a = field3d((24, 20, 256))
     c1, p1, d1, s1 = _roundtrip_device(a, 1e-3)
     assert s1["narrow_codes"] == 1
-    try:
-        sz3_amd.lib().sz3hip_debug_flags(64)   # forbid the narrow mode
+    with sz3_amd.debug_flags(sz3_amd.Dbg.K1_NO_NARROW):  # forbid the narrow mode
         c0, p0, d0, s0 = _roundtrip_device(a, 1e-3)
-    finally:
-        sz3_amd.lib().sz3hip_debug_flags(0)
     assert s0["narrow_codes"] == 0
     assert np.array_equal(c0, c1) and np.array_equal(p0, p1) and np.array_equal(d0, d1)
     # rough data: the probe must refuse the narrow mode (deltas of a few hundred lattice steps)
@@ -261,7 +257,7 @@ def test_small_quantiser_lorenzo(shape, dtype, qb, eb, sigma, nan):
 
 def test_two_class_code_book_and_its_fallback():
     """wide alphabet (> 4096 symbols): the two-class code book (frequent symbols one by one + one rare class) and, forced by
-    debug flag 1024, the one-class construction it falls back to both give a decodable stream within the bound; the class
+    Dbg.CB_ONE_CLASS, the one-class construction it falls back to both give a decodable stream within the bound; the class
     form may cost at most 0.5 % of the size"""
     a = field3d((128, 160, 192))
     dev = torch.device("cuda:0")
@@ -270,9 +266,8 @@ def test_two_class_code_book_and_its_fallback():
     cap = dc.payload_bound(a.size)
     out = torch.empty_like(t)
     sizes, lens = [], []
-    try:
-        for flag in (0, 1024):
-            sz3_amd.lib().sz3hip_debug_flags(flag)
+    for flag in (0, sz3_amd.Dbg.CB_ONE_CLASS):
+        with sz3_amd.debug_flags(flag):
             pl = torch.empty(cap, dtype=torch.uint8, device=dev)
             conf = sz3_amd.Config(*a.shape)
             conf.cmprAlgo = sz3_amd.ALGO_INTERP
@@ -285,8 +280,6 @@ def test_two_class_code_book_and_its_fallback():
             assert h["sym_count"] > 4096 and szh_ref.kraft(sec["lens"]) <= 1.0
             sizes.append(n)
             lens.append(sec["lens"])
-    finally:
-        sz3_amd.lib().sz3hip_debug_flags(0)
     assert not np.array_equal(lens[0], lens[1])          # the two constructions really differ ...
     assert sizes[1] <= sizes[0] <= 1.005 * sizes[1]       # ... and the class form costs next to nothing
 
@@ -427,9 +420,8 @@ def test_every_element_a_listed_delta(shape):
     dev = torch.device("cuda:0")
     t = torch.from_numpy(a).to(dev)
     res = []
-    try:
-        for flag in (0, 2097152):
-            sz3_amd.lib().sz3hip_debug_flags(flag)
+    for flag in (0, sz3_amd.Dbg.DEC_NO_HALF):
+        with sz3_amd.debug_flags(flag):
             dc = sz3_amd.DeviceCompressor(a.size, np.float32)
             cap = dc.payload_bound(a.size, worst_case=True)
             pl = torch.empty(cap, dtype=torch.uint8, device=dev)
@@ -445,8 +437,6 @@ def test_every_element_a_listed_delta(shape):
             dc.decompress(pl.data_ptr(), size, out.data_ptr(), 0)
             torch.cuda.synchronize()
             res.append(out.cpu().numpy())
-    finally:
-        sz3_amd.lib().sz3hip_debug_flags(0)
     assert np.array_equal(res[0], res[1])
     assert np.max(np.abs(res[0].astype(np.float64) - a.astype(np.float64))) <= 1e-4
 
@@ -727,22 +717,21 @@ def test_outlier_lists_beyond_the_sort_workgroups_reach_are_sorted_by_finish():
 
 
 def test_wide_code_book_with_and_without_the_compaction_launch():
-    """Round 5: the wide code book's keys are compacted by k_cb_compact over the whole chip in front of the book's launch; debug flag 1
+    """Round 5: the wide code book's keys are compacted by k_cb_compact over the whole chip in front of the book's launch; Dbg.CB_COMPACT_IN_WG
     keeps the compaction inside the book's workgroup. Same book, same payload — on an interpolation stream (thousands of symbols, the
     two-class construction), on a rough Lorenzo stream, and across the repeat of stage 2 that a mispredicted book form causes."""
     dev = torch.device("cuda:0")
-    L = sz3_amd.lib()
     a = field3d((96, 96, 96), seed=4)
     rough = (a + np.random.default_rng(2).normal(0, 0.2, a.shape)).astype(np.float32)
     cases = [(a, sz3_amd.ALGO_INTERP, 1e-5), (rough, sz3_amd.ALGO_LORENZO_REG, 1e-3), (a, sz3_amd.ALGO_INTERP, 1e-2)]
     outs = {}
-    for flag in (0, 1):
+    COMPACT_IN_WG = int(sz3_amd.Dbg.CB_COMPACT_IN_WG)
+    for flag in (0, COMPACT_IN_WG):
         dc = sz3_amd.DeviceCompressor(a.size, np.float32)   # one context through all cases: small and wide books alternate (mispredicted forms)
         dc.set_deterministic(True)
         cap = dc.payload_bound(a.size, worst_case=True)
         pl = torch.empty(cap, dtype=torch.uint8, device=dev)
-        L.sz3hip_debug_flags(flag)
-        try:
+        with sz3_amd.debug_flags(flag):
             for k, (arr, algo, eb) in enumerate(cases + cases[:1]):
                 conf = sz3_amd.Config(*arr.shape)
                 conf.cmprAlgo = algo
@@ -755,7 +744,5 @@ def test_wide_code_book_with_and_without_the_compaction_launch():
                 dc.decompress(pl.data_ptr(), size, o.data_ptr(), 0)
                 torch.cuda.synchronize()
                 assert float((o.double() - t.double()).abs().max()) <= eb
-        finally:
-            L.sz3hip_debug_flags(0)
     for k in range(4):
-        assert outs[(0, k)] == outs[(1, k)], "case %d: payloads differ" % k
+        assert outs[(0, k)] == outs[(COMPACT_IN_WG, k)], "case %d: payloads differ" % k

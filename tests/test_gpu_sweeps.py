@@ -10,6 +10,8 @@ import sys
 
 import pytest
 
+import sz3_amd
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -17,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run(tool, seed, n, flags=None):
     env = dict(os.environ, SEED=str(seed), N=str(n))
     if flags is not None:
-        env["DBG_FLAGS"] = str(flags)
+        env["DBG_FLAGS"] = str(int(flags))  # (the checks read a number)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "checks", tool)], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
@@ -36,8 +38,8 @@ def test_interp_sweep(seed):
 
 
 def test_interp_sweep_through_the_level_kernels():
-    """debug flag 4194304: every level of every 3-D case runs in the level kernels (the sweep's arrays are below their size)"""
-    out = _run("interp_sweep.py", 13, 40, flags=4194304)
+    """Dbg.INTERP_LEVELS_ANY_SIZE: every level of every 3-D case runs in the level kernels (the sweep's arrays are below their size)"""
+    out = _run("interp_sweep.py", 13, 40, flags=sz3_amd.Dbg.INTERP_LEVELS_ANY_SIZE)
     assert "mismatches: 0" in out, out[-3000:]
 
 

@@ -1,4 +1,4 @@
-"""8192^2 f32 at 0.15 (VERDICT round 3, item 4's 2-D figure) through the 2-D block decoders (debug flags 0 / 65536): bit for bit the
+"""8192^2 f32 at 0.15 (VERDICT round 3, item 4's 2-D figure) through the 2-D block decoders (debug flags 0 / Dbg.BLKDEC_PER_FRONT): bit for bit the
 same, and the decompress time of each (device-resident, events)"""
 import sys, os, time
 import numpy as np
@@ -18,7 +18,8 @@ conf.absErrorBound = eb
 conf.lorenzo, conf.lorenzo2, conf.regression = 1, 0, 1
 blob, _ = sz3_amd.compress(a, conf)
 outs = {}
-for flag in (0, 65536, 0, 65536):
+PER_FRONT = int(sz3_amd.Dbg.BLKDEC_PER_FRONT)
+for flag in (0, PER_FRONT, 0, PER_FRONT):
     sz3_amd.lib().sz3hip_debug_flags(flag)
     out = np.empty_like(a)
     for _ in range(3):

@@ -1,4 +1,4 @@
-"""the C4a slab through the 3-D block decoders (debug flags 0 / 65536): the same array bit for bit; ctl[1] of k_blk_wave3 is not raised
+"""the C4a slab through the 3-D block decoders (debug flags 0 / Dbg.BLKDEC_PER_FRONT): the same array bit for bit; ctl[1] of k_blk_wave3 is not raised
 (the output would differ); a few repetitions, since the exchange between groups is a matter of timing"""
 import sys, os
 import numpy as np
@@ -17,7 +17,7 @@ conf.lorenzo, conf.lorenzo2, conf.regression = 1, int(os.environ.get("L2", "0"))
 blob, _ = sz3_amd.compress(a, conf)
 outs = []
 for rep in range(4):
-    for flag in (0, 65536):
+    for flag in (0, sz3_amd.Dbg.BLKDEC_PER_FRONT):
         sz3_amd.lib().sz3hip_debug_flags(flag)
         dec, _ = sz3_amd.decompress(blob, dtype, shape)
         outs.append(dec)

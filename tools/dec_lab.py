@@ -11,7 +11,7 @@ a = field3d((S, S, S)); dev = torch.device("cuda:0")
 d_in = torch.from_numpy(a).to(dev)
 stream = torch.cuda.current_stream().cuda_stream
 name = os.path.basename(os.environ.get("SZ3HIP_LIB", "default"))
-FLAGS = [int(x) for x in sys.argv[1:]] or [0]   # sz3hip_debug_flags values to time (2: the one-symbol table instead of the multi-symbol one)
+FLAGS = [int(x) for x in sys.argv[1:]] or [0]   # sz3hip_debug_flags values to time, the numbers of sz3_amd.Dbg (2 = Dbg.DEC_MULTI_SYM: the multi-symbol table, lab build)
 for flag, (label, algo, eb) in [(f, c) for f in FLAGS for c in (("C2", sz3_amd.ALGO_LORENZO_REG, 1e-3), ("C3", sz3_amd.ALGO_INTERP_LORENZO, 1e-4))]:
     sz3_amd.lib().sz3hip_debug_flags(0)
     conf = sz3_amd.Config(S, S, S); conf.cmprAlgo = algo; conf.regression = 0; conf.absErrorBound = eb

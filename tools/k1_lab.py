@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A/B timings of stage 1 (the predictor kernel) across builds of the kernels: SZ3HIP_LIB=<variant .so> python tools/k1_lab.py [flags...]
-(flags = sz3hip_debug_flags values; with a LAB_ABLATE build 1 = no histogram atomics, 2 = no code stores: results are wrong)."""
+(flags = sz3hip_debug_flags values, the numbers of sz3_amd.Dbg / include/sz3hip_debug.h; with a LAB_ABLATE build 1 = Dbg.K1_LAB_NO_HIST, no histogram
+atomics, 2 = Dbg.K1_NO_CODE_STORES, no code stores: results are wrong)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
