@@ -162,6 +162,24 @@ size_t sz3hip_compress_from_device(const sz3hip_config *conf, int dataType, cons
                                    void *stream);
 int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, void *d_out, const int64_t *strides,
                                 void *stream);
+/* Coarse decode: every 2^level-th point of a stream, bit for bit what a full decode puts at those positions. The
+ * interpolation predictor is multilevel: a point whose coordinates are all multiples of 2^k is final before the levels of stride 2^(k-1)
+ * and finer run, so a preview at 1/2, 1/4, 1/8 ... resolution needs neither the full-size array nor the finest (most expensive) levels.
+ * sz3hip_coarse_dims: the coarse array's extents, ((dims[i] - 1) >> level) + 1 for each of conf->N extents, slowest first (extents of 1
+ * are kept), into dims_out[conf->N]. A pure function: no device. level outside 0 .. 30, N outside 1 .. 4 or an extent of 0: SZ3HIP_EINVAL.
+ * sz3hip_decompress_coarse_to_device: sz3hip_decompress_to_device for the coarse array. conf is overwritten from the trailer and stays
+ * the FULL array's Config; d_out is a view of sz3hip_coarse_dims(conf, level) extents (the caller learns them from sz3hip_peek_config);
+ * strides, pointer and stream rules are sz3hip_decompress_to_device's. SZ3HIP_FLOAT and SZ3HIP_DOUBLE; the integer element types are
+ * SZ3HIP_EUNSUPPORTED. Level 0 is sz3hip_decompress_to_device itself. Every container that call decodes is decoded:
+ *  - fast path, a single-stream interpolation container (this library's id 17 or a stock ALGO_INTERP stream): the codes and raw values of
+ *    the coarse points are gathered and the level kernels run on the compact array — a contiguous output is written in place, a strided one
+ *    through the slot's buffer and the strided scatter; nothing of full size is written (the Huffman stage still decodes every code);
+ *  - everything else (Lorenzo and block streams, ALGO_NOPRED, ALGO_LOSSLESS, the stock 1-D chain, conf->openmp slabs and pipelined
+ *    pieces): the full array is decoded as sz3hip_decompress_to_device does, into a scratch array of FULL size that the library allocates
+ *    in device memory for the call, and the coarse view of it is gathered by the strided gather kernel. This path needs that much HBM. */
+int sz3hip_coarse_dims(const sz3hip_config *conf, int level, uint64_t *dims_out);
+int sz3hip_decompress_coarse_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, void *d_out,
+                                       const int64_t *strides, void *stream);
 /* (test and measurement hook) the strided gather alone: the view (N extents, element strides) of d_in into the contiguous d_out on stream,
  * integers widened to f64 as the compress call does; asynchronous */
 int sz3hip_debug_gather(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream);
@@ -264,6 +282,13 @@ int sz3hip_compress_device(sz3hip_ctx *ctx, const sz3hip_config *conf, const voi
                            size_t *payload_size, void *stream);
 /* inverse: payload (device) -> d_out (device, n elements). Synchronises once to read the 160-byte header. */
 int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, void *d_out, void *stream);
+/* the same for every 2^level-th point of an interpolation payload (predictor id 1; see sz3hip_coarse_dims above): d_out receives
+ * prod(((dims[i] - 1) >> level) + 1) elements, contiguous, bit for bit the full decode's values at those points. Header parse and Huffman
+ * stage are sz3hip_decompress_device's; then the coarse points' codes are gathered into a buffer of max_n / 2 + 8 codes that the
+ * context's first coarse call allocates and the context keeps (later calls allocate nothing), and the level kernels run on the compact
+ * array. Level 0 is sz3hip_decompress_device itself; a level outside 0 .. 30 is SZ3HIP_EINVAL. Any other predictor: SZ3HIP_EUNSUPPORTED —
+ * a device context has no full-size scratch of its own; sz3hip_decompress_coarse_to_device decodes every container. */
+int sz3hip_decompress_device_coarse(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, void *d_out, void *stream);
 
 /* diagnostics of the last compress on this ctx (valid after sz3hip_compress_finish) */
 typedef struct sz3hip_stats {

@@ -210,6 +210,12 @@ def lib():
     L.sz3hip_decompress_to_device.restype = C.c_int
     L.sz3hip_decompress_to_device.argtypes = [P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, P(C.c_int64), C.c_void_p]
     L.sz3hip_peek_config.argtypes = [P(_CConfig), C.c_void_p, C.c_size_t]
+    L.sz3hip_coarse_dims.restype = C.c_int
+    L.sz3hip_coarse_dims.argtypes = [P(_CConfig), C.c_int, P(C.c_uint64)]
+    L.sz3hip_decompress_coarse_to_device.restype = C.c_int
+    L.sz3hip_decompress_coarse_to_device.argtypes = [P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, P(C.c_int64), C.c_void_p]
+    L.sz3hip_decompress_device_coarse.restype = C.c_int
+    L.sz3hip_decompress_device_coarse.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
     L.sz3hip_verify_device.restype = C.c_int
     L.sz3hip_verify_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), C.c_void_p, P(C.c_int64), C.c_double,
                                        P(_CVerifyStats), C.c_void_p]
@@ -511,6 +517,42 @@ def decompress(blob, dtype, shape=None, out=None, device=None, stream=None):
     return dec.reshape(shape), conf
 
 
+def coarse_dims(conf, level):
+    """extents of the array of every 2**level-th point of conf's array (sz3hip_coarse_dims): ``len(range(0, D, 2**level))`` per extent,
+    slowest first, extents of 1 kept. Needs no device."""
+    out = (C.c_uint64 * 4)()
+    _check(lib().sz3hip_coarse_dims(C.byref(conf._c), int(level), out))
+    return tuple(int(out[i]) for i in range(conf.N))
+
+
+def decompress_coarse(blob, dtype, level, out=None, device=None, stream=None):
+    """Every 2**level-th point of a container, bit for bit what ``decompress(blob, dtype, device=...)[0][::2**level, ...]`` holds, without
+    the full-size array where the container is a single interpolation stream (sz3hip_decompress_coarse_to_device). Device only:
+    `device=` allocates a tensor of coarse_dims(conf, level) there, or `out=` is a tensor of that shape on a HIP device, also a view.
+    float32 / float64. Returns (tensor, Config) — the Config is the FULL array's. `stream` as for decompress."""
+    blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
+    npdt = _np_dtype(dtype)
+    dt = _dtype_id(npdt)
+    if out is None and device is None:
+        raise ValueError("decompress_coarse decodes into device memory: pass device= or out=")
+    if out is not None and not _gpu_tensor(out):
+        raise ValueError("out must be a tensor on a HIP device")
+    if dt > 1:  # (the library's own refusal, before anything is parsed or allocated)
+        _check(lib().sz3hip_decompress_coarse_to_device(C.byref(Config(1)._c), dt, blob.ctypes.data, blob.size, int(level), None, None, None))
+    conf = Config(1)
+    _check(lib().sz3hip_peek_config(C.byref(conf._c), blob.ctypes.data, blob.size))
+    cd = coarse_dims(conf, level)
+    import torch
+    if out is None:
+        out = torch.empty(cd, dtype=getattr(torch, npdt.name), device=device)
+    if _np_dtype(out.dtype) != npdt or tuple(out.shape) != cd:
+        raise ValueError("out must be a %s tensor of shape %s" % (npdt, cd))
+    strides = (C.c_int64 * len(cd))(*[int(st) for st in out.stride()])
+    _check(lib().sz3hip_decompress_coarse_to_device(C.byref(conf._c), dt, blob.ctypes.data, blob.size, int(level), out.data_ptr(), strides,
+                                                    _stream_handle(out.device, stream)))
+    return out, conf
+
+
 class VerifyStats(dict):
     """the fields of sz3hip_verify_stats (include/sz3hip.h), as items and as attributes"""
     __getattr__ = dict.__getitem__
@@ -637,6 +679,10 @@ class DeviceCompressor:
 
     def decompress(self, d_payload, size, d_out, stream=0):
         _check(lib().sz3hip_decompress_device(self._h, d_payload, int(size), d_out, stream))
+
+    def decompress_coarse(self, d_payload, size, level, d_out, stream=0):
+        """every 2**level-th point of an interpolation payload into d_out (prod(coarse_dims) elements, contiguous)"""
+        _check(lib().sz3hip_decompress_device_coarse(self._h, d_payload, int(size), int(level), d_out, stream))
 
     def stats(self):
         st = _CStats()

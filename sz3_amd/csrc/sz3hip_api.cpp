@@ -219,7 +219,7 @@ static void ctx_free(sz3hip_ctx *c) {
                     c->d_chunk_words, c->d_chunk_off, c->d_carry, c->d_state, c->d_tables, c->d_segtot, c->d_minmax, c->d_samples, c->d_trial_work, c->d_trial_codes,
                     c->d_trial, c->d_passes, c->d_np,  // (d_trial_counters / d_trial_hist live inside d_trial's block)
                     c->d_blk_sel, c->d_blk_coef, c->d_blk_rank, c->d_blk_comp, c->d_blk_side, c->d_blk_counters,
-                    c->bk[1].enc, c->bk[1].lens, c->bk[1].info, c->d_seg_bits, c->d_seg_base, c->d_half32, c->d_sub_bits, c->d_fuse_scratch};
+                    c->bk[1].enc, c->bk[1].lens, c->bk[1].info, c->d_seg_bits, c->d_seg_base, c->d_half32, c->d_sub_bits, c->d_fuse_scratch, c->d_coarse_codes};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (c->book_stream) {
@@ -2212,12 +2212,24 @@ int szi_stock_export(sz3hip_ctx *ctx, const szg_geom *g, const uint64_t *d_blk_b
 }
 int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom *g, const uint64_t *d_blk_base, const uint16_t *d_em,
                      const void *d_unpred, uint64_t n_unpred, uint32_t *d_tile_cnt, uint64_t *d_tile_base, uint64_t *d_vout_idx, void *d_vout_val,
-                     uint32_t *d_bad, void *d_out, void *stream) {
+                     uint32_t *d_bad, void *d_out, void *stream, int coarse_level) {
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
-    uint64_t num = 1;
-    for (int i = 0; i < p->N; i++) num *= p->dims[i];
+    uint64_t num = 1, nc = 1;
+    for (int i = 0; i < p->N; i++) {
+        num *= p->dims[i];
+        nc *= ((p->dims[i] - 1) >> coarse_level) + 1;
+    }
     if (num > ctx->max_n) return fail(SZ3HIP_EINVAL, "array exceeds the context capacity");
+    if (coarse_level > 0) {  // (d_out: the coarse grid. The code buffer: as in sz3hip_decompress_device_coarse)
+        if (p->anchor_stride & (p->anchor_stride - 1)) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (anchor stride)");
+        if (!ctx->d_coarse_codes) {
+            const uint64_t cap = ctx->max_n / 2 + 8;
+            HIPCHK(hipMalloc((void **)&ctx->d_coarse_codes, (cap + 64) * 2));
+            ctx->coarse_codes_cap = cap;
+        }
+        if (nc > ctx->coarse_codes_cap) return fail(SZ3HIP_EINVAL, "the coarse grid exceeds the context capacity");
+    }
     HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
     if (szk_launch_stock_to_elem(ctx->dtype, g, d_blk_base, d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, ctx->d_codes, d_vout_idx, d_vout_val, d_bad, s))
         return fail(SZ3HIP_EHIP, "stock import kernels failed");
@@ -2233,7 +2245,10 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
     ip.eb = p->eb;
     ip.radius = p->radius;
     // (the lists are the caller's own arrays: handed over as offsets from a null base)
-    if (szk_launch_interp_decompress(ctx->dtype, &ip, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, ctx->d_codes, d_out, s))
+    if (coarse_level > 0
+            ? szk_launch_interp_decompress_coarse(ctx->dtype, &ip, coarse_level, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred,
+                                                  ctx->d_codes, ctx->d_coarse_codes, d_out, s)
+            : szk_launch_interp_decompress(ctx->dtype, &ip, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, ctx->d_codes, d_out, s))
         return fail(SZ3HIP_EHIP, "interpolation decoder launch failed");
     uint32_t bad = 0;
     HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
@@ -2282,8 +2297,9 @@ extern "C" int sz3hip_debug_decode_info(sz3hip_ctx *ctx, uint32_t *out4) {
     return 0;
 }
 
-extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, void *d_out,
-                                        void *stream) {
+// sz3hip_decompress_device (level 0) and sz3hip_decompress_device_coarse (level >= 1: an interpolation payload's points at multiples of
+// 2^level) share the header's parse and the Huffman stage; they differ in the reconstruction alone
+static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, void *d_out, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
     ctx->blk_pre_cleared = false;  // (a block stream's decoder counts in the same counter block)
@@ -2325,6 +2341,21 @@ extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, 
     szh_offsets o;
     szk_host_offsets(&h, &o);
     if (o.end > payload_size || h.payload_bytes != o.end) return fail(SZ3HIP_EFORMAT, "truncated SZH1 payload");
+    if (level > 0) {
+        if (h.predictor != 1)
+            return fail(SZ3HIP_EUNSUPPORTED, "sz3hip_decompress_device_coarse reads interpolation payloads only (this one's predictor id is %d): a device context has "
+                        "no full-size scratch of its own — sz3hip_decompress_coarse_to_device decodes every container", h.predictor);
+        if (h.ndim < 1 || h.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
+        if (h.anchor_stride & (h.anchor_stride - 1)) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header (anchor stride %llu is no power of two)", (unsigned long long)h.anchor_stride);
+        if (!ctx->d_coarse_codes) {  // (the context's first coarse call; kept: later calls allocate nothing)
+            const uint64_t cap = ctx->max_n / 2 + 8;
+            HIPCHK(hipMalloc((void **)&ctx->d_coarse_codes, (cap + 64) * 2));
+            ctx->coarse_codes_cap = cap;
+        }
+        uint64_t nc = 1;
+        for (int i = 0; i < 4; i++) nc *= ((h.dims[i] - 1) >> level) + 1;
+        if (nc > ctx->coarse_codes_cap) return fail(SZ3HIP_EINVAL, "the coarse grid exceeds the context capacity");
+    }
     const uint8_t *pl = (const uint8_t *)d_payload;
     szk_blk_params bp;
     szk_blk_scratch sc;
@@ -2477,8 +2508,12 @@ extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, 
         ip.beta = h.interp_beta;
         ip.eb = h.eb;
         ip.radius = (int)h.radius;
-        dense2_for(ctx, ip);
-        rc = szk_launch_interp_decompress(ctx->dtype, &ip, pl, o.vout_idx, o.vout_val, h.n_vout, ctx->d_codes, d_out, s);
+        if (level > 0) {
+            rc = szk_launch_interp_decompress_coarse(ctx->dtype, &ip, level, pl, o.vout_idx, o.vout_val, h.n_vout, ctx->d_codes, ctx->d_coarse_codes, d_out, s);
+        } else {
+            dense2_for(ctx, ip);
+            rc = szk_launch_interp_decompress(ctx->dtype, &ip, pl, o.vout_idx, o.vout_val, h.n_vout, ctx->d_codes, d_out, s);
+        }
     } else if (h.predictor == 2) {
         // codes -> deltas, then the blocks in anti-diagonal fronts once the side stream has the choices and coefficients
         rc = szk_launch_blk_decompress(ctx->dtype, ctx->d_codes, d_out, &bp, &sc, pl, &h, &o, ctx->d_blk_coef, s, ctx->ev_join);
@@ -2489,4 +2524,22 @@ extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, 
     if (rc) return fail(SZ3HIP_EHIP, "reconstruct kernel launch failed (%d)", rc);
     return 0;
 }
-
+extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, void *d_out,
+                                        void *stream) {
+    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream);
+}
+extern "C" int sz3hip_decompress_device_coarse(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, void *d_out, void *stream) {
+    if (!ctx) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_coarse: no context");
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "coarse level %d is outside 0 .. 30", level);
+    return decompress_device_impl(ctx, d_payload, payload_size, level, d_out, stream);
+}
+extern "C" int sz3hip_coarse_dims(const sz3hip_config *conf, int level, uint64_t *dims_out) {
+    if (!conf || !dims_out) return fail(SZ3HIP_EINVAL, "sz3hip_coarse_dims: NULL argument");
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "coarse level %d is outside 0 .. 30", level);
+    if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
+    for (int i = 0; i < conf->N; i++) {
+        if (conf->dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+        dims_out[i] = ((conf->dims[i] - 1) >> level) + 1;
+    }
+    return 0;
+}

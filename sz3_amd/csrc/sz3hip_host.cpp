@@ -1073,6 +1073,14 @@ struct DevOut {
     bool delivered = false;
 };
 static thread_local DevOut *t_devout = nullptr;
+// sz3hip_decompress_coarse_to_device, fast path: the interpolation stream this thread decodes is wanted at every 2^level-th point only
+// (t_devout is then the coarse array's view)
+static thread_local int t_coarse_level = 0;
+static uint64_t coarse_num(const sz3hip_config *conf, int level) {
+    uint64_t n = 1;
+    for (int i = 0; i < conf->N; i++) n *= ((conf->dims[i] - 1) >> level) + 1;
+    return n;
+}
 static hipError_t devout_from_device(DevOut &o, const void *src) {  // (src: the decoded array, dataType elements, complete)
     o.delivered = true;
     if (src == o.ptr) return hipSuccess;
@@ -1741,7 +1749,13 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
     HIPCHK(hipSetDevice(s->device));
     int rc;
     if ((rc = slot_ctx(s, conf->num))) return rc;
-    if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, (size_t)conf->num * tsize))) return rc;
+    const int coarse = t_devout ? t_coarse_level : 0;
+    const size_t out_bytes = (size_t)(coarse ? coarse_num(conf, coarse) : conf->num) * tsize;
+    void *dst = coarse && t_devout->view.contig ? (void *)t_devout->ptr : nullptr;  // (a coarse decode's contiguous output is written where it lies)
+    if (!dst) {
+        if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, out_bytes))) return rc;
+        dst = s->dev_in;
+    }
     const uint64_t ntiles_z = (n + 1023) / 1024;
     const uint64_t nsub = (bit_bytes * 8 + 4095) / 4096;
     const uint32_t nc = (uint32_t)tr.t.size();
@@ -1804,9 +1818,9 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
         } else if (rd == -3) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
         else if (rd) return fail(SZ3HIP_EHIP, "stock stream: device Huffman decoder failed (%d)", rd);
     }
-    rc = szi_stock_import(s->ctx, &sp, &g, d_blk, d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, d_vidx, d_vval, d_bad, s->dev_in, s->stream);
+    rc = szi_stock_import(s->ctx, &sp, &g, d_blk, d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, d_vidx, d_vval, d_bad, dst, s->stream, coarse);
     if (rc) return rc;
-    HIPCHK(d2h_out(decData, s->dev_in, (size_t)conf->num * tsize));
+    HIPCHK(d2h_out(decData, dst, out_bytes));
     return 0;
 }
 
@@ -2957,7 +2971,9 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
         return fail(SZ3HIP_EINVAL, "the stream holds %s data but %s output was requested", dtype_is_int(conf->dataType) ? "integer" : "floating-point",
                     is_int ? "integer" : "floating-point");
     if ((rc = slot_ctx(s, conf->num))) return rc;
-    const size_t cbytes = (size_t)conf->num * (cdt == SZ3HIP_FLOAT ? 4 : 8);
+    const int coarse = t_devout && !is_int ? t_coarse_level : 0;
+    if (coarse && hdr.predictor != 1) return fail(SZ3HIP_EFORMAT, "the Config names the interpolation stream but the payload's predictor id is %d", (int)hdr.predictor);
+    const size_t cbytes = (size_t)(coarse ? coarse_num(conf, coarse) : conf->num) * (cdt == SZ3HIP_FLOAT ? 4 : 8);
     // (a device call's contiguous f32 / f64 array is decoded where it lies)
     void *dst = t_devout && t_devout->view.contig && !is_int ? (void *)t_devout->ptr : nullptr;
     if (!dst) {
@@ -2967,12 +2983,13 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
     if ((rc = ensure_dev(&s->dev_payload, &s->dev_payload_bytes, std::max<size_t>(raw_len + 64, is_int ? raw_bytes : 0)))) return rc;
     HIPCHK(hipMemcpy(s->dev_payload, s->pin, raw_len, hipMemcpyHostToDevice));
     stamp(1);
-    rc = sz3hip_decompress_device(s->ctx, s->dev_payload, raw_len, dst, s->stream);
+    rc = coarse ? sz3hip_decompress_device_coarse(s->ctx, s->dev_payload, raw_len, coarse, dst, s->stream)
+                : sz3hip_decompress_device(s->ctx, s->dev_payload, raw_len, dst, s->stream);
     if (rc) return rc;
     if (!is_int) {
         HIPCHK(hipStreamSynchronize(s->stream));
         stamp(2);
-        HIPCHK(d2h_out(decData, dst, raw_bytes));
+        HIPCHK(d2h_out(decData, dst, coarse ? cbytes : raw_bytes));
     } else if (t_devout) {  // (narrowed straight into the caller's view)
         t_devout->delivered = true;
         if (szk_launch_scatter(dataType, 1, s->dev_in, t_devout->ptr, &t_devout->view, s->stream)) return fail(SZ3HIP_EHIP, "integer narrowing kernel failed");
@@ -3206,6 +3223,95 @@ extern "C" int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, co
     if (conf->openmp) return decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &dev);
     SlotLease lease(dev.device, dtype_compute(dataType));
     return decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &dev, 0, conf->dims[0]);
+}
+
+// Every 2^level-th point of a container. Fast path: a single interpolation stream, decoded on the compact grid
+// (decompress_blob / stock_decompress_interp under t_coarse_level). Everything else: the full decode into a scratch array of the call, then
+// the strided gather of its coarse view.
+extern "C" int sz3hip_decompress_coarse_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, void *d_out,
+                                                  const int64_t *strides, void *stream) {
+    if (!dtype_ok(dataType))
+        return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "coarse level %d is outside 0 .. 30", level);
+    if (dtype_is_int(dataType)) return fail(SZ3HIP_EUNSUPPORTED, "the coarse decode reads float / double arrays; integer element types are not supported yet");
+    if (level == 0) return sz3hip_decompress_to_device(conf, dataType, cmpData, cmpSize, d_out, strides, stream);
+    int rc = sz3hip_peek_config(conf, cmpData, cmpSize);
+    if (rc) return rc;
+    if (zs::load()) return SZ3HIP_EZSTD;
+    sz3hip_config cc = *conf;  // the coarse array's extents (conf stays the full array's)
+    if ((rc = sz3hip_coarse_dims(conf, level, cc.dims))) return rc;
+    cc.num = coarse_num(conf, level);
+    DevArray dev;
+    if ((rc = dev_array(&cc, strides, d_out, true, &dev))) return rc;
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(cmpData) + 8;
+    uint64_t payload;
+    memcpy(&payload, p, 8);
+    p += 8;
+    DeviceGuard guard;
+    HIPCHK(hipSetDevice(dev.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (what the caller queued on d_out comes first)
+    std::unique_lock<std::shared_mutex> all(g_host_mu, std::defer_lock);
+    std::shared_lock<std::shared_mutex> some(g_host_mu, std::defer_lock);
+    if (conf->openmp) all.lock();
+    else some.lock();
+    const size_t es = dtype_size(dataType);
+    if (!conf->openmp && (conf->cmprAlgo == SZ3HIP_ALGO_HIP_INTERP || conf->cmprAlgo == SZ3HIP_ALGO_INTERP)) {
+        SlotLease lease(dev.device, dtype_compute(dataType));
+        HostSlot *s = lease.s;
+        if (!s->stream) HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        DevOut o;
+        o.ptr = dev.ptr;
+        o.view = dev.view;
+        o.dataType = dataType;
+        o.stream = s->stream;
+        t_devout = &o;
+        t_coarse_level = level;
+        rc = decompress_blob(s, conf, dataType, p, (size_t)payload, nullptr);
+        t_devout = nullptr;
+        t_coarse_level = 0;
+        if (rc) return rc;
+        if (!o.delivered) return fail(SZ3HIP_EHIP, "the coarse decode did not deliver its array");
+        HIPCHK(hipStreamSynchronize(s->stream));
+        return 0;
+    }
+    // the full array, decoded as sz3hip_decompress_to_device does, into a scratch of this call; then its coarse view
+    struct Scratch {
+        void *p = nullptr;
+        ~Scratch() {
+            if (p) (void)hipFree(p);
+        }
+    } full, packed;
+    if (hipMalloc(&full.p, std::max<size_t>((size_t)conf->num * es, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SZ3HIP_EHIP, "no device memory for the full-size scratch (%zu bytes) this container's coarse decode needs", (size_t)conf->num * es);
+    }
+    DevArray fd;
+    if ((rc = dev_array(conf, nullptr, full.p, true, &fd))) return rc;
+    if (conf->openmp) rc = decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &fd);
+    else {
+        SlotLease lease(dev.device, dtype_compute(dataType));
+        rc = decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &fd, 0, conf->dims[0]);
+    }
+    if (rc) return rc;
+    szk_view gv = fd.view;  // (contiguous: element strides of the full array; every 2^level-th point of each extent)
+    gv.contig = 0;
+    for (int i = 0; i < 4; i++) {
+        gv.str[i] = gv.dims[i] > 1 ? gv.str[i] * ((int64_t)1 << level) : 0;
+        gv.dims[i] = ((gv.dims[i] - 1) >> level) + 1;
+    }
+    hipStream_t cs = (hipStream_t)stream;
+    void *dense = dev.ptr;
+    if (!dev.view.contig) {
+        if (hipMalloc(&packed.p, std::max<size_t>((size_t)cc.num * es, 16)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SZ3HIP_EHIP, "no device memory for the coarse array (%zu bytes)", (size_t)cc.num * es);
+        }
+        dense = packed.p;
+    }
+    if (szk_launch_gather(dataType, 0, full.p, &gv, dense, nullptr, cs)) return fail(SZ3HIP_EHIP, "gather kernel failed");
+    if (!dev.view.contig && szk_launch_scatter(dataType, 0, dense, dev.ptr, &dev.view, cs)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
+    HIPCHK(hipStreamSynchronize(cs));
+    return 0;
 }
 
 // ---- sz3hip_verify_device: the error statistics of two device arrays (kernels: sz3hip_verify.hip) ---------------------------------

@@ -1044,6 +1044,71 @@ __global__ __launch_bounds__(256) void k_scatter_raw(const uint8_t *__restrict__
     }
 }
 
+// ---- coarse decode: the points whose coordinates are all multiples of 2^k, as a compact array ------
+// full: the array's extents in the last N of four places (1 in front), cd: ((D - 1) >> k) + 1 of each
+struct szk_coarse_geom {
+    uint64_t full[4], cd[4];
+    uint64_t off[3];  // element offsets of the three slower dimensions of the full array
+    uint32_t k;
+    uint32_t rx;      // lanes along a coarse row: a power of two <= 256; the workgroup takes 256 / rx rows
+    uint32_t xblocks; // workgroups along a row (each 4 * rx points)
+};
+// k_scatter_raw for the coarse grid: a record whose point is off the grid is dropped
+template <typename T>
+__global__ __launch_bounds__(256) void k_scatter_raw_coarse(const uint8_t *__restrict__ payload, uint64_t idx_off, uint64_t val_off, uint64_t cnt,
+                                                            uint64_t n, szk_coarse_geom g, uint64_t nc, T *__restrict__ out) {
+    const uint64_t *idx = reinterpret_cast<const uint64_t *>(payload + idx_off);
+    const T *val = reinterpret_cast<const T *>(payload + val_off);
+    const uint64_t mask = (1ull << g.k) - 1;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * 256) {
+        uint64_t r = idx[i];
+        if (r >= n) continue;
+        const uint64_t c3 = r % g.full[3];
+        r /= g.full[3];
+        const uint64_t c2 = r % g.full[2];
+        r /= g.full[2];
+        const uint64_t c1 = r % g.full[1], c0 = r / g.full[1];
+        if ((c0 | c1 | c2 | c3) & mask) continue;
+        const uint64_t o = (((c0 >> g.k) * g.cd[1] + (c1 >> g.k)) * g.cd[2] + (c2 >> g.k)) * g.cd[3] + (c3 >> g.k);
+        if (o < nc) out[o] = val[i];
+    }
+}
+// the full per-element code array -> the coarse grid's dense code array. Only the rows whose slower coordinates are multiples of 2^k are
+// read; lanes run along the row. k = 1: a lane reads the (even, odd) pair as one 32-bit word and keeps the low half (rows that start at an
+// odd element, and a row's last point when the odd neighbour lies beyond the row, read 16 bits).
+__global__ __launch_bounds__(256) void k_coarse_codes(const uint16_t *__restrict__ in, uint16_t *__restrict__ out, szk_coarse_geom g, uint64_t rows) {
+    const uint64_t b = blockIdx.x;
+    const uint64_t rb = b / g.xblocks;
+    const uint32_t xb = (uint32_t)(b - rb * g.xblocks);
+    const uint32_t tx = threadIdx.x & (g.rx - 1), ty = threadIdx.x / g.rx;
+    const uint64_t row = rb * (256 / g.rx) + ty;
+    if (row >= rows) return;
+    uint64_t r = row;
+    const uint64_t c2 = r % g.cd[2];
+    r /= g.cd[2];
+    const uint64_t c1 = r % g.cd[1], c0 = r / g.cd[1];
+    const uint64_t src = (c0 * g.off[0] + c1 * g.off[1] + c2 * g.off[2]) << g.k;
+    const uint16_t *rp = in + src;
+    uint16_t *op = out + row * g.cd[3];
+    const bool pairs = g.k == 1 && !(src & 1);
+    const uint64_t x0 = (uint64_t)xb * 4 * g.rx + tx;
+    uint32_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint64_t x = x0 + (uint64_t)j * g.rx;
+        v[j] = 0;
+        if (x < g.cd[3]) {
+            if (pairs && 2 * x + 1 < g.full[3]) v[j] = reinterpret_cast<const uint32_t *>(rp)[x] & 0xFFFFu;
+            else v[j] = rp[x << g.k];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint64_t x = x0 + (uint64_t)j * g.rx;
+        if (x < g.cd[3]) op[x] = (uint16_t)v[j];
+    }
+}
+
 // ---- host side: the level / pass schedule (InterpolationDecomposition::init :176-213, compress :79-147) -----------
 static void nth_permutation(int N, int id, int *perm) {  // lexicographic order = std::next_permutation sequence
     int p[4] = {0, 1, 2, 3};
@@ -1068,7 +1133,9 @@ static void nth_permutation(int N, int id, int *perm) {  // lexicographic order 
 int szk_interp_novec = 0;  // test hook: force the one-point-per-thread kernels
 
 // the level / pass schedule as a list (kind 0: anchor grid, 1: first point without anchors, 2: directional pass)
-static int build_schedule(const szk_interp_params &ip, bool dec, uint32_t nbatch, std::vector<szk_interp_pass> &out) {
+// level_shift k > 0 (coarse decode): ip describes the compact grid of every 2^k-th point of a larger array — its extents and its anchor
+// stride are the array's, divided; its level l is the array's level l + k, which is the number the per-level bound goes by
+static int build_schedule(const szk_interp_params &ip, bool dec, uint32_t nbatch, std::vector<szk_interp_pass> &out, int level_shift = 0) {
     const int N = ip.N;
     szk_interp_pass p;
     memset(&p, 0, sizeof(p));
@@ -1135,10 +1202,11 @@ static int build_schedule(const szk_interp_params &ip, bool dec, uint32_t nbatch
     p.kind = 2;
     for (int level = interp_level; level > 0; level--) {
         double cur_eb = ip.eb;  // per-level bound :103-117
+        const int eb_level = level + level_shift;
         if (ip.alpha < 0) {
-            cur_eb = level >= 3 ? ip.eb * 0.5 : ip.eb;
+            cur_eb = eb_level >= 3 ? ip.eb * 0.5 : ip.eb;
         } else if (ip.alpha >= 1) {
-            double r = pow(ip.alpha, level - 1);
+            double r = pow(ip.alpha, eb_level - 1);
             if (r > ip.beta) r = ip.beta;
             cur_eb = ip.eb / r;
         }
@@ -1249,9 +1317,9 @@ static int launch_level(const szk_interp_pass &p, const int *perm, const T *in, 
 
 // in: the originals (compression with the level kernels: never written; nullptr = w holds a working copy of them)
 template <typename T, bool DEC>
-static int run_interp(const szk_interp_params &ip, const T *in, T *w, uint16_t *codes, hipStream_t s, uint32_t nbatch = 1) {
+static int run_interp(const szk_interp_params &ip, const T *in, T *w, uint16_t *codes, hipStream_t s, uint32_t nbatch = 1, int level_shift = 0) {
     std::vector<szk_interp_pass> sched;
-    if (build_schedule(ip, DEC, nbatch, sched)) return -1;
+    if (build_schedule(ip, DEC, nbatch, sched, level_shift)) return -1;
     const bool levels = nbatch == 1 && szk_interp_levels_ok(&ip) && (DEC || in != nullptr);
     int perm[4];
     nth_permutation(ip.N, ip.direction, perm);
@@ -1366,6 +1434,56 @@ int szk_launch_interp_decompress(int dtype, const szk_interp_params *ip, const u
     }
     return dtype == 0 ? run_interp<float, true>(*ip, (const float *)nullptr, (float *)d_out, codes, s)
                       : run_interp<double, true>(*ip, (const double *)nullptr, (double *)d_out, codes, s);
+}
+
+// Every 2^k-th point of the array ip describes (ip: the FULL array's parameters), into the compact array d_out of prod(((D - 1) >> k) + 1)
+// elements: the codes and the raw values of those points are gathered (codes -> codes_coarse), then the existing level / pass kernels run
+// on the compact grid with the anchor stride divided and the levels numbered as in the full array. Nothing of full size is written.
+int szk_launch_interp_decompress_coarse(int dtype, const szk_interp_params *ip, int k, const uint8_t *payload, uint64_t vout_idx_off,
+                                        uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, uint16_t *codes_coarse, void *d_out, hipStream_t s) {
+    if (k < 1 || k > 30 || ip->N < 1 || ip->N > 4) return -1;
+    const uint64_t A = ip->anchor_stride;
+    if (A & (A - 1)) return -3;  // (the levels' strides and the anchor grid only nest for a power of two)
+    szk_coarse_geom g;
+    memset(&g, 0, sizeof(g));
+    g.k = (uint32_t)k;
+    uint64_t num = 1, nc = 1;
+    bool use_anchor = false;
+    for (int i = 0; i < 4; i++) {
+        const int j = i - (4 - ip->N);
+        g.full[i] = j >= 0 ? ip->dims[j] : 1;
+        if (g.full[i] == 0) return -1;
+        g.cd[i] = ((g.full[i] - 1) >> k) + 1;
+        num *= g.full[i];
+        nc *= g.cd[i];
+        if (g.full[i] > A) use_anchor = true;
+    }
+    g.off[2] = g.full[3];
+    g.off[1] = g.off[2] * g.full[2];
+    g.off[0] = g.off[1] * g.full[1];
+    g.rx = 1;
+    while (g.rx < 256 && g.rx < g.cd[3]) g.rx *= 2;
+    const uint64_t xblocks = (g.cd[3] + 4ull * g.rx - 1) / (4ull * g.rx), rows = nc / g.cd[3], rpb = 256 / g.rx;
+    const uint64_t nblocks = ((rows + rpb - 1) / rpb) * xblocks;
+    if (xblocks > 0xFFFFFFFFull || nblocks > 0x7FFFFFFFull) return -1;
+    g.xblocks = (uint32_t)xblocks;
+    hipLaunchKernelGGL(k_coarse_codes, dim3((uint32_t)nblocks), dim3(256), 0, s, codes, codes_coarse, g, rows);
+    if (n_vout) {
+        const uint32_t gr = (uint32_t)((n_vout + 255) / 256 < 4096 ? (n_vout + 255) / 256 : 4096);
+        if (dtype == 0) hipLaunchKernelGGL((k_scatter_raw_coarse<float>), dim3(gr), dim3(256), 0, s, payload, vout_idx_off, vout_val_off, n_vout, num, g, nc, (float *)d_out);
+        else hipLaunchKernelGGL((k_scatter_raw_coarse<double>), dim3(gr), dim3(256), 0, s, payload, vout_idx_off, vout_val_off, n_vout, num, g, nc, (double *)d_out);
+    }
+    if (A > 0 && use_anchor && (1ull << k) >= A) {  // every coarse point is an anchor: the raw values are the result
+        hipError_t e = hipGetLastError();
+        return e == hipSuccess ? 0 : (int)e;
+    }
+    szk_interp_params cip = *ip;
+    for (int i = 0; i < ip->N; i++) cip.dims[i] = g.cd[4 - ip->N + i];
+    cip.anchor_stride = A >> k;  // (0 only where the full array takes the first-point path too: no extent above A)
+    cip.dense2 = nullptr;
+    cip.dense2_elems = 0;
+    return dtype == 0 ? run_interp<float, true>(cip, (const float *)nullptr, (float *)d_out, codes_coarse, s, 1, k)
+                      : run_interp<double, true>(cip, (const double *)nullptr, (double *)d_out, codes_coarse, s, 1, k);
 }
 
 // ---- ALGO_INTERP_LORENZO tuner: device side (SZ_compress_Interp_lorenzo, api/impl/SZAlgoInterp.hpp:122-286) ---------

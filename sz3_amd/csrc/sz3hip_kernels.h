@@ -371,6 +371,10 @@ int szk_launch_interp_compress(int dtype, const szk_interp_params *ip, const voi
                                uint64_t *hist, hipStream_t s);
 int szk_launch_interp_decompress(int dtype, const szk_interp_params *ip, const uint8_t *payload, uint64_t vout_idx_off,
                                  uint64_t vout_val_off, uint64_t n_vout, uint16_t *codes, void *d_out, hipStream_t s);
+// coarse decode (level k >= 1): ip = the full array's parameters, codes = its per-element codes, codes_coarse = room for the coarse grid's
+// codes, d_out = prod(((D - 1) >> k) + 1) elements. -3: an anchor stride that is no power of two
+int szk_launch_interp_decompress_coarse(int dtype, const szk_interp_params *ip, int k, const uint8_t *payload, uint64_t vout_idx_off,
+                                        uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, uint16_t *codes_coarse, void *d_out, hipStream_t s);
 
 int szk_launch_profile_blocks(int dtype, const void *d_in, int N, const uint64_t *dims, uint64_t bs, uint64_t stride, double abseb,
                               uint8_t *d_flags, uint64_t *total_out, hipStream_t s);
