@@ -180,6 +180,32 @@ int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, const char *c
 int sz3hip_coarse_dims(const sz3hip_config *conf, int level, uint64_t *dims_out);
 int sz3hip_decompress_coarse_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, void *d_out,
                                        const int64_t *strides, void *stream);
+/* Region decode: the values of one box of the array, bit for bit what a full decode puts there, in work sized to the box (DESIGN.md
+ * section 12). A point of an interpolation stream depends on a stencil of a few strides of its own level, so a box depends on a pyramid of
+ * windows, one per level, not on the array. lo / ext hold one entry per conf->N extent, slowest first; the box is [lo[j], lo[j] + ext[j]).
+ * sz3hip_region_plan_for: a pure function (no device). It validates the box and says what the region decode of it touches; it reads conf->N,
+ * dims, interpAlgo, interpDirection and interpAnchorStride (negative: the default of the dimension count). ext[j] == 0, a box that leaves the
+ * array or a NULL argument: SZ3HIP_EINVAL; an anchor stride that is no power of two: SZ3HIP_EUNSUPPORTED.
+ * sz3hip_decompress_region_to_device: sz3hip_decompress_to_device for the box. conf is overwritten from the trailer and stays the FULL
+ * array's Config; d_out is a view of ext extents; strides, pointer, stream and synchrony rules are sz3hip_decompress_to_device's.
+ * SZ3HIP_FLOAT and SZ3HIP_DOUBLE; the integer element types are SZ3HIP_EUNSUPPORTED. A box equal to the whole array gives the full decode's
+ * array. Every container that call decodes is decoded:
+ *  - fast path, a single-stream interpolation container (this library's id 17 or a stock ALGO_INTERP stream): one compact buffer per level
+ *    holds the level's window, the raw values that lie in a window are scattered, the passes run over the windows and the box is gathered
+ *    from the finest buffer; nothing of full size is written (the Huffman stage still decodes every code);
+ *  - everything else (Lorenzo and block streams, ALGO_NOPRED, ALGO_LOSSLESS, the stock 1-D chain, conf->openmp slabs and pipelined pieces,
+ *    an anchor stride that is no power of two): the full array is decoded as sz3hip_decompress_to_device does, into a scratch array of FULL
+ *    size that the library allocates in device memory for the call, and the box is gathered from it. This path needs that much HBM. */
+typedef struct sz3hip_region_plan {
+    int32_t n_levels;      /* interpolation levels that run (0: every point of the box is an anchor / the first point) */
+    uint32_t stride[32];   /* stride s of level i, coarsest first */
+    uint64_t win_lo[32][4], win_hi[32][4]; /* inclusive window, full-array coordinates, that level i READS (its "input window"), per conf->N extents */
+    uint64_t points;       /* predicted points over all passes */
+    uint64_t scratch_elems; /* elements of T the call needs in device memory besides d_out */
+} sz3hip_region_plan;
+int sz3hip_region_plan_for(const sz3hip_config *conf, const uint64_t *lo, const uint64_t *ext, sz3hip_region_plan *out);
+int sz3hip_decompress_region_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, const uint64_t *lo, const uint64_t *ext,
+                                       void *d_out, const int64_t *strides, void *stream);
 /* (test and measurement hook) the strided gather alone: the view (N extents, element strides) of d_in into the contiguous d_out on stream,
  * integers widened to f64 as the compress call does; asynchronous */
 int sz3hip_debug_gather(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream);
@@ -289,6 +315,19 @@ int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, size_t payl
  * array. Level 0 is sz3hip_decompress_device itself; a level outside 0 .. 30 is SZ3HIP_EINVAL. Any other predictor: SZ3HIP_EUNSUPPORTED —
  * a device context has no full-size scratch of its own; sz3hip_decompress_coarse_to_device decodes every container. */
 int sz3hip_decompress_device_coarse(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, void *d_out, void *stream);
+/* the same for one box of an interpolation payload (predictor id 1; see sz3hip_region_plan_for above): lo / ext hold one entry per extent
+ * the payload's header names, d_out receives prod(ext) elements, contiguous, bit for bit the full decode's values in the box. Header parse and
+ * Huffman stage are sz3hip_decompress_device's; the box's checks come before any launch. The context's first region call allocates the levels'
+ * buffers (plan.scratch_elems elements; grown when a later plan needs more) and the context keeps them: a call whose plan fits allocates
+ * nothing. Any other predictor: SZ3HIP_EUNSUPPORTED — a device context has no full-size scratch of its own;
+ * sz3hip_decompress_region_to_device decodes every container. */
+int sz3hip_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const uint64_t *lo, const uint64_t *ext, void *d_out,
+                                    void *stream);
+/* test hook: the capacity of the context's region scratch, in elements (0 before its first region call) */
+uint64_t sz3hip_debug_region_scratch(const sz3hip_ctx *ctx);
+/* test hook: the number of region decodes of this process that ran over the box's windows (the fast path of either call); a container
+ * that went through the full-decode fallback does not count */
+uint64_t sz3hip_debug_region_fast_calls(void);
 
 /* diagnostics of the last compress on this ctx (valid after sz3hip_compress_finish) */
 typedef struct sz3hip_stats {

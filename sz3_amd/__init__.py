@@ -113,6 +113,12 @@ class _CStats(C.Structure):
                 ("narrow_codes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _CRegionPlan(C.Structure):
+    """sz3hip_region_plan (include/sz3hip.h)"""
+    _fields_ = [("n_levels", C.c_int32), ("stride", C.c_uint32 * 32), ("win_lo", (C.c_uint64 * 4) * 32), ("win_hi", (C.c_uint64 * 4) * 32),
+                ("points", C.c_uint64), ("scratch_elems", C.c_uint64)]
+
+
 class _CVerifyStats(C.Structure):
     """sz3hip_verify_stats (include/sz3hip.h)"""
     _fields_ = ([(k, C.c_uint64) for k in ("n", "n_nonfinite", "n_nonfinite_mismatch", "n_over", "first_over", "argmax")] +
@@ -216,6 +222,17 @@ def lib():
     L.sz3hip_decompress_coarse_to_device.argtypes = [P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, P(C.c_int64), C.c_void_p]
     L.sz3hip_decompress_device_coarse.restype = C.c_int
     L.sz3hip_decompress_device_coarse.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+    L.sz3hip_region_plan_for.restype = C.c_int
+    L.sz3hip_region_plan_for.argtypes = [P(_CConfig), P(C.c_uint64), P(C.c_uint64), P(_CRegionPlan)]
+    L.sz3hip_decompress_region_to_device.restype = C.c_int
+    L.sz3hip_decompress_region_to_device.argtypes = [P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, P(C.c_uint64), P(C.c_uint64), C.c_void_p, P(C.c_int64),
+                                                     C.c_void_p]
+    L.sz3hip_decompress_device_region.restype = C.c_int
+    L.sz3hip_decompress_device_region.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(C.c_uint64), P(C.c_uint64), C.c_void_p, C.c_void_p]
+    L.sz3hip_debug_region_fast_calls.restype = C.c_uint64
+    L.sz3hip_debug_region_fast_calls.argtypes = []
+    L.sz3hip_debug_region_scratch.restype = C.c_uint64
+    L.sz3hip_debug_region_scratch.argtypes = [C.c_void_p]
     L.sz3hip_verify_device.restype = C.c_int
     L.sz3hip_verify_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), C.c_void_p, P(C.c_int64), C.c_double,
                                        P(_CVerifyStats), C.c_void_p]
@@ -517,6 +534,56 @@ def decompress(blob, dtype, shape=None, out=None, device=None, stream=None):
     return dec.reshape(shape), conf
 
 
+def _box(conf, lo, shape):
+    lo, shape = tuple(int(v) for v in lo), tuple(int(v) for v in shape)
+    if len(lo) != conf.N or len(shape) != conf.N:
+        raise ValueError("lo and shape need one entry per extent of the array (%d)" % conf.N)
+    if any(v < 0 for v in lo) or any(v < 0 for v in shape):
+        raise ValueError("lo and shape must not be negative")
+    return (C.c_uint64 * 4)(*lo), (C.c_uint64 * 4)(*shape), shape
+
+
+def region_plan(conf, lo, shape):
+    """what the region decode of the box [lo, lo + shape) of conf's array touches (sz3hip_region_plan_for): a dict with n_levels, strides
+    (coarsest first), windows (per level the inclusive (lo, hi) tuples of the window the level reads, full-array coordinates), points
+    (predicted points over all passes) and scratch_elems. Needs no device."""
+    clo, cext, _ = _box(conf, lo, shape)
+    plan = _CRegionPlan()
+    _check(lib().sz3hip_region_plan_for(C.byref(conf._c), clo, cext, C.byref(plan)))
+    n, N = int(plan.n_levels), conf.N
+    return {"n_levels": n, "strides": tuple(int(plan.stride[i]) for i in range(n)),
+            "windows": tuple((tuple(int(plan.win_lo[i][j]) for j in range(N)), tuple(int(plan.win_hi[i][j]) for j in range(N))) for i in range(n)),
+            "points": int(plan.points), "scratch_elems": int(plan.scratch_elems)}
+
+
+def decompress_region(blob, dtype, lo, shape, out=None, device=None, stream=None):
+    """The box [lo, lo + shape) of a container, bit for bit what ``decompress(blob, dtype, device=...)[0]`` holds there, in work sized to the
+    box where the container is a single interpolation stream (sz3hip_decompress_region_to_device). Device only: `device=` allocates a tensor
+    of `shape` there, or `out=` is a tensor of that shape on a HIP device, also a view. float32 / float64. Returns (tensor, Config) — the
+    Config is the FULL array's. `stream` as for decompress."""
+    blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
+    npdt = _np_dtype(dtype)
+    dt = _dtype_id(npdt)
+    if out is None and device is None:
+        raise ValueError("decompress_region decodes into device memory: pass device= or out=")
+    if out is not None and not _gpu_tensor(out):
+        raise ValueError("out must be a tensor on a HIP device")
+    if dt > 1:  # (the library's own refusal, before anything is parsed or allocated)
+        _check(lib().sz3hip_decompress_region_to_device(C.byref(Config(1)._c), dt, blob.ctypes.data, blob.size, None, None, None, None, None))
+    conf = Config(1)
+    _check(lib().sz3hip_peek_config(C.byref(conf._c), blob.ctypes.data, blob.size))
+    clo, cext, shape = _box(conf, lo, shape)
+    import torch
+    if out is None:
+        out = torch.empty(shape, dtype=getattr(torch, npdt.name), device=device)
+    if _np_dtype(out.dtype) != npdt or tuple(out.shape) != shape:
+        raise ValueError("out must be a %s tensor of shape %s" % (npdt, shape))
+    strides = (C.c_int64 * len(shape))(*[int(st) for st in out.stride()])
+    _check(lib().sz3hip_decompress_region_to_device(C.byref(conf._c), dt, blob.ctypes.data, blob.size, clo, cext, out.data_ptr(), strides,
+                                                    _stream_handle(out.device, stream)))
+    return out, conf
+
+
 def coarse_dims(conf, level):
     """extents of the array of every 2**level-th point of conf's array (sz3hip_coarse_dims): ``len(range(0, D, 2**level))`` per extent,
     slowest first, extents of 1 kept. Needs no device."""
@@ -683,6 +750,17 @@ class DeviceCompressor:
     def decompress_coarse(self, d_payload, size, level, d_out, stream=0):
         """every 2**level-th point of an interpolation payload into d_out (prod(coarse_dims) elements, contiguous)"""
         _check(lib().sz3hip_decompress_device_coarse(self._h, d_payload, int(size), int(level), d_out, stream))
+
+    def decompress_region(self, d_payload, size, lo, shape, d_out, stream=0):
+        """the box [lo, lo + shape) of an interpolation payload into d_out (prod(shape) elements, contiguous)"""
+        lo, shape = tuple(int(v) for v in lo), tuple(int(v) for v in shape)
+        if len(lo) != len(shape) or not 1 <= len(lo) <= 4:
+            raise ValueError("lo and shape need one entry per extent of the array")
+        _check(lib().sz3hip_decompress_device_region(self._h, d_payload, int(size), (C.c_uint64 * 4)(*lo), (C.c_uint64 * 4)(*shape), d_out, stream))
+
+    def region_scratch(self):
+        """capacity of the context's region scratch in elements (0 before its first region call)"""
+        return int(lib().sz3hip_debug_region_scratch(self._h))
 
     def stats(self):
         st = _CStats()

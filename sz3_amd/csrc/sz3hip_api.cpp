@@ -219,7 +219,7 @@ static void ctx_free(sz3hip_ctx *c) {
                     c->d_chunk_words, c->d_chunk_off, c->d_carry, c->d_state, c->d_tables, c->d_segtot, c->d_minmax, c->d_samples, c->d_trial_work, c->d_trial_codes,
                     c->d_trial, c->d_passes, c->d_np,  // (d_trial_counters / d_trial_hist live inside d_trial's block)
                     c->d_blk_sel, c->d_blk_coef, c->d_blk_rank, c->d_blk_comp, c->d_blk_side, c->d_blk_counters,
-                    c->bk[1].enc, c->bk[1].lens, c->bk[1].info, c->d_seg_bits, c->d_seg_base, c->d_half32, c->d_sub_bits, c->d_fuse_scratch, c->d_coarse_codes};
+                    c->bk[1].enc, c->bk[1].lens, c->bk[1].info, c->d_seg_bits, c->d_seg_base, c->d_half32, c->d_sub_bits, c->d_fuse_scratch, c->d_coarse_codes, c->d_region};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (c->book_stream) {
@@ -2210,11 +2210,90 @@ int szi_stock_export(sz3hip_ctx *ctx, const szg_geom *g, const uint64_t *d_blk_b
     ctx->stage1_done = ctx->stage2_done = false;  // (this call ends here: no device payload is made of it)
     return 0;
 }
+// ---- region decode: the box's checks, the plan, the context's scratch ----
+static int region_check_box(int N, const uint64_t *dims, const uint64_t *lo, const uint64_t *ext) {
+    if (!lo || !ext) return fail(SZ3HIP_EINVAL, "the region's %s is NULL", !lo ? "lo" : "ext");
+    if (N < 1 || N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++) {
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+        if (ext[i] == 0) return fail(SZ3HIP_EINVAL, "the region has extent 0 in dimension %d", i);
+        if (lo[i] >= dims[i] || ext[i] > dims[i] - lo[i])
+            return fail(SZ3HIP_EINVAL, "the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", (unsigned long long)lo[i], (unsigned long long)lo[i],
+                        (unsigned long long)ext[i], i, (unsigned long long)dims[i]);
+    }
+    return 0;
+}
+static int region_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const uint64_t *lo, const uint64_t *ext,
+                           szk_region_geom *g) {
+    int rc = region_check_box(N, dims, lo, ext);
+    if (rc) return rc;
+    int nperm = 1;
+    for (int i = 2; i <= N; i++) nperm *= i;
+    if (N == 1) direction = 0;
+    if (direction < 0 || direction >= nperm) return fail(SZ3HIP_EINVAL, "interpDirection out of range");
+    rc = szk_region_geometry(N, dims, interp_id ? 1 : 0, direction, anchor_stride, lo, ext, g);
+    if (rc == -3)
+        return fail(SZ3HIP_EUNSUPPORTED, "the region decode needs an anchor stride that is 0 or a power of two (this one is %llu): the levels' strides and the "
+                    "anchor grid do not nest otherwise", (unsigned long long)anchor_stride);
+    if (rc) return fail(SZ3HIP_EINVAL, "the region's windows cannot be laid out (extents too large)");
+    return 0;
+}
+extern "C" int sz3hip_region_plan_for(const sz3hip_config *conf, const uint64_t *lo, const uint64_t *ext, sz3hip_region_plan *out) {
+    if (!conf || !lo || !ext || !out) return fail(SZ3HIP_EINVAL, "sz3hip_region_plan_for: NULL argument (%s)", !conf ? "conf" : !lo ? "lo" : !ext ? "ext" : "out");
+    if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
+    static const int def_anchor[4] = {4096, 128, 32, 16};  // SZAlgoInterp.hpp:20-24
+    const uint64_t anchor = conf->interpAnchorStride < 0 ? (uint64_t)def_anchor[conf->N - 1] : (uint64_t)conf->interpAnchorStride;
+    uint64_t dims[4];
+    for (int i = 0; i < conf->N; i++) dims[i] = conf->dims[i];
+    szk_region_geom g;
+    int rc = region_geometry(conf->N, dims, conf->interpAlgo, conf->interpDirection, anchor, lo, ext, &g);
+    if (rc) return rc;
+    memset(out, 0, sizeof(*out));
+    out->n_levels = g.n_levels;
+    for (int b = 0; b < g.n_levels; b++) {
+        out->stride[b] = (uint32_t)g.lv[b].s;
+        for (int j = 0; j < g.N; j++) {
+            out->win_lo[b][j] = g.lv[b].in_lo[j];
+            out->win_hi[b][j] = g.lv[b].in_hi[j];
+        }
+    }
+    out->points = g.points;
+    out->scratch_elems = g.scratch_elems;
+    return 0;
+}
+// the context's region scratch: made by its first region call, grown when a plan needs more, kept
+static int region_reserve(sz3hip_ctx *ctx, uint64_t elems) {
+    if (elems <= ctx->region_cap) return 0;
+    const size_t tsz = ctx->dtype == SZ3HIP_FLOAT ? 4 : 8;
+    if (ctx->d_region) {
+        HIPCHK(hipDeviceSynchronize());  // (an earlier call's kernels may still read it)
+        HIPCHK(hipFree(ctx->d_region));
+    }
+    ctx->d_region = nullptr;
+    ctx->region_cap = 0;
+    if (hipMalloc(&ctx->d_region, elems * tsz + 64) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->d_region = nullptr;
+        return fail(SZ3HIP_EHIP, "no device memory for the region decode's scratch (%zu bytes)", (size_t)(elems * tsz));
+    }
+    ctx->region_cap = elems;
+    return 0;
+}
+extern "C" uint64_t sz3hip_debug_region_scratch(const sz3hip_ctx *ctx) { return ctx ? ctx->region_cap : 0; }
+// test hook: region decodes that ran over the box's windows (the fast path) in this process; the full-decode fallback does not count
+static std::atomic<uint64_t> g_region_fast_calls{0};
+extern "C" uint64_t sz3hip_debug_region_fast_calls(void) { return g_region_fast_calls.load(); }
+
 int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom *g, const uint64_t *d_blk_base, const uint16_t *d_em,
                      const void *d_unpred, uint64_t n_unpred, uint32_t *d_tile_cnt, uint64_t *d_tile_base, uint64_t *d_vout_idx, void *d_vout_val,
-                     uint32_t *d_bad, void *d_out, void *stream, int coarse_level) {
+                     uint32_t *d_bad, void *d_out, void *stream, int coarse_level, const szi_region *region) {
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
+    szk_region_geom rg;
+    if (region) {  // (d_out: the box. The windows and the context's scratch, before anything is launched)
+        int rr = region_geometry(p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, region->lo, region->ext, &rg);
+        if (rr || (rr = region_reserve(ctx, rg.scratch_elems))) return rr;
+    }
     uint64_t num = 1, nc = 1;
     for (int i = 0; i < p->N; i++) {
         num *= p->dims[i];
@@ -2245,7 +2324,11 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
     ip.eb = p->eb;
     ip.radius = p->radius;
     // (the lists are the caller's own arrays: handed over as offsets from a null base)
-    if (coarse_level > 0
+    if (region) g_region_fast_calls++;
+    if (region
+            ? szk_launch_interp_decompress_region(ctx->dtype, &ip, &rg, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, ctx->d_codes,
+                                                  ctx->d_region, d_out, s)
+        : coarse_level > 0
             ? szk_launch_interp_decompress_coarse(ctx->dtype, &ip, coarse_level, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred,
                                                   ctx->d_codes, ctx->d_coarse_codes, d_out, s)
             : szk_launch_interp_decompress(ctx->dtype, &ip, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, ctx->d_codes, d_out, s))
@@ -2298,8 +2381,11 @@ extern "C" int sz3hip_debug_decode_info(sz3hip_ctx *ctx, uint32_t *out4) {
 }
 
 // sz3hip_decompress_device (level 0) and sz3hip_decompress_device_coarse (level >= 1: an interpolation payload's points at multiples of
-// 2^level) share the header's parse and the Huffman stage; they differ in the reconstruction alone
-static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, void *d_out, void *stream) {
+// 2^level) share the header's parse and the Huffman stage; they differ in the reconstruction alone. So does
+// sz3hip_decompress_device_region (region: the box of an interpolation payload; level is 0 then).
+static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, void *d_out, void *stream, const uint64_t *rlo = nullptr,
+                                  const uint64_t *rext = nullptr) {
+    const bool region = rlo != nullptr;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
     ctx->blk_pre_cleared = false;  // (a block stream's decoder counts in the same counter block)
@@ -2355,6 +2441,15 @@ static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t
         uint64_t nc = 1;
         for (int i = 0; i < 4; i++) nc *= ((h.dims[i] - 1) >> level) + 1;
         if (nc > ctx->coarse_codes_cap) return fail(SZ3HIP_EINVAL, "the coarse grid exceeds the context capacity");
+    }
+    szk_region_geom rg;
+    if (region) {
+        if (h.predictor != 1)
+            return fail(SZ3HIP_EUNSUPPORTED, "sz3hip_decompress_device_region reads interpolation payloads only (this one's predictor id is %d): a device context has "
+                        "no full-size scratch of its own — sz3hip_decompress_region_to_device decodes every container", h.predictor);
+        if (h.ndim < 1 || h.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
+        int rr = region_geometry(h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, rlo, rext, &rg);
+        if (rr || (rr = region_reserve(ctx, rg.scratch_elems))) return rr;
     }
     const uint8_t *pl = (const uint8_t *)d_payload;
     szk_blk_params bp;
@@ -2508,7 +2603,10 @@ static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t
         ip.beta = h.interp_beta;
         ip.eb = h.eb;
         ip.radius = (int)h.radius;
-        if (level > 0) {
+        if (region) {
+            g_region_fast_calls++;
+            rc = szk_launch_interp_decompress_region(ctx->dtype, &ip, &rg, pl, o.vout_idx, o.vout_val, h.n_vout, ctx->d_codes, ctx->d_region, d_out, s);
+        } else if (level > 0) {
             rc = szk_launch_interp_decompress_coarse(ctx->dtype, &ip, level, pl, o.vout_idx, o.vout_val, h.n_vout, ctx->d_codes, ctx->d_coarse_codes, d_out, s);
         } else {
             dense2_for(ctx, ip);
@@ -2532,6 +2630,17 @@ extern "C" int sz3hip_decompress_device_coarse(sz3hip_ctx *ctx, const void *d_pa
     if (!ctx) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_coarse: no context");
     if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "coarse level %d is outside 0 .. 30", level);
     return decompress_device_impl(ctx, d_payload, payload_size, level, d_out, stream);
+}
+int szi_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_region *region, void *d_out, void *stream) {
+    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream, region->lo, region->ext);
+}
+// (lo / ext: one entry per extent the payload's header names)
+extern "C" int sz3hip_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const uint64_t *lo, const uint64_t *ext, void *d_out,
+                                               void *stream) {
+    if (!ctx) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_region: no context");
+    if (!lo || !ext) return fail(SZ3HIP_EINVAL, "the region's %s is NULL", !lo ? "lo" : "ext");
+    if (!d_payload || !d_out) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_region: the %s is NULL", !d_payload ? "payload" : "output array");
+    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream, lo, ext);
 }
 extern "C" int sz3hip_coarse_dims(const sz3hip_config *conf, int level, uint64_t *dims_out) {
     if (!conf || !dims_out) return fail(SZ3HIP_EINVAL, "sz3hip_coarse_dims: NULL argument");

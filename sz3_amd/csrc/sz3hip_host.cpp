@@ -1076,6 +1076,14 @@ static thread_local DevOut *t_devout = nullptr;
 // sz3hip_decompress_coarse_to_device, fast path: the interpolation stream this thread decodes is wanted at every 2^level-th point only
 // (t_devout is then the coarse array's view)
 static thread_local int t_coarse_level = 0;
+// sz3hip_decompress_region_to_device, fast path: the interpolation stream this thread decodes is wanted in this box only (t_devout is then the
+// box's view)
+static thread_local const szi_region *t_region = nullptr;
+static uint64_t region_num(const sz3hip_config *conf, const szi_region *r) {
+    uint64_t n = 1;
+    for (int i = 0; i < conf->N; i++) n *= r->ext[i];
+    return n;
+}
 static uint64_t coarse_num(const sz3hip_config *conf, int level) {
     uint64_t n = 1;
     for (int i = 0; i < conf->N; i++) n *= ((conf->dims[i] - 1) >> level) + 1;
@@ -1750,8 +1758,9 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
     int rc;
     if ((rc = slot_ctx(s, conf->num))) return rc;
     const int coarse = t_devout ? t_coarse_level : 0;
-    const size_t out_bytes = (size_t)(coarse ? coarse_num(conf, coarse) : conf->num) * tsize;
-    void *dst = coarse && t_devout->view.contig ? (void *)t_devout->ptr : nullptr;  // (a coarse decode's contiguous output is written where it lies)
+    const szi_region *region = t_devout ? t_region : nullptr;
+    const size_t out_bytes = (size_t)(region ? region_num(conf, region) : coarse ? coarse_num(conf, coarse) : conf->num) * tsize;
+    void *dst = (coarse || region) && t_devout->view.contig ? (void *)t_devout->ptr : nullptr;  // (a coarse / region decode's contiguous output is written where it lies)
     if (!dst) {
         if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, out_bytes))) return rc;
         dst = s->dev_in;
@@ -1818,7 +1827,7 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
         } else if (rd == -3) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
         else if (rd) return fail(SZ3HIP_EHIP, "stock stream: device Huffman decoder failed (%d)", rd);
     }
-    rc = szi_stock_import(s->ctx, &sp, &g, d_blk, d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, d_vidx, d_vval, d_bad, dst, s->stream, coarse);
+    rc = szi_stock_import(s->ctx, &sp, &g, d_blk, d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, d_vidx, d_vval, d_bad, dst, s->stream, coarse, region);
     if (rc) return rc;
     HIPCHK(d2h_out(decData, dst, out_bytes));
     return 0;
@@ -2973,7 +2982,10 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
     if ((rc = slot_ctx(s, conf->num))) return rc;
     const int coarse = t_devout && !is_int ? t_coarse_level : 0;
     if (coarse && hdr.predictor != 1) return fail(SZ3HIP_EFORMAT, "the Config names the interpolation stream but the payload's predictor id is %d", (int)hdr.predictor);
-    const size_t cbytes = (size_t)(coarse ? coarse_num(conf, coarse) : conf->num) * (cdt == SZ3HIP_FLOAT ? 4 : 8);
+    const szi_region *region = t_devout && !is_int ? t_region : nullptr;
+    if (region && hdr.predictor != 1) return fail(SZ3HIP_EFORMAT, "the Config names the interpolation stream but the payload's predictor id is %d", (int)hdr.predictor);
+    if (region && hdr.ndim != (uint32_t)conf->N) return fail(SZ3HIP_EFORMAT, "the payload's extent count does not match the Config");
+    const size_t cbytes = (size_t)(region ? region_num(conf, region) : coarse ? coarse_num(conf, coarse) : conf->num) * (cdt == SZ3HIP_FLOAT ? 4 : 8);
     // (a device call's contiguous f32 / f64 array is decoded where it lies)
     void *dst = t_devout && t_devout->view.contig && !is_int ? (void *)t_devout->ptr : nullptr;
     if (!dst) {
@@ -2983,13 +2995,14 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
     if ((rc = ensure_dev(&s->dev_payload, &s->dev_payload_bytes, std::max<size_t>(raw_len + 64, is_int ? raw_bytes : 0)))) return rc;
     HIPCHK(hipMemcpy(s->dev_payload, s->pin, raw_len, hipMemcpyHostToDevice));
     stamp(1);
-    rc = coarse ? sz3hip_decompress_device_coarse(s->ctx, s->dev_payload, raw_len, coarse, dst, s->stream)
-                : sz3hip_decompress_device(s->ctx, s->dev_payload, raw_len, dst, s->stream);
+    rc = region   ? szi_decompress_device_region(s->ctx, s->dev_payload, raw_len, region, dst, s->stream)
+         : coarse ? sz3hip_decompress_device_coarse(s->ctx, s->dev_payload, raw_len, coarse, dst, s->stream)
+                  : sz3hip_decompress_device(s->ctx, s->dev_payload, raw_len, dst, s->stream);
     if (rc) return rc;
     if (!is_int) {
         HIPCHK(hipStreamSynchronize(s->stream));
         stamp(2);
-        HIPCHK(d2h_out(decData, dst, coarse ? cbytes : raw_bytes));
+        HIPCHK(d2h_out(decData, dst, coarse || region ? cbytes : raw_bytes));
     } else if (t_devout) {  // (narrowed straight into the caller's view)
         t_devout->delivered = true;
         if (szk_launch_scatter(dataType, 1, s->dev_in, t_devout->ptr, &t_devout->view, s->stream)) return fail(SZ3HIP_EHIP, "integer narrowing kernel failed");
@@ -3309,6 +3322,111 @@ extern "C" int sz3hip_decompress_coarse_to_device(sz3hip_config *conf, int dataT
         dense = packed.p;
     }
     if (szk_launch_gather(dataType, 0, full.p, &gv, dense, nullptr, cs)) return fail(SZ3HIP_EHIP, "gather kernel failed");
+    if (!dev.view.contig && szk_launch_scatter(dataType, 0, dense, dev.ptr, &dev.view, cs)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
+    HIPCHK(hipStreamSynchronize(cs));
+    return 0;
+}
+
+// One box of a container. Fast path: a single interpolation stream, decoded over the box's windows (decompress_blob /
+// stock_decompress_interp under t_region). Everything else: the full decode into a scratch array of the call, then the strided gather of the
+// box, a view of that array whose base is offset by lo.
+extern "C" int sz3hip_decompress_region_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, const uint64_t *lo, const uint64_t *ext,
+                                                  void *d_out, const int64_t *strides, void *stream) {
+    if (!dtype_ok(dataType))
+        return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
+    if (dtype_is_int(dataType)) return fail(SZ3HIP_EUNSUPPORTED, "the region decode reads float / double arrays; integer element types are not supported yet");
+    if (!conf || !lo || !ext) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_region_to_device: NULL argument (%s)", !conf ? "conf" : !lo ? "lo" : "ext");
+    int rc = sz3hip_peek_config(conf, cmpData, cmpSize);
+    if (rc) return rc;
+    if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
+    szi_region box;
+    memset(&box, 0, sizeof(box));
+    sz3hip_config bc = *conf;  // the box's extents (conf stays the full array's)
+    bc.num = 1;
+    for (int i = 0; i < conf->N; i++) {
+        if (ext[i] == 0) return fail(SZ3HIP_EINVAL, "the region has extent 0 in dimension %d", i);
+        if (lo[i] >= conf->dims[i] || ext[i] > conf->dims[i] - lo[i])
+            return fail(SZ3HIP_EINVAL, "the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", (unsigned long long)lo[i], (unsigned long long)lo[i],
+                        (unsigned long long)ext[i], i, (unsigned long long)conf->dims[i]);
+        box.lo[i] = lo[i];
+        box.ext[i] = ext[i];
+        bc.dims[i] = ext[i];
+        bc.num *= ext[i];
+    }
+    if (zs::load()) return SZ3HIP_EZSTD;
+    DevArray dev;
+    if ((rc = dev_array(&bc, strides, d_out, true, &dev))) return rc;
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(cmpData) + 8;
+    uint64_t payload;
+    memcpy(&payload, p, 8);
+    p += 8;
+    DeviceGuard guard;
+    HIPCHK(hipSetDevice(dev.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (what the caller queued on d_out comes first)
+    std::unique_lock<std::shared_mutex> all(g_host_mu, std::defer_lock);
+    std::shared_lock<std::shared_mutex> some(g_host_mu, std::defer_lock);
+    if (conf->openmp) all.lock();
+    else some.lock();
+    const size_t es = dtype_size(dataType);
+    if (!conf->openmp && (conf->cmprAlgo == SZ3HIP_ALGO_HIP_INTERP || conf->cmprAlgo == SZ3HIP_ALGO_INTERP)) {
+        SlotLease lease(dev.device, dtype_compute(dataType));
+        HostSlot *s = lease.s;
+        if (!s->stream) HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        DevOut o;
+        o.ptr = dev.ptr;
+        o.view = dev.view;
+        o.dataType = dataType;
+        o.stream = s->stream;
+        t_devout = &o;
+        t_region = &box;
+        rc = decompress_blob(s, conf, dataType, p, (size_t)payload, nullptr);
+        t_devout = nullptr;
+        t_region = nullptr;
+        if (rc != SZ3HIP_EUNSUPPORTED) {  // (an anchor stride that is no power of two: the windows do not nest, the full decode below)
+            if (rc) return rc;
+            if (!o.delivered) return fail(SZ3HIP_EHIP, "the region decode did not deliver its array");
+            HIPCHK(hipStreamSynchronize(s->stream));
+            return 0;
+        }
+    }
+    // the full array, decoded as sz3hip_decompress_to_device does, into a scratch of this call; then the box of it
+    struct Scratch {
+        void *p = nullptr;
+        ~Scratch() {
+            if (p) (void)hipFree(p);
+        }
+    } full, packed;
+    if (hipMalloc(&full.p, std::max<size_t>((size_t)conf->num * es, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SZ3HIP_EHIP, "no device memory for the full-size scratch (%zu bytes) this container's region decode needs", (size_t)conf->num * es);
+    }
+    DevArray fd;
+    if ((rc = dev_array(conf, nullptr, full.p, true, &fd))) return rc;
+    if (conf->openmp) rc = decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &fd);
+    else {
+        SlotLease lease(dev.device, dtype_compute(dataType));
+        rc = decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &fd, 0, conf->dims[0]);
+    }
+    if (rc) return rc;
+    szk_view gv = fd.view;  // (contiguous: element strides of the full array; the box's extents, its base offset by lo)
+    gv.contig = 0;
+    int64_t corner = 0;
+    for (int i = 0; i < conf->N; i++) {
+        const int k = 4 - conf->N + i;
+        corner += (int64_t)lo[i] * gv.str[k];
+        gv.dims[k] = ext[i];
+        if (ext[i] == 1) gv.str[k] = 0;
+    }
+    hipStream_t cs = (hipStream_t)stream;
+    void *dense = dev.ptr;
+    if (!dev.view.contig) {
+        if (hipMalloc(&packed.p, std::max<size_t>((size_t)bc.num * es, 16)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SZ3HIP_EHIP, "no device memory for the region's array (%zu bytes)", (size_t)bc.num * es);
+        }
+        dense = packed.p;
+    }
+    if (szk_launch_gather(dataType, 0, (const char *)full.p + corner * (int64_t)es, &gv, dense, nullptr, cs)) return fail(SZ3HIP_EHIP, "gather kernel failed");
     if (!dev.view.contig && szk_launch_scatter(dataType, 0, dense, dev.ptr, &dev.view, cs)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
     HIPCHK(hipStreamSynchronize(cs));
     return 0;

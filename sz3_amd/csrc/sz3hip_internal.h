@@ -24,6 +24,12 @@ struct szi_stock_params {  // what InterpolationDecomposition::save holds beside
     double alpha, beta, eb;
     int radius;
 };
+// region decode: the box [lo, lo + ext) of the array, one entry per extent of the stream, slowest first
+struct szi_region {
+    uint64_t lo[4], ext[4];
+};
+// sz3hip_decompress_device_region with the box in one struct (the host API's slots call it)
+int szi_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_region *region, void *d_out, void *stream);
 // after sz3hip_compress_stage1 chose interpolation (header predictor 1): waits for it, reports its parameters and the number of
 // unpredictable values (the anchor grid included); SZ3HIP_EUNSUPPORTED when stage 1 took another predictor
 int szi_stock_stage1_outcome(sz3hip_ctx *ctx, szi_stock_params *out, uint64_t *n_unpred, void *stream);
@@ -33,7 +39,8 @@ int szi_stock_export(sz3hip_ctx *ctx, const szg_geom *g, const uint64_t *d_blk_b
 // the inverse: emission-order codes + unpredictable values of a stock ALGO_INTERP stream -> the reconstructed array
 int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom *g, const uint64_t *d_blk_base, const uint16_t *d_em,
                      const void *d_unpred, uint64_t n_unpred, uint32_t *d_tile_cnt, uint64_t *d_tile_base, uint64_t *d_vout_idx, void *d_vout_val,
-                     uint32_t *d_bad, void *d_out, void *stream, int coarse_level = 0);  // (coarse_level k >= 1: d_out receives every 2^k-th point only)
+                     uint32_t *d_bad, void *d_out, void *stream, int coarse_level = 0,  // (coarse_level k >= 1: d_out receives every 2^k-th point only)
+                     const szi_region *region = nullptr);                                // (region: d_out receives the box only, contiguous)
 int szi_stage1_with_larger_lists(sz3hip_ctx *ctx, const sz3hip_config *conf, const void *d_in, uint64_t need, void *stream, bool any_number = false);
 // The default algorithm's tuner run from the HOST copy of an array while that array is being copied to the device (the host API: the tuner's
 // launches, round trips and host-side pricing vanish behind the copy). conf: the call's Config with its absolute bound; the next
@@ -97,6 +104,8 @@ struct sz3hip_ctx {
     uint32_t *h_ovf;   // pinned: the previous decode's overflow flag, fetched with this call's header
     uint16_t *d_coarse_codes;   // coarse decode: the coarse grid's dense code array, max_n / 2 + 8 codes (made by the context's first coarse call, kept)
     uint64_t coarse_codes_cap;
+    void *d_region;             // region decode: the levels' compact buffers (made by the context's first region call, grown when a plan needs more, kept)
+    uint64_t region_cap;        // ... in elements of the context's type
     void *s2_payload;  // stage 2's arguments, kept for the repeat after a mispredicted code-book form
     size_t s2_cap;
     // Two code books: bk[book_idx] is the last one a call of this context completed with (-1: none yet). Stage 2 builds this

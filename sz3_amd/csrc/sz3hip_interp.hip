@@ -25,17 +25,10 @@
 #include "sz3hip_format.h"
 #include "sz3hip_kernels.h"
 #include "sz3hip_devutil.h"
+#include "sz3hip_interp_rules.h"  // ip_* and the case selection (shared with sz3hip_region.hip)
 
 #define IH_WIN 1024  // LDS histogram window (bins) around the radius
 
-
-// ---- Interpolators.hpp:12-39 ---------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ T ip_linear(T a, T b) { return (a + b) / 2; }
-template <typename T> __device__ __forceinline__ T ip_linear1(T a, T b) { return (T)(-0.5 * (double)a + 1.5 * (double)b); }
-template <typename T> __device__ __forceinline__ T ip_quad_1(T a, T b, T c) { return (3 * a + 6 * b - c) / 8; }
-template <typename T> __device__ __forceinline__ T ip_quad_2(T a, T b, T c) { return (-a + 6 * b + 3 * c) / 8; }
-template <typename T> __device__ __forceinline__ T ip_quad_3(T a, T b, T c) { return (3 * a - 10 * b + 15 * c) / 8; }
-template <typename T> __device__ __forceinline__ T ip_cubic(T a, T b, T c, T d) { return (-a + 9 * b + 9 * c - d) / 16; }
 
 // Unpredictable values (code 0: the raw value stays in the array) are NOT appended by the pass kernels: the histogram pass
 // that reads every code anyway (k_hist_codes) collects their indices and values into the list, through per-wave LDS queues
@@ -90,37 +83,7 @@ __device__ __forceinline__ void interp_point(T *__restrict__ w, uint16_t *__rest
     const int64_t st = (int64_t)(p.s * p.off[p.dir]);
     T *d = w + idx;
     bool deferred = false;
-    T pred;
-    if (p.old_api) {  // interpolation_1d, InterpolationDecomposition.hpp:248-293 (N <= 2)
-        if (p.interp_id == 0 || n < 5) {
-            if (i + 1 < n) pred = ip_linear<T>(d[-st], d[st]);
-            else pred = n < 4 ? d[-st] : ip_linear1<T>(d[-3 * st], d[-st]);
-        } else {
-            if (i == 1) pred = ip_quad_1<T>(d[-st], d[st], d[3 * st]);
-            else if (i + 3 < n) pred = ip_cubic<T>(d[-3 * st], d[-st], d[st], d[3 * st]);
-            else if (i + 1 < n) pred = ip_quad_2<T>(d[-3 * st], d[-st], d[st]);
-            else pred = ip_quad_3<T>(d[-5 * st], d[-3 * st], d[-st]);
-        }
-    } else if (p.interp_id == 0) {  // interpolation_1d_fastest_dim_first, linear branch :334-351
-        if (i + 1 < n) {
-            pred = ip_linear<T>(d[-st], d[st]);
-        } else if (n < 3) {
-            pred = d[-st];
-        } else {
-            deferred = true;  // reads d[-2*st]: a point of this same pass -> second launch
-            pred = p.subpass ? ip_linear1<T>(d[-2 * st], d[-st]) : (T)0;
-        }
-    } else {  // cubic branch :352-399
-        if (i >= 3) {
-            if (i + 3 < n) pred = ip_cubic<T>(d[-3 * st], d[-st], d[st], d[3 * st]);
-            else if (i + 1 < n) pred = ip_quad_2<T>(d[-3 * st], d[-st], d[st]);
-            else pred = ip_linear1<T>(d[-3 * st], d[-st]);
-        } else {
-            if (i + 3 < n) pred = ip_quad_1<T>(d[-st], d[st], d[3 * st]);
-            else if (i + 1 < n) pred = ip_linear<T>(d[-st], d[st]);
-            else pred = d[-st];
-        }
-    }
+    const T pred = interp_predict<T>(d, st, i, n, p.old_api, p.interp_id, p.subpass, deferred);
     if ((p.subpass != 0) != deferred) return;
     if (DEC) {
         const int code = codes[idx];
@@ -1130,6 +1093,40 @@ static void nth_permutation(int N, int id, int *perm) {  // lexicographic order 
     for (int i = 0; i < N; i++) perm[i] = p[i];
 }
 
+void szk_interp_perm(int N, int id, int *perm) { nth_permutation(N, id, perm); }
+// init() :176-213: the number of interpolation levels that run (level l has stride 2^(l-1); with anchors the anchor grid takes the place
+// of the coarsest one) and the anchor stride in effect (0: no extent exceeds it, the first point is predicted by 0 instead)
+int szk_interp_level_count(int N, const uint64_t *dims, uint64_t anchor_stride, uint64_t *anchor_eff) {
+    uint64_t anchor = anchor_stride;
+    int interp_level = -1;
+    bool use_anchor = false;
+    for (int i = 0; i < N; i++) {
+        const int lv = (int)ceil(log2((double)dims[i]));
+        if (interp_level < lv) interp_level = lv;
+        if (dims[i] > anchor) use_anchor = true;
+    }
+    if (!use_anchor) anchor = 0;
+    if (anchor > 0) {
+        const int maxl = (int)log2((double)anchor) + 1;
+        if (maxl <= interp_level) interp_level = maxl;
+        interp_level--;
+    }
+    *anchor_eff = anchor;
+    return interp_level;
+}
+// the error bound of a level (compress :103-117); eb_level: the level's number in the full array
+double szk_interp_level_eb(double eb, double alpha, double beta, int eb_level) {
+    double cur_eb = eb;
+    if (alpha < 0) {
+        cur_eb = eb_level >= 3 ? eb * 0.5 : eb;
+    } else if (alpha >= 1) {
+        double r = pow(alpha, eb_level - 1);
+        if (r > beta) r = beta;
+        cur_eb = eb / r;
+    }
+    return cur_eb;
+}
+
 int szk_interp_novec = 0;  // test hook: force the one-point-per-thread kernels
 
 // the level / pass schedule as a list (kind 0: anchor grid, 1: first point without anchors, 2: directional pass)
@@ -1156,19 +1153,8 @@ static int build_schedule(const szk_interp_params &ip, bool dec, uint32_t nbatch
     p.vout_val = ip.vout_val;
     p.out_cap = ip.out_cap;
     // init(): levels and whether anchors are used
-    uint64_t anchor = ip.anchor_stride;
-    int interp_level = -1;
-    bool use_anchor = false;
-    for (int i = 0; i < N; i++) {
-        const int lv = (int)ceil(log2((double)p.dims[i]));
-        if (interp_level < lv) interp_level = lv;
-        if (p.dims[i] > anchor) use_anchor = true;
-    }
-    if (!use_anchor) anchor = 0;
-    if (anchor > 0) {
-        const int maxl = (int)log2((double)anchor) + 1;
-        if (maxl <= interp_level) interp_level = maxl;
-    }
+    uint64_t anchor;
+    int interp_level = szk_interp_level_count(N, p.dims, ip.anchor_stride, &anchor);
     int perm[4], pos[4];
     nth_permutation(N, ip.direction, perm);
     for (int k = 0; k < N; k++) pos[perm[k]] = k;
@@ -1197,19 +1183,10 @@ static int build_schedule(const szk_interp_params &ip, bool dec, uint32_t nbatch
             p.subpass = 0;
             out.push_back(p);
         }
-        interp_level--;
     }
     p.kind = 2;
     for (int level = interp_level; level > 0; level--) {
-        double cur_eb = ip.eb;  // per-level bound :103-117
-        const int eb_level = level + level_shift;
-        if (ip.alpha < 0) {
-            cur_eb = eb_level >= 3 ? ip.eb * 0.5 : ip.eb;
-        } else if (ip.alpha >= 1) {
-            double r = pow(ip.alpha, eb_level - 1);
-            if (r > ip.beta) r = ip.beta;
-            cur_eb = ip.eb / r;
-        }
+        const double cur_eb = szk_interp_level_eb(ip.eb, ip.alpha, ip.beta, level + level_shift);
         p.eb = cur_eb;
         p.eb_recip = 1.0 / cur_eb;
         p.s = 1ull << (level - 1);

@@ -375,6 +375,36 @@ int szk_launch_interp_decompress(int dtype, const szk_interp_params *ip, const u
 // codes, d_out = prod(((D - 1) >> k) + 1) elements. -3: an anchor stride that is no power of two
 int szk_launch_interp_decompress_coarse(int dtype, const szk_interp_params *ip, int k, const uint8_t *payload, uint64_t vout_idx_off,
                                         uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, uint16_t *codes_coarse, void *d_out, hipStream_t s);
+// the schedule's arithmetic that build_schedule shares with the region decode: the pass order of a direction id, the number of levels that
+// run with the anchor stride in effect (0: the first-point path), a level's error bound
+void szk_interp_perm(int N, int id, int *perm);
+int szk_interp_level_count(int N, const uint64_t *dims, uint64_t anchor_stride, uint64_t *anchor_eff);
+double szk_interp_level_eb(double eb, double alpha, double beta, int eb_level);
+
+// ---- region decode of an interpolation stream (sz3hip_region.hip) ----
+#define SZK_REGION_MAX_LEVELS 32
+struct szk_region_level {  // one level, stride s: its windows (inclusive, full-array coordinates) and its compact buffer
+    uint64_t s;
+    uint64_t out_lo[4], out_hi[4];  // the points of the level that the box depends on
+    uint64_t in_lo[4], in_hi[4];    // what predicting them reads: the output window of level 2 s
+    uint64_t wlo[4], cnt[4], boff[4];  // the buffer: the grid of stride s from wlo (in_lo rounded down to a multiple of 2 s) to in_hi, its element strides
+    uint64_t elems, base;           // its size and where it starts in the scratch array
+};
+struct szk_region_geom {
+    int N, interp_id, n_levels, nbuf;  // nbuf = max(n_levels, 1): lv[0] is the coarsest level, lv[nbuf - 1] has stride 1
+    int perm[4];
+    uint64_t anchor;                   // the anchor stride in effect (0: first-point path)
+    uint64_t dims[4], lo[4], ext[4];
+    szk_region_level lv[SZK_REGION_MAX_LEVELS];
+    uint64_t points, scratch_elems;
+};
+// a pure host function. 0, -1 (bad box / extents), -3 (an anchor stride that is no power of two)
+int szk_region_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const uint64_t *lo, const uint64_t *ext,
+                        szk_region_geom *g);
+uint64_t szk_region_pass_window(const szk_region_geom *g, int b, int k, uint64_t *first, uint64_t *step, uint64_t *cnt);
+// ip = the full array's parameters, codes = its per-element codes, scratch = g->scratch_elems elements, d_out = prod(ext) elements, contiguous
+int szk_launch_interp_decompress_region(int dtype, const szk_interp_params *ip, const szk_region_geom *g, const uint8_t *payload, uint64_t vout_idx_off,
+                                        uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, void *scratch, void *d_out, hipStream_t s);
 
 int szk_launch_profile_blocks(int dtype, const void *d_in, int N, const uint64_t *dims, uint64_t bs, uint64_t stride, double abseb,
                               uint8_t *d_flags, uint64_t *total_out, hipStream_t s);
