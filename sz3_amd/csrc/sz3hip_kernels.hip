@@ -4570,14 +4570,14 @@ __global__ __launch_bounds__(256) void k_pack(const uint16_t *__restrict__ codes
 // looks up PAIRS of codes: a 128 x 128 table over the byte values t in [64, 192) (deltas -63 .. +64 around the mode of a one-byte
 // stream, byte 127; 64 KB of LDS: entry = (code words of t0 and t1 joined) << 5 | their length, 0 when one of them has no code word
 // or the two take more than 27 bits) — one lookup and one shift per TWO symbols. A workgroup is 1024 threads (16 waves share the
-// table: 64 KB + 16 stages of 3 KB, one workgroup per CU); three code registers per lane are in flight (the chunk being packed and
-// the next two: 16 waves x 3 KB per CU cover the HBM latency at the 3 TB/s the launch reads with).
+// table: 64 KB + 16 stages of 4 KB, one workgroup per CU); a wave works in units of four chunks: the codes of the unit being packed
+// and of the next one are in registers, the unit's fast-tier chunks share the stage and leave it in one copy-out of 16 bytes per lane.
 //   fast tier (wave-uniform test): every byte of the chunk inside the window, every pair in the table, every lane's two octets <= 64 bits:
 //     8 lookups, 2 emissions of 3 ds_or each;
 //   otherwise the chunk goes symbol by symbol through the 256-entry tables like k_pack — pairs (<= 48 bits: code words up to 24 bits,
 //     the books of round 6's sampled form give symbols the sample did not meet such lengths) joined to quads and octets where EVERY
 //     lane's fit 64 bits (wave-uniform), emitted as octets, quads or pairs.
-// Same bit stream as k_pack (same book, same chunk table): tests/test_gpu_stages.py compares the two byte for byte.
+// Same bit stream as k_pack (same book, same chunk table): tests/test_gpu_packb.py and tests/test_gpu_packb_units.py compare the two byte for byte.
 // Role workgroups (the two list sorts; the book role is k_pack's: this kernel is launched where no book is built beside the packer)
 // come first in the grid, the assembly's last (see the kernel).
 // ------------------------------------------------------------------------------------------------------------
@@ -4592,9 +4592,12 @@ __device__ __forceinline__ void packb_emit(uint64_t *stage, uint64_t val, uint32
     atomicOr(reinterpret_cast<unsigned long long *>(&stage[q]), (unsigned long long)(v >> sh));
     atomicOr(reinterpret_cast<unsigned long long *>(&stage[q + 1]), (unsigned long long)((v << 1) << (63u - sh)));  // (= v << (64 - sh), and 0 for sh = 0)
 }
-// one chunk: the lane's 16 code bytes (w[0] = symbols 0 .. 3, low byte first) into the wave's stage; returns the chunk's word count
+// one chunk: the lane's 16 code bytes (w[0] = symbols 0 .. 3, low byte first) into the wave's stage; returns the chunk's word count.
+// A fast-tier chunk lands behind the `staged` 32-bit words the unit has in the stage already (fast = true); any other chunk first
+// calls flush() — the caller copies out what is staged — and then lands at the stage's start (fast = false).
+template <typename Flush>
 __device__ __forceinline__ uint32_t packb_chunk(const uint4 &cw, const uint32_t *__restrict__ s_pair, const uint32_t *__restrict__ s_enc8,
-                                                const uint8_t *__restrict__ s_len8, uint64_t *stage) {
+                                                const uint8_t *__restrict__ s_len8, uint64_t *stage, uint32_t staged, bool &fast_tier, Flush &&flush) {
     const uint32_t w[4] = {cw.x, cw.y, cw.z, cw.w};
     // ---- fast tier ----
     {
@@ -4603,8 +4606,8 @@ __device__ __forceinline__ uint32_t packb_chunk(const uint4 &cw, const uint32_t 
         uint32_t e[8];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            // entry of the pair (t0, t1): index (t1 & 127) << 7 | ((t0 ^ t1) & 127) — the XOR spreads the lookups over the LDS banks (a bank
-            // is the index's low five bits: with t0 alone a smooth field's symbols, a dozen values around the mode, meet in a dozen banks)
+            // entry of the pair (t0, t1): index (t1 & 127) << 7 | ((t0 ^ t1) & 127) — the XOR spreads the lookups over the LDS banks (the bank
+            // of a 32-bit LDS read is the index's low five bits — the chip's 64 banks serve its 64- and 128-bit reads: with t0 alone a smooth field's symbols, a dozen values around the mode, meet in a dozen banks)
             const uint32_t m = w[k] & 0x7F7F7F7Fu, x = m ^ (m >> 8), m1 = m >> 16, x1 = x >> 16;
             const uint32_t a0 = ((x & 0x7Fu) << 2) | ((m & 0x7F00u) << 1), a1 = ((x1 & 0x7Fu) << 2) | ((m1 & 0x7F00u) << 1);
             e[2 * k] = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(s_pair) + a0);
@@ -4627,13 +4630,16 @@ __device__ __forceinline__ uint32_t packb_chunk(const uint4 &cw, const uint32_t 
             const uint32_t bits = OL[0] + OL[1];
             const uint32_t incl = wave_incl_scan(bits);
             const uint32_t total_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
-            const uint32_t pos = incl - bits;
+            const uint32_t pos = 32u * staged + incl - bits;
             packb_emit(stage, O[0], OL[0], pos);
             packb_emit(stage, O[1], OL[1], pos + OL[0]);
+            fast_tier = true;
             return (total_bits + 31u) >> 5;
         }
     }
     // ---- symbol by symbol ----
+    fast_tier = false;
+    flush();
     uint64_t P[8];
     uint32_t PL[8];
 #pragma unroll
@@ -4684,11 +4690,14 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
                                                         const uint16_t *__restrict__ chunk_words, const uint64_t *__restrict__ group_off, szk_mode mode,
                                                         uint32_t sym_add, const szk_state *__restrict__ state, uint8_t *__restrict__ payload,
                                                         szk_asm_params ap, uint32_t pack_blocks, uint32_t split, szk_role_params rp, uint32_t only_sampled) {
-    constexpr int STAGE_WORDS = SZH_CHUNK_SYMS * SZH_MAX_LEN / 32 + 4;  // + slack for the unconditional 3-word emit
+    constexpr int STAGE_WORDS = SZH_CHUNK_SYMS * SZH_MAX_LEN / 32 + 4;  // one chunk symbol by symbol, + slack for the unconditional second word of an emit
+    constexpr uint32_t PB_BATCH = 4;                                    // chunks of a work unit
+    constexpr int UNIT_STAGE = PB_BATCH * 128 + 8;                      // 64-bit words: four fast-tier chunks of at most 64 lanes x 128 bits, + the same slack (a multiple of 16 bytes)
+    static_assert(2 * UNIT_STAGE >= STAGE_WORDS && UNIT_STAGE % 2 == 0, "the unit's stage also holds one chunk of the slow tiers");
     __shared__ __align__(16) uint32_t s_pair[128 * 128];
     __shared__ uint32_t s_enc8[256];  // code word by byte value ...
     __shared__ uint8_t s_plen8[256];  // ... and its length
-    __shared__ __align__(8) uint64_t s_stage[PB_WAVES][STAGE_WORDS / 2];
+    __shared__ __align__(16) uint64_t s_stage[PB_WAVES][UNIT_STAGE];
     // (launched beside k_pack behind the two-launch form of stage 1 — only_sampled: this kernel then packs, sorts and assembles only
     // when the call codes with its sampled book, k_pack otherwise)
     if ((only_sampled & SZK_PACKB_ONLY_SAMPLED) && !(ap.samp_words && ap.samp_words[SZK_SAMP_READY] && szk_is_narrow(mode))) return;
@@ -4713,7 +4722,9 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     if (!szk_is_narrow(mode)) return;  // stage 1 assumed one-byte codes, the probe says two: nothing to pack (the assembly reports it, the call is repeated)
     const uint64_t n_full = n / SZH_CHUNK_SYMS, n_chunks = (n + SZH_CHUNK_SYMS - 1) / SZH_CHUNK_SYMS;
     (void)split;
-    const uint32_t wv = threadIdx.x / WAVE;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));  // (wave-uniform, and known to be: the unit loop's control and addresses are scalar)
+    // (numbering the waves across the workgroups — wave_gid = wv * pack_blocks + bid, so that the partial last round runs one or two units
+    // per compute unit — was measured and not taken: 4.6 us while every unit's copy-out sat in front of the next wait, nothing since)
     const uint64_t wave_gid = (uint64_t)bid * PB_WAVES + wv, nwaves = (uint64_t)pack_blocks * PB_WAVES;
     const int lane = lane_id();
     const uint8_t *c8 = reinterpret_cast<const uint8_t *>(codes) + (uint64_t)lane * ENC_PER_LANE;
@@ -4724,41 +4735,129 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     // (one load of the group's counts). Units are dealt round-robin over the launch's waves, so that at any time the chip reads one
     // window of consecutive units (16 MB of codes) and writes one window of the stream: a wave that owned a whole group — 4096 separate
     // streams of 32 KB over the chip — was a third slower whenever the codes came from HBM rather than from the memory-side cache.
-    // The loads of a unit are issued together, a unit ahead — on gfx9 a wave's loads and stores share one counter (vmcnt) and complete
-    // out of order with respect to each other, so waiting for a load means waiting for every store issued before: once per unit here,
-    // once per chunk in k_pack's loop (whose wave then idles through the store acknowledgement of its previous chunk).
-    constexpr uint32_t PB_BATCH = 4;
+    // The loads of a unit — four chunks, the group's counts, the group's offset: six instructions — are issued together, a unit ahead,
+    // and UNCONDITIONALLY: every index is clamped to a valid one (a chunk past the last whole one is fetched and not used, a wave's last
+    // unit fetches itself again), so that the compiler sees six loads behind the ones it waits for and waits with a count — behind a
+    // guarded load (a branch around it) it cannot count and waits for everything in flight, the loads just issued included.
     const uint64_t n_units = (n_full + PB_BATCH - 1) / PB_BATCH;
 #ifdef SZ3HIP_LAB  // (lab build: what the launch's time is made of — only_sampled bits SZK_PACKB_LAB_NO_STORES: no stores of the stream, SZK_PACKB_LAB_ONE_UNIT: every unit reads the first unit's codes)
     const bool lab_nost = (only_sampled & SZK_PACKB_LAB_NO_STORES) != 0, lab_nold = (only_sampled & SZK_PACKB_LAB_ONE_UNIT) != 0;
 #else
     constexpr bool lab_nost = false, lab_nold = false;
 #endif
-    auto fetch = [&](uint64_t ch) { return ch < n_full ? *reinterpret_cast<const uint4 *>(c8 + (lab_nold ? ch % (4 * nwaves) : ch) * SZH_CHUNK_SYMS) : make_uint4(0u, 0u, 0u, 0u); };
-    auto front_of = [&](uint64_t unit) -> uint32_t {  // (one lane-parallel load: the counts of the group's chunks in front of the unit)
-        const uint64_t c_lo = unit * PB_BATCH, grp = c_lo / PACK_GROUP;
+    struct unit_regs {
+        uint4 c[PB_BATCH];  // the lane's 16 codes of each chunk
+        uint32_t fr;        // lane < the unit's first chunk in its group: that chunk's words (else unused)
+        uint64_t go;        // the group's offset
+    };
+    auto load_unit = [&](unit_regs &r, uint64_t u) {  // (u < n_units; n_full >= 1 and n_chunks >= 1: the launch's condition)
+        const uint64_t c_lo = u * PB_BATCH, grp = c_lo / PACK_GROUP;
+#pragma unroll
+        for (uint32_t j = 0; j < PB_BATCH; j++) {
+            uint64_t ch = c_lo + j < n_full ? c_lo + j : n_full - 1;
+            if (lab_nold) ch %= 4 * nwaves;
+            r.c[j] = *reinterpret_cast<const uint4 *>(c8 + ch * SZH_CHUNK_SYMS);
+        }
+        const uint64_t ci = grp * PACK_GROUP + (uint32_t)lane;
+        r.fr = chunk_words[ci < n_chunks ? ci : n_chunks - 1];
+        r.go = group_off[grp];
+    };
+    uint32_t *const stage32 = reinterpret_cast<uint32_t *>(stage);
+    uint4 *const stage128 = reinterpret_cast<uint4 *>(stage);
+    typedef uint32_t u32x4_dw __attribute__((ext_vector_type(4), aligned(4)));  // (a run of the stream starts at any 32-bit word)
+    // the staged words of a unit to the stream, 16 bytes per lane and trip, the stage zeroed behind the read; the words of the last,
+    // partial 16 bytes go one per lane in front. (stream word w is the high half of stage[w / 2] for even w, the low half for odd w)
+    auto copy_out = [&](uint32_t *out, uint32_t nw) {
+        const uint32_t tail = nw & 3u, w_t = (nw & ~3u) + (uint32_t)lane;
+        if ((uint32_t)lane < tail) {
+            const uint32_t v = stage32[w_t ^ 1u];
+            if (!lab_nost || v == 0x12345678u) out[w_t] = __builtin_bswap32(v);
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (uint32_t t = 0; t < PB_BATCH; t++) {
+            const uint32_t i = t * WAVE + (uint32_t)lane;
+            if (4u * i < nw) {
+                const uint4 v = stage128[i];
+                stage128[i] = make_uint4(0u, 0u, 0u, 0u);
+                if (4u * i + 4u <= nw && (!lab_nost || v.x == 0x12345678u)) {
+                    u32x4_dw o;
+                    o.x = __builtin_bswap32(v.y);  // bytes in stream order (see sz3hip_format.h)
+                    o.y = __builtin_bswap32(v.x);
+                    o.z = __builtin_bswap32(v.w);
+                    o.w = __builtin_bswap32(v.z);
+                    *reinterpret_cast<u32x4_dw *>(out + 4u * i) = o;
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    // one unit: fast-tier chunks one behind the other in the stage (chunk j starts at the word where chunk j - 1 ended: whole words, as
+    // in the stream) and one copy-out; a chunk of the other tiers has what is staged copied out first, then goes through the stage alone.
+    // What a unit leaves staged at its end is copied out by the NEXT unit, behind that unit's wait for its loads: vmcnt retires in order,
+    // so a wait for loads is a wait for every store issued before the loads behind them — stores issued in front of the wait would be
+    // waited for at once, stores issued behind it have a whole unit's time until the next wait.
+    uint32_t *pend_out = out_base;
+    uint32_t pend = 0;
+    auto copy_pending = [&]() {
+        if (pend) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            copy_out(pend_out, pend);
+            pend = 0;
+        }
+    };
+    auto pack_unit = [&](const unit_regs &r, uint64_t unit) {
+        const uint64_t c_lo = unit * PB_BATCH;
         const uint32_t first = (uint32_t)(c_lo % PACK_GROUP);
-        return ((uint32_t)lane < first && grp * PACK_GROUP + lane < n_chunks) ? chunk_words[grp * PACK_GROUP + lane] : 0u;
+        uint32_t *out = out_base + r.go + wave_sum((uint32_t)lane < first ? r.fr : 0u);  // (the unit's last load: the wait is here)
+        __builtin_amdgcn_sched_barrier(0);
+        copy_pending();
+        uint32_t staged = 0;
+        auto flush = [&]() {
+            if (staged) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                copy_out(out, staged);
+                out += staged;
+                staged = 0;
+            }
+        };
+#pragma unroll
+        for (uint32_t j = 0; j < PB_BATCH; j++) {
+            if (c_lo + j < n_full) {  // (wave-uniform: whole chunks only — the ragged last one is packed apart)
+                bool fast_tier;
+                const uint32_t nwords = packb_chunk(r.c[j], s_pair, s_enc8, s_plen8, stage, staged, fast_tier, flush);
+                if (fast_tier) {
+                    staged += nwords;
+                } else {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    for (uint32_t i = 2 * lane; i < nwords + 2; i += 2 * WAVE) {  // copy out and re-zero the stage, two words per lane
+                        const uint64_t v = stage[i >> 1];
+                        stage[i >> 1] = 0;
+                        if (lab_nost && v != 0x123456789abcdefull) continue;
+                        if (i < nwords) out[i] = __builtin_bswap32((uint32_t)(v >> 32));
+                        if (i + 1 < nwords) out[i + 1] = __builtin_bswap32((uint32_t)v);
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    out += nwords;
+                }
+            }
+        }
+        pend_out = out;
+        pend = staged;
     };
     uint64_t unit = wave_gid;
-    uint4 cur[PB_BATCH], nxt[PB_BATCH];
-    uint32_t fr_cur = 0, fr_nxt = 0;
-    uint64_t go_cur = 0, go_nxt = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < PB_BATCH; j++) cur[j] = make_uint4(0u, 0u, 0u, 0u);
-    if (unit < n_units) {
-#pragma unroll
-        for (uint32_t j = 0; j < PB_BATCH; j++) cur[j] = fetch(unit * PB_BATCH + j);
-        fr_cur = front_of(unit);
-        go_cur = group_off[unit * PB_BATCH / PACK_GROUP];
-    }
+    unit_regs ra, rb;
+    load_unit(ra, unit < n_units ? unit : n_units - 1);
     // the tables: single symbols by byte value, then the pairs of the window from them
     if (threadIdx.x < 256u) {
         const uint32_t e = g_enc[threadIdx.x != 255u ? threadIdx.x + sym_add : 0u];
         s_enc8[threadIdx.x] = e >> 5;
         s_plen8[threadIdx.x] = (uint8_t)(e & 31u);
     }
-    for (int i = lane; i < STAGE_WORDS / 2; i += WAVE) stage[i] = 0;
+    for (int i = lane; i < UNIT_STAGE; i += WAVE) stage[i] = 0;
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < 128u * 128u; i += PB_THREADS) {
         const uint32_t i1 = i >> 7, i0 = (i & 127u) ^ i1;        // window indices t & 127 of the first and the second symbol (the table is swizzled: packb_chunk)
@@ -4768,38 +4867,21 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
         s_pair[i] = (l0 && l1 && len <= 27u) ? ((((s_enc8[t0] << l1) | s_enc8[t1]) << 5) | len) : 0u;
     }
     __syncthreads();
-    for (; unit < n_units; unit += nwaves) {
-        const uint64_t nu = unit + nwaves;
-        if (nu < n_units) {
-#pragma unroll
-            for (uint32_t j = 0; j < PB_BATCH; j++) nxt[j] = fetch(nu * PB_BATCH + j);
-            fr_nxt = front_of(nu);
-            go_nxt = group_off[nu * PB_BATCH / PACK_GROUP];
-        }
-        uint32_t *out = out_base + go_cur + wave_sum(fr_cur);
-        const uint64_t c_lo = unit * PB_BATCH;
-#pragma unroll
-        for (uint32_t j = 0; j < PB_BATCH; j++) {
-            if (c_lo + j < n_full) {  // (wave-uniform: whole chunks only — the ragged last one is packed apart)
-                const uint32_t nwords = packb_chunk(cur[j], s_pair, s_enc8, s_plen8, stage);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                for (uint32_t i = 2 * lane; i < nwords + 2; i += 2 * WAVE) {  // copy out and re-zero the stage for the next chunk, two words per lane
-                    const uint64_t v = stage[i >> 1];
-                    stage[i >> 1] = 0;
-                    if (lab_nost && v != 0x123456789abcdefull) continue;
-                    if (i < nwords) out[i] = __builtin_bswap32((uint32_t)(v >> 32));  // bytes in stream order (see sz3hip_format.h)
-                    if (i + 1 < nwords) out[i + 1] = __builtin_bswap32((uint32_t)v);
-                }
-                __builtin_amdgcn_wave_barrier();
-                out += nwords;
-            }
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < PB_BATCH; j++) cur[j] = nxt[j];
-        fr_cur = fr_nxt;
-        go_cur = go_nxt;
+    // two units per trip, the register sets swapping roles: no moves at the back edge, which would need the next unit's codes at once
+    while (unit < n_units) {
+        uint64_t nu = unit + nwaves;
+        load_unit(rb, nu < n_units ? nu : unit);
+        __builtin_amdgcn_sched_barrier(0);  // (the loads first: a use of the current unit moved in front of them would wait there)
+        pack_unit(ra, unit);
+        unit = nu;
+        if (unit >= n_units) break;
+        nu = unit + nwaves;
+        load_unit(ra, nu < n_units ? nu : unit);
+        __builtin_amdgcn_sched_barrier(0);
+        pack_unit(rb, unit);
+        unit = nu;
     }
+    copy_pending();
     if (n_full < n_chunks && wave_gid == 0) {  // ragged tail: the missing symbols have no bits — packed symbol by symbol
         const uint64_t base = n_full * SZH_CHUNK_SYMS + (uint64_t)lane * ENC_PER_LANE;
         const uint8_t *cb = reinterpret_cast<const uint8_t *>(codes);
