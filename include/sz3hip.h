@@ -206,6 +206,43 @@ typedef struct sz3hip_region_plan {
 int sz3hip_region_plan_for(const sz3hip_config *conf, const uint64_t *lo, const uint64_t *ext, sz3hip_region_plan *out);
 int sz3hip_decompress_region_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, const uint64_t *lo, const uint64_t *ext,
                                        void *d_out, const int64_t *strides, void *stream);
+/* Tile decode: one box of the grid of every 2^level-th point — the tile of an image pyramid — bit for bit the full decode's values, in work
+ * sized to the box, the Huffman stage included. lo / ext are in COARSE-grid coordinates, one entry per conf->N extent,
+ * slowest first; the box [lo, lo + ext) must lie inside sz3hip_coarse_dims(conf, level). d_out holds ext extents; its value at coarse
+ * coordinate c is the full decode's value at c << level. Level 0 is the region decode (sz3hip_decompress_region_to_device is this call at
+ * level 0); the whole coarse grid as box gives sz3hip_decompress_coarse_to_device's array.
+ * sz3hip_tile_plan_for: a pure function (no device). region: the region plan of the box on the coarse grid — windows in coarse-grid
+ * coordinates, level strides in coarse steps; with anchors in use and 2^level at or beyond the anchor stride every coarse point is an anchor
+ * (n_levels 0, points 0). units_total: decoder units (512 codes each) of the stream's code array, ceil(num / 512). units_needed: the units
+ * the tile's passes read a code from — for every line of a pass window along the fastest dimension, every unit from the one that holds the
+ * code of the line's first lattice point to the one that holds its last, and unit 0 where the first point (an array without anchors) is read.
+ * sz3hip_tile_units_for: those units, strictly ascending, into units[0 .. cap); *n_needed is set even when cap is too small (then
+ * SZ3HIP_ECAPACITY). A pure function.
+ * Errors of the three: level outside 0 .. 30, ext[j] == 0, a box that leaves the coarse grid or a NULL argument: SZ3HIP_EINVAL before any
+ * launch; an anchor stride that is no power of two: SZ3HIP_EUNSUPPORTED from the two pure functions (sz3hip_decompress_tile_to_device then
+ * takes the fallback).
+ * sz3hip_decompress_tile_to_device: pointer, stride, stream and synchrony rules are sz3hip_decompress_region_to_device's; conf comes back as
+ * the FULL array's Config; SZ3HIP_FLOAT and SZ3HIP_DOUBLE. Fast path and fallback are the region decode's: the fallback (everything that is no
+ * single interpolation stream, or an anchor stride that is no power of two) decodes the full array into a scratch of the call and gathers the
+ * view whose strides are multiplied by 2^level and whose base lies at lo << level.
+ * Sparse decode: on the fast path of this library's own interpolation stream (container id 17) the Huffman stage decodes the needed units
+ * alone when they are few — at most half of the stream's and at most max(32768, an eighth of them) —; otherwise, and for stock ALGO_INTERP streams (whose codes come through the stock
+ * decoder), every unit as before. sz3hip_set_sparse_decode(0) switches it off for the process (default on; SZ3HIP_SPARSE_DECODE=0 / 1 in the
+ * environment decides before the first call of either function). The values do not depend on it. */
+typedef struct sz3hip_tile_plan {
+    sz3hip_region_plan region; /* windows, strides, points, scratch_elems: in COARSE-grid coordinates (the grid of sz3hip_coarse_dims(conf, level)) */
+    uint64_t units_total;      /* decoder units of the stream's code array: ceil(num / 512) */
+    uint64_t units_needed;     /* units the tile's passes read a code from */
+} sz3hip_tile_plan;
+int sz3hip_tile_plan_for(const sz3hip_config *conf, int level, const uint64_t *lo, const uint64_t *ext, sz3hip_tile_plan *out);
+int sz3hip_tile_units_for(const sz3hip_config *conf, int level, const uint64_t *lo, const uint64_t *ext, uint32_t *units, uint64_t cap, uint64_t *n_needed);
+int sz3hip_decompress_tile_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const uint64_t *lo,
+                                     const uint64_t *ext, void *d_out, const int64_t *strides, void *stream);
+void sz3hip_set_sparse_decode(int on);
+int sz3hip_get_sparse_decode(void);
+/* test hook, process-wide and cumulative: decoder units the Huffman stage of the tile / region calls' fast path decoded, and units their
+ * streams held (equal where the stage ran densely) */
+void sz3hip_debug_tile_units(uint64_t *decoded, uint64_t *total);
 /* (test and measurement hook) the strided gather alone: the view (N extents, element strides) of d_in into the contiguous d_out on stream,
  * integers widened to f64 as the compress call does; asynchronous */
 int sz3hip_debug_gather(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream);
@@ -323,6 +360,11 @@ int sz3hip_decompress_device_coarse(sz3hip_ctx *ctx, const void *d_payload, size
  * sz3hip_decompress_region_to_device decodes every container. */
 int sz3hip_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const uint64_t *lo, const uint64_t *ext, void *d_out,
                                     void *stream);
+/* the same for a box of the grid of every 2^level-th point (see sz3hip_tile_plan_for above; level 0 is sz3hip_decompress_device_region, which
+ * is this call). The context's first tile / region call also allocates the unit list — a pinned and a device array of max_n / 512 + 1 entries —
+ * and keeps it; the list travels by one asynchronous copy on `stream` in front of the Huffman stage's launch. */
+int sz3hip_decompress_device_tile(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, const uint64_t *lo, const uint64_t *ext,
+                                  void *d_out, void *stream);
 /* test hook: the capacity of the context's region scratch, in elements (0 before its first region call) */
 uint64_t sz3hip_debug_region_scratch(const sz3hip_ctx *ctx);
 /* test hook: the number of region decodes of this process that ran over the box's windows (the fast path of either call); a container

@@ -119,6 +119,11 @@ class _CRegionPlan(C.Structure):
                 ("points", C.c_uint64), ("scratch_elems", C.c_uint64)]
 
 
+class _CTilePlan(C.Structure):
+    """sz3hip_tile_plan (include/sz3hip.h)"""
+    _fields_ = [("region", _CRegionPlan), ("units_total", C.c_uint64), ("units_needed", C.c_uint64)]
+
+
 class _CVerifyStats(C.Structure):
     """sz3hip_verify_stats (include/sz3hip.h)"""
     _fields_ = ([(k, C.c_uint64) for k in ("n", "n_nonfinite", "n_nonfinite_mismatch", "n_over", "first_over", "argmax")] +
@@ -229,6 +234,21 @@ def lib():
                                                      C.c_void_p]
     L.sz3hip_decompress_device_region.restype = C.c_int
     L.sz3hip_decompress_device_region.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(C.c_uint64), P(C.c_uint64), C.c_void_p, C.c_void_p]
+    L.sz3hip_tile_plan_for.restype = C.c_int
+    L.sz3hip_tile_plan_for.argtypes = [P(_CConfig), C.c_int, P(C.c_uint64), P(C.c_uint64), P(_CTilePlan)]
+    L.sz3hip_tile_units_for.restype = C.c_int
+    L.sz3hip_tile_units_for.argtypes = [P(_CConfig), C.c_int, P(C.c_uint64), P(C.c_uint64), C.c_void_p, C.c_uint64, P(C.c_uint64)]
+    L.sz3hip_decompress_tile_to_device.restype = C.c_int
+    L.sz3hip_decompress_tile_to_device.argtypes = [P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_int, P(C.c_uint64), P(C.c_uint64), C.c_void_p,
+                                                   P(C.c_int64), C.c_void_p]
+    L.sz3hip_decompress_device_tile.restype = C.c_int
+    L.sz3hip_decompress_device_tile.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, P(C.c_uint64), P(C.c_uint64), C.c_void_p, C.c_void_p]
+    L.sz3hip_set_sparse_decode.restype = None
+    L.sz3hip_set_sparse_decode.argtypes = [C.c_int]
+    L.sz3hip_get_sparse_decode.restype = C.c_int
+    L.sz3hip_get_sparse_decode.argtypes = []
+    L.sz3hip_debug_tile_units.restype = None
+    L.sz3hip_debug_tile_units.argtypes = [P(C.c_uint64), P(C.c_uint64)]
     L.sz3hip_debug_region_fast_calls.restype = C.c_uint64
     L.sz3hip_debug_region_fast_calls.argtypes = []
     L.sz3hip_debug_region_scratch.restype = C.c_uint64
@@ -543,6 +563,13 @@ def _box(conf, lo, shape):
     return (C.c_uint64 * 4)(*lo), (C.c_uint64 * 4)(*shape), shape
 
 
+def _region_plan_dict(plan, N):
+    n = int(plan.n_levels)
+    return {"n_levels": n, "strides": tuple(int(plan.stride[i]) for i in range(n)),
+            "windows": tuple((tuple(int(plan.win_lo[i][j]) for j in range(N)), tuple(int(plan.win_hi[i][j]) for j in range(N))) for i in range(n)),
+            "points": int(plan.points), "scratch_elems": int(plan.scratch_elems)}
+
+
 def region_plan(conf, lo, shape):
     """what the region decode of the box [lo, lo + shape) of conf's array touches (sz3hip_region_plan_for): a dict with n_levels, strides
     (coarsest first), windows (per level the inclusive (lo, hi) tuples of the window the level reads, full-array coordinates), points
@@ -550,10 +577,75 @@ def region_plan(conf, lo, shape):
     clo, cext, _ = _box(conf, lo, shape)
     plan = _CRegionPlan()
     _check(lib().sz3hip_region_plan_for(C.byref(conf._c), clo, cext, C.byref(plan)))
-    n, N = int(plan.n_levels), conf.N
-    return {"n_levels": n, "strides": tuple(int(plan.stride[i]) for i in range(n)),
-            "windows": tuple((tuple(int(plan.win_lo[i][j]) for j in range(N)), tuple(int(plan.win_hi[i][j]) for j in range(N))) for i in range(n)),
-            "points": int(plan.points), "scratch_elems": int(plan.scratch_elems)}
+    return _region_plan_dict(plan, conf.N)
+
+
+def tile_plan(conf, level, lo, shape):
+    """what the tile decode of the box [lo, lo + shape) of the grid of every 2**level-th point of conf's array touches
+    (sz3hip_tile_plan_for): a dict with region (region_plan's dict, in coarse-grid coordinates), units_total and units_needed. Needs no
+    device."""
+    clo, cext, _ = _box(conf, lo, shape)
+    plan = _CTilePlan()
+    _check(lib().sz3hip_tile_plan_for(C.byref(conf._c), int(level), clo, cext, C.byref(plan)))
+    return {"region": _region_plan_dict(plan.region, conf.N), "units_total": int(plan.units_total), "units_needed": int(plan.units_needed)}
+
+
+def tile_units(conf, level, lo, shape):
+    """the decoder units (512 codes each) the tile's passes read a code from, strictly ascending, as a numpy uint32 array
+    (sz3hip_tile_units_for). Needs no device."""
+    clo, cext, _ = _box(conf, lo, shape)
+    n = C.c_uint64(0)
+    rc = lib().sz3hip_tile_units_for(C.byref(conf._c), int(level), clo, cext, None, 0, C.byref(n))
+    if rc != -2:  # (SZ3HIP_ECAPACITY with the count: the list's size; 0: an empty list)
+        _check(rc)
+    units = np.empty(int(n.value), dtype=np.uint32)
+    if units.size:
+        _check(lib().sz3hip_tile_units_for(C.byref(conf._c), int(level), clo, cext, units.ctypes.data, units.size, C.byref(n)))
+    return units
+
+
+def set_sparse_decode(on=True):
+    """on (the default): the Huffman stage of a tile / region decode decodes only the units the box needs where they are few"""
+    lib().sz3hip_set_sparse_decode(int(on))
+
+
+def get_sparse_decode():
+    return bool(lib().sz3hip_get_sparse_decode())
+
+
+def debug_tile_units():
+    """(decoded, total): units the Huffman stage of this process's tile / region decodes decoded, and units their streams held"""
+    d, t = C.c_uint64(0), C.c_uint64(0)
+    lib().sz3hip_debug_tile_units(C.byref(d), C.byref(t))
+    return int(d.value), int(t.value)
+
+
+def decompress_tile(blob, dtype, level, lo, shape, out=None, device=None, stream=None):
+    """The box [lo, lo + shape) of the grid of every 2**level-th point of a container — bit for bit
+    ``decompress(blob, dtype, device=...)[0][::2**level, ...][box]`` — in work sized to the box where the container is a single
+    interpolation stream (sz3hip_decompress_tile_to_device). lo / shape are coarse-grid coordinates. Arguments and result as for
+    decompress_region, which is level 0."""
+    blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
+    npdt = _np_dtype(dtype)
+    dt = _dtype_id(npdt)
+    if out is None and device is None:
+        raise ValueError("decompress_tile decodes into device memory: pass device= or out=")
+    if out is not None and not _gpu_tensor(out):
+        raise ValueError("out must be a tensor on a HIP device")
+    if dt > 1:  # (the library's own refusal, before anything is parsed or allocated)
+        _check(lib().sz3hip_decompress_tile_to_device(C.byref(Config(1)._c), dt, blob.ctypes.data, blob.size, int(level), None, None, None, None, None))
+    conf = Config(1)
+    _check(lib().sz3hip_peek_config(C.byref(conf._c), blob.ctypes.data, blob.size))
+    clo, cext, shape = _box(conf, lo, shape)
+    import torch
+    if out is None:
+        out = torch.empty(shape, dtype=getattr(torch, npdt.name), device=device)
+    if _np_dtype(out.dtype) != npdt or tuple(out.shape) != shape:
+        raise ValueError("out must be a %s tensor of shape %s" % (npdt, shape))
+    strides = (C.c_int64 * len(shape))(*[int(st) for st in out.stride()])
+    _check(lib().sz3hip_decompress_tile_to_device(C.byref(conf._c), dt, blob.ctypes.data, blob.size, int(level), clo, cext, out.data_ptr(), strides,
+                                                  _stream_handle(out.device, stream)))
+    return out, conf
 
 
 def decompress_region(blob, dtype, lo, shape, out=None, device=None, stream=None):
@@ -757,6 +849,14 @@ class DeviceCompressor:
         if len(lo) != len(shape) or not 1 <= len(lo) <= 4:
             raise ValueError("lo and shape need one entry per extent of the array")
         _check(lib().sz3hip_decompress_device_region(self._h, d_payload, int(size), (C.c_uint64 * 4)(*lo), (C.c_uint64 * 4)(*shape), d_out, stream))
+
+    def decompress_tile(self, d_payload, size, level, lo, shape, d_out, stream=0):
+        """the box [lo, lo + shape) of the grid of every 2**level-th point of an interpolation payload into d_out (prod(shape) elements,
+        contiguous); lo / shape are coarse-grid coordinates"""
+        lo, shape = tuple(int(v) for v in lo), tuple(int(v) for v in shape)
+        if len(lo) != len(shape) or not 1 <= len(lo) <= 4:
+            raise ValueError("lo and shape need one entry per extent of the array")
+        _check(lib().sz3hip_decompress_device_tile(self._h, d_payload, int(size), int(level), (C.c_uint64 * 4)(*lo), (C.c_uint64 * 4)(*shape), d_out, stream))
 
     def region_scratch(self):
         """capacity of the context's region scratch in elements (0 before its first region call)"""

@@ -248,6 +248,9 @@ static void ctx_free(sz3hip_ctx *c) {
     if (c->h_blk_side_hdr) (void)hipHostFree(c->h_blk_side_hdr);
     if (c->d_blk_stats5) (void)hipFree(c->d_blk_stats5);
     if (c->h_ovf) (void)hipHostFree(c->h_ovf);
+    if (c->d_units) (void)hipFree(c->d_units);
+    if (c->h_units) (void)hipHostFree(c->h_units);
+    free(c->unit_bits);
     for (int i = 0; i < ST_COUNT; i++)
         for (int j = 0; j < 2; j++)
             if (c->ev[i][j]) (void)hipEventDestroy(c->ev[i][j]);
@@ -2223,31 +2226,49 @@ static int region_check_box(int N, const uint64_t *dims, const uint64_t *lo, con
     }
     return 0;
 }
+// (level: the tile's, 0 for a region. dims / anchor_stride: the full array's; lo / ext: coordinates of the grid of every 2^level-th point)
 static int region_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const uint64_t *lo, const uint64_t *ext,
-                           szk_region_geom *g) {
-    int rc = region_check_box(N, dims, lo, ext);
+                           szk_region_geom *g, int level = 0) {
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
+    uint64_t cd[4] = {0, 0, 0, 0};
+    for (int i = 0; i < N && i < 4; i++) cd[i] = dims[i] ? ((dims[i] - 1) >> level) + 1 : 0;
+    int rc = region_check_box(N, cd, lo, ext);
     if (rc) return rc;
     int nperm = 1;
     for (int i = 2; i <= N; i++) nperm *= i;
     if (N == 1) direction = 0;
     if (direction < 0 || direction >= nperm) return fail(SZ3HIP_EINVAL, "interpDirection out of range");
-    rc = szk_region_geometry(N, dims, interp_id ? 1 : 0, direction, anchor_stride, lo, ext, g);
+    rc = szk_tile_geometry(N, dims, interp_id ? 1 : 0, direction, anchor_stride, level, lo, ext, g);
     if (rc == -3)
         return fail(SZ3HIP_EUNSUPPORTED, "the region decode needs an anchor stride that is 0 or a power of two (this one is %llu): the levels' strides and the "
                     "anchor grid do not nest otherwise", (unsigned long long)anchor_stride);
     if (rc) return fail(SZ3HIP_EINVAL, "the region's windows cannot be laid out (extents too large)");
     return 0;
 }
-extern "C" int sz3hip_region_plan_for(const sz3hip_config *conf, const uint64_t *lo, const uint64_t *ext, sz3hip_region_plan *out) {
-    if (!conf || !lo || !ext || !out) return fail(SZ3HIP_EINVAL, "sz3hip_region_plan_for: NULL argument (%s)", !conf ? "conf" : !lo ? "lo" : !ext ? "ext" : "out");
+// the geometry of a Config's tile (level 0: region); *num: the full array's element count
+static int conf_geometry(const sz3hip_config *conf, int level, const uint64_t *lo, const uint64_t *ext, szk_region_geom *g, uint64_t *num) {
     if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
     static const int def_anchor[4] = {4096, 128, 32, 16};  // SZAlgoInterp.hpp:20-24
     const uint64_t anchor = conf->interpAnchorStride < 0 ? (uint64_t)def_anchor[conf->N - 1] : (uint64_t)conf->interpAnchorStride;
     uint64_t dims[4];
-    for (int i = 0; i < conf->N; i++) dims[i] = conf->dims[i];
+    *num = 1;
+    for (int i = 0; i < conf->N; i++) {
+        dims[i] = conf->dims[i];
+        *num *= dims[i];
+    }
+    return region_geometry(conf->N, dims, conf->interpAlgo, conf->interpDirection, anchor, lo, ext, g, level);
+}
+static void plan_from(const szk_region_geom &g, sz3hip_region_plan *out);
+extern "C" int sz3hip_region_plan_for(const sz3hip_config *conf, const uint64_t *lo, const uint64_t *ext, sz3hip_region_plan *out) {
+    if (!conf || !lo || !ext || !out) return fail(SZ3HIP_EINVAL, "sz3hip_region_plan_for: NULL argument (%s)", !conf ? "conf" : !lo ? "lo" : !ext ? "ext" : "out");
     szk_region_geom g;
-    int rc = region_geometry(conf->N, dims, conf->interpAlgo, conf->interpDirection, anchor, lo, ext, &g);
+    uint64_t num;
+    int rc = conf_geometry(conf, 0, lo, ext, &g, &num);
     if (rc) return rc;
+    plan_from(g, out);
+    return 0;
+}
+static void plan_from(const szk_region_geom &g, sz3hip_region_plan *out) {
     memset(out, 0, sizeof(*out));
     out->n_levels = g.n_levels;
     for (int b = 0; b < g.n_levels; b++) {
@@ -2259,6 +2280,87 @@ extern "C" int sz3hip_region_plan_for(const sz3hip_config *conf, const uint64_t 
     }
     out->points = g.points;
     out->scratch_elems = g.scratch_elems;
+}
+// ---- tile decode: a box of the 2^level-coarse grid, and the decoder units its passes read a code from ----
+// sparse decode: the Huffman stage of a tile / region call decodes the needed units only when they are few.
+// The limit: at most half of the stream's units (the issue's starting value), and at most max(32768, an eighth of them). Measured at C3
+// (262 144 units): 4.7 k and 17.5 k units needed — Huffman stage 193 / 210 us against the dense launch's 350; 66 k — 356 .. 427 us with the
+// list's 0.3 .. 0.4 ms of host time inside, no gain; all of them — 1002 us, 2.8 times the dense launch. The list form stops winning between
+// 17.5 k and 66 k units; 32768 is an eighth of what one dense launch keeps in flight on 256 CUs.
+static uint64_t sparse_limit(uint64_t total) {
+    static const int pct = [] {  // (lab: SZ3HIP_LAB_SPARSE_PCT = the limit in per cent of the units, nothing else; tools/tile_lab.py measures with it)
+        const char *e = getenv("SZ3HIP_LAB_SPARSE_PCT");
+        const int v = e && *e ? atoi(e) : -1;
+        return v > 100 ? 100 : v;
+    }();
+    if (pct >= 0) return total * (uint64_t)pct / 100;
+    return std::min<uint64_t>(total / 2, std::max<uint64_t>(32768, total / 8));
+}
+static std::atomic<int> g_sparse_decode{-1};  // (sz3hip_set_sparse_decode; -1: SZ3HIP_SPARSE_DECODE decides at the first call, default on)
+extern "C" void sz3hip_set_sparse_decode(int on) { g_sparse_decode.store(on ? 1 : 0); }
+extern "C" int sz3hip_get_sparse_decode(void) {
+    if (g_sparse_decode.load() < 0) {
+        const char *e = getenv("SZ3HIP_SPARSE_DECODE");
+        g_sparse_decode.store(e && *e ? (atoi(e) ? 1 : 0) : 1);
+    }
+    return g_sparse_decode.load();
+}
+static std::atomic<uint64_t> g_tile_units_decoded{0}, g_tile_units_total{0};
+extern "C" void sz3hip_debug_tile_units(uint64_t *decoded, uint64_t *total) {
+    if (decoded) *decoded = g_tile_units_decoded.load();
+    if (total) *total = g_tile_units_total.load();
+}
+static inline uint64_t units_of(uint64_t num) { return (num + SZH_UNIT_SYMS - 1) / SZH_UNIT_SYMS; }
+// the marked units of `bits`, ascending, into out[0 .. cap); returns how many there are
+static uint64_t units_from_bits(const uint64_t *bits, uint64_t units_total, uint32_t *out, uint64_t cap) {
+    uint64_t n = 0;
+    for (uint64_t w = 0, nw = (units_total + 63) / 64; w < nw; w++)
+        for (uint64_t m = bits[w]; m; m &= m - 1) {
+            if (n < cap) out[n] = (uint32_t)(w * 64 + (uint64_t)__builtin_ctzll(m));
+            n++;
+        }
+    return n;
+}
+extern "C" int sz3hip_tile_units_for(const sz3hip_config *conf, int level, const uint64_t *lo, const uint64_t *ext, uint32_t *units, uint64_t cap,
+                                     uint64_t *n_needed) {
+    if (!conf || !lo || !ext || !n_needed || (!units && cap))
+        return fail(SZ3HIP_EINVAL, "sz3hip_tile_units_for: NULL argument (%s)", !conf ? "conf" : !lo ? "lo" : !ext ? "ext" : !n_needed ? "n_needed" : "units");
+    szk_region_geom g;
+    uint64_t num;
+    int rc = conf_geometry(conf, level, lo, ext, &g, &num);
+    if (rc) return rc;
+    const uint64_t total = units_of(num);
+    if (total > 0xFFFFFFFFull) return fail(SZ3HIP_EINVAL, "the array has more decoder units than a 32-bit index names");
+    std::vector<uint64_t> bits((size_t)((total + 63) / 64), 0);
+    szk_tile_mark_units(&g, bits.data(), ~0ull);
+    *n_needed = units_from_bits(bits.data(), total, units, cap);
+    if (*n_needed > cap) return fail(SZ3HIP_ECAPACITY, "the tile needs %llu decoder units, the list holds %llu", (unsigned long long)*n_needed, (unsigned long long)cap);
+    return 0;
+}
+extern "C" int sz3hip_tile_plan_for(const sz3hip_config *conf, int level, const uint64_t *lo, const uint64_t *ext, sz3hip_tile_plan *out) {
+    if (!conf || !lo || !ext || !out) return fail(SZ3HIP_EINVAL, "sz3hip_tile_plan_for: NULL argument (%s)", !conf ? "conf" : !lo ? "lo" : !ext ? "ext" : "out");
+    szk_region_geom g;
+    uint64_t num;
+    int rc = conf_geometry(conf, level, lo, ext, &g, &num);
+    if (rc) return rc;
+    memset(out, 0, sizeof(*out));
+    plan_from(g, &out->region);
+    out->units_total = units_of(num);
+    if (out->units_total > 0xFFFFFFFFull) return fail(SZ3HIP_EINVAL, "the array has more decoder units than a 32-bit index names");
+    std::vector<uint64_t> bits((size_t)((out->units_total + 63) / 64), 0);
+    out->units_needed = szk_tile_mark_units(&g, bits.data(), ~0ull);
+    return 0;
+}
+// the context's unit list: a pinned and a device array of max_n / 512 + 1 entries and the host's bit per unit, made by its first tile / region
+// call, kept
+static int tile_units_reserve(sz3hip_ctx *ctx) {
+    if (ctx->d_units) return 0;
+    const uint64_t cap = ctx->max_n / SZH_UNIT_SYMS + 1;
+    if (!ctx->unit_bits) ctx->unit_bits = (uint64_t *)malloc((size_t)((cap + 63) / 64) * 8);
+    if (!ctx->unit_bits) return fail(SZ3HIP_EHIP, "no memory for the tile decode's unit list");
+    if (!ctx->h_units) HIPCHK(hipHostMalloc((void **)&ctx->h_units, cap * 4));
+    HIPCHK(hipMalloc((void **)&ctx->d_units, cap * 4));
+    ctx->units_cap = cap;
     return 0;
 }
 // the context's region scratch: made by its first region call, grown when a plan needs more, kept
@@ -2291,7 +2393,7 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
     HIPCHK(hipSetDevice(ctx->device));
     szk_region_geom rg;
     if (region) {  // (d_out: the box. The windows and the context's scratch, before anything is launched)
-        int rr = region_geometry(p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, region->lo, region->ext, &rg);
+        int rr = region_geometry(p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, region->lo, region->ext, &rg, region->level);
         if (rr || (rr = region_reserve(ctx, rg.scratch_elems))) return rr;
     }
     uint64_t num = 1, nc = 1;
@@ -2324,7 +2426,11 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
     ip.eb = p->eb;
     ip.radius = p->radius;
     // (the lists are the caller's own arrays: handed over as offsets from a null base)
-    if (region) g_region_fast_calls++;
+    if (region) {  // (a stock stream's codes come through the stock decoder: every unit)
+        g_region_fast_calls++;
+        g_tile_units_decoded += units_of(num);
+        g_tile_units_total += units_of(num);
+    }
     if (region
             ? szk_launch_interp_decompress_region(ctx->dtype, &ip, &rg, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, ctx->d_codes,
                                                   ctx->d_region, d_out, s)
@@ -2383,8 +2489,9 @@ extern "C" int sz3hip_debug_decode_info(sz3hip_ctx *ctx, uint32_t *out4) {
 // sz3hip_decompress_device (level 0) and sz3hip_decompress_device_coarse (level >= 1: an interpolation payload's points at multiples of
 // 2^level) share the header's parse and the Huffman stage; they differ in the reconstruction alone. So does
 // sz3hip_decompress_device_region (region: the box of an interpolation payload; level is 0 then).
+// (rlevel: the tile's level — lo / ext are coordinates of the grid of every 2^rlevel-th point)
 static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, void *d_out, void *stream, const uint64_t *rlo = nullptr,
-                                  const uint64_t *rext = nullptr) {
+                                  const uint64_t *rext = nullptr, int rlevel = 0) {
     const bool region = rlo != nullptr;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
@@ -2448,8 +2555,8 @@ static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t
             return fail(SZ3HIP_EUNSUPPORTED, "sz3hip_decompress_device_region reads interpolation payloads only (this one's predictor id is %d): a device context has "
                         "no full-size scratch of its own — sz3hip_decompress_region_to_device decodes every container", h.predictor);
         if (h.ndim < 1 || h.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
-        int rr = region_geometry(h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, rlo, rext, &rg);
-        if (rr || (rr = region_reserve(ctx, rg.scratch_elems))) return rr;
+        int rr = region_geometry(h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, rlo, rext, &rg, rlevel);
+        if (rr || (rr = region_reserve(ctx, rg.scratch_elems)) || (rr = tile_units_reserve(ctx))) return rr;
     }
     const uint8_t *pl = (const uint8_t *)d_payload;
     szk_blk_params bp;
@@ -2522,6 +2629,27 @@ static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t
                                    ctx->d_chunk_off, ctx->d_counters + 3, s);
     if (rc) return fail(SZ3HIP_EHIP, "dec_tables kernel launch failed (%d)", rc);
     szk_dec_params dp;
+    dp.unit_list = nullptr;
+    dp.n_list = 0;
+    if (region) {
+        // the units the tile's passes read a code from (built while the tables' launch runs); few enough: the Huffman stage decodes those alone.
+        // The other units keep what the code array held — the list covers every read
+        const uint64_t total = units_of(h.n), limit = sparse_limit(total);
+        uint64_t n_list = total;
+        if (sz3hip_get_sparse_decode() && total <= ctx->units_cap) {
+            memset(ctx->unit_bits, 0, (size_t)((total + 63) / 64) * 8);
+            if (szk_tile_mark_units(&rg, ctx->unit_bits, limit) <= limit) {
+                n_list = units_from_bits(ctx->unit_bits, total, ctx->h_units, ctx->units_cap);
+                for (uint64_t i = 0; i < n_list; i++)
+                    if (ctx->h_units[i] >= total) return fail(SZ3HIP_EHIP, "the tile's unit list names a unit the stream does not have");
+                if (n_list) HIPCHK(hipMemcpyAsync(ctx->d_units, ctx->h_units, n_list * 4, hipMemcpyHostToDevice, s));
+                dp.unit_list = ctx->d_units;
+                dp.n_list = n_list;
+            }
+        }
+        g_tile_units_decoded += n_list;
+        g_tile_units_total += total;
+    }
     dp.n = h.n;
     dp.n_chunks = h.n_chunks;
     dp.bitstream_off = o.bitstream;
@@ -2632,7 +2760,7 @@ extern "C" int sz3hip_decompress_device_coarse(sz3hip_ctx *ctx, const void *d_pa
     return decompress_device_impl(ctx, d_payload, payload_size, level, d_out, stream);
 }
 int szi_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_region *region, void *d_out, void *stream) {
-    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream, region->lo, region->ext);
+    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream, region->lo, region->ext, region->level);
 }
 // (lo / ext: one entry per extent the payload's header names)
 extern "C" int sz3hip_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const uint64_t *lo, const uint64_t *ext, void *d_out,
@@ -2641,6 +2769,15 @@ extern "C" int sz3hip_decompress_device_region(sz3hip_ctx *ctx, const void *d_pa
     if (!lo || !ext) return fail(SZ3HIP_EINVAL, "the region's %s is NULL", !lo ? "lo" : "ext");
     if (!d_payload || !d_out) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_region: the %s is NULL", !d_payload ? "payload" : "output array");
     return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream, lo, ext);
+}
+// (level 0 is sz3hip_decompress_device_region)
+extern "C" int sz3hip_decompress_device_tile(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, const uint64_t *lo, const uint64_t *ext,
+                                             void *d_out, void *stream) {
+    if (!ctx) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_tile: no context");
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
+    if (!lo || !ext) return fail(SZ3HIP_EINVAL, "the tile's %s is NULL", !lo ? "lo" : "ext");
+    if (!d_payload || !d_out) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_tile: the %s is NULL", !d_payload ? "payload" : "output array");
+    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream, lo, ext, level);
 }
 extern "C" int sz3hip_coarse_dims(const sz3hip_config *conf, int level, uint64_t *dims_out) {
     if (!conf || !dims_out) return fail(SZ3HIP_EINVAL, "sz3hip_coarse_dims: NULL argument");

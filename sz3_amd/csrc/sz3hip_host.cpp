@@ -3327,27 +3327,31 @@ extern "C" int sz3hip_decompress_coarse_to_device(sz3hip_config *conf, int dataT
     return 0;
 }
 
-// One box of a container. Fast path: a single interpolation stream, decoded over the box's windows (decompress_blob /
-// stock_decompress_interp under t_region). Everything else: the full decode into a scratch array of the call, then the strided gather of the
-// box, a view of that array whose base is offset by lo.
-extern "C" int sz3hip_decompress_region_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, const uint64_t *lo, const uint64_t *ext,
-                                                  void *d_out, const int64_t *strides, void *stream) {
+// One box of a container, or of its grid of every 2^level-th point (section 13: lo / ext are then that grid's
+// coordinates). Fast path: a single interpolation stream, decoded over the box's windows (decompress_blob / stock_decompress_interp under
+// t_region). Everything else: the full decode into a scratch array of the call, then the strided gather of the box, a view of that array
+// whose strides are multiplied by 2^level and whose base is offset by lo << level.
+static int tile_to_device(const char *who, sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const uint64_t *lo, const uint64_t *ext,
+                          void *d_out, const int64_t *strides, void *stream) {
     if (!dtype_ok(dataType))
         return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
     if (dtype_is_int(dataType)) return fail(SZ3HIP_EUNSUPPORTED, "the region decode reads float / double arrays; integer element types are not supported yet");
-    if (!conf || !lo || !ext) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_region_to_device: NULL argument (%s)", !conf ? "conf" : !lo ? "lo" : "ext");
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
+    if (!conf || !lo || !ext) return fail(SZ3HIP_EINVAL, "%s: NULL argument (%s)", who, !conf ? "conf" : !lo ? "lo" : "ext");
     int rc = sz3hip_peek_config(conf, cmpData, cmpSize);
     if (rc) return rc;
     if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
     szi_region box;
     memset(&box, 0, sizeof(box));
+    box.level = level;
     sz3hip_config bc = *conf;  // the box's extents (conf stays the full array's)
     bc.num = 1;
     for (int i = 0; i < conf->N; i++) {
+        const uint64_t cd = conf->dims[i] ? ((conf->dims[i] - 1) >> level) + 1 : 0;  // (the grid's extent: the array's at level 0)
         if (ext[i] == 0) return fail(SZ3HIP_EINVAL, "the region has extent 0 in dimension %d", i);
-        if (lo[i] >= conf->dims[i] || ext[i] > conf->dims[i] - lo[i])
+        if (lo[i] >= cd || ext[i] > cd - lo[i])
             return fail(SZ3HIP_EINVAL, "the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", (unsigned long long)lo[i], (unsigned long long)lo[i],
-                        (unsigned long long)ext[i], i, (unsigned long long)conf->dims[i]);
+                        (unsigned long long)ext[i], i, (unsigned long long)cd);
         box.lo[i] = lo[i];
         box.ext[i] = ext[i];
         bc.dims[i] = ext[i];
@@ -3413,9 +3417,9 @@ extern "C" int sz3hip_decompress_region_to_device(sz3hip_config *conf, int dataT
     int64_t corner = 0;
     for (int i = 0; i < conf->N; i++) {
         const int k = 4 - conf->N + i;
-        corner += (int64_t)lo[i] * gv.str[k];
+        corner += (int64_t)(lo[i] << level) * gv.str[k];
         gv.dims[k] = ext[i];
-        if (ext[i] == 1) gv.str[k] = 0;
+        gv.str[k] = ext[i] == 1 ? 0 : gv.str[k] * ((int64_t)1 << level);
     }
     hipStream_t cs = (hipStream_t)stream;
     void *dense = dev.ptr;
@@ -3430,6 +3434,14 @@ extern "C" int sz3hip_decompress_region_to_device(sz3hip_config *conf, int dataT
     if (!dev.view.contig && szk_launch_scatter(dataType, 0, dense, dev.ptr, &dev.view, cs)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
     HIPCHK(hipStreamSynchronize(cs));
     return 0;
+}
+extern "C" int sz3hip_decompress_region_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, const uint64_t *lo, const uint64_t *ext,
+                                                  void *d_out, const int64_t *strides, void *stream) {
+    return tile_to_device("sz3hip_decompress_region_to_device", conf, dataType, cmpData, cmpSize, 0, lo, ext, d_out, strides, stream);
+}
+extern "C" int sz3hip_decompress_tile_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const uint64_t *lo,
+                                                const uint64_t *ext, void *d_out, const int64_t *strides, void *stream) {
+    return tile_to_device("sz3hip_decompress_tile_to_device", conf, dataType, cmpData, cmpSize, level, lo, ext, d_out, strides, stream);
 }
 
 // ---- sz3hip_verify_device: the error statistics of two device arrays (kernels: sz3hip_verify.hip) ---------------------------------

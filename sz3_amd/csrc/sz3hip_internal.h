@@ -25,8 +25,10 @@ struct szi_stock_params {  // what InterpolationDecomposition::save holds beside
     int radius;
 };
 // region decode: the box [lo, lo + ext) of the array, one entry per extent of the stream, slowest first
+// tile decode (section 13): level k > 0 — the box is one of the grid of every 2^k-th point, in that grid's coordinates
 struct szi_region {
     uint64_t lo[4], ext[4];
+    int level;
 };
 // sz3hip_decompress_device_region with the box in one struct (the host API's slots call it)
 int szi_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_region *region, void *d_out, void *stream);
@@ -106,6 +108,9 @@ struct sz3hip_ctx {
     uint64_t coarse_codes_cap;
     void *d_region;             // region decode: the levels' compact buffers (made by the context's first region call, grown when a plan needs more, kept)
     uint64_t region_cap;        // ... in elements of the context's type
+    uint32_t *h_units, *d_units;  // tile / region decode: the decoder units to decode, pinned and on the device (max_n / 512 + 1 entries; made by the first such call, kept)
+    uint64_t units_cap;
+    uint64_t *unit_bits;          // ... and the host's bit per unit they are built in
     void *s2_payload;  // stage 2's arguments, kept for the repeat after a mispredicted code-book form
     size_t s2_cap;
     // Two code books: bk[book_idx] is the last one a call of this context completed with (-1: none yet). Stage 2 builds this

@@ -273,6 +273,10 @@ struct szk_dec_params {
     uint32_t ms;           // half, f32 data, a code book of at most 16-bit words and 1024 symbols: the multi-symbol table form (tables->mlut)
     uint32_t *ovf;         // half: raised on a value outside int16
     const uint32_t *gate;  // non-null: the kernel runs only when *gate != 0
+    // the list form (plain code output only): lane g of the launch decodes unit unit_list[g], ascending, n_list of them;
+    // the other units' codes stay what they were. nullptr: every unit
+    const uint32_t *unit_list;
+    uint64_t n_list;
 };
 
 // ---- block-composed predictor: Lorenzo-1 / Lorenzo-2 / regression per block (sz3hip_regress.hip) ----
@@ -394,7 +398,9 @@ struct szk_region_geom {
     int N, interp_id, n_levels, nbuf;  // nbuf = max(n_levels, 1): lv[0] is the coarsest level, lv[nbuf - 1] has stride 1
     int perm[4];
     uint64_t anchor;                   // the anchor stride in effect (0: first-point path)
-    uint64_t dims[4], lo[4], ext[4];
+    uint64_t dims[4], lo[4], ext[4];   // the grid the windows lie on (a tile of level `shift`: the coarse grid) and the box, in its coordinates
+    int shift;                         // the tile's level k: grid point c is the full array's point c << k
+    uint64_t full[4];                  // the full array's extents (== dims for shift 0)
     szk_region_level lv[SZK_REGION_MAX_LEVELS];
     uint64_t points, scratch_elems;
 };
@@ -402,6 +408,11 @@ struct szk_region_geom {
 int szk_region_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const uint64_t *lo, const uint64_t *ext,
                         szk_region_geom *g);
 uint64_t szk_region_pass_window(const szk_region_geom *g, int b, int k, uint64_t *first, uint64_t *step, uint64_t *cnt);
+// the tile of level `level`: dims / anchor_stride are the FULL array's, lo / ext coarse-grid coordinates
+int szk_tile_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, int level, const uint64_t *lo, const uint64_t *ext,
+                      szk_region_geom *g);
+// the decoder units the tile's passes read a code from, as bits (zeroed by the caller, one per unit); stops past `limit`; returns the count
+uint64_t szk_tile_mark_units(const szk_region_geom *g, uint64_t *bits, uint64_t limit);
 // ip = the full array's parameters, codes = its per-element codes, scratch = g->scratch_elems elements, d_out = prod(ext) elements, contiguous
 int szk_launch_interp_decompress_region(int dtype, const szk_interp_params *ip, const szk_region_geom *g, const uint8_t *payload, uint64_t vout_idx_off,
                                         uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, void *scratch, void *d_out, hipStream_t s);

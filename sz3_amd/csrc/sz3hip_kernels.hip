@@ -5178,10 +5178,14 @@ __device__ __forceinline__ QO dec_dout(const szk_dec_params &p, uint64_t elem) {
 // the symbol's place (a lookup's three sums at k, k + 1, k + 2: with fewer than three code words the next lookup overwrites the
 // repeats), a block of 32 symbols leaves through the same cooperative path as before. Code words beyond 12 bits, listed deltas
 // (symbol 0), the last two symbols of a row or a unit: one at a time through the canonical-code arithmetic (ms_single).
-template <int QB, bool HALF = false, bool MS = false>
+// LIST (QB = 0): lane g of the launch decodes unit p.unit_list[g] — the units a tile's passes read a code from —
+// instead of unit g. A wave's units are then no offset group: a lane sums the chunk_words of the chunks before its own in its group itself
+// (at most 31 two-byte loads from one 64-byte line), and its values leave by the direct stores (the staging needs 64 consecutive units).
+template <int QB, bool HALF = false, bool MS = false, bool LIST = false>
 __global__ __launch_bounds__(256) void k_decode(const uint8_t *__restrict__ payload, szk_dec_params p,
                                                 uint16_t *__restrict__ codes) {
     static_assert(!MS || (QB == 4 && HALF), "the multi-symbol form decodes f32 Lorenzo streams into the half-width chain");
+    static_assert(!LIST || QB == 0, "the list form writes plain codes");
     using QO = typename std::conditional<QB == 8, int64_t, int32_t>::type;
     if (p.gate && *p.gate == 0) return;  // (the full-width chain behind a half-width one that did not overflow)
     constexpr uint32_t UNIT = SZH_UNIT_SYMS;
@@ -5221,11 +5225,21 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t *__restrict__ payl
     const uint32_t base_rank = MS ? 0u : (K < max_len ? p.tables->first_rank[K + 1] : n_coded);  // (MS: the whole book, at most SORTED_LDS symbols)
     for (uint32_t e = threadIdx.x; e < SORTED_LDS && base_rank + e < n_coded; e += 256) s_sorted[e] = sorted[base_rank + e];
     __syncthreads();
-    const uint64_t unit = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (LIST) {
+        if (slot >= p.n_list) return;
+    }
+    const uint64_t unit = LIST ? (uint64_t)p.unit_list[LIST ? slot : 0] : slot;
     const uint64_t n_units = (p.n + UNIT - 1) / UNIT;
     static_assert(64 / SZH_SUBS == PACK_GROUP, "a wave's units are one offset group");
     uint32_t woff_in, nwords;
-    {
+    if constexpr (LIST) {
+        const uint64_t ch = unit / SZH_SUBS;
+        nwords = ch < p.n_chunks ? (uint32_t)p.chunk_words[ch] : 0u;
+        woff_in = 0;
+        if (ch < p.n_chunks)
+            for (uint64_t c = ch & ~(uint64_t)(PACK_GROUP - 1); c < ch; c++) woff_in += (uint32_t)p.chunk_words[c];
+    } else {
         const uint64_t ch = unit / SZH_SUBS;
         nwords = ch < p.n_chunks ? (uint32_t)p.chunk_words[ch] : 0u;
         const uint32_t mine = (unit % SZH_SUBS) == 0 ? nwords : 0u;  // (a chunk counts once: at its first unit)
@@ -5239,7 +5253,7 @@ __global__ __launch_bounds__(256) void k_decode(const uint8_t *__restrict__ payl
     uint16_t *out = codes + s0;
     QO *qout = QB ? reinterpret_cast<QO *>(p.q_out) + s0 : nullptr;
     // (wave-uniform: all 64 lanes decode full units — everywhere but in the array's last wave)
-    const bool coop = !(p.reserved & SZK_DEC_DBG_DIRECT_STORES) && __ballot(nsym == UNIT) == ~0ull;
+    const bool coop = LIST ? false : !(p.reserved & SZK_DEC_DBG_DIRECT_STORES) && __ballot(nsym == UNIT) == ~0ull;
     uint4 *stage = s_out[threadIdx.x / WAVE];
     uint8_t *wave_out = QB ? reinterpret_cast<uint8_t *>(p.q_out) + (s0 - (uint64_t)lane_id() * UNIT) * ELT
                            : reinterpret_cast<uint8_t *>(codes + (s0 - (uint64_t)lane_id() * UNIT));
@@ -6786,7 +6800,11 @@ int szk_launch_decode(const uint8_t *payload, const szk_dec_params *p, uint16_t 
         const char *e = getenv("SZ3HIP_LAB_DEC_LDS");
         return e ? (uint32_t)atoi(e) : 0u;
     }();
-    if (!p->scan_row) hipLaunchKernelGGL((k_decode<0>), dim3((uint32_t)nb), dim3(256), pad, s, payload, *p, codes);
+    if (p->unit_list) {  // the list form: plain codes of the listed units only
+        if (p->scan_row || p->n_list > n_units) return -1;
+        if (p->n_list)
+            hipLaunchKernelGGL((k_decode<0, false, false, true>), dim3((uint32_t)((p->n_list + 255) / 256)), dim3(256), pad, s, payload, *p, codes);
+    } else if (!p->scan_row) hipLaunchKernelGGL((k_decode<0>), dim3((uint32_t)nb), dim3(256), pad, s, payload, *p, codes);
     else if (p->q_bytes == 8 && p->half) hipLaunchKernelGGL((k_decode<8, true>), dim3((uint32_t)nb), dim3(256), pad, s, payload, *p, codes);
     else if (p->q_bytes == 8) hipLaunchKernelGGL((k_decode<8>), dim3((uint32_t)nb), dim3(256), pad, s, payload, *p, codes);
 #ifdef SZ3HIP_LAB  // (the multi-symbol table form — round 5, slower than the one-symbol table — lab build only)

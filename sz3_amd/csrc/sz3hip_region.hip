@@ -23,8 +23,9 @@
 // ---- host: the windows ----------------------------------------------------------------------------------------------------------------
 static inline uint64_t sub_sat(uint64_t a, uint64_t b) { return a > b ? a - b : 0; }
 
-int szk_region_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const uint64_t *lo, const uint64_t *ext,
-                        szk_region_geom *g) {
+// all_anchor: every point of the grid is an anchor (a tile of a level at or beyond the anchor stride): no level runs, no first point
+static int region_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, bool all_anchor, const uint64_t *lo,
+                           const uint64_t *ext, szk_region_geom *g) {
     memset(g, 0, sizeof(*g));
     if (N < 1 || N > 4) return -1;
     if (anchor_stride & (anchor_stride - 1)) return -3;  // (the levels' strides and the anchor grid only nest for a power of two)
@@ -34,10 +35,14 @@ int szk_region_geometry(int N, const uint64_t *dims, int interp_id, int directio
     g->interp_id = interp_id;
     g->n_levels = szk_interp_level_count(N, dims, anchor_stride, &g->anchor);
     if (g->n_levels < 0) g->n_levels = 0;
+    if (all_anchor) {
+        g->n_levels = 0;
+        g->anchor = 1;
+    }
     if (g->n_levels > SZK_REGION_MAX_LEVELS) return -1;
     szk_interp_perm(N, direction, g->perm);
     for (int j = 0; j < N; j++) {
-        g->dims[j] = dims[j];
+        g->dims[j] = g->full[j] = dims[j];
         g->lo[j] = lo[j];
         g->ext[j] = ext[j];
     }
@@ -85,6 +90,117 @@ int szk_region_geometry(int N, const uint64_t *dims, int interp_id, int directio
         }
     return 0;
 }
+int szk_region_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const uint64_t *lo, const uint64_t *ext,
+                        szk_region_geom *g) {
+    return region_geometry(N, dims, interp_id, direction, anchor_stride, false, lo, ext, g);
+}
+// The tile of level k: the grid of every 2^k-th point is itself an interpolation problem — extents ((D - 1) >> k) + 1,
+// anchor stride A >> k, its level l the array's level l + k — so the windows, buffers and pass lattices are the region decode's on that grid, in
+// coarse coordinates; g->shift and g->full say where a coarse point's code and raw record lie in the full array. With anchors in use and
+// 2^k >= A every coarse point is an anchor. Level 0 is szk_region_geometry.
+int szk_tile_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, int level, const uint64_t *lo, const uint64_t *ext,
+                      szk_region_geom *g) {
+    memset(g, 0, sizeof(*g));
+    if (N < 1 || N > 4 || level < 0 || level > 30) return -1;
+    if (anchor_stride & (anchor_stride - 1)) return -3;
+    uint64_t cd[4];
+    bool use_anchor = false;
+    for (int j = 0; j < N; j++) {
+        if (dims[j] == 0) return -1;
+        cd[j] = ((dims[j] - 1) >> level) + 1;
+        if (dims[j] > anchor_stride) use_anchor = true;
+    }
+    const bool all_anchor = level > 0 && anchor_stride > 0 && use_anchor && (1ull << level) >= anchor_stride;
+    // (A >> k is 0 only where the full array takes the first-point path too — no extent above A — or where every coarse point is an anchor)
+    int rc = region_geometry(N, cd, interp_id, direction, all_anchor ? 0 : anchor_stride >> level, all_anchor, lo, ext, g);
+    if (rc) return rc;
+    g->shift = level;
+    for (int j = 0; j < N; j++) g->full[j] = dims[j];
+    return 0;
+}
+
+// ---- host: the decoder units a tile's passes read a code from ----------------------------------------------------
+// A row-run is one line of a pass window along x; it marks every unit from the one that holds the code of its first lattice point to the
+// one that holds its last. Where the lines of a slower dimension follow each other at most a unit apart their runs join into one interval
+// (the next line's first unit is at most one past the previous line's first, which the previous run covers): that dimension is not walked.
+// bits: one bit per unit, ceil(units_total / 64) words, zeroed by the caller. limit: stop once more than that many units are marked
+// (the caller then decodes densely); returns the number marked (exact when <= limit).
+uint64_t szk_tile_mark_units(const szk_region_geom *g, uint64_t *bits, uint64_t limit) {
+    const int N = g->N;
+    uint64_t off[4] = {0, 0, 0, 0}, run = 1;
+    for (int j = N - 1; j >= 0; j--) {
+        off[j] = run << g->shift;  // a coarse step in the full code array
+        run *= g->full[j];
+    }
+    uint64_t marked = 0;
+    auto mark = [&](uint64_t i0, uint64_t i1) {
+        const uint64_t u0 = i0 / SZH_UNIT_SYMS, u1 = i1 / SZH_UNIT_SYMS;
+        for (uint64_t w = u0 >> 6; w <= (u1 >> 6); w++) {
+            uint64_t m = ~0ull;
+            if (w == (u0 >> 6)) m &= ~0ull << (u0 & 63);
+            if (w == (u1 >> 6)) m &= ~0ull >> (63 - (u1 & 63));
+            marked += (uint64_t)__builtin_popcountll(m & ~bits[w]);
+            bits[w] |= m;
+        }
+    };
+    if (g->anchor == 0) {  // the first point reads codes[0] when the coarsest window holds it
+        bool at0 = true;
+        for (int j = 0; j < N; j++) at0 = at0 && g->lv[0].wlo[j] == 0;
+        if (at0) mark(0, 0);
+    }
+    if (g->n_levels > 0 && N >= 2 && limit != ~0ull) {
+        // a bound from below before any marking (a large box must not pay for a list it will not use): the lines of the finest level's last
+        // pass start in units of their own where a step of the dimension above x is at least a unit
+        uint64_t first[4], step[4], cnt[4], lines = 1;
+        if (szk_region_pass_window(g, g->n_levels - 1, N - 1, first, step, cnt) && off[N - 2] >= SZH_UNIT_SYMS) {
+            for (int j = 0; j < N - 1; j++) lines *= cnt[j];
+            if (lines > limit) return lines;
+        }
+    }
+    for (int b = g->n_levels - 1; b >= 0 && marked <= limit; b--)  // (finest first: the most units)
+        for (int k = 0; k < N && marked <= limit; k++) {
+            uint64_t first[4], step[4], cnt[4];
+            if (szk_region_pass_window(g, b, k, first, step, cnt) == 0) continue;
+            uint64_t i0 = 0, i1 = 0;  // the first line's run
+            for (int j = 0; j < N; j++) i0 += first[j] * off[j];
+            i1 = i0 + (cnt[N - 1] - 1) * step[N - 1] * off[N - 1];
+            int walk = N - 1;  // dimensions [0, walk) are walked, [walk, N - 1) joined into the run
+            while (walk > 0 && (cnt[walk - 1] == 1 || step[walk - 1] * off[walk - 1] <= SZH_UNIT_SYMS)) {
+                i1 += (cnt[walk - 1] - 1) * step[walk - 1] * off[walk - 1];
+                walk--;
+            }
+            if (walk == 0) {
+                mark(i0, i1);
+                continue;
+            }
+            // the innermost walked dimension runs in the loop below, the ones above it in the odometer q
+            const int in = walk - 1;
+            const uint64_t dstep = step[in] * off[in], n = cnt[in], span = i1 - i0;
+            uint64_t q[4] = {0, 0, 0, 0};
+            for (;;) {
+                uint64_t a = i0;
+                for (int j = 0; j < in; j++) a += q[j] * step[j] * off[j];
+                for (uint64_t t = 0; t < n; t++, a += dstep) {
+                    const uint64_t u0 = a / SZH_UNIT_SYMS, u1 = (a + span) / SZH_UNIT_SYMS;
+                    if (u0 == u1) {  // (the usual line: inside one unit)
+                        const uint64_t o = bits[u0 >> 6];
+                        marked += ((o >> (u0 & 63)) & 1) ^ 1;
+                        bits[u0 >> 6] = o | (1ull << (u0 & 63));
+                    } else {
+                        mark(a, a + span);
+                    }
+                }
+                if (marked > limit) break;
+                int j = in - 1;
+                for (; j >= 0; j--) {
+                    if (++q[j] < cnt[j]) break;
+                    q[j] = 0;
+                }
+                if (j < 0) break;
+            }
+        }
+    return marked;
+}
 
 // pass k of level b (buffer b): the lattice points it predicts inside its window — per dimension the first coordinate, the step and the count.
 // The lattice is build_schedule's (the pass's own axis: odd multiples of s; axes of earlier passes: every multiple; later ones: even
@@ -118,6 +234,7 @@ struct szk_region_bufs {
     uint64_t full[4];
     uint64_t wlo[SZK_REGION_MAX_LEVELS][4], cnt[SZK_REGION_MAX_LEVELS][4], base[SZK_REGION_MAX_LEVELS];
     uint32_t nbuf;
+    uint32_t shift;  // a tile of level k: wlo / cnt are coarse coordinates, a record's are the full array's — off the coarse grid it is dropped
 };
 // k_scatter_raw for the region: a record goes into the buffer of the level that predicts its point — the largest stride that divides all
 // its coordinates, capped at the coarsest level (whose buffer also holds the anchors / the first point) — and is dropped outside that
@@ -137,6 +254,9 @@ __global__ __launch_bounds__(256) void k_region_scatter_raw(const uint8_t *__res
         r /= g.full[2];
         c[1] = r % g.full[1];
         c[0] = r / g.full[1];
+        if ((c[0] | c[1] | c[2] | c[3]) & ((1ull << g.shift) - 1)) continue;
+#pragma unroll
+        for (int j = 0; j < 4; j++) c[j] >>= g.shift;
         const uint64_t any = c[0] | c[1] | c[2] | c[3];
         const uint32_t top = g.nbuf - 1;  // log2 of the coarsest buffer's stride
         const uint32_t tz = any ? (uint32_t)(__ffsll((long long)any) - 1) : 64u;
@@ -240,18 +360,19 @@ template <typename T>
 static int run_region(const szk_interp_params &ip, const szk_region_geom &g, const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off,
                       uint64_t n_vout, const uint16_t *codes, T *scratch, T *d_out, hipStream_t s) {
     const int N = g.N;
-    uint64_t num = 1, off[4] = {0, 0, 0, 0};
+    uint64_t num = 1, off[4] = {0, 0, 0, 0};  // off: a step of the (coarse) grid in the FULL code array
     for (int j = N - 1; j >= 0; j--) {
-        off[j] = num;
-        num *= g.dims[j];
+        off[j] = num << g.shift;
+        num *= g.full[j];
     }
     if (n_vout) {
         szk_region_bufs rb;
         memset(&rb, 0, sizeof(rb));
         rb.nbuf = (uint32_t)g.nbuf;
+        rb.shift = (uint32_t)g.shift;
         for (int i = 0; i < 4; i++) {
             const int j = i - (4 - N);
-            rb.full[i] = j >= 0 ? g.dims[j] : 1;
+            rb.full[i] = j >= 0 ? g.full[j] : 1;
             for (int b = 0; b < g.nbuf; b++) {
                 rb.wlo[b][i] = j >= 0 ? g.lv[b].wlo[j] : 0;
                 rb.cnt[b][i] = j >= 0 ? g.lv[b].cnt[j] : 1;
@@ -286,7 +407,7 @@ static int run_region(const szk_interp_params &ip, const szk_region_geom &g, con
             if (nb > 0x7FFFFFFFull) return -1;
             hipLaunchKernelGGL((k_region_regrid<T>), dim3((uint32_t)nb), dim3(256), 0, s, (const T *)(scratch + up.base), scratch + lv.base, rg);
         }
-        const int level = g.n_levels - b;  // the level's number in the full array: stride 2^(level - 1)
+        const int level = g.n_levels - b;  // the level's number on the grid: stride 2^(level - 1); in the full array it is level + shift
         szk_region_pass p;
         memset(&p, 0, sizeof(p));
         p.N = N;
@@ -297,7 +418,7 @@ static int run_region(const szk_interp_params &ip, const szk_region_geom &g, con
         p.ls = (uint32_t)(level - 1);
         p.bsz = 32ull * lv.s;
         p.belems = lv.elems;
-        p.eb = szk_interp_level_eb(ip.eb, ip.alpha, ip.beta, level);
+        p.eb = szk_interp_level_eb(ip.eb, ip.alpha, ip.beta, level + g.shift);
         for (int j = 0; j < N; j++) {
             p.dims[j] = g.dims[j];
             p.off[j] = off[j];
@@ -339,9 +460,9 @@ static int run_region(const szk_interp_params &ip, const szk_region_geom &g, con
 
 int szk_launch_interp_decompress_region(int dtype, const szk_interp_params *ip, const szk_region_geom *g, const uint8_t *payload, uint64_t vout_idx_off,
                                         uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, void *scratch, void *d_out, hipStream_t s) {
-    if (g->N != ip->N || g->nbuf < 1) return -1;
+    if (g->N != ip->N || g->nbuf < 1 || g->shift < 0 || g->shift > 30) return -1;
     for (int j = 0; j < ip->N; j++)
-        if (g->dims[j] != ip->dims[j]) return -1;
+        if (g->full[j] != ip->dims[j] || g->dims[j] != ((ip->dims[j] - 1) >> g->shift) + 1) return -1;
     return dtype == 0 ? run_region<float>(*ip, *g, payload, vout_idx_off, vout_val_off, n_vout, codes, (float *)scratch, (float *)d_out, s)
                       : run_region<double>(*ip, *g, payload, vout_idx_off, vout_val_off, n_vout, codes, (double *)scratch, (double *)d_out, s);
 }
