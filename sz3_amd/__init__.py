@@ -620,32 +620,42 @@ def debug_tile_units():
     return int(d.value), int(t.value)
 
 
-def decompress_tile(blob, dtype, level, lo, shape, out=None, device=None, stream=None):
-    """The box [lo, lo + shape) of the grid of every 2**level-th point of a container — bit for bit
-    ``decompress(blob, dtype, device=...)[0][::2**level, ...][box]`` — in work sized to the box where the container is a single
-    interpolation stream (sz3hip_decompress_tile_to_device). lo / shape are coarse-grid coordinates. Arguments and result as for
-    decompress_region, which is level 0."""
+def _decompress_partial(name, blob, dtype, probe_args, shape_of, out, device, stream):
+    """The body of decompress_coarse / decompress_region / decompress_tile (name), over the library's sz3hip_<name>_to_device.
+    shape_of(conf) -> (the output's shape, the call's arguments between cmpSize and d_out); probe_args() -> those arguments for an
+    integer dtype, which the library refuses before it reads a box."""
     blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
     npdt = _np_dtype(dtype)
     dt = _dtype_id(npdt)
     if out is None and device is None:
-        raise ValueError("decompress_tile decodes into device memory: pass device= or out=")
+        raise ValueError("%s decodes into device memory: pass device= or out=" % name)
     if out is not None and not _gpu_tensor(out):
         raise ValueError("out must be a tensor on a HIP device")
+    call = getattr(lib(), "sz3hip_%s_to_device" % name)
     if dt > 1:  # (the library's own refusal, before anything is parsed or allocated)
-        _check(lib().sz3hip_decompress_tile_to_device(C.byref(Config(1)._c), dt, blob.ctypes.data, blob.size, int(level), None, None, None, None, None))
+        _check(call(C.byref(Config(1)._c), dt, blob.ctypes.data, blob.size, *probe_args(), None, None, None))
     conf = Config(1)
     _check(lib().sz3hip_peek_config(C.byref(conf._c), blob.ctypes.data, blob.size))
-    clo, cext, shape = _box(conf, lo, shape)
+    shape, args = shape_of(conf)
     import torch
     if out is None:
         out = torch.empty(shape, dtype=getattr(torch, npdt.name), device=device)
     if _np_dtype(out.dtype) != npdt or tuple(out.shape) != shape:
         raise ValueError("out must be a %s tensor of shape %s" % (npdt, shape))
     strides = (C.c_int64 * len(shape))(*[int(st) for st in out.stride()])
-    _check(lib().sz3hip_decompress_tile_to_device(C.byref(conf._c), dt, blob.ctypes.data, blob.size, int(level), clo, cext, out.data_ptr(), strides,
-                                                  _stream_handle(out.device, stream)))
+    _check(call(C.byref(conf._c), dt, blob.ctypes.data, blob.size, *args, out.data_ptr(), strides, _stream_handle(out.device, stream)))
     return out, conf
+
+
+def decompress_tile(blob, dtype, level, lo, shape, out=None, device=None, stream=None):
+    """The box [lo, lo + shape) of the grid of every 2**level-th point of a container — bit for bit
+    ``decompress(blob, dtype, device=...)[0][::2**level, ...][box]`` — in work sized to the box where the container is a single
+    interpolation stream (sz3hip_decompress_tile_to_device). lo / shape are coarse-grid coordinates. Arguments and result as for
+    decompress_region, which is level 0."""
+    def shape_of(conf):
+        clo, cext, box = _box(conf, lo, shape)
+        return box, (int(level), clo, cext)
+    return _decompress_partial("decompress_tile", blob, dtype, lambda: (int(level), None, None), shape_of, out, device, stream)
 
 
 def decompress_region(blob, dtype, lo, shape, out=None, device=None, stream=None):
@@ -653,27 +663,10 @@ def decompress_region(blob, dtype, lo, shape, out=None, device=None, stream=None
     box where the container is a single interpolation stream (sz3hip_decompress_region_to_device). Device only: `device=` allocates a tensor
     of `shape` there, or `out=` is a tensor of that shape on a HIP device, also a view. float32 / float64. Returns (tensor, Config) — the
     Config is the FULL array's. `stream` as for decompress."""
-    blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
-    npdt = _np_dtype(dtype)
-    dt = _dtype_id(npdt)
-    if out is None and device is None:
-        raise ValueError("decompress_region decodes into device memory: pass device= or out=")
-    if out is not None and not _gpu_tensor(out):
-        raise ValueError("out must be a tensor on a HIP device")
-    if dt > 1:  # (the library's own refusal, before anything is parsed or allocated)
-        _check(lib().sz3hip_decompress_region_to_device(C.byref(Config(1)._c), dt, blob.ctypes.data, blob.size, None, None, None, None, None))
-    conf = Config(1)
-    _check(lib().sz3hip_peek_config(C.byref(conf._c), blob.ctypes.data, blob.size))
-    clo, cext, shape = _box(conf, lo, shape)
-    import torch
-    if out is None:
-        out = torch.empty(shape, dtype=getattr(torch, npdt.name), device=device)
-    if _np_dtype(out.dtype) != npdt or tuple(out.shape) != shape:
-        raise ValueError("out must be a %s tensor of shape %s" % (npdt, shape))
-    strides = (C.c_int64 * len(shape))(*[int(st) for st in out.stride()])
-    _check(lib().sz3hip_decompress_region_to_device(C.byref(conf._c), dt, blob.ctypes.data, blob.size, clo, cext, out.data_ptr(), strides,
-                                                    _stream_handle(out.device, stream)))
-    return out, conf
+    def shape_of(conf):
+        clo, cext, box = _box(conf, lo, shape)
+        return box, (clo, cext)
+    return _decompress_partial("decompress_region", blob, dtype, lambda: (None, None), shape_of, out, device, stream)
 
 
 def coarse_dims(conf, level):
@@ -689,27 +682,7 @@ def decompress_coarse(blob, dtype, level, out=None, device=None, stream=None):
     the full-size array where the container is a single interpolation stream (sz3hip_decompress_coarse_to_device). Device only:
     `device=` allocates a tensor of coarse_dims(conf, level) there, or `out=` is a tensor of that shape on a HIP device, also a view.
     float32 / float64. Returns (tensor, Config) — the Config is the FULL array's. `stream` as for decompress."""
-    blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
-    npdt = _np_dtype(dtype)
-    dt = _dtype_id(npdt)
-    if out is None and device is None:
-        raise ValueError("decompress_coarse decodes into device memory: pass device= or out=")
-    if out is not None and not _gpu_tensor(out):
-        raise ValueError("out must be a tensor on a HIP device")
-    if dt > 1:  # (the library's own refusal, before anything is parsed or allocated)
-        _check(lib().sz3hip_decompress_coarse_to_device(C.byref(Config(1)._c), dt, blob.ctypes.data, blob.size, int(level), None, None, None))
-    conf = Config(1)
-    _check(lib().sz3hip_peek_config(C.byref(conf._c), blob.ctypes.data, blob.size))
-    cd = coarse_dims(conf, level)
-    import torch
-    if out is None:
-        out = torch.empty(cd, dtype=getattr(torch, npdt.name), device=device)
-    if _np_dtype(out.dtype) != npdt or tuple(out.shape) != cd:
-        raise ValueError("out must be a %s tensor of shape %s" % (npdt, cd))
-    strides = (C.c_int64 * len(cd))(*[int(st) for st in out.stride()])
-    _check(lib().sz3hip_decompress_coarse_to_device(C.byref(conf._c), dt, blob.ctypes.data, blob.size, int(level), out.data_ptr(), strides,
-                                                    _stream_handle(out.device, stream)))
-    return out, conf
+    return _decompress_partial("decompress_coarse", blob, dtype, lambda: (int(level),), lambda conf: (coarse_dims(conf, level), (int(level),)), out, device, stream)
 
 
 class VerifyStats(dict):

@@ -2231,7 +2231,7 @@ static int region_geometry(int N, const uint64_t *dims, int interp_id, int direc
                            szk_region_geom *g, int level = 0) {
     if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
     uint64_t cd[4] = {0, 0, 0, 0};
-    for (int i = 0; i < N && i < 4; i++) cd[i] = dims[i] ? ((dims[i] - 1) >> level) + 1 : 0;
+    for (int i = 0; i < N && i < 4; i++) cd[i] = szi_coarse_extent(dims[i], level);
     int rc = region_check_box(N, cd, lo, ext);
     if (rc) return rc;
     int nperm = 1;
@@ -2386,30 +2386,48 @@ extern "C" uint64_t sz3hip_debug_region_scratch(const sz3hip_ctx *ctx) { return 
 static std::atomic<uint64_t> g_region_fast_calls{0};
 extern "C" uint64_t sz3hip_debug_region_fast_calls(void) { return g_region_fast_calls.load(); }
 
+// ---- the partial request (szi_partial, DESIGN.md sections 11 - 13) on a context ----
+static inline bool is_box(const szi_partial *q) { return q && q->kind == SZI_BOX; }
+static inline bool is_coarse(const szi_partial *q) { return q && q->kind == SZI_COARSE; }
+// the context's coarse code array: made by its first coarse call, kept (later calls allocate nothing); then the call's grid against it
+static int coarse_reserve(sz3hip_ctx *ctx, int N, const uint64_t *dims, int level) {
+    if (!ctx->d_coarse_codes) {
+        const uint64_t cap = ctx->max_n / 2 + 8;
+        HIPCHK(hipMalloc((void **)&ctx->d_coarse_codes, (cap + 64) * 2));
+        ctx->coarse_codes_cap = cap;
+    }
+    const szi_partial grid = {SZI_COARSE, level, {}, {}};
+    if (szi_partial_num(&grid, N, dims) > ctx->coarse_codes_cap) return fail(SZ3HIP_EINVAL, "the coarse grid exceeds the context capacity");
+    return 0;
+}
+// The reconstruction of an interpolation stream for a request: the whole array, its coarse grid or a box (rg: the box's geometry).
+// The lists as the launchers take them: a payload and offsets into it, or the null base and pointers as offsets.
+static int launch_interp_recon(sz3hip_ctx *ctx, const szk_interp_params *ip, const szi_partial *part, const szk_region_geom *rg, const uint8_t *base,
+                               uint64_t vout_idx, uint64_t vout_val, uint64_t n_vout, void *d_out, hipStream_t s) {
+    if (is_box(part)) {
+        g_region_fast_calls++;
+        return szk_launch_interp_decompress_region(ctx->dtype, ip, rg, base, vout_idx, vout_val, n_vout, ctx->d_codes, ctx->d_region, d_out, s);
+    }
+    if (is_coarse(part)) return szk_launch_interp_decompress_coarse(ctx->dtype, ip, part->level, base, vout_idx, vout_val, n_vout, ctx->d_codes, ctx->d_coarse_codes, d_out, s);
+    return szk_launch_interp_decompress(ctx->dtype, ip, base, vout_idx, vout_val, n_vout, ctx->d_codes, d_out, s);
+}
+
 int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom *g, const uint64_t *d_blk_base, const uint16_t *d_em,
                      const void *d_unpred, uint64_t n_unpred, uint32_t *d_tile_cnt, uint64_t *d_tile_base, uint64_t *d_vout_idx, void *d_vout_val,
-                     uint32_t *d_bad, void *d_out, void *stream, int coarse_level, const szi_region *region) {
+                     uint32_t *d_bad, void *d_out, void *stream, const szi_partial *part) {
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
     szk_region_geom rg;
-    if (region) {  // (d_out: the box. The windows and the context's scratch, before anything is launched)
-        int rr = region_geometry(p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, region->lo, region->ext, &rg, region->level);
+    if (is_box(part)) {  // (d_out: the box. The windows and the context's scratch, before anything is launched)
+        int rr = region_geometry(p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, part->lo, part->ext, &rg, part->level);
         if (rr || (rr = region_reserve(ctx, rg.scratch_elems))) return rr;
     }
-    uint64_t num = 1, nc = 1;
-    for (int i = 0; i < p->N; i++) {
-        num *= p->dims[i];
-        nc *= ((p->dims[i] - 1) >> coarse_level) + 1;
-    }
+    const uint64_t num = szi_partial_num(nullptr, p->N, p->dims);
     if (num > ctx->max_n) return fail(SZ3HIP_EINVAL, "array exceeds the context capacity");
-    if (coarse_level > 0) {  // (d_out: the coarse grid. The code buffer: as in sz3hip_decompress_device_coarse)
+    if (is_coarse(part)) {  // (d_out: the coarse grid)
         if (p->anchor_stride & (p->anchor_stride - 1)) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (anchor stride)");
-        if (!ctx->d_coarse_codes) {
-            const uint64_t cap = ctx->max_n / 2 + 8;
-            HIPCHK(hipMalloc((void **)&ctx->d_coarse_codes, (cap + 64) * 2));
-            ctx->coarse_codes_cap = cap;
-        }
-        if (nc > ctx->coarse_codes_cap) return fail(SZ3HIP_EINVAL, "the coarse grid exceeds the context capacity");
+        int rr = coarse_reserve(ctx, p->N, p->dims, part->level);
+        if (rr) return rr;
     }
     HIPCHK(hipMemsetAsync(d_bad, 0, 4, s));
     if (szk_launch_stock_to_elem(ctx->dtype, g, d_blk_base, d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, ctx->d_codes, d_vout_idx, d_vout_val, d_bad, s))
@@ -2426,18 +2444,11 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
     ip.eb = p->eb;
     ip.radius = p->radius;
     // (the lists are the caller's own arrays: handed over as offsets from a null base)
-    if (region) {  // (a stock stream's codes come through the stock decoder: every unit)
-        g_region_fast_calls++;
+    if (is_box(part)) {  // (a stock stream's codes come through the stock decoder: every unit)
         g_tile_units_decoded += units_of(num);
         g_tile_units_total += units_of(num);
     }
-    if (region
-            ? szk_launch_interp_decompress_region(ctx->dtype, &ip, &rg, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, ctx->d_codes,
-                                                  ctx->d_region, d_out, s)
-        : coarse_level > 0
-            ? szk_launch_interp_decompress_coarse(ctx->dtype, &ip, coarse_level, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred,
-                                                  ctx->d_codes, ctx->d_coarse_codes, d_out, s)
-            : szk_launch_interp_decompress(ctx->dtype, &ip, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, ctx->d_codes, d_out, s))
+    if (launch_interp_recon(ctx, &ip, part, &rg, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, d_out, s))
         return fail(SZ3HIP_EHIP, "interpolation decoder launch failed");
     uint32_t bad = 0;
     HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
@@ -2486,19 +2497,12 @@ extern "C" int sz3hip_debug_decode_info(sz3hip_ctx *ctx, uint32_t *out4) {
     return 0;
 }
 
-// sz3hip_decompress_device (level 0) and sz3hip_decompress_device_coarse (level >= 1: an interpolation payload's points at multiples of
-// 2^level) share the header's parse and the Huffman stage; they differ in the reconstruction alone. So does
-// sz3hip_decompress_device_region (region: the box of an interpolation payload; level is 0 then).
-// (rlevel: the tile's level — lo / ext are coordinates of the grid of every 2^rlevel-th point)
-static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, void *d_out, void *stream, const uint64_t *rlo = nullptr,
-                                  const uint64_t *rext = nullptr, int rlevel = 0) {
-    const bool region = rlo != nullptr;
-    hipStream_t s = (hipStream_t)stream;
+// Every device decode starts here: the payload's header, fetched and checked, and its sections' offsets.
+static int decode_header(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, hipStream_t s, szh_header &h, szh_offsets &o) {
     HIPCHK(hipSetDevice(ctx->device));
     ctx->blk_pre_cleared = false;  // (a block stream's decoder counts in the same counter block)
     if (payload_size < sizeof(szh_header)) return fail(SZ3HIP_EFORMAT, "payload shorter than its header");
-    szh_header h;
-    uint32_t *ovf = reinterpret_cast<uint32_t *>(ctx->d_counters + 12);  // overflow flag of the half-width chain (see below)
+    uint32_t *ovf = reinterpret_cast<uint32_t *>(ctx->d_counters + 12);  // overflow flag of the half-width chain (decode_body)
     if (!ctx->h_ovf) {
         HIPCHK(hipHostMalloc((void **)&ctx->h_ovf, 8));
         *ctx->h_ovf = 0;
@@ -2531,23 +2535,24 @@ static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t
         h.sym_min + h.sym_count > SZH_HIST_BINS || h.max_len > SZH_MAX_LEN || h.radius < 2 || h.radius > 32768 ||
         h.qbytes != (h.dtype == 0 ? 4 : 8) || h.n_vout > h.n || h.n_dout > h.n || h.bitstream_words > payload_size / 4)
         return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
-    szh_offsets o;
     szk_host_offsets(&h, &o);
     if (o.end > payload_size || h.payload_bytes != o.end) return fail(SZ3HIP_EFORMAT, "truncated SZH1 payload");
-    if (level > 0) {
+    return 0;
+}
+// sz3hip_decompress_device (part null) and the partial decodes of an interpolation payload (szi_partial: its points at multiples of 2^level,
+// DESIGN.md §11; a box of it, §12, or of that grid, §13) share the header's parse and the Huffman stage; they differ in the units a box
+// has decoded and in the reconstruction.
+static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header &h, const szh_offsets &o, const szi_partial *part, void *d_out, hipStream_t s) {
+    const bool region = is_box(part);
+    uint32_t *ovf = reinterpret_cast<uint32_t *>(ctx->d_counters + 12);  // overflow flag of the half-width chain (see below)
+    if (is_coarse(part)) {
         if (h.predictor != 1)
             return fail(SZ3HIP_EUNSUPPORTED, "sz3hip_decompress_device_coarse reads interpolation payloads only (this one's predictor id is %d): a device context has "
                         "no full-size scratch of its own — sz3hip_decompress_coarse_to_device decodes every container", h.predictor);
         if (h.ndim < 1 || h.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
         if (h.anchor_stride & (h.anchor_stride - 1)) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header (anchor stride %llu is no power of two)", (unsigned long long)h.anchor_stride);
-        if (!ctx->d_coarse_codes) {  // (the context's first coarse call; kept: later calls allocate nothing)
-            const uint64_t cap = ctx->max_n / 2 + 8;
-            HIPCHK(hipMalloc((void **)&ctx->d_coarse_codes, (cap + 64) * 2));
-            ctx->coarse_codes_cap = cap;
-        }
-        uint64_t nc = 1;
-        for (int i = 0; i < 4; i++) nc *= ((h.dims[i] - 1) >> level) + 1;
-        if (nc > ctx->coarse_codes_cap) return fail(SZ3HIP_EINVAL, "the coarse grid exceeds the context capacity");
+        int rr = coarse_reserve(ctx, 4, h.dims, part->level);
+        if (rr) return rr;
     }
     szk_region_geom rg;
     if (region) {
@@ -2555,7 +2560,7 @@ static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t
             return fail(SZ3HIP_EUNSUPPORTED, "sz3hip_decompress_device_region reads interpolation payloads only (this one's predictor id is %d): a device context has "
                         "no full-size scratch of its own — sz3hip_decompress_region_to_device decodes every container", h.predictor);
         if (h.ndim < 1 || h.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
-        int rr = region_geometry(h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, rlo, rext, &rg, rlevel);
+        int rr = region_geometry(h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, part->lo, part->ext, &rg, part->level);
         if (rr || (rr = region_reserve(ctx, rg.scratch_elems)) || (rr = tile_units_reserve(ctx))) return rr;
     }
     const uint8_t *pl = (const uint8_t *)d_payload;
@@ -2731,15 +2736,8 @@ static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t
         ip.beta = h.interp_beta;
         ip.eb = h.eb;
         ip.radius = (int)h.radius;
-        if (region) {
-            g_region_fast_calls++;
-            rc = szk_launch_interp_decompress_region(ctx->dtype, &ip, &rg, pl, o.vout_idx, o.vout_val, h.n_vout, ctx->d_codes, ctx->d_region, d_out, s);
-        } else if (level > 0) {
-            rc = szk_launch_interp_decompress_coarse(ctx->dtype, &ip, level, pl, o.vout_idx, o.vout_val, h.n_vout, ctx->d_codes, ctx->d_coarse_codes, d_out, s);
-        } else {
-            dense2_for(ctx, ip);
-            rc = szk_launch_interp_decompress(ctx->dtype, &ip, pl, o.vout_idx, o.vout_val, h.n_vout, ctx->d_codes, d_out, s);
-        }
+        if (!region && !is_coarse(part)) dense2_for(ctx, ip);
+        rc = launch_interp_recon(ctx, &ip, part, &rg, pl, o.vout_idx, o.vout_val, h.n_vout, d_out, s);
     } else if (h.predictor == 2) {
         // codes -> deltas, then the blocks in anti-diagonal fronts once the side stream has the choices and coefficients
         rc = szk_launch_blk_decompress(ctx->dtype, ctx->d_codes, d_out, &bp, &sc, pl, &h, &o, ctx->d_blk_coef, s, ctx->ev_join);
@@ -2750,17 +2748,35 @@ static int decompress_device_impl(sz3hip_ctx *ctx, const void *d_payload, size_t
     if (rc) return fail(SZ3HIP_EHIP, "reconstruct kernel launch failed (%d)", rc);
     return 0;
 }
+int szi_decompress_device_partial(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_partial *part, void *d_out, void *stream) {
+    szh_header h;
+    szh_offsets o;
+    int rc = decode_header(ctx, d_payload, payload_size, (hipStream_t)stream, h, o);
+    return rc ? rc : decode_body(ctx, d_payload, h, o, part && part->kind != SZI_FULL ? part : nullptr, d_out, (hipStream_t)stream);
+}
+// lo / ext of a context's box call hold one entry per extent the PAYLOAD's header names: the header is read before they are
+static int device_box(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, const uint64_t *lo, const uint64_t *ext, void *d_out, void *stream) {
+    szh_header h;
+    szh_offsets o;
+    int rc = decode_header(ctx, d_payload, payload_size, (hipStream_t)stream, h, o);
+    if (rc) return rc;
+    szi_partial q = {SZI_BOX, level, {}, {}};
+    for (uint32_t i = 0; i < h.ndim && h.ndim <= 4; i++) {  // (an extent count outside 1 .. 4: decode_body's refusal)
+        q.lo[i] = lo[i];
+        q.ext[i] = ext[i];
+    }
+    return decode_body(ctx, d_payload, h, o, &q, d_out, (hipStream_t)stream);
+}
 extern "C" int sz3hip_decompress_device(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, void *d_out,
                                         void *stream) {
-    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream);
+    return szi_decompress_device_partial(ctx, d_payload, payload_size, nullptr, d_out, stream);
 }
+// (level 0 is sz3hip_decompress_device)
 extern "C" int sz3hip_decompress_device_coarse(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, void *d_out, void *stream) {
     if (!ctx) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_coarse: no context");
     if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "coarse level %d is outside 0 .. 30", level);
-    return decompress_device_impl(ctx, d_payload, payload_size, level, d_out, stream);
-}
-int szi_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_region *region, void *d_out, void *stream) {
-    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream, region->lo, region->ext, region->level);
+    const szi_partial q = {level ? SZI_COARSE : SZI_FULL, level, {}, {}};
+    return szi_decompress_device_partial(ctx, d_payload, payload_size, &q, d_out, stream);
 }
 // (lo / ext: one entry per extent the payload's header names)
 extern "C" int sz3hip_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const uint64_t *lo, const uint64_t *ext, void *d_out,
@@ -2768,7 +2784,7 @@ extern "C" int sz3hip_decompress_device_region(sz3hip_ctx *ctx, const void *d_pa
     if (!ctx) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_region: no context");
     if (!lo || !ext) return fail(SZ3HIP_EINVAL, "the region's %s is NULL", !lo ? "lo" : "ext");
     if (!d_payload || !d_out) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_region: the %s is NULL", !d_payload ? "payload" : "output array");
-    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream, lo, ext);
+    return device_box(ctx, d_payload, payload_size, 0, lo, ext, d_out, stream);
 }
 // (level 0 is sz3hip_decompress_device_region)
 extern "C" int sz3hip_decompress_device_tile(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, const uint64_t *lo, const uint64_t *ext,
@@ -2777,7 +2793,7 @@ extern "C" int sz3hip_decompress_device_tile(sz3hip_ctx *ctx, const void *d_payl
     if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
     if (!lo || !ext) return fail(SZ3HIP_EINVAL, "the tile's %s is NULL", !lo ? "lo" : "ext");
     if (!d_payload || !d_out) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_tile: the %s is NULL", !d_payload ? "payload" : "output array");
-    return decompress_device_impl(ctx, d_payload, payload_size, 0, d_out, stream, lo, ext, level);
+    return device_box(ctx, d_payload, payload_size, level, lo, ext, d_out, stream);
 }
 extern "C" int sz3hip_coarse_dims(const sz3hip_config *conf, int level, uint64_t *dims_out) {
     if (!conf || !dims_out) return fail(SZ3HIP_EINVAL, "sz3hip_coarse_dims: NULL argument");
@@ -2785,7 +2801,7 @@ extern "C" int sz3hip_coarse_dims(const sz3hip_config *conf, int level, uint64_t
     if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
     for (int i = 0; i < conf->N; i++) {
         if (conf->dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
-        dims_out[i] = ((conf->dims[i] - 1) >> level) + 1;
+        dims_out[i] = szi_coarse_extent(conf->dims[i], level);
     }
     return 0;
 }

@@ -1073,22 +1073,23 @@ struct DevOut {
     bool delivered = false;
 };
 static thread_local DevOut *t_devout = nullptr;
-// sz3hip_decompress_coarse_to_device, fast path: the interpolation stream this thread decodes is wanted at every 2^level-th point only
-// (t_devout is then the coarse array's view)
-static thread_local int t_coarse_level = 0;
-// sz3hip_decompress_region_to_device, fast path: the interpolation stream this thread decodes is wanted in this box only (t_devout is then the
-// box's view)
-static thread_local const szi_region *t_region = nullptr;
-static uint64_t region_num(const sz3hip_config *conf, const szi_region *r) {
-    uint64_t n = 1;
-    for (int i = 0; i < conf->N; i++) n *= r->ext[i];
-    return n;
-}
-static uint64_t coarse_num(const sz3hip_config *conf, int level) {
-    uint64_t n = 1;
-    for (int i = 0; i < conf->N; i++) n *= ((conf->dims[i] - 1) >> level) + 1;
-    return n;
-}
+// partial_to_device, fast path: the interpolation stream this thread decodes is wanted at these points only (t_devout is then their
+// array's view). Installed and cleared together with t_devout, whichever way the scope is left.
+static thread_local const szi_partial *t_partial = nullptr;
+struct DevOutScope {
+    DevOut *const prev_out = t_devout;
+    const szi_partial *const prev_part = t_partial;
+    DevOutScope(DevOut *o, const szi_partial *part = nullptr) {
+        t_devout = o;
+        t_partial = part;
+    }
+    ~DevOutScope() {
+        t_devout = prev_out;
+        t_partial = prev_part;
+    }
+    DevOutScope(const DevOutScope &) = delete;
+    DevOutScope &operator=(const DevOutScope &) = delete;
+};
 static hipError_t devout_from_device(DevOut &o, const void *src) {  // (src: the decoded array, dataType elements, complete)
     o.delivered = true;
     if (src == o.ptr) return hipSuccess;
@@ -1757,10 +1758,9 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
     HIPCHK(hipSetDevice(s->device));
     int rc;
     if ((rc = slot_ctx(s, conf->num))) return rc;
-    const int coarse = t_devout ? t_coarse_level : 0;
-    const szi_region *region = t_devout ? t_region : nullptr;
-    const size_t out_bytes = (size_t)(region ? region_num(conf, region) : coarse ? coarse_num(conf, coarse) : conf->num) * tsize;
-    void *dst = (coarse || region) && t_devout->view.contig ? (void *)t_devout->ptr : nullptr;  // (a coarse / region decode's contiguous output is written where it lies)
+    const szi_partial *part = t_partial;
+    const size_t out_bytes = (size_t)szi_partial_num(part, conf) * tsize;
+    void *dst = part && t_devout->view.contig ? (void *)t_devout->ptr : nullptr;  // (a partial decode's contiguous output is written where it lies)
     if (!dst) {
         if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, out_bytes))) return rc;
         dst = s->dev_in;
@@ -1827,7 +1827,7 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
         } else if (rd == -3) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
         else if (rd) return fail(SZ3HIP_EHIP, "stock stream: device Huffman decoder failed (%d)", rd);
     }
-    rc = szi_stock_import(s->ctx, &sp, &g, d_blk, d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, d_vidx, d_vval, d_bad, dst, s->stream, coarse, region);
+    rc = szi_stock_import(s->ctx, &sp, &g, d_blk, d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, d_vidx, d_vval, d_bad, dst, s->stream, part);
     if (rc) return rc;
     HIPCHK(d2h_out(decData, dst, out_bytes));
     return 0;
@@ -2980,12 +2980,10 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
         return fail(SZ3HIP_EINVAL, "the stream holds %s data but %s output was requested", dtype_is_int(conf->dataType) ? "integer" : "floating-point",
                     is_int ? "integer" : "floating-point");
     if ((rc = slot_ctx(s, conf->num))) return rc;
-    const int coarse = t_devout && !is_int ? t_coarse_level : 0;
-    if (coarse && hdr.predictor != 1) return fail(SZ3HIP_EFORMAT, "the Config names the interpolation stream but the payload's predictor id is %d", (int)hdr.predictor);
-    const szi_region *region = t_devout && !is_int ? t_region : nullptr;
-    if (region && hdr.predictor != 1) return fail(SZ3HIP_EFORMAT, "the Config names the interpolation stream but the payload's predictor id is %d", (int)hdr.predictor);
-    if (region && hdr.ndim != (uint32_t)conf->N) return fail(SZ3HIP_EFORMAT, "the payload's extent count does not match the Config");
-    const size_t cbytes = (size_t)(region ? region_num(conf, region) : coarse ? coarse_num(conf, coarse) : conf->num) * (cdt == SZ3HIP_FLOAT ? 4 : 8);
+    const szi_partial *part = is_int ? nullptr : t_partial;
+    if (part && hdr.predictor != 1) return fail(SZ3HIP_EFORMAT, "the Config names the interpolation stream but the payload's predictor id is %d", (int)hdr.predictor);
+    if (part && part->kind == SZI_BOX && hdr.ndim != (uint32_t)conf->N) return fail(SZ3HIP_EFORMAT, "the payload's extent count does not match the Config");
+    const size_t cbytes = (size_t)szi_partial_num(part, conf) * (cdt == SZ3HIP_FLOAT ? 4 : 8);
     // (a device call's contiguous f32 / f64 array is decoded where it lies)
     void *dst = t_devout && t_devout->view.contig && !is_int ? (void *)t_devout->ptr : nullptr;
     if (!dst) {
@@ -2995,14 +2993,12 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
     if ((rc = ensure_dev(&s->dev_payload, &s->dev_payload_bytes, std::max<size_t>(raw_len + 64, is_int ? raw_bytes : 0)))) return rc;
     HIPCHK(hipMemcpy(s->dev_payload, s->pin, raw_len, hipMemcpyHostToDevice));
     stamp(1);
-    rc = region   ? szi_decompress_device_region(s->ctx, s->dev_payload, raw_len, region, dst, s->stream)
-         : coarse ? sz3hip_decompress_device_coarse(s->ctx, s->dev_payload, raw_len, coarse, dst, s->stream)
-                  : sz3hip_decompress_device(s->ctx, s->dev_payload, raw_len, dst, s->stream);
+    rc = szi_decompress_device_partial(s->ctx, s->dev_payload, raw_len, part, dst, s->stream);
     if (rc) return rc;
     if (!is_int) {
         HIPCHK(hipStreamSynchronize(s->stream));
         stamp(2);
-        HIPCHK(d2h_out(decData, dst, coarse || region ? cbytes : raw_bytes));
+        HIPCHK(d2h_out(decData, dst, part ? cbytes : raw_bytes));
     } else if (t_devout) {  // (narrowed straight into the caller's view)
         t_devout->delivered = true;
         if (szk_launch_scatter(dataType, 1, s->dev_in, t_devout->ptr, &t_devout->view, s->stream)) return fail(SZ3HIP_EHIP, "integer narrowing kernel failed");
@@ -3030,9 +3026,11 @@ int decode_blob_to(HostSlot *s, const sz3hip_config *conf, int dataType, const u
     // the paths that write the array on the host write it here (malloc: pages nobody touches cost nothing)
     std::unique_ptr<uint8_t, void (*)(void *)> h((uint8_t *)malloc(std::max<size_t>(bytes, 1)), free);
     if (!h) return fail(SZ3HIP_EHIP, "out of host memory (%zu bytes)", bytes);
-    t_devout = &o;
-    int rc = decompress_blob(s, conf, dataType, p, payload, h.get());
-    t_devout = nullptr;
+    int rc;
+    {
+        DevOutScope scope(&o);
+        rc = decompress_blob(s, conf, dataType, p, payload, h.get());
+    }
     if (rc || o.delivered) return rc;
     if (o.view.contig) {
         HIPCHK(hipMemcpyAsync(o.ptr, h.get(), bytes, hipMemcpyHostToDevice, s->stream));
@@ -3238,128 +3236,66 @@ extern "C" int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, co
     return decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &dev, 0, conf->dims[0]);
 }
 
-// Every 2^level-th point of a container. Fast path: a single interpolation stream, decoded on the compact grid
-// (decompress_blob / stock_decompress_interp under t_coarse_level). Everything else: the full decode into a scratch array of the call, then
-// the strided gather of its coarse view.
-extern "C" int sz3hip_decompress_coarse_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, void *d_out,
-                                                  const int64_t *strides, void *stream) {
-    if (!dtype_ok(dataType))
-        return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
-    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "coarse level %d is outside 0 .. 30", level);
-    if (dtype_is_int(dataType)) return fail(SZ3HIP_EUNSUPPORTED, "the coarse decode reads float / double arrays; integer element types are not supported yet");
-    if (level == 0) return sz3hip_decompress_to_device(conf, dataType, cmpData, cmpSize, d_out, strides, stream);
-    int rc = sz3hip_peek_config(conf, cmpData, cmpSize);
-    if (rc) return rc;
-    if (zs::load()) return SZ3HIP_EZSTD;
-    sz3hip_config cc = *conf;  // the coarse array's extents (conf stays the full array's)
-    if ((rc = sz3hip_coarse_dims(conf, level, cc.dims))) return rc;
-    cc.num = coarse_num(conf, level);
-    DevArray dev;
-    if ((rc = dev_array(&cc, strides, d_out, true, &dev))) return rc;
-    const unsigned char *p = reinterpret_cast<const unsigned char *>(cmpData) + 8;
-    uint64_t payload;
-    memcpy(&payload, p, 8);
-    p += 8;
-    DeviceGuard guard;
-    HIPCHK(hipSetDevice(dev.device));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (what the caller queued on d_out comes first)
-    std::unique_lock<std::shared_mutex> all(g_host_mu, std::defer_lock);
-    std::shared_lock<std::shared_mutex> some(g_host_mu, std::defer_lock);
-    if (conf->openmp) all.lock();
-    else some.lock();
-    const size_t es = dtype_size(dataType);
-    if (!conf->openmp && (conf->cmprAlgo == SZ3HIP_ALGO_HIP_INTERP || conf->cmprAlgo == SZ3HIP_ALGO_INTERP)) {
-        SlotLease lease(dev.device, dtype_compute(dataType));
-        HostSlot *s = lease.s;
-        if (!s->stream) HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        DevOut o;
-        o.ptr = dev.ptr;
-        o.view = dev.view;
-        o.dataType = dataType;
-        o.stream = s->stream;
-        t_devout = &o;
-        t_coarse_level = level;
-        rc = decompress_blob(s, conf, dataType, p, (size_t)payload, nullptr);
-        t_devout = nullptr;
-        t_coarse_level = 0;
-        if (rc) return rc;
-        if (!o.delivered) return fail(SZ3HIP_EHIP, "the coarse decode did not deliver its array");
-        HIPCHK(hipStreamSynchronize(s->stream));
-        return 0;
+// the request's view of the contiguous full array fd: strides multiplied by 2^level, the box's extents; returns the element offset of its corner
+static int64_t partial_view(const szi_partial &q, int N, const uint64_t *out_dims, const szk_view &fd, szk_view *gv) {
+    *gv = fd;
+    gv->contig = 0;
+    int64_t corner = 0;
+    for (int i = 0; i < N; i++) {
+        const int k = 4 - N + i;
+        if (q.kind == SZI_BOX) corner += (int64_t)(q.lo[i] << q.level) * fd.str[k];
+        gv->dims[k] = out_dims[i];
+        gv->str[k] = out_dims[i] == 1 ? 0 : fd.str[k] * ((int64_t)1 << q.level);
     }
-    // the full array, decoded as sz3hip_decompress_to_device does, into a scratch of this call; then its coarse view
-    struct Scratch {
-        void *p = nullptr;
-        ~Scratch() {
-            if (p) (void)hipFree(p);
-        }
-    } full, packed;
-    if (hipMalloc(&full.p, std::max<size_t>((size_t)conf->num * es, 16)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SZ3HIP_EHIP, "no device memory for the full-size scratch (%zu bytes) this container's coarse decode needs", (size_t)conf->num * es);
-    }
-    DevArray fd;
-    if ((rc = dev_array(conf, nullptr, full.p, true, &fd))) return rc;
-    if (conf->openmp) rc = decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &fd);
-    else {
-        SlotLease lease(dev.device, dtype_compute(dataType));
-        rc = decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &fd, 0, conf->dims[0]);
-    }
-    if (rc) return rc;
-    szk_view gv = fd.view;  // (contiguous: element strides of the full array; every 2^level-th point of each extent)
-    gv.contig = 0;
-    for (int i = 0; i < 4; i++) {
-        gv.str[i] = gv.dims[i] > 1 ? gv.str[i] * ((int64_t)1 << level) : 0;
-        gv.dims[i] = ((gv.dims[i] - 1) >> level) + 1;
-    }
-    hipStream_t cs = (hipStream_t)stream;
-    void *dense = dev.ptr;
-    if (!dev.view.contig) {
-        if (hipMalloc(&packed.p, std::max<size_t>((size_t)cc.num * es, 16)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SZ3HIP_EHIP, "no device memory for the coarse array (%zu bytes)", (size_t)cc.num * es);
-        }
-        dense = packed.p;
-    }
-    if (szk_launch_gather(dataType, 0, full.p, &gv, dense, nullptr, cs)) return fail(SZ3HIP_EHIP, "gather kernel failed");
-    if (!dev.view.contig && szk_launch_scatter(dataType, 0, dense, dev.ptr, &dev.view, cs)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
-    HIPCHK(hipStreamSynchronize(cs));
-    return 0;
+    return corner;
 }
-
-// One box of a container, or of its grid of every 2^level-th point (section 13: lo / ext are then that grid's
-// coordinates). Fast path: a single interpolation stream, decoded over the box's windows (decompress_blob / stock_decompress_interp under
-// t_region). Everything else: the full decode into a scratch array of the call, then the strided gather of the box, a view of that array
-// whose strides are multiplied by 2^level and whose base is offset by lo << level.
-static int tile_to_device(const char *who, sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const uint64_t *lo, const uint64_t *ext,
-                          void *d_out, const int64_t *strides, void *stream) {
+// The partial decodes of a container (DESIGN.md sections 11 - 13): every 2^level-th point (SZI_COARSE), one box of the array (SZI_BOX at
+// level 0) or of its grid of every 2^level-th point (SZI_BOX; lo / ext are then that grid's coordinates). Fast path: a single
+// interpolation stream, decoded on the compact grid or over the box's windows (decompress_blob / stock_decompress_interp under t_partial).
+// Everything else: the full decode into a scratch array of the call, then the strided gather of the request's view of that array.
+// Where the kinds differ:
+//   - the checks' order. Box: dtype in range, integer dtype, level, NULL conf / lo / ext, peek, N, the box against the grid.
+//     Coarse: dtype in range, level, integer dtype, peek — and level 0 IS sz3hip_decompress_to_device, after those three.
+//   - the coarse fast path returns whatever decompress_blob returns, the format error for an anchor stride that is no power of two
+//     included; the box fast path falls through to the full decode on SZ3HIP_EUNSUPPORTED alone (such a stride: the windows do not nest).
+// conf comes back as the FULL array's Config in every case, also where the box is refused.
+static int partial_to_device(const char *who, sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int kind, int level, const uint64_t *lo,
+                             const uint64_t *ext, void *d_out, const int64_t *strides, void *stream) {
+    const bool box = kind == SZI_BOX;
+    const char *what = box ? "region" : "coarse";
     if (!dtype_ok(dataType))
         return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
-    if (dtype_is_int(dataType)) return fail(SZ3HIP_EUNSUPPORTED, "the region decode reads float / double arrays; integer element types are not supported yet");
-    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
-    if (!conf || !lo || !ext) return fail(SZ3HIP_EINVAL, "%s: NULL argument (%s)", who, !conf ? "conf" : !lo ? "lo" : "ext");
+    if (!box && (level < 0 || level > 30)) return fail(SZ3HIP_EINVAL, "coarse level %d is outside 0 .. 30", level);
+    if (dtype_is_int(dataType)) return fail(SZ3HIP_EUNSUPPORTED, "the %s decode reads float / double arrays; integer element types are not supported yet", what);
+    if (box && (level < 0 || level > 30)) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
+    if (box && (!conf || !lo || !ext)) return fail(SZ3HIP_EINVAL, "%s: NULL argument (%s)", who, !conf ? "conf" : !lo ? "lo" : "ext");
+    if (!box && level == 0) return sz3hip_decompress_to_device(conf, dataType, cmpData, cmpSize, d_out, strides, stream);
     int rc = sz3hip_peek_config(conf, cmpData, cmpSize);
     if (rc) return rc;
-    if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
-    szi_region box;
-    memset(&box, 0, sizeof(box));
-    box.level = level;
-    sz3hip_config bc = *conf;  // the box's extents (conf stays the full array's)
-    bc.num = 1;
-    for (int i = 0; i < conf->N; i++) {
-        const uint64_t cd = conf->dims[i] ? ((conf->dims[i] - 1) >> level) + 1 : 0;  // (the grid's extent: the array's at level 0)
-        if (ext[i] == 0) return fail(SZ3HIP_EINVAL, "the region has extent 0 in dimension %d", i);
-        if (lo[i] >= cd || ext[i] > cd - lo[i])
-            return fail(SZ3HIP_EINVAL, "the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", (unsigned long long)lo[i], (unsigned long long)lo[i],
-                        (unsigned long long)ext[i], i, (unsigned long long)cd);
-        box.lo[i] = lo[i];
-        box.ext[i] = ext[i];
-        bc.dims[i] = ext[i];
-        bc.num *= ext[i];
+    szi_partial q;
+    memset(&q, 0, sizeof(q));
+    q.kind = kind;
+    q.level = level;
+    sz3hip_config oc = *conf;  // the output array's extents (conf stays the full array's)
+    if (box) {
+        if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
+        for (int i = 0; i < conf->N; i++) {
+            const uint64_t cd = szi_coarse_extent(conf->dims[i], level);  // (the grid's extent: the array's at level 0)
+            if (ext[i] == 0) return fail(SZ3HIP_EINVAL, "the region has extent 0 in dimension %d", i);
+            if (lo[i] >= cd || ext[i] > cd - lo[i])
+                return fail(SZ3HIP_EINVAL, "the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", (unsigned long long)lo[i], (unsigned long long)lo[i],
+                            (unsigned long long)ext[i], i, (unsigned long long)cd);
+            q.lo[i] = lo[i];
+            q.ext[i] = oc.dims[i] = ext[i];
+        }
+        if (zs::load()) return SZ3HIP_EZSTD;  // (twice on purpose: behind the box's checks, in front of the coarse extents' — each kind's order of refusals)
+    } else {
+        if (zs::load()) return SZ3HIP_EZSTD;
+        if ((rc = sz3hip_coarse_dims(conf, level, oc.dims))) return rc;
     }
-    if (zs::load()) return SZ3HIP_EZSTD;
+    oc.num = szi_partial_num(&q, conf);
     DevArray dev;
-    if ((rc = dev_array(&bc, strides, d_out, true, &dev))) return rc;
+    if ((rc = dev_array(&oc, strides, d_out, true, &dev))) return rc;
     const unsigned char *p = reinterpret_cast<const unsigned char *>(cmpData) + 8;
     uint64_t payload;
     memcpy(&payload, p, 8);
@@ -3381,19 +3317,18 @@ static int tile_to_device(const char *who, sz3hip_config *conf, int dataType, co
         o.view = dev.view;
         o.dataType = dataType;
         o.stream = s->stream;
-        t_devout = &o;
-        t_region = &box;
-        rc = decompress_blob(s, conf, dataType, p, (size_t)payload, nullptr);
-        t_devout = nullptr;
-        t_region = nullptr;
-        if (rc != SZ3HIP_EUNSUPPORTED) {  // (an anchor stride that is no power of two: the windows do not nest, the full decode below)
+        {
+            DevOutScope scope(&o, &q);
+            rc = decompress_blob(s, conf, dataType, p, (size_t)payload, nullptr);
+        }
+        if (!box || rc != SZ3HIP_EUNSUPPORTED) {
             if (rc) return rc;
-            if (!o.delivered) return fail(SZ3HIP_EHIP, "the region decode did not deliver its array");
+            if (!o.delivered) return fail(SZ3HIP_EHIP, "the %s decode did not deliver its array", what);
             HIPCHK(hipStreamSynchronize(s->stream));
             return 0;
         }
     }
-    // the full array, decoded as sz3hip_decompress_to_device does, into a scratch of this call; then the box of it
+    // the full array, decoded as sz3hip_decompress_to_device does, into a scratch of this call; then the request's view of it
     struct Scratch {
         void *p = nullptr;
         ~Scratch() {
@@ -3402,7 +3337,7 @@ static int tile_to_device(const char *who, sz3hip_config *conf, int dataType, co
     } full, packed;
     if (hipMalloc(&full.p, std::max<size_t>((size_t)conf->num * es, 16)) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(SZ3HIP_EHIP, "no device memory for the full-size scratch (%zu bytes) this container's region decode needs", (size_t)conf->num * es);
+        return fail(SZ3HIP_EHIP, "no device memory for the full-size scratch (%zu bytes) this container's %s decode needs", (size_t)conf->num * es, what);
     }
     DevArray fd;
     if ((rc = dev_array(conf, nullptr, full.p, true, &fd))) return rc;
@@ -3412,21 +3347,14 @@ static int tile_to_device(const char *who, sz3hip_config *conf, int dataType, co
         rc = decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &fd, 0, conf->dims[0]);
     }
     if (rc) return rc;
-    szk_view gv = fd.view;  // (contiguous: element strides of the full array; the box's extents, its base offset by lo)
-    gv.contig = 0;
-    int64_t corner = 0;
-    for (int i = 0; i < conf->N; i++) {
-        const int k = 4 - conf->N + i;
-        corner += (int64_t)(lo[i] << level) * gv.str[k];
-        gv.dims[k] = ext[i];
-        gv.str[k] = ext[i] == 1 ? 0 : gv.str[k] * ((int64_t)1 << level);
-    }
+    szk_view gv;
+    const int64_t corner = partial_view(q, conf->N, oc.dims, fd.view, &gv);
     hipStream_t cs = (hipStream_t)stream;
     void *dense = dev.ptr;
     if (!dev.view.contig) {
-        if (hipMalloc(&packed.p, std::max<size_t>((size_t)bc.num * es, 16)) != hipSuccess) {
+        if (hipMalloc(&packed.p, std::max<size_t>((size_t)oc.num * es, 16)) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(SZ3HIP_EHIP, "no device memory for the region's array (%zu bytes)", (size_t)bc.num * es);
+            return fail(SZ3HIP_EHIP, box ? "no device memory for the region's array (%zu bytes)" : "no device memory for the coarse array (%zu bytes)", (size_t)oc.num * es);
         }
         dense = packed.p;
     }
@@ -3435,13 +3363,17 @@ static int tile_to_device(const char *who, sz3hip_config *conf, int dataType, co
     HIPCHK(hipStreamSynchronize(cs));
     return 0;
 }
+extern "C" int sz3hip_decompress_coarse_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, void *d_out,
+                                                  const int64_t *strides, void *stream) {
+    return partial_to_device("sz3hip_decompress_coarse_to_device", conf, dataType, cmpData, cmpSize, SZI_COARSE, level, nullptr, nullptr, d_out, strides, stream);
+}
 extern "C" int sz3hip_decompress_region_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, const uint64_t *lo, const uint64_t *ext,
                                                   void *d_out, const int64_t *strides, void *stream) {
-    return tile_to_device("sz3hip_decompress_region_to_device", conf, dataType, cmpData, cmpSize, 0, lo, ext, d_out, strides, stream);
+    return partial_to_device("sz3hip_decompress_region_to_device", conf, dataType, cmpData, cmpSize, SZI_BOX, 0, lo, ext, d_out, strides, stream);
 }
 extern "C" int sz3hip_decompress_tile_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const uint64_t *lo,
                                                 const uint64_t *ext, void *d_out, const int64_t *strides, void *stream) {
-    return tile_to_device("sz3hip_decompress_tile_to_device", conf, dataType, cmpData, cmpSize, level, lo, ext, d_out, strides, stream);
+    return partial_to_device("sz3hip_decompress_tile_to_device", conf, dataType, cmpData, cmpSize, SZI_BOX, level, lo, ext, d_out, strides, stream);
 }
 
 // ---- sz3hip_verify_device: the error statistics of two device arrays (kernels: sz3hip_verify.hip) ---------------------------------

@@ -24,14 +24,26 @@ struct szi_stock_params {  // what InterpolationDecomposition::save holds beside
     double alpha, beta, eb;
     int radius;
 };
-// region decode: the box [lo, lo + ext) of the array, one entry per extent of the stream, slowest first
-// tile decode (section 13): level k > 0 — the box is one of the grid of every 2^k-th point, in that grid's coordinates
-struct szi_region {
+// A partial decode (DESIGN.md sections 11 - 13): the one way "this interpolation stream is wanted only at these points" travels inside
+// the library. A null pointer, or SZI_FULL, is the full decode.
+//   SZI_COARSE  every 2^level-th point of the array (level >= 1; lo / ext unused)
+//   SZI_BOX     the box [lo, lo + ext) of the grid of every 2^level-th point, in that grid's coordinates, one entry per extent of the
+//               stream, slowest first (level 0: the region decode — the box is one of the array itself)
+enum { SZI_FULL = 0, SZI_COARSE, SZI_BOX };
+struct szi_partial {
+    int kind, level;
     uint64_t lo[4], ext[4];
-    int level;
 };
-// sz3hip_decompress_device_region with the box in one struct (the host API's slots call it)
-int szi_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_region *region, void *d_out, void *stream);
+static inline uint64_t szi_coarse_extent(uint64_t d, int level) { return d ? ((d - 1) >> level) + 1 : 0; }
+// the element count of q's output for an array of N extents
+static inline uint64_t szi_partial_num(const szi_partial *q, int N, const uint64_t *dims) {
+    uint64_t n = 1;
+    for (int i = 0; i < N; i++) n *= !q || q->kind == SZI_FULL ? dims[i] : q->kind == SZI_BOX ? q->ext[i] : szi_coarse_extent(dims[i], q->level);
+    return n;
+}
+static inline uint64_t szi_partial_num(const szi_partial *q, const sz3hip_config *conf) { return szi_partial_num(q, conf->N, conf->dims); }
+// sz3hip_decompress_device with a partial request (the host API's slots call it; part null: the full decode)
+int szi_decompress_device_partial(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_partial *part, void *d_out, void *stream);
 // after sz3hip_compress_stage1 chose interpolation (header predictor 1): waits for it, reports its parameters and the number of
 // unpredictable values (the anchor grid included); SZ3HIP_EUNSUPPORTED when stage 1 took another predictor
 int szi_stock_stage1_outcome(sz3hip_ctx *ctx, szi_stock_params *out, uint64_t *n_unpred, void *stream);
@@ -41,8 +53,7 @@ int szi_stock_export(sz3hip_ctx *ctx, const szg_geom *g, const uint64_t *d_blk_b
 // the inverse: emission-order codes + unpredictable values of a stock ALGO_INTERP stream -> the reconstructed array
 int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom *g, const uint64_t *d_blk_base, const uint16_t *d_em,
                      const void *d_unpred, uint64_t n_unpred, uint32_t *d_tile_cnt, uint64_t *d_tile_base, uint64_t *d_vout_idx, void *d_vout_val,
-                     uint32_t *d_bad, void *d_out, void *stream, int coarse_level = 0,  // (coarse_level k >= 1: d_out receives every 2^k-th point only)
-                     const szi_region *region = nullptr);                                // (region: d_out receives the box only, contiguous)
+                     uint32_t *d_bad, void *d_out, void *stream, const szi_partial *part = nullptr);  // (part: d_out receives its points only, contiguous)
 int szi_stage1_with_larger_lists(sz3hip_ctx *ctx, const sz3hip_config *conf, const void *d_in, uint64_t need, void *stream, bool any_number = false);
 // The default algorithm's tuner run from the HOST copy of an array while that array is being copied to the device (the host API: the tuner's
 // launches, round trips and host-side pricing vanish behind the copy). conf: the call's Config with its absolute bound; the next

@@ -13,68 +13,11 @@ import pytest
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
 from sz3_amd import Dbg  # noqa: E402
+from partial_cases import CODES, DEV, EB, FALLBACKS, INTERP_IDS, conf_for, container, device_payload, raw, smooth, spiky  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
 L.sz3hip_last_error_code.restype = C.c_int
-DEV = "cuda:0"
-EB = 1e-2
-INTERP_IDS = (sz3_amd.ALGO_INTERP, sz3_amd.ALGO_HIP_INTERP)
-
-
-def _codes():  # the error enum of include/sz3hip.h
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sz3hip.h")) as f:
-        txt = f.read()
-    return {m.group(1): int(m.group(2)) for m in re.finditer(r"(SZ3HIP_E[A-Z]+) = (-?\d+)", txt)}
-
-
-CODES = _codes()
-
-
-def smooth(shape, dtype="float32", seed=7):
-    """a smooth N-D field (periods of 37 .. 61 points, four times that in 1-D; amplitude ~1) with noise of sigma 1e-3: at the bound 1e-2
-    most codes are the central one"""
-    ix = np.indices(shape, dtype=np.float64)
-    w = 4.0 if len(shape) == 1 else 1.0  # (a 1-D array of a few thousand points has no other extent to pay for the stream's fixed part)
-    f = np.ones(shape)
-    for i, x in enumerate(ix):
-        f = f * np.sin(2 * np.pi * x / (w * (61 - 7 * i)) + 0.4 * i)
-    f = f + 0.25 * np.sin(2 * np.pi * sum((i + 1) * x for i, x in enumerate(ix)) / (w * 37))
-    f = f + np.random.default_rng(seed).normal(0.0, 1e-3, size=shape)
-    return f.astype(dtype)
-
-
-def spiky(shape=(65, 47, 130), n_spikes=200, seed=11):
-    """the 3-D field with spikes of 1e6 at seeded positions: unpredictable values on and off every coarse grid"""
-    a = smooth(shape)
-    rng = np.random.default_rng(seed)
-    pos = np.stack([rng.integers(0, d, n_spikes) for d in shape], axis=1)
-    a[tuple(pos.T)] = 1e6
-    return a, pos
-
-
-def conf_for(shape, algo=sz3_amd.ALGO_INTERP, eb=EB, **kw):
-    """quantbinCnt 1024: the payload stores a code length per symbol from the smallest to the largest in use, and symbol 0 (anchors,
-    unpredictable points) is always in use — under the default 65536 bins that table alone is 32 KB, more than the smallest arrays here
-    hold, and the dispatcher then writes them lossless (payload >= array). +-512 bins at this bound cover the fields' residuals."""
-    c = sz3_amd.Config(*shape)
-    c.cmprAlgo = algo
-    c.errorBoundMode = sz3_amd.EB_ABS
-    c.absErrorBound = eb
-    c.quantbinCnt = 1024
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def container(a, conf):
-    return sz3_amd.compress(np.ascontiguousarray(a), conf)[0].copy()
-
-
-def raw(t):
-    return t.contiguous().cpu().numpy().reshape(-1).view(np.uint8)
 
 
 def subsampled(full, k):
@@ -184,14 +127,6 @@ def test_stock_format(shape):
 
 
 # ---- fallback containers: the full decode, then the strided gather ---------------------------------------------------------
-FALLBACKS = [
-    ("lorenzo", dict(algo=sz3_amd.ALGO_LORENZO_REG, lorenzo=1, lorenzo2=0, regression=0)),
-    ("blocks_default", dict(algo=sz3_amd.ALGO_LORENZO_REG)),
-    ("nopred", dict(algo=sz3_amd.ALGO_NOPRED)),
-    ("lossless", dict(algo=sz3_amd.ALGO_INTERP_LORENZO, eb=0.0)),
-]
-
-
 @pytest.mark.parametrize("name,kw", FALLBACKS, ids=[f[0] for f in FALLBACKS])
 def test_fallback_containers(name, kw):
     shape = (40, 48, 56)
@@ -264,19 +199,6 @@ def test_level_0_is_decompress(interp_case):
 
 
 # ---- device context --------------------------------------------------------------------------------------------------------
-def device_payload(a, conf):
-    dc = sz3_amd.DeviceCompressor(a.size, a.dtype)
-    cap = dc.payload_bound(a.size, worst_case=True)
-    t = torch.from_numpy(a).to(DEV)
-    pl = torch.empty(cap, dtype=torch.uint8, device=DEV)
-    s = torch.cuda.current_stream().cuda_stream
-    size = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, s)
-    full = torch.empty_like(t)
-    dc.decompress(pl.data_ptr(), size, full.data_ptr(), s)
-    torch.cuda.synchronize()
-    return dc, pl, size, full
-
-
 def ctx_coarse(dc, pl, size, conf, k):
     out = torch.full(sz3_amd.coarse_dims(conf, k), 77.0, dtype=torch.float32, device=DEV)
     dc.decompress_coarse(pl.data_ptr(), size, k, out.data_ptr(), torch.cuda.current_stream().cuda_stream)

@@ -2,7 +2,7 @@
 every container the device call decodes, with the interpolation streams taking the fast path (the passes over the box's windows, one compact
 buffer per level). The one assertion everywhere is raw-byte identity with the full decode's slice; there are no tolerances.
 
-The fields, bounds and the 1024 quantisation bins are those of test_gpu_coarse.py (which says why); a case that must be a lossy interpolation
+The fields, bounds and the 1024 quantisation bins are those of partial_cases.py (conf_for says why); a case that must be a lossy interpolation
 stream asserts the trailer's cmprAlgo instead of skipping."""
 import ctypes as C
 
@@ -12,87 +12,11 @@ import pytest
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
 from sz3_amd import Dbg  # noqa: E402
+from partial_cases import CODES, DEV, EB, FALLBACKS, INTERP_IDS, box_slices, boxes_of, conf_for, container, device_payload, raw, smooth, spiky  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
 L.sz3hip_last_error_code.restype = C.c_int
-DEV = "cuda:0"
-EB = 1e-2
-INTERP_IDS = (sz3_amd.ALGO_INTERP, sz3_amd.ALGO_HIP_INTERP)
-
-
-def _codes():  # the error enum of include/sz3hip.h
-    import os
-    import re
-    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sz3hip.h")) as f:
-        txt = f.read()
-    return {m.group(1): int(m.group(2)) for m in re.finditer(r"(SZ3HIP_E[A-Z]+) = (-?\d+)", txt)}
-
-
-CODES = _codes()
-
-
-def smooth(shape, dtype="float32", seed=7):
-    """a smooth N-D field (periods of 37 .. 61 points, four times that in 1-D; amplitude ~1) with noise of sigma 1e-3"""
-    ix = np.indices(shape, dtype=np.float64)
-    w = 4.0 if len(shape) == 1 else 1.0
-    f = np.ones(shape)
-    for i, x in enumerate(ix):
-        f = f * np.sin(2 * np.pi * x / (w * (61 - 7 * i)) + 0.4 * i)
-    f = f + 0.25 * np.sin(2 * np.pi * sum((i + 1) * x for i, x in enumerate(ix)) / (w * 37))
-    f = f + np.random.default_rng(seed).normal(0.0, 1e-3, size=shape)
-    return f.astype(dtype)
-
-
-def spiky(shape=(65, 47, 130), n_spikes=200, seed=11):
-    """the 3-D field with spikes of 1e6 at seeded positions (test_gpu_coarse.py's): unpredictable values inside and outside every window"""
-    a = smooth(shape)
-    rng = np.random.default_rng(seed)
-    pos = np.stack([rng.integers(0, d, n_spikes) for d in shape], axis=1)
-    a[tuple(pos.T)] = 1e6
-    return a, pos
-
-
-def conf_for(shape, algo=sz3_amd.ALGO_INTERP, eb=EB, **kw):
-    c = sz3_amd.Config(*shape)
-    c.cmprAlgo = algo
-    c.errorBoundMode = sz3_amd.EB_ABS
-    c.absErrorBound = eb
-    c.quantbinCnt = 1024
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
-def container(a, conf):
-    return sz3_amd.compress(np.ascontiguousarray(a), conf)[0].copy()
-
-
-def raw(t):
-    return t.contiguous().cpu().numpy().reshape(-1).view(np.uint8)
-
-
-def box_slices(lo, ext):
-    return tuple(slice(a, a + e) for a, e in zip(lo, ext))
-
-
-def boxes_of(shape):
-    """the boxes of the geometry cases: the whole array; one interior point with odd coordinates; a box at the origin corner; one ending at the
-    far corner; one with odd lo that straddles the coordinates 32 and 64 along x (where x is shorter: odd lo, to the row's end); one of extent 1
-    in the slowest dimension"""
-    N = len(shape)
-    whole = ((0,) * N, tuple(shape))
-    point = (tuple(min(d - 1, (d // 2) | 1) for d in shape), (1,) * N)
-    origin = ((0,) * N, tuple(max(1, min(d, d // 3 + 1)) for d in shape))
-    far_ext = tuple(max(1, min(d, d // 4 + 2)) for d in shape)
-    far = (tuple(d - e for d, e in zip(shape, far_ext)), far_ext)
-    x = shape[-1]
-    xlo = 29 if x > 69 else 3
-    lo = tuple(min(d - 1, 1) for d in shape[:-1]) + (xlo,)
-    straddle = (lo, tuple(max(1, min(5, d - a)) for d, a in zip(shape[:-1], lo)) + (min(40, x - xlo),))
-    slab_lo = (min(shape[0] - 1, 5),) + tuple(min(d - 1, 2) for d in shape[1:])
-    slab = (slab_lo, (1,) + tuple(d - a for d, a in zip(shape[1:], slab_lo[1:])))
-    return [whole, point, origin, far, straddle, slab]
 
 
 def check_boxes(blob, dtype, boxes, algos=None, full=None):
@@ -221,14 +145,6 @@ def test_stock_format(shape):
 
 
 # ---- fallback containers: the full decode, then the strided gather of the box ---------------------------------------------------
-FALLBACKS = [
-    ("lorenzo", dict(algo=sz3_amd.ALGO_LORENZO_REG, lorenzo=1, lorenzo2=0, regression=0)),
-    ("blocks_default", dict(algo=sz3_amd.ALGO_LORENZO_REG)),
-    ("nopred", dict(algo=sz3_amd.ALGO_NOPRED)),
-    ("lossless", dict(algo=sz3_amd.ALGO_INTERP_LORENZO, eb=0.0)),
-]
-
-
 @pytest.mark.parametrize("name,kw", FALLBACKS, ids=[f[0] for f in FALLBACKS])
 def test_fallback_containers(name, kw):
     shape = (40, 48, 56)
@@ -297,19 +213,6 @@ def test_waits_for_the_producer(interp_case):
 
 
 # ---- device context ------------------------------------------------------------------------------------------------------------
-def device_payload(a, conf):
-    dc = sz3_amd.DeviceCompressor(a.size, a.dtype)
-    cap = dc.payload_bound(a.size, worst_case=True)
-    t = torch.from_numpy(a).to(DEV)
-    pl = torch.empty(cap, dtype=torch.uint8, device=DEV)
-    s = torch.cuda.current_stream().cuda_stream
-    size = dc.compress(conf, t.data_ptr(), pl.data_ptr(), cap, s)
-    full = torch.empty_like(t)
-    dc.decompress(pl.data_ptr(), size, full.data_ptr(), s)
-    torch.cuda.synchronize()
-    return dc, pl, size, full
-
-
 def ctx_region(dc, pl, size, lo, ext):
     out = torch.full(ext, 77.0, dtype=torch.float32, device=DEV)
     dc.decompress_region(pl.data_ptr(), size, lo, ext, out.data_ptr(), torch.cuda.current_stream().cuda_stream)

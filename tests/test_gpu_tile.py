@@ -1,7 +1,7 @@
 """Tile decode on the MI355X: decompress_tile(blob, dtype, k, lo, shape) is, bit for bit, decompress(blob, dtype)[::2**k, ...][box] — the box
 of the grid of every 2^k-th point — with the Huffman stage of this library's own interpolation streams decoding only the units the box needs.
 The one assertion on values everywhere is raw-byte identity with the full decode's slice; there are no tolerances. Fields, bound and the 1024
-quantisation bins are test_gpu_region.py's."""
+quantisation bins are partial_cases.py's."""
 import ctypes as C
 
 import numpy as np
@@ -9,14 +9,10 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
-import test_gpu_region as G  # noqa: E402
+from partial_cases import CODES, DEV, FALLBACKS, INTERP_IDS, box_slices, boxes_of, conf_for, container, device_payload, raw, smooth, spiky  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
-DEV = G.DEV
-CODES = G.CODES
-INTERP_IDS = G.INTERP_IDS
-smooth, spiky, conf_for, container, raw, boxes_of, box_slices = G.smooth, G.spiky, G.conf_for, G.container, G.raw, G.boxes_of, G.box_slices
 DEF_ANCHOR = (4096, 128, 32, 16)
 
 
@@ -264,7 +260,7 @@ def test_stale_codes():
 
 
 # ---- fallback containers: the full decode, then the strided gather of the view -------------------------------------------------
-@pytest.mark.parametrize("name,kw", G.FALLBACKS, ids=[f[0] for f in G.FALLBACKS])
+@pytest.mark.parametrize("name,kw", FALLBACKS, ids=[f[0] for f in FALLBACKS])
 def test_fallback_containers(name, kw):
     """(an anchor stride that is no power of two takes this path too, but no such container can be written here: the compressor refuses the
     stride. tests/test_tile_cpu.py checks the plan's SZ3HIP_EUNSUPPORTED, which is what sends the to-device call here)"""
@@ -363,7 +359,7 @@ def test_host_pointer_and_bad_boxes_are_refused_before_any_launch(interp_case):
 def test_device_context_and_its_scratch():
     shape = (65, 47, 130)
     conf = conf_for(shape)
-    dc, pl, size, full = G.device_payload(smooth(shape), conf)
+    dc, pl, size, full = device_payload(smooth(shape), conf)
     assert dc.region_scratch() == 0
     out = torch.full((4, 4, 4), 77.0, dtype=torch.float32, device=DEV)
     s = torch.cuda.current_stream().cuda_stream
@@ -395,9 +391,49 @@ def test_device_context_refuses_a_lorenzo_payload():
     shape = (40, 48, 56)
     out = torch.full((4, 4, 4), 77.0, dtype=torch.float32, device=DEV)
     s = torch.cuda.current_stream().cuda_stream
-    dc, pl, size, _ = G.device_payload(smooth(shape), conf_for(shape, algo=sz3_amd.ALGO_LORENZO_REG, lorenzo=1, lorenzo2=0, regression=0))
+    dc, pl, size, _ = device_payload(smooth(shape), conf_for(shape, algo=sz3_amd.ALGO_LORENZO_REG, lorenzo=1, lorenzo2=0, regression=0))
     with pytest.raises(sz3_amd.SZ3HipError) as e:
         dc.decompress_tile(pl.data_ptr(), size, 1, (1, 1, 1), (4, 4, 4), out.data_ptr(), s)
     assert e.value.code == CODES["SZ3HIP_EUNSUPPORTED"]
     torch.cuda.synchronize()
     assert bool((out == 77).all())
+
+
+# ---- a failed partial call leaves nothing behind on its thread -----------------------------------------------------------------
+def test_a_failed_partial_call_leaves_nothing_installed():
+    """one thread. A coarse, a region and a tile call of a blob cut 40 bytes short each return an error (the trailer's: the call ends at
+    its peek). The same three calls of a blob whose trailer is intact and whose lossless block states one byte more than it holds: the peek
+    passes and the call fails inside the decode, in libzstd's check, where the thread's output view and partial request are installed.
+    After all six, the full decode of the intact blob on that thread — into device memory and into a host array — is the reference full
+    decode, bit for bit, and a tile call of it its slice"""
+    shape = (33, 20, 17)
+    blob = container(smooth(shape), conf_for(shape))
+    full, conf = sz3_amd.decompress(blob, np.float32, device=DEV)
+    assert conf.cmprAlgo in INTERP_IDS
+    k, lo, ext = 1, (3, 2, 1), (9, 5, 6)
+
+    def calls(b):
+        return (lambda: sz3_amd.decompress_coarse(b, np.float32, 1, device=DEV),
+                lambda: sz3_amd.decompress_region(b, np.float32, lo, ext, device=DEV),
+                lambda: sz3_amd.decompress_tile(b, np.float32, k, lo, ext, device=DEV))
+
+    for call in calls(blob[:-40].copy()):
+        with pytest.raises(sz3_amd.SZ3HipError) as e:
+            call()
+        assert e.value.code < 0
+    bad = blob.copy()  # [magic, version][u64 payload bytes][u64 length of the lossless block's content][zstd frames][Config]
+    bad[16:24] = np.array([int(bad[16:24].view(np.uint64)[0]) + 1], np.uint64).view(np.uint8)
+    c = sz3_amd.Config(1)
+    assert L.sz3hip_peek_config(C.byref(c._c), bad.ctypes.data, bad.size) == 0 and c.dims == conf.dims, "the peek must pass: the decode is what fails"
+    for call in calls(bad):
+        before = L.sz3hip_debug_region_fast_calls()
+        with pytest.raises(sz3_amd.SZ3HipError) as e:
+            call()
+        assert e.value.code == CODES["SZ3HIP_EZSTD"] and "ZSTD_decompress" in str(e.value), "the error must be the decode's, not the peek's"
+        assert L.sz3hip_debug_region_fast_calls() == before
+    again, c2 = sz3_amd.decompress(blob, np.float32, device=DEV)
+    assert tuple(again.shape) == shape == c2.dims and np.array_equal(raw(again), raw(full))
+    host, _ = sz3_amd.decompress(blob, np.float32, shape)
+    assert np.array_equal(host.reshape(-1).view(np.uint8), raw(full)), "a host decode on this thread must land in its host array"
+    got, _ = sz3_amd.decompress_tile(blob, np.float32, k, lo, ext, device=DEV)
+    assert np.array_equal(raw(got), raw(coarse_view(full, k)[box_slices(lo, ext)]))
