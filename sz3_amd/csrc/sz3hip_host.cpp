@@ -535,6 +535,14 @@ struct HostSlot {
     bool busy = false;  // leased to a single-slab call (g_pool_mu)
 };
 std::shared_mutex g_host_mu;
+struct HostLock {  // for the length of a call: exclusive (multi-slab and pieced calls) or shared (single-slab calls)
+    std::unique_lock<std::shared_mutex> all{g_host_mu, std::defer_lock};
+    std::shared_lock<std::shared_mutex> some{g_host_mu, std::defer_lock};
+    explicit HostLock(bool exclusive) {
+        if (exclusive) all.lock();
+        else some.lock();
+    }
+};
 std::mutex g_pool_mu;  // the slot list and the leases
 std::vector<std::unique_ptr<HostSlot>> g_slots;
 sz3hip_comm *g_comm;
@@ -890,7 +898,6 @@ struct Prefault {
     }
     ~Prefault() { wait(); }
 };
-static thread_local Prefault *t_prefault = nullptr;
 // The pieces of a container decoded on one GPU do not copy their slabs out themselves: each hands its (destination, source, length) to the
 // calling thread, which sends them through the staging ring in piece order, back to back.
 struct D2hGate {
@@ -922,13 +929,6 @@ struct D2hGate {
         cv->notify_all();
     }
 };
-static thread_local D2hGate *t_gate = nullptr;
-// SZ3HIP_TIMING: a piece's way through the pipelined reader (ms since the call began)
-static thread_local double *t_stamps = nullptr;
-static thread_local std::chrono::steady_clock::time_point t_stamp0;
-static inline void stamp(int k) {
-    if (t_stamps) t_stamps[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_stamp0).count();
-}
 // The decoded array to the caller's memory. A large one goes through pinned staging buffers (round 5): the copy engine fills a ring of
 // 4 MB buffers at link speed, the pool's threads copy them on into the caller's array — whose pages, if they have never been touched,
 // are faulted in by those threads, many at a time (page faults take the address space's lock for reading only). What this replaces:
@@ -1062,52 +1062,56 @@ static hipError_t d2h_staged(void *dst, const void *src, size_t bytes) {
     return e != hipSuccess ? e : f;
 }
 static bool d2h_staging_wanted(size_t bytes) { return bytes >= (32u << 20) && env_int("SZ3HIP_D2H_STAGED", 1) != 0; }
-// sz3hip_decompress_to_device: where the blob being decoded by this thread goes — a view of the caller's device array. The decoders hand
-// their result to d2h_out as they do for the host API, and it lands in the view instead (nothing when a decoder wrote it in place);
-// a blob decoded on the host (ALGO_LOSSLESS, the stock 1-D chain) never reaches d2h_out and is copied in afterwards (decode_blob_to).
-struct DevOut {
-    char *ptr = nullptr;
+// Where the array of the ONE blob a call of the decode chain reads goes, and what of it is wanted. The entry points build it; decompress_blob,
+// the stock readers, d2h_out and stamp take it by reference.
+//   host: the caller's host array (null on the partial fast path, whose every decoder delivers into the view).
+//   dev .. delivered: sz3hip_decompress_to_device and the partial decodes — a view of the caller's device array (dev != null). The decoders
+//     hand their result to d2h_out as they do for the host API, and it lands in the view instead (nothing when a decoder wrote it in
+//     place); a blob decoded on the host (ALGO_LOSSLESS, the stock 1-D chain) is written to `host`, never reaches d2h_out, leaves
+//     `delivered` false and is copied in afterwards (decode_blob_to).
+//   part: the interpolation stream is wanted at these points only (partial_to_device's fast path; the view is then their array's).
+//   gate: a piece of the pipelined reader hands its copy out to the calling thread; prefault: sz3hip_decompress populates the pages of
+//     `host` beside the decode; stamps: SZ3HIP_TIMING, a piece's way through the pipelined reader (ms since stamp0, the call's begin).
+struct DecodeOut {
+    void *host = nullptr;
+    char *dev = nullptr;
     szk_view view{};
     int dataType = 0;
     hipStream_t stream = nullptr;
     bool delivered = false;
-};
-static thread_local DevOut *t_devout = nullptr;
-// partial_to_device, fast path: the interpolation stream this thread decodes is wanted at these points only (t_devout is then their
-// array's view). Installed and cleared together with t_devout, whichever way the scope is left.
-static thread_local const szi_partial *t_partial = nullptr;
-struct DevOutScope {
-    DevOut *const prev_out = t_devout;
-    const szi_partial *const prev_part = t_partial;
-    DevOutScope(DevOut *o, const szi_partial *part = nullptr) {
-        t_devout = o;
-        t_partial = part;
+    const szi_partial *part = nullptr;
+    D2hGate *gate = nullptr;
+    Prefault *prefault = nullptr;
+    double *stamps = nullptr;
+    std::chrono::steady_clock::time_point stamp0;
+    explicit DecodeOut(void *host_dst) : host(host_dst) {}
+    void to_rows(const DevArray &d, uint64_t lo, uint64_t hi, int dt, hipStream_t st) {  // the device variant: rows [lo, hi) of d
+        dev = d.slab(lo, hi, dtype_size(dt), &view);
+        dataType = dt;
+        stream = st;
     }
-    ~DevOutScope() {
-        t_devout = prev_out;
-        t_partial = prev_part;
-    }
-    DevOutScope(const DevOutScope &) = delete;
-    DevOutScope &operator=(const DevOutScope &) = delete;
+    bool in_place() const { return dev && view.contig; }  // (contiguous device output is decoded where it lies)
 };
-static hipError_t devout_from_device(DevOut &o, const void *src) {  // (src: the decoded array, dataType elements, complete)
-    o.delivered = true;
-    if (src == o.ptr) return hipSuccess;
-    if (szk_launch_scatter(o.dataType, 0, src, o.ptr, &o.view, o.stream)) return hipErrorLaunchFailure;
-    return hipStreamSynchronize(o.stream);
+static inline void stamp(const DecodeOut &out, int k) {
+    if (out.stamps) out.stamps[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - out.stamp0).count();
 }
-static hipError_t d2h_out(void *dst, const void *src, size_t bytes) {
-    if (t_devout) return devout_from_device(*t_devout, src);
-    if (t_gate && !t_gate->passed) {  // (a piece of a pipelined read: the calling thread copies, in piece order)
-        t_gate->hand_over(dst, src, bytes);
+static hipError_t d2h_out(DecodeOut &out, const void *src, size_t bytes) {  // (src: the decoded array, complete on the device)
+    if (out.dev) {
+        out.delivered = true;
+        if (src == out.dev) return hipSuccess;
+        if (szk_launch_scatter(out.dataType, 0, src, out.dev, &out.view, out.stream)) return hipErrorLaunchFailure;
+        return hipStreamSynchronize(out.stream);
+    }
+    if (out.gate && !out.gate->passed) {  // (a piece of a pipelined read: the calling thread copies, in piece order)
+        out.gate->hand_over(out.host, src, bytes);
         return hipSuccess;
     }
     if (d2h_staging_wanted(bytes)) {
-        const hipError_t e = d2h_staged(dst, src, bytes);
+        const hipError_t e = d2h_staged(out.host, src, bytes);
         if (e != hipErrorOutOfMemory) return e;  // (no pinned ring: the plain copy)
     }
-    if (t_prefault) t_prefault->wait();
-    return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+    if (out.prefault) out.prefault->wait();
+    return hipMemcpy(out.host, src, bytes, hipMemcpyDeviceToHost);
 }
 // the slot's payload buffer, carved up for the stock path's kernels: sizes are asked for first, then the buffer is grown once
 struct DevArena {
@@ -1290,7 +1294,7 @@ int stock_encode_interp(SlabJob &j) {
     return 0;
 }
 // the main code stream of a stock container onto the device: tree, bits -> codes (the device's self-synchronising decoder, the host walk
-// behind it). What stock_decompress_interp / _lorenzo_reg spell out in place, as a helper for the readers added in round 5.
+// behind it), for the three stock readers. Codes that were made on the host are on the device when stock_huff_run returns.
 struct StockHuffDev {
     uint16_t *d_em;
     uint8_t *d_bits, *d_t;
@@ -1351,7 +1355,7 @@ static int stock_huff_run(HostSlot *s, const StockHuffDev &h, const stock::Tree 
     return 0;
 }
 // A stock ALGO_NOPRED stream (SZDispatcher.hpp:92-93 -> api/impl/SZAlgoNopred.hpp:26-34): quantizer, tree, codes — value = recover(0, code)
-int stock_decompress_nopred(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, void *decData) {
+int stock_decompress_nopred(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, DecodeOut &out) {
     const int cdt = dtype_compute(dataType);
     const size_t tsize = cdt == SZ3HIP_FLOAT ? 4 : 8;
     if (payload < 8) return fail(SZ3HIP_EFORMAT, "truncated payload");
@@ -1389,7 +1393,7 @@ int stock_decompress_nopred(HostSlot *s, const sz3hip_config *conf, int dataType
     HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     if (bad) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (more zero codes than unpredictable values)");
-    HIPCHK(d2h_out(decData, s->dev_in, (size_t)conf->num * tsize));
+    HIPCHK(d2h_out(out, s->dev_in, (size_t)conf->num * tsize));
     return 0;
 }
 // ... and WRITTEN (sz3hip_set_stock_format + cmprAlgo ALGO_NOPRED)
@@ -1733,7 +1737,7 @@ int stock_encode_lorenzo_reg(SlabJob &j) {
     }
     return 0;
 }
-int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, void *decData) {
+int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, DecodeOut &out) {
     const int cdt = dtype_compute(dataType);
     const size_t tsize = cdt == SZ3HIP_FLOAT ? 4 : 8;
     if (payload < 8) return fail(SZ3HIP_EFORMAT, "truncated payload");
@@ -1758,23 +1762,20 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
     HIPCHK(hipSetDevice(s->device));
     int rc;
     if ((rc = slot_ctx(s, conf->num))) return rc;
-    const szi_partial *part = t_partial;
+    const szi_partial *part = out.part;
     const size_t out_bytes = (size_t)szi_partial_num(part, conf) * tsize;
-    void *dst = part && t_devout->view.contig ? (void *)t_devout->ptr : nullptr;  // (a partial decode's contiguous output is written where it lies)
+    void *dst = part && out.in_place() ? (void *)out.dev : nullptr;  // (a partial decode's contiguous output is written where it lies)
     if (!dst) {
         if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, out_bytes))) return rc;
         dst = s->dev_in;
     }
     const uint64_t ntiles_z = (n + 1023) / 1024;
-    const uint64_t nsub = (bit_bytes * 8 + 4095) / 4096;
-    const uint32_t nc = (uint32_t)tr.t.size();
-    uint16_t *d_em;
-    uint8_t *d_unpred, *d_vval, *d_bits, *d_t;
-    uint64_t *d_vidx, *d_tile_base, *d_blk, *d_start, *d_last, *d_next, *d_base;
-    uint32_t *d_tile_cnt, *d_bad, *d_L, *d_R, *d_lut, *d_count, *d_flags;
-    int32_t *d_C;
+    StockHuffDev hd;
+    uint8_t *d_unpred, *d_vval;
+    uint64_t *d_vidx, *d_tile_base, *d_blk;
+    uint32_t *d_tile_cnt, *d_bad;
     DevArena ar;
-    ar.ask(&d_em, (size_t)n * 2);
+    stock_huff_ask(ar, hd, n, bit_bytes, (uint32_t)tr.t.size());
     ar.ask(&d_unpred, (size_t)n_unpred * tsize + 8);
     ar.ask(&d_vval, (size_t)n_unpred * tsize + 8);
     ar.ask(&d_vidx, (size_t)n_unpred * 8 + 8);
@@ -1782,54 +1783,13 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
     ar.ask(&d_tile_base, (size_t)(ntiles_z + 1) * 8);
     ar.ask(&d_blk, bb.size() * 8 + 8);
     ar.ask(&d_bad, 64);
-    ar.ask(&d_bits, (size_t)bit_bytes + 16);
-    ar.ask(&d_L, (size_t)nc * 4);
-    ar.ask(&d_R, (size_t)nc * 4);
-    ar.ask(&d_C, (size_t)nc * 4);
-    ar.ask(&d_t, nc);
-    ar.ask(&d_lut, 4096 * 4);
-    ar.ask(&d_start, (size_t)(nsub + 2) * 8);
-    ar.ask(&d_last, (size_t)(nsub + 2) * 8);
-    ar.ask(&d_next, (size_t)(nsub + 2) * 8);
-    ar.ask(&d_base, (size_t)(nsub + 2) * 8);
-    ar.ask(&d_count, (size_t)(nsub + 2) * 4);
-    ar.ask(&d_flags, 64);
     if (ar.commit(s)) return SZ3HIP_EHIP;
     HIPCHK(hipMemcpyAsync(d_blk, bb.data(), bb.size() * 8, hipMemcpyHostToDevice, s->stream));
     if (n_unpred) HIPCHK(hipMemcpyAsync(d_unpred, unpred, (size_t)n_unpred * tsize, hipMemcpyHostToDevice, s->stream));
-    std::vector<uint16_t> em_host;
-    if (tr.t[0]) {  // a single symbol: no bits at all (encoder/HuffmanEncoder.hpp:233-237)
-        const int32_t v = tr.C[0] + offset;
-        if (v < 0 || v > 65535) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (symbol)");
-        em_host.assign((size_t)n, (uint16_t)v);
-        HIPCHK(hipMemcpyAsync(d_em, em_host.data(), (size_t)n * 2, hipMemcpyHostToDevice, s->stream));
-    } else if (stock_host_huffman()) {
-        em_host.resize((size_t)n);
-        if (!stock::host_decode(tr, offset, bits, (size_t)bit_bytes, n, em_host.data())) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
-        HIPCHK(hipMemcpyAsync(d_em, em_host.data(), (size_t)n * 2, hipMemcpyHostToDevice, s->stream));
-    } else {
-        std::vector<uint32_t> lut;
-        stock::make_lut(tr, lut);
-        HIPCHK(hipMemsetAsync(d_bits + (bit_bytes & ~(uint64_t)3), 0, 16, s->stream));  // (the last word's tail reads as zeros)
-        HIPCHK(hipMemcpyAsync(d_bits, bits, (size_t)bit_bytes, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_L, tr.L.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_R, tr.R.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_C, tr.C.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_t, tr.t.data(), nc, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_lut, lut.data(), 4096 * 4, hipMemcpyHostToDevice, s->stream));
-        szk_stock_tree_dev td{d_L, d_R, d_C, d_t, d_lut, nc, offset};
-        int passes = 0;
-        const int rd = szk_launch_stock_huff_decode(&td, (const uint32_t *)d_bits, bit_bytes, n, d_start, d_last, d_next, d_base, d_count, d_flags, d_em, &passes, s->stream);
-        if (rd == -4) {  // the restart points did not settle within the pass cap: the bit-serial walk on the host
-            em_host.resize((size_t)n);
-            if (!stock::host_decode(tr, offset, bits, (size_t)bit_bytes, n, em_host.data())) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
-            HIPCHK(hipMemcpyAsync(d_em, em_host.data(), (size_t)n * 2, hipMemcpyHostToDevice, s->stream));
-        } else if (rd == -3) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
-        else if (rd) return fail(SZ3HIP_EHIP, "stock stream: device Huffman decoder failed (%d)", rd);
-    }
-    rc = szi_stock_import(s->ctx, &sp, &g, d_blk, d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, d_vidx, d_vval, d_bad, dst, s->stream, part);
+    if ((rc = stock_huff_run(s, hd, tr, offset, bits, bit_bytes, n))) return rc;
+    rc = szi_stock_import(s->ctx, &sp, &g, d_blk, hd.d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, d_vidx, d_vval, d_bad, dst, s->stream, part);
     if (rc) return rc;
-    HIPCHK(d2h_out(decData, dst, out_bytes));
+    HIPCHK(d2h_out(out, dst, out_bytes));
     return 0;
 }
 
@@ -1904,7 +1864,7 @@ static bool slr_coefficients(const sz3hip_config *conf, const stock::LorenzoReg 
     }
     return true;
 }
-int stock_decompress_lorenzo_reg(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, void *decData) {
+int stock_decompress_lorenzo_reg(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, DecodeOut &out) {
     const int cdt = dtype_compute(dataType);
     const size_t tsize = cdt == SZ3HIP_FLOAT ? 4 : 8;
     const int N = conf->N;
@@ -1952,16 +1912,13 @@ int stock_decompress_lorenzo_reg(HostSlot *s, const sz3hip_config *conf, int dat
     int rc;
     if ((rc = slot_ctx(s, conf->num))) return rc;
     if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, (size_t)conf->num * tsize))) return rc;
-    const uint64_t n = lr.n, bit_bytes = lr.bit_bytes;
-    const uint64_t ntiles_z = (n + 1023) / 1024, nsub = (bit_bytes * 8 + 4095) / 4096;
-    const uint32_t nc = (uint32_t)lr.tree.t.size();
-    uint16_t *d_em;
-    uint8_t *d_unpred, *d_bits, *d_t, *d_kind, *d_coef;
-    uint64_t *d_tile_base, *d_start, *d_last, *d_next, *d_base;
-    uint32_t *d_tile_cnt, *d_bad, *d_L, *d_R, *d_lut, *d_count, *d_flags;
-    int32_t *d_C;
+    const uint64_t n = lr.n, ntiles_z = (n + 1023) / 1024;
+    StockHuffDev hd;
+    uint8_t *d_unpred, *d_kind, *d_coef;
+    uint64_t *d_tile_base;
+    uint32_t *d_tile_cnt, *d_bad;
     DevArena ar;
-    ar.ask(&d_em, (size_t)n * 2 + 2048);
+    stock_huff_ask(ar, hd, n, lr.bit_bytes, (uint32_t)lr.tree.t.size());
     ar.ask(&d_unpred, (size_t)lr.q.n_unpred * tsize + 8);
     ar.ask(&d_kind, (size_t)nblocks + 8);
     const size_t CS = N == 4 ? 8 : 4;
@@ -1969,64 +1926,23 @@ int stock_decompress_lorenzo_reg(HostSlot *s, const sz3hip_config *conf, int dat
     ar.ask(&d_tile_cnt, (size_t)ntiles_z * 4 + 8);
     ar.ask(&d_tile_base, (size_t)(ntiles_z + 1) * 8);
     ar.ask(&d_bad, 64);
-    ar.ask(&d_bits, (size_t)bit_bytes + 16);
-    ar.ask(&d_L, (size_t)nc * 4);
-    ar.ask(&d_R, (size_t)nc * 4);
-    ar.ask(&d_C, (size_t)nc * 4);
-    ar.ask(&d_t, nc);
-    ar.ask(&d_lut, 4096 * 4);
-    ar.ask(&d_start, (size_t)(nsub + 2) * 8);
-    ar.ask(&d_last, (size_t)(nsub + 2) * 8);
-    ar.ask(&d_next, (size_t)(nsub + 2) * 8);
-    ar.ask(&d_base, (size_t)(nsub + 2) * 8);
-    ar.ask(&d_count, (size_t)(nsub + 2) * 4);
-    ar.ask(&d_flags, 64);
     if (ar.commit(s)) return SZ3HIP_EHIP;
     HIPCHK(hipMemsetAsync(d_bad, 0, 64, s->stream));
     HIPCHK(hipMemcpyAsync(d_kind, kind.data(), (size_t)nblocks, hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipMemcpyAsync(d_coef, cdt == SZ3HIP_FLOAT ? (const void *)cf32.data() : (const void *)cf64.data(), (size_t)nblocks * CS * tsize, hipMemcpyHostToDevice, s->stream));
     if (lr.q.n_unpred) HIPCHK(hipMemcpyAsync(d_unpred, lr.q.unpred, (size_t)lr.q.n_unpred * tsize, hipMemcpyHostToDevice, s->stream));
-    std::vector<uint16_t> em_host;
-    if (lr.tree.t[0]) {  // a single symbol: no bits at all (encoder/HuffmanEncoder.hpp:233-237)
-        const int32_t v = lr.tree.C[0] + lr.offset;
-        if (v < 0 || v > 65535) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (symbol)");
-        em_host.assign((size_t)n, (uint16_t)v);
-        HIPCHK(hipMemcpyAsync(d_em, em_host.data(), (size_t)n * 2, hipMemcpyHostToDevice, s->stream));
-    } else if (stock_host_huffman()) {
-        em_host.resize((size_t)n);
-        if (!stock::host_decode(lr.tree, lr.offset, lr.bits, (size_t)bit_bytes, n, em_host.data())) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
-        HIPCHK(hipMemcpyAsync(d_em, em_host.data(), (size_t)n * 2, hipMemcpyHostToDevice, s->stream));
-    } else {
-        std::vector<uint32_t> lut;
-        stock::make_lut(lr.tree, lut);
-        HIPCHK(hipMemsetAsync(d_bits + (bit_bytes & ~(uint64_t)3), 0, 16, s->stream));  // (the last word's tail reads as zeros)
-        HIPCHK(hipMemcpyAsync(d_bits, lr.bits, (size_t)bit_bytes, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_L, lr.tree.L.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_R, lr.tree.R.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_C, lr.tree.C.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_t, lr.tree.t.data(), nc, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipMemcpyAsync(d_lut, lut.data(), 4096 * 4, hipMemcpyHostToDevice, s->stream));
-        szk_stock_tree_dev td{d_L, d_R, d_C, d_t, d_lut, nc, lr.offset};
-        int passes = 0;
-        const int rd = szk_launch_stock_huff_decode(&td, (const uint32_t *)d_bits, bit_bytes, n, d_start, d_last, d_next, d_base, d_count, d_flags, d_em, &passes, s->stream);
-        if (rd == -4) {  // the restart points did not settle within the pass cap: the bit-serial walk on the host
-            em_host.resize((size_t)n);
-            if (!stock::host_decode(lr.tree, lr.offset, lr.bits, (size_t)bit_bytes, n, em_host.data())) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
-            HIPCHK(hipMemcpyAsync(d_em, em_host.data(), (size_t)n * 2, hipMemcpyHostToDevice, s->stream));
-        } else if (rd == -3) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
-        else if (rd) return fail(SZ3HIP_EHIP, "stock stream: device Huffman decoder failed (%d)", rd);
-    }
+    if ((rc = stock_huff_run(s, hd, lr.tree, lr.offset, lr.bits, lr.bit_bytes, n))) return rc;
     if (N == 1 && !env_int("SZ3HIP_STOCK_1D_ON_DEVICE", 0)) {
-        // a 1-D array is one chain of roundings: walked on the host over the codes the device decoded (sz3hip_stock_host.cpp,
-        // lorenzo_reg_read_1d; SZ3HIP_STOCK_1D_ON_DEVICE=1 keeps round 4's one-lane kernel, k_slr_chain, for comparison)
+        // a 1-D array is one chain of roundings: walked on the host over the codes the device decoded, into the host destination
+        // (sz3hip_stock_host.cpp, lorenzo_reg_read_1d; SZ3HIP_STOCK_1D_ON_DEVICE=1 keeps round 4's one-lane kernel, k_slr_chain, for comparison)
         std::vector<uint16_t> em((size_t)n);
-        HIPCHK(hipMemcpyAsync(em.data(), d_em, (size_t)n * 2, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(em.data(), hd.d_em, (size_t)n * 2, hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
         const bool okw = cdt == SZ3HIP_FLOAT
                              ? stock::lorenzo_reg_read_1d<float>(n, B, lr.q.eb, lr.q.radius, em.data(), kind.data(), cf32.data(), reinterpret_cast<const float *>(lr.q.unpred),
-                                                                 lr.q.n_unpred, reinterpret_cast<float *>(decData))
+                                                                 lr.q.n_unpred, reinterpret_cast<float *>(out.host))
                              : stock::lorenzo_reg_read_1d<double>(n, B, lr.q.eb, lr.q.radius, em.data(), kind.data(), cf64.data(), reinterpret_cast<const double *>(lr.q.unpred),
-                                                                  lr.q.n_unpred, reinterpret_cast<double *>(decData));
+                                                                  lr.q.n_unpred, reinterpret_cast<double *>(out.host));
         if (!okw) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (more zero codes than unpredictable values)");
         return 0;
     }
@@ -2042,7 +1958,7 @@ int stock_decompress_lorenzo_reg(HostSlot *s, const sz3hip_config *conf, int dat
     sp.nbw = (uint32_t)nb4[0];
     sp.eb = lr.q.eb;
     sp.radius = (uint32_t)lr.q.radius;
-    sp.codes = d_em;
+    sp.codes = hd.d_em;
     sp.kind = d_kind;
     sp.coef = d_coef;
     sp.unpred = d_unpred;
@@ -2055,7 +1971,7 @@ int stock_decompress_lorenzo_reg(HostSlot *s, const sz3hip_config *conf, int dat
     HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     if (bad) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (more zero codes than unpredictable values)");
-    HIPCHK(d2h_out(decData, s->dev_in, (size_t)conf->num * tsize));
+    HIPCHK(d2h_out(out, s->dev_in, (size_t)conf->num * tsize));
     return 0;
 }
 
@@ -2566,11 +2482,8 @@ size_t compress_impl(const sz3hip_config *config, int dataType, const void *data
     const size_t payload_cap = cmpCap - 16 - 2 * sz3hip_config_save(&conf, tmp);
     size_t payload_size = 0;
 
-    std::unique_lock<std::shared_mutex> all(g_host_mu, std::defer_lock);
-    std::shared_lock<std::shared_mutex> some(g_host_mu, std::defer_lock);
     const int pieces = g_stock_format.load() > 0 ? 0 : piece_count(conf, dataType);
-    if (conf.openmp || pieces) all.lock();
-    else some.lock();
+    HostLock lock(conf.openmp || pieces);
     DeviceGuard guard;
     if (conf.openmp) {  // SZ_compress_impl, api/impl/SZImpl.hpp:10-20
         payload_size = compress_slabs(conf, dataType, data, dev, w.p, payload_cap);
@@ -2706,7 +2619,7 @@ extern "C" size_t sz3hip_compress_from_device(const sz3hip_config *config, int d
 }
 
 namespace {
-int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, void *decData);
+int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, DecodeOut &out);
 }
 // What ONE algorithm of the reference's dispatcher does (SZ_compress_LorenzoReg / SZ_compress_Interp ... and their
 // SZ_decompress_* counterparts, api/impl/SZDispatcher.hpp:28-42, 89-99): the bytes between the 16-byte header and the
@@ -2743,7 +2656,8 @@ extern "C" int sz3hip_decompress_blob(const sz3hip_config *conf, int dataType, c
     std::shared_lock<std::shared_mutex> lock(g_host_mu);
     DeviceGuard guard;
     SlotLease lease(host_device(), dtype_compute(dataType));
-    return decompress_blob(lease.s, conf, dataType, reinterpret_cast<const unsigned char *>(blob), size, decData);
+    DecodeOut out(decData);
+    return decompress_blob(lease.s, conf, dataType, reinterpret_cast<const unsigned char *>(blob), size, out);
 }
 
 // one process per GPU: this rank's slab of SZ_compress_OMP, the exchanges through the rank communicator
@@ -2930,8 +2844,9 @@ extern "C" int sz3hip_peek_config(sz3hip_config *conf, const char *cmpData, size
 
 namespace {
 // SZ_decompress_dispatcher (api/impl/SZDispatcher.hpp:79-100) for one blob: `payload` bytes at p, conf = the Config that
-// describes it, decData receives conf->num elements of dataType
-int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, void *decData) {
+// describes it, `out` receives conf->num elements of dataType (the points of out.part: floating-point streams of the interpolation
+// predictor only; integer output is decoded in full). ALGO_LOSSLESS and the stock 1-D chain write out.host themselves.
+int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, DecodeOut &out) {
     const bool is_int = dtype_is_int(dataType);
     const int cdt = dtype_compute(dataType);
     const size_t es = dtype_size(dataType);
@@ -2945,14 +2860,14 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
         uint64_t len = 0;
         if (payload >= 8) memcpy(&len, p, 8);
         if (len != raw_bytes) return fail(SZ3HIP_EFORMAT, "Decompressed data size does not match the original data size");
-        return zs::decompress_frames(p, payload, (uint8_t *)decData, raw_bytes) == raw_bytes ? 0 : SZ3HIP_EZSTD;
+        return zs::decompress_frames(p, payload, (uint8_t *)out.host, raw_bytes) == raw_bytes ? 0 : SZ3HIP_EZSTD;
     }
     if (conf->cmprAlgo == SZ3HIP_ALGO_INTERP && !is_int)  // a stock SZ3 stream of the interpolation compressor (SZDispatcher.hpp:89-91)
-        return stock_decompress_interp(s, conf, dataType, p, payload, decData);
+        return stock_decompress_interp(s, conf, dataType, p, payload, out);
     if (conf->cmprAlgo == SZ3HIP_ALGO_LORENZO_REG && !is_int)  // ... of the Lorenzo / regression compressor (:85-88)
-        return stock_decompress_lorenzo_reg(s, conf, dataType, p, payload, decData);
+        return stock_decompress_lorenzo_reg(s, conf, dataType, p, payload, out);
     if (conf->cmprAlgo == SZ3HIP_ALGO_NOPRED && !is_int)  // ... of the no-prediction compressor (:92-93)
-        return stock_decompress_nopred(s, conf, dataType, p, payload, decData);
+        return stock_decompress_nopred(s, conf, dataType, p, payload, out);
     if (conf->cmprAlgo != SZ3HIP_ALGO_HIP_LORENZO && conf->cmprAlgo != SZ3HIP_ALGO_HIP_INTERP)
         return fail(SZ3HIP_EUNSUPPORTED,
                     "stream uses cmprAlgo %d of the CPU reference; this library decodes its own GPU streams (ids %d, %d), stock ALGO_INTERP / "
@@ -2967,7 +2882,7 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
     int rc;
     if ((rc = ensure_pin(s, raw_len))) return rc;
     if (zs::decompress_frames(p, payload, (uint8_t *)s->pin, raw_len) != raw_len) return SZ3HIP_EZSTD;
-    stamp(0);
+    stamp(out, 0);
     // the SZH1 header is authoritative for the GPU streams: element count and type are checked before anything is launched
     szh_header hdr;
     memcpy(&hdr, s->pin, sizeof(hdr));
@@ -2980,64 +2895,58 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
         return fail(SZ3HIP_EINVAL, "the stream holds %s data but %s output was requested", dtype_is_int(conf->dataType) ? "integer" : "floating-point",
                     is_int ? "integer" : "floating-point");
     if ((rc = slot_ctx(s, conf->num))) return rc;
-    const szi_partial *part = is_int ? nullptr : t_partial;
+    const szi_partial *part = is_int ? nullptr : out.part;
     if (part && hdr.predictor != 1) return fail(SZ3HIP_EFORMAT, "the Config names the interpolation stream but the payload's predictor id is %d", (int)hdr.predictor);
     if (part && part->kind == SZI_BOX && hdr.ndim != (uint32_t)conf->N) return fail(SZ3HIP_EFORMAT, "the payload's extent count does not match the Config");
     const size_t cbytes = (size_t)szi_partial_num(part, conf) * (cdt == SZ3HIP_FLOAT ? 4 : 8);
     // (a device call's contiguous f32 / f64 array is decoded where it lies)
-    void *dst = t_devout && t_devout->view.contig && !is_int ? (void *)t_devout->ptr : nullptr;
+    void *dst = out.in_place() && !is_int ? (void *)out.dev : nullptr;
     if (!dst) {
         if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, cbytes))) return rc;
         dst = s->dev_in;
     }
     if ((rc = ensure_dev(&s->dev_payload, &s->dev_payload_bytes, std::max<size_t>(raw_len + 64, is_int ? raw_bytes : 0)))) return rc;
     HIPCHK(hipMemcpy(s->dev_payload, s->pin, raw_len, hipMemcpyHostToDevice));
-    stamp(1);
+    stamp(out, 1);
     rc = szi_decompress_device_partial(s->ctx, s->dev_payload, raw_len, part, dst, s->stream);
     if (rc) return rc;
     if (!is_int) {
         HIPCHK(hipStreamSynchronize(s->stream));
-        stamp(2);
-        HIPCHK(d2h_out(decData, dst, part ? cbytes : raw_bytes));
-    } else if (t_devout) {  // (narrowed straight into the caller's view)
-        t_devout->delivered = true;
-        if (szk_launch_scatter(dataType, 1, s->dev_in, t_devout->ptr, &t_devout->view, s->stream)) return fail(SZ3HIP_EHIP, "integer narrowing kernel failed");
+        stamp(out, 2);
+        HIPCHK(d2h_out(out, dst, part ? cbytes : raw_bytes));
+    } else if (out.dev) {  // (narrowed straight into the caller's view)
+        out.delivered = true;
+        if (szk_launch_scatter(dataType, 1, s->dev_in, out.dev, &out.view, s->stream)) return fail(SZ3HIP_EHIP, "integer narrowing kernel failed");
         HIPCHK(hipStreamSynchronize(s->stream));
     } else {
         rc = szk_launch_f64_to_int(dataType, (const double *)s->dev_in, conf->num, s->dev_payload, s->stream);
         if (rc) return fail(SZ3HIP_EHIP, "integer narrowing kernel failed");
         HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(d2h_out(decData, s->dev_payload, raw_bytes));
+        HIPCHK(d2h_out(out, s->dev_payload, raw_bytes));
     }
     return 0;
 }
 
-// One blob to the host array at host_dst, or (dev) to rows [lo, hi) of the caller's device array
-int decode_blob_to(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, void *host_dst, const DevArray *dev, uint64_t lo,
+// One blob to the host array o.host, or (dev) to rows [lo, hi) of the caller's device array (o: this call's own copy, made the device variant here)
+int decode_blob_to(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, DecodeOut o, const DevArray *dev, uint64_t lo,
                    uint64_t hi) {
-    if (!dev) return decompress_blob(s, conf, dataType, p, payload, host_dst);
+    if (!dev) return decompress_blob(s, conf, dataType, p, payload, o);
     HIPCHK(hipSetDevice(s->device));
     if (!s->stream) HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     const size_t bytes = (size_t)conf->num * dtype_size(dataType);
-    DevOut o;
-    o.ptr = dev->slab(lo, hi, dtype_size(dataType), &o.view);
-    o.dataType = dataType;
-    o.stream = s->stream;
     // the paths that write the array on the host write it here (malloc: pages nobody touches cost nothing)
     std::unique_ptr<uint8_t, void (*)(void *)> h((uint8_t *)malloc(std::max<size_t>(bytes, 1)), free);
     if (!h) return fail(SZ3HIP_EHIP, "out of host memory (%zu bytes)", bytes);
-    int rc;
-    {
-        DevOutScope scope(&o);
-        rc = decompress_blob(s, conf, dataType, p, payload, h.get());
-    }
+    o.host = h.get();
+    o.to_rows(*dev, lo, hi, dataType, s->stream);
+    int rc = decompress_blob(s, conf, dataType, p, payload, o);
     if (rc || o.delivered) return rc;
     if (o.view.contig) {
-        HIPCHK(hipMemcpyAsync(o.ptr, h.get(), bytes, hipMemcpyHostToDevice, s->stream));
+        HIPCHK(hipMemcpyAsync(o.dev, h.get(), bytes, hipMemcpyHostToDevice, s->stream));
     } else {
         if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, bytes))) return rc;
         HIPCHK(hipMemcpyAsync(s->dev_in, h.get(), bytes, hipMemcpyHostToDevice, s->stream));
-        if (szk_launch_scatter(dataType, 0, s->dev_in, o.ptr, &o.view, s->stream)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
+        if (szk_launch_scatter(dataType, 0, s->dev_in, o.dev, &o.view, s->stream)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
     }
     HIPCHK(hipStreamSynchronize(s->stream));
     return 0;
@@ -3103,17 +3012,16 @@ int decompress_slabs(const sz3hip_config *conf, int dataType, const unsigned cha
             gt.cv = &cv;
         }
         auto piece = [&](int g) {
-            t_gate = dev ? nullptr : &gates[g];  // (a device call's pieces write their own rows: nothing for this thread to copy)
-            if (timing) {
-                t_stamps = &stamps[(size_t)g * 5];
-                t_stamp0 = t_call;
-            }
             uint64_t lo, hi;
             slab_range(*conf, G, g, &lo, &hi);
-            rcs[g] = decode_blob_to(slots[g], &ct[g], dataType, blobs + start[g], (size_t)size[g], decData ? (unsigned char *)decData + lo * base * es : nullptr, dev, lo, hi);
+            DecodeOut out(decData ? (unsigned char *)decData + lo * base * es : nullptr);
+            out.gate = dev ? nullptr : &gates[g];  // (a device call's pieces write their own rows: nothing for this thread to copy)
+            if (timing) {
+                out.stamps = &stamps[(size_t)g * 5];
+                out.stamp0 = t_call;
+            }
+            rcs[g] = decode_blob_to(slots[g], &ct[g], dataType, blobs + start[g], (size_t)size[g], out, dev, lo, hi);
             if (rcs[g]) errs[g] = sz3hip_last_error();
-            t_gate = nullptr;
-            t_stamps = nullptr;
             gates[g].finish();
         };
         std::vector<std::thread> pth;
@@ -3164,7 +3072,7 @@ int decompress_slabs(const sz3hip_config *conf, int dataType, const unsigned cha
         for (int g = t; g < G; g += ndev) {
             uint64_t lo, hi;
             slab_range(*conf, G, g, &lo, &hi);
-            rcs[g] = decode_blob_to(slots[g], &ct[g], dataType, blobs + start[g], (size_t)size[g], decData ? (unsigned char *)decData + lo * base * es : nullptr, dev, lo, hi);
+            rcs[g] = decode_blob_to(slots[g], &ct[g], dataType, blobs + start[g], (size_t)size[g], DecodeOut(decData ? (unsigned char *)decData + lo * base * es : nullptr), dev, lo, hi);
             if (rcs[g]) errs[g] = sz3hip_last_error();
         }
     };
@@ -3196,19 +3104,15 @@ extern "C" int sz3hip_decompress(sz3hip_config *conf, int dataType, const char *
     uint64_t payload;
     memcpy(&payload, p, 8);
     p += 8;
-    std::unique_lock<std::shared_mutex> all(g_host_mu, std::defer_lock);
-    std::shared_lock<std::shared_mutex> some(g_host_mu, std::defer_lock);
-    if (conf->openmp) all.lock();
-    else some.lock();
+    HostLock lock(conf->openmp);
     DeviceGuard guard;
     if (conf->openmp) return decompress_slabs(conf, dataType, p, (size_t)payload, decData, nullptr);  // SZ_decompress_impl, SZImpl.hpp:22-32
     Prefault pf;  // (the output array's pages, populated beside the work below — when the copy out will not go through the staging ring)
     if (!d2h_staging_wanted((size_t)conf->num * dtype_size(dataType))) pf.start(decData, (size_t)conf->num * dtype_size(dataType));
-    t_prefault = &pf;
+    DecodeOut out(decData);
+    out.prefault = &pf;
     SlotLease lease(host_device(), dtype_compute(dataType));
-    const int rcd = decompress_blob(lease.s, conf, dataType, p, (size_t)payload, decData);
-    t_prefault = nullptr;
-    return rcd;
+    return decompress_blob(lease.s, conf, dataType, p, (size_t)payload, out);
 }
 
 extern "C" int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, void *d_out, const int64_t *strides,
@@ -3227,13 +3131,10 @@ extern "C" int sz3hip_decompress_to_device(sz3hip_config *conf, int dataType, co
     DeviceGuard guard;
     HIPCHK(hipSetDevice(dev.device));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (what the caller queued on d_out comes first)
-    std::unique_lock<std::shared_mutex> all(g_host_mu, std::defer_lock);
-    std::shared_lock<std::shared_mutex> some(g_host_mu, std::defer_lock);
-    if (conf->openmp) all.lock();
-    else some.lock();
+    HostLock lock(conf->openmp);
     if (conf->openmp) return decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &dev);
     SlotLease lease(dev.device, dtype_compute(dataType));
-    return decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &dev, 0, conf->dims[0]);
+    return decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, DecodeOut(nullptr), &dev, 0, conf->dims[0]);
 }
 
 // the request's view of the contiguous full array fd: strides multiplied by 2^level, the box's extents; returns the element offset of its corner
@@ -3251,7 +3152,7 @@ static int64_t partial_view(const szi_partial &q, int N, const uint64_t *out_dim
 }
 // The partial decodes of a container (DESIGN.md sections 11 - 13): every 2^level-th point (SZI_COARSE), one box of the array (SZI_BOX at
 // level 0) or of its grid of every 2^level-th point (SZI_BOX; lo / ext are then that grid's coordinates). Fast path: a single
-// interpolation stream, decoded on the compact grid or over the box's windows (decompress_blob / stock_decompress_interp under t_partial).
+// interpolation stream, decoded on the compact grid or over the box's windows (decompress_blob / stock_decompress_interp with DecodeOut::part).
 // Everything else: the full decode into a scratch array of the call, then the strided gather of the request's view of that array.
 // Where the kinds differ:
 //   - the checks' order. Box: dtype in range, integer dtype, level, NULL conf / lo / ext, peek, N, the box against the grid.
@@ -3303,24 +3204,16 @@ static int partial_to_device(const char *who, sz3hip_config *conf, int dataType,
     DeviceGuard guard;
     HIPCHK(hipSetDevice(dev.device));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (what the caller queued on d_out comes first)
-    std::unique_lock<std::shared_mutex> all(g_host_mu, std::defer_lock);
-    std::shared_lock<std::shared_mutex> some(g_host_mu, std::defer_lock);
-    if (conf->openmp) all.lock();
-    else some.lock();
+    HostLock lock(conf->openmp);
     const size_t es = dtype_size(dataType);
     if (!conf->openmp && (conf->cmprAlgo == SZ3HIP_ALGO_HIP_INTERP || conf->cmprAlgo == SZ3HIP_ALGO_INTERP)) {
         SlotLease lease(dev.device, dtype_compute(dataType));
         HostSlot *s = lease.s;
         if (!s->stream) HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        DevOut o;
-        o.ptr = dev.ptr;
-        o.view = dev.view;
-        o.dataType = dataType;
-        o.stream = s->stream;
-        {
-            DevOutScope scope(&o, &q);
-            rc = decompress_blob(s, conf, dataType, p, (size_t)payload, nullptr);
-        }
+        DecodeOut o(nullptr);  // (no host destination: the interpolation streams' decoders deliver into the view or fail)
+        o.to_rows(dev, 0, oc.dims[0], dataType, s->stream);
+        o.part = &q;
+        rc = decompress_blob(s, conf, dataType, p, (size_t)payload, o);
         if (!box || rc != SZ3HIP_EUNSUPPORTED) {
             if (rc) return rc;
             if (!o.delivered) return fail(SZ3HIP_EHIP, "the %s decode did not deliver its array", what);
@@ -3344,7 +3237,7 @@ static int partial_to_device(const char *who, sz3hip_config *conf, int dataType,
     if (conf->openmp) rc = decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &fd);
     else {
         SlotLease lease(dev.device, dtype_compute(dataType));
-        rc = decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, nullptr, &fd, 0, conf->dims[0]);
+        rc = decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, DecodeOut(nullptr), &fd, 0, conf->dims[0]);
     }
     if (rc) return rc;
     szk_view gv;
