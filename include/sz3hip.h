@@ -466,6 +466,10 @@ int sz3hip_debug_decode_info(sz3hip_ctx *ctx, uint32_t *out4);
 void sz3hip_debug_force_generic(int on);
 /* development switches (bit mask, process-wide; 0 = product behaviour): an OR of enum sz3hip_dbg, sz3hip_debug.h, which says what each bit gates */
 void sz3hip_debug_flags(int flags);
+/* The second word of development switches: an OR of enum sz3hip_dbg2 (include/sz3hip_debug.h). */
+void sz3hip_debug_flags2(int flags);
+/* Launches the encoder of the last stage 2 enqueued in this process, from the bits / segment pass to the packer (for tests). */
+int sz3hip_last_encode_launches(void);
 
 /* ---- (4) multi-GPU exchange over RCCL / xGMI ------------------------------------------------------------------- */
 typedef struct sz3hip_comm sz3hip_comm;

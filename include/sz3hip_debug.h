@@ -92,4 +92,9 @@ enum sz3hip_dbg {
     SZ3HIP_DBG_BLK_NO_SELECT = -2147483647 - 1 /* blk_all_lorenzo: no selection pass, the fit pass chooses by its own wave sums */
 };
 
+/* The second word, sz3hip_debug_flags2(): one bit, one meaning. 0 in production. */
+enum sz3hip_dbg2 {
+    SZ3HIP_DBG2_PACK_SCAN_LAUNCH = 1       /* szk_launch_encode: the offset scan of the sampled stage 2 in a launch of its own (k_scan_groups) where k_pack_b would scan the groups' sums itself */
+};
+
 #endif

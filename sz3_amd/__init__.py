@@ -80,6 +80,12 @@ class Dbg(enum.IntFlag):
     BLK_NO_SELECT = 2147483648
 
 
+class Dbg2(enum.IntFlag):
+    """The second word of development switches (sz3hip_debug_flags2): enum sz3hip_dbg2 of include/sz3hip_debug.h without the
+    SZ3HIP_DBG2_ prefix, same values. One bit, one meaning."""
+    PACK_SCAN_LAUNCH = 1
+
+
 class SZ3HipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("sz3hip error %d: %s" % (code, msg))
@@ -360,6 +366,22 @@ def debug_flags(flags):
         yield
     finally:
         L.sz3hip_debug_flags(0)
+
+
+@contextlib.contextmanager
+def debug_flags2(flags):
+    """``with sz3_amd.debug_flags2(Dbg2.X):`` the same for the second word of switches (sz3hip_debug_flags2)."""
+    L = lib()
+    L.sz3hip_debug_flags2(int(flags))
+    try:
+        yield
+    finally:
+        L.sz3hip_debug_flags2(0)
+
+
+def last_encode_launches():
+    """launches the encoder of the last stage 2 enqueued, the packer's included (sz3hip_last_encode_launches)"""
+    return int(lib().sz3hip_last_encode_launches())
 
 
 _SZ_TYPES = {"float32": 0, "float64": 1, "uint8": 2, "int8": 3, "uint16": 4, "int16": 5, "uint32": 6, "int32": 7, "uint64": 8, "int64": 9}

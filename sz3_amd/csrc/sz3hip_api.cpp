@@ -1808,6 +1808,7 @@ static int stage2_launch(sz3hip_ctx *ctx, void *d_payload, size_t cap, hipStream
     if (how == S2_SAMPLED) {  // the book is in its slot (stage 1 built it): the packer's launch carries the two sort roles, nothing else
         er.roles = 1;
         er.no_book = 1;
+        er.sampled = 1;
         er.hist = ctx->d_hist;
         er.cb = &cb;
         er.used_lens = ctx->bk[used].lens;
@@ -2477,6 +2478,8 @@ extern "C" void sz3hip_debug_flags(int flags) {
     szk_interp_novec = (flags & SZ3HIP_DBG_INTERP_NO_VEC) != 0;  // interpolation without the 8-wide level-1 kernels and without the level kernels
     szk_interp_min_blocks = (flags & SZ3HIP_DBG_INTERP_LEVELS_ANY_SIZE) ? 1 : 256;  // level kernels whatever the array's size
 }
+extern "C" void sz3hip_debug_flags2(int flags) { szk_dbg_flags2 = flags; }
+extern "C" int sz3hip_last_encode_launches(void) { return szk_encode_launches; }
 extern "C" int sz3hip_debug_codebook_info(sz3hip_ctx *ctx, uint64_t *out16) {
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipDeviceSynchronize());

@@ -214,6 +214,7 @@ struct szk_merge_args {         // what the merge launch needs of a fused stage 
 struct szk_encode_roles {
     int roles;                  // the packer's launch carries the book role (this call's code book + the verdict) and the two sort roles
     int no_book;                // ... the sort roles only: the book is built elsewhere (wide alphabets: k_codebook<1> on the side stream)
+    int sampled;                // the sampled stage 2: the book is stage 1's, nothing rides in the scan's launch (k_pack_b may scan the offsets itself)
     const uint64_t *hist;
     const szk_cb_params *cb;    // this call's book: fresh slot, part_hint = 0, range words ready
     const uint8_t *used_lens;   // code lengths of the book the packer runs with
@@ -594,5 +595,7 @@ int szk_launch_reconstruct_half(const uint8_t *payload, const szh_header *h, con
 void szk_host_offsets(const szh_header *h, szh_offsets *o);
 extern int szk_force_generic;
 extern int szk_dbg_flags;
+extern int szk_dbg_flags2;       // sz3hip_debug_flags2(): an OR of enum sz3hip_dbg2
+extern int szk_encode_launches;  // launches the last szk_launch_encode enqueued, the packer's included
 
 #endif

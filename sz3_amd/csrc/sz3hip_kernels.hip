@@ -3991,9 +3991,12 @@ __device__ void scan_groups_body(uint16_t *__restrict__ chunk_words, uint64_t n_
 // offset scan, all over the chip: one 16-byte load = 8 segments = 2 chunks per lane (coalesced), 16 consecutive lanes = one
 // group of 32 chunks, summed by a DPP reduction over the row of 16 lanes. *seg_made == 0 (stage 1 ran another form than the
 // host assumed): all counts are zero — the packer's output is thrown away anyway, it only must stay inside the payload.
+// do_layout: no scan launch follows (k_pack_b scans the groups' sums itself) — the payload's layout, which that launch carries, is made
+// here by one thread: layout_pre reads the outlier counts and the alphabet, final since stage 1, and nothing the scan produces.
 __global__ __launch_bounds__(256) void k_seg_chunks(const uint16_t *__restrict__ seg_bits, uint64_t n_segs, const uint32_t *seg_made,
                                                     uint16_t *__restrict__ chunk_words, uint64_t n_chunks, uint32_t *__restrict__ group_sums,
-                                                    uint16_t *__restrict__ sub_bits) {
+                                                    uint16_t *__restrict__ sub_bits, szk_layout_params lp, int do_layout) {
+    if (do_layout && blockIdx.x == 0 && threadIdx.x == 255) layout_pre(lp);
     const bool seg_ok = *seg_made != 0;
     const uint64_t n_vec = (n_segs + 7) / 8;
     const uint64_t n_vec16 = (n_vec + 15) / 16 * 16;  // whole groups
@@ -4165,7 +4168,7 @@ __device__ __forceinline__ uint32_t pack_chunk(const uint16_t (&c)[ENC_PER_LANE]
 // header + side sections (lens, chunk table, outliers) into the payload. Everything it reads is final before the packer
 // starts (outlier counts and alphabet since the code book, chunk table and total since the offset scan), so it runs as a few
 // extra workgroups of the packer's launch instead of a launch of its own.
-__device__ void assemble_body(const szk_asm_params &p, uint64_t tid, uint64_t nth) {
+__device__ void assemble_body(const szk_asm_params &p, uint64_t tid, uint64_t nth, const uint64_t *total_in = nullptr) {  // total_in: the bit stream's words where *p.total_words is written by this very launch
     // (the header and the offsets live in LDS, not in private memory: as locals their arrays went to scratch, and a kernel that
     // uses scratch at all pays for it in every wave — the packer this body rides on ran 213 -> 288 us at C4's slab)
     __shared__ szh_header s_h0, s_h;
@@ -4181,7 +4184,7 @@ __device__ void assemble_body(const szk_asm_params &p, uint64_t tid, uint64_t nt
         szh_header &h = s_h;
         szh_offsets &oo = s_oo;
         h = s_h0;
-        h.bitstream_words = *p.total_words;
+        h.bitstream_words = total_in ? *total_in : *p.total_words;
         szh_compute_offsets(h, oo);
         h.payload_bytes = oo.end;
         *reinterpret_cast<szh_header *>(p.payload) = h;
@@ -4686,10 +4689,20 @@ __device__ __forceinline__ uint32_t packb_chunk(const uint4 &cw, const uint32_t 
     }
     return (total_bits + 31u) >> 5;
 }
+// SCAN (the sampled stage 2 of arrays of at most PB_SCAN_GROUPS offset groups): no k_scan_groups launch in front. The groups' word counts
+// (group_sums, k_seg_chunks' — complete at the kernel boundary) are scanned by EVERY packer workgroup, in LDS and beside the pair-table
+// build (one 16-byte load per thread, wave scans, sixteen wave partials, the two barriers of the table build): the exclusive offsets
+// stay in s_goff as 32-bit words (4096 groups x 32 chunks x 768 words < 2^32) and the unit loop takes a group's offset from there. No
+// workgroup waits for another. The first packer workgroup also writes the offsets and the total to memory (group_off_w, total_w) for
+// launches behind this one; the assembly's first workgroup, which needs the total INSIDE this launch, sums the counts itself.
+#define PB_SCAN_GROUPS 4096u
+template <bool SCAN>
 __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restrict__ codes, uint64_t n, const uint32_t *__restrict__ g_enc,
                                                         const uint16_t *__restrict__ chunk_words, const uint64_t *__restrict__ group_off, szk_mode mode,
                                                         uint32_t sym_add, const szk_state *__restrict__ state, uint8_t *__restrict__ payload,
-                                                        szk_asm_params ap, uint32_t pack_blocks, uint32_t split, szk_role_params rp, uint32_t only_sampled) {
+                                                        szk_asm_params ap, uint32_t pack_blocks, uint32_t split, szk_role_params rp, uint32_t only_sampled,
+                                                        const uint32_t *__restrict__ group_sums, uint32_t n_groups, uint64_t *__restrict__ group_off_w,
+                                                        uint64_t *__restrict__ total_w) {
     constexpr int STAGE_WORDS = SZH_CHUNK_SYMS * SZH_MAX_LEN / 32 + 4;  // one chunk symbol by symbol, + slack for the unconditional second word of an emit
     constexpr uint32_t PB_BATCH = 4;                                    // chunks of a work unit
     constexpr int UNIT_STAGE = PB_BATCH * 128 + 8;                      // 64-bit words: four fast-tier chunks of at most 64 lanes x 128 bits, + the same slack (a multiple of 16 bytes)
@@ -4698,6 +4711,19 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     __shared__ uint32_t s_enc8[256];  // code word by byte value ...
     __shared__ uint8_t s_plen8[256];  // ... and its length
     __shared__ __align__(16) uint64_t s_stage[PB_WAVES][UNIT_STAGE];
+    __shared__ __align__(16) uint32_t s_goff[SCAN ? PB_SCAN_GROUPS : 4u];  // SCAN: the groups' exclusive word offsets
+    __shared__ uint32_t s_gw[PB_WAVES];                                     // ... and the waves' partial sums
+    __shared__ uint64_t s_total;
+    // the thread's four group sums (groups 4 * threadIdx.x ...; zero past the last group: the words behind it are whatever was there)
+    auto load_sums = [&]() -> uint4 {
+        const uint32_t g0 = 4u * threadIdx.x;
+        uint4 q = make_uint4(0u, 0u, 0u, 0u);
+        if (g0 < n_groups) q = *reinterpret_cast<const uint4 *>(group_sums + g0);  // (16-byte aligned, inside the array: szk_launch_encode)
+        q.y = g0 + 1u < n_groups ? q.y : 0u;
+        q.z = g0 + 2u < n_groups ? q.z : 0u;
+        q.w = g0 + 3u < n_groups ? q.w : 0u;
+        return q;
+    };
     // (launched beside k_pack behind the two-launch form of stage 1 — only_sampled: this kernel then packs, sorts and assembles only
     // when the call codes with its sampled book, k_pack otherwise)
     if ((only_sampled & SZK_PACKB_ONLY_SAMPLED) && !(ap.samp_words && ap.samp_words[SZK_SAMP_READY] && szk_is_narrow(mode))) return;
@@ -4714,7 +4740,18 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     const uint32_t asm_blocks = gridDim.x - roles - pack_blocks;
     if (blockIdx.x >= roles + pack_blocks) {
         const uint32_t ab = blockIdx.x - roles - pack_blocks;
-        assemble_body(ap, (uint64_t)ab * PB_THREADS + threadIdx.x, (uint64_t)asm_blocks * PB_THREADS);
+        if (SCAN && ab == 0) {  // (the header's workgroup: the stream's length is the sum of the groups' counts)
+            const uint4 q = load_sums();
+            const uint32_t ws = wave_sum(q.x + q.y + q.z + q.w);
+            if (lane_id() == 0) s_gw[threadIdx.x / WAVE] = ws;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                uint64_t t = 0;
+                for (uint32_t w = 0; w < PB_WAVES; w++) t += s_gw[w];
+                s_total = t;
+            }
+        }
+        assemble_body(ap, (uint64_t)ab * PB_THREADS + threadIdx.x, (uint64_t)asm_blocks * PB_THREADS, SCAN ? &s_total : nullptr);
         if (!ap.lists_by_roles) assemble_lists(ap, (uint64_t)ab * PB_THREADS + threadIdx.x, (uint64_t)asm_blocks * PB_THREADS);
         return;
     }
@@ -4750,7 +4787,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
         uint32_t fr;        // lane < the unit's first chunk in its group: that chunk's words (else unused)
         uint64_t go;        // the group's offset
     };
-    auto load_unit = [&](unit_regs &r, uint64_t u) {  // (u < n_units; n_full >= 1 and n_chunks >= 1: the launch's condition)
+    auto load_unit_mem = [&](unit_regs &r, uint64_t u) {  // (u < n_units; n_full >= 1 and n_chunks >= 1: the launch's condition)
         const uint64_t c_lo = u * PB_BATCH, grp = c_lo / PACK_GROUP;
 #pragma unroll
         for (uint32_t j = 0; j < PB_BATCH; j++) {
@@ -4760,7 +4797,11 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
         }
         const uint64_t ci = grp * PACK_GROUP + (uint32_t)lane;
         r.fr = chunk_words[ci < n_chunks ? ci : n_chunks - 1];
-        r.go = group_off[grp];
+        if (!SCAN) r.go = group_off[grp];
+    };
+    auto load_unit = [&](unit_regs &r, uint64_t u) {
+        load_unit_mem(r, u);
+        if (SCAN) r.go = s_goff[(u * PB_BATCH) / PACK_GROUP];  // (an LDS read, a unit ahead like the loads: no scalar load is outstanding in the loop)
     };
     uint32_t *const stage32 = reinterpret_cast<uint32_t *>(stage);
     uint4 *const stage128 = reinterpret_cast<uint4 *>(stage);
@@ -4810,7 +4851,8 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     auto pack_unit = [&](const unit_regs &r, uint64_t unit) {
         const uint64_t c_lo = unit * PB_BATCH;
         const uint32_t first = (uint32_t)(c_lo % PACK_GROUP);
-        uint32_t *out = out_base + r.go + wave_sum((uint32_t)lane < first ? r.fr : 0u);  // (the unit's last load: the wait is here)
+        const uint64_t go = SCAN ? (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)r.go) : r.go;  // (wave-uniform either way)
+        uint32_t *out = out_base + go + wave_sum((uint32_t)lane < first ? r.fr : 0u);  // (the unit's last load: the wait is here)
         __builtin_amdgcn_sched_barrier(0);
         copy_pending();
         uint32_t staged = 0;
@@ -4850,7 +4892,15 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     };
     uint64_t unit = wave_gid;
     unit_regs ra, rb;
-    load_unit(ra, unit < n_units ? unit : n_units - 1);
+    uint4 gq = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t g_mine = 0, g_incl = 0;
+    if (SCAN) gq = load_sums();
+    load_unit_mem(ra, unit < n_units ? unit : n_units - 1);
+    if (SCAN) {
+        g_mine = gq.x + gq.y + gq.z + gq.w;
+        g_incl = wave_incl_scan(g_mine);
+        if (lane == WAVE - 1) s_gw[wv] = g_incl;
+    }
     // the tables: single symbols by byte value, then the pairs of the window from them
     if (threadIdx.x < 256u) {
         const uint32_t e = g_enc[threadIdx.x != 255u ? threadIdx.x + sym_add : 0u];
@@ -4859,6 +4909,19 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     }
     for (int i = lane; i < UNIT_STAGE; i += WAVE) stage[i] = 0;
     __syncthreads();
+    if (SCAN) {
+        uint32_t run = g_incl - g_mine;
+        for (uint32_t w = 0; w < PB_WAVES; w++) run += w < wv ? s_gw[w] : 0u;
+        const uint4 o = make_uint4(run, run + gq.x, run + gq.x + gq.y, run + gq.x + gq.y + gq.z);
+        reinterpret_cast<uint4 *>(s_goff)[threadIdx.x] = o;
+        if (bid == 0) {
+            const uint32_t g0 = 4u * threadIdx.x, ov[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++)
+                if (g0 + k < n_groups) group_off_w[g0 + k] = ov[k];
+            if (threadIdx.x == PB_THREADS - 1u) *total_w = (uint64_t)run + g_mine;
+        }
+    }
     for (uint32_t i = threadIdx.x; i < 128u * 128u; i += PB_THREADS) {
         const uint32_t i1 = i >> 7, i0 = (i & 127u) ^ i1;        // window indices t & 127 of the first and the second symbol (the table is swizzled: packb_chunk)
         const uint32_t t0 = i0 < 64u ? i0 + 128u : i0, t1 = i1 < 64u ? i1 + 128u : i1;  // byte values in [64, 192)
@@ -4867,6 +4930,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
         s_pair[i] = (l0 && l1 && len <= 27u) ? ((((s_enc8[t0] << l1) | s_enc8[t1]) << 5) | len) : 0u;
     }
     __syncthreads();
+    if (SCAN) ra.go = s_goff[((unit < n_units ? unit : n_units - 1) * PB_BATCH) / PACK_GROUP];
     // two units per trip, the register sets swapping roles: no moves at the back edge, which would need the next unit's codes at once
     while (unit < n_units) {
         uint64_t nu = unit + nwaves;
@@ -4912,7 +4976,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
         const uint32_t before = wave_sum(bp);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
-        uint32_t *out = out_base + group_off[grp] + before;
+        uint32_t *out = out_base + (SCAN ? (uint64_t)s_goff[grp] : group_off[grp]) + before;
         for (uint32_t i = lane; i < nwords; i += WAVE) out[i] = __builtin_bswap32((uint32_t)(stage[i >> 1] >> ((i & 1u) ? 0 : 32)));
     }
 }
@@ -6330,6 +6394,8 @@ int szk_launch_minmax(int dtype, const void *d_in, uint64_t n, double *d_partial
 
 int szk_force_generic = 0;  // test hook: route every shape through the generic kernel
 int szk_dbg_flags = 0;     // sz3hip_debug_flags(): an OR of enum sz3hip_dbg
+int szk_dbg_flags2 = 0;    // sz3hip_debug_flags2(): an OR of enum sz3hip_dbg2
+int szk_encode_launches = 0;
 
 // persistent grid = resident workgroups of the kernel on this device (occupancy API x CU count), capped by the
 // number of hist_partial rows and by the tile count
@@ -6657,16 +6723,6 @@ int szk_launch_encode(const uint16_t *codes, uint64_t n, const uint32_t *d_enc, 
         fp.hist = er->fold_hist;
         fp.range = er->fold_range;
     }
-    const uint16_t *scan_in = nullptr;
-    if (seg_bits) {  // segments -> chunk word counts + group sums, all over the chip; the scan then walks one u32 per group
-        const uint64_t n_segs = (n + 255) / 256;
-        uint32_t *gsums = reinterpret_cast<uint32_t *>(group_off + (n_chunks + PACK_GROUP - 1) / PACK_GROUP + 1);  // behind the offsets (same array)
-        hipLaunchKernelGGL(k_seg_chunks, dim3((uint32_t)std::min<uint64_t>(((n_segs + 7) / 8 + 255) / 256, 1024)), dim3(256), 0, s, seg_bits, n_segs, seg_made,
-                           chunk_words, n_chunks, gsums, sub_bits);
-        scan_in = reinterpret_cast<const uint16_t *>(gsums);
-    }
-    hipLaunchKernelGGL(k_scan_groups, dim3(fp.nrows ? 65 : 1), dim3(1024), 0, s, chunk_words, n_chunks, group_off, total_words, *layout, 1, scan_in,
-                       (uint64_t)0, seg_made, fp);
     szk_role_params rp{};
     szk_asm_params apv = asmp ? *asmp : szk_asm_params{};
     if (er && er->roles && asmp) {
@@ -6682,6 +6738,35 @@ int szk_launch_encode(const uint16_t *codes, uint64_t n, const uint32_t *d_enc, 
         apv.lists_by_roles = 1;
     }
     const uint32_t rb = rp.on ? ROLE_BLOCKS : 0u;
+    // one-byte codes (stage 1's one-launch form assumed them; a probe that says otherwise voids the call) and no book built beside the
+    // packer: the pair-table packer, one 1024-thread workgroup per CU (SZ3HIP_DBG_PACK_OLD: k_pack as before)
+    const bool packb = !mg && asmp && !(rp.on && !rp.no_book) && n_chunks >= 4096 &&
+                       ((asmp->assumed_narrow && !(szk_dbg_flags & SZ3HIP_DBG_PACK_OLD)) || asmp->samp_words);
+    // (a call that may code with its sampled book is k_pack_b's whatever the debug flag says: k_pack's one-byte path takes code words
+    // up to 16 bits. Behind the two-launch form of stage 1 — a context's first call — whether it does is known on the device only:
+    // both packers are launched and the one whose case it is not returns at once)
+    uint32_t beside = packb && asmp->samp_words && !asmp->assumed_narrow ? SZK_PACKB_ONLY_SAMPLED : 0u;
+    // The sampled stage 2 in three launches: k_pack_b scans the groups' sums itself (see the kernel) where its table holds them, nothing
+    // else rides in the scan's launch and no second packer needs the offsets in memory; the layout then rides in the segment pass.
+    // (SZ3HIP_DBG2_PACK_SCAN_LAUNCH: the scan's own launch as everywhere else)
+    const uint64_t n_groups = (n_chunks + PACK_GROUP - 1) / PACK_GROUP;
+    const bool scan_in_pack = packb && seg_bits && er && er->sampled && !beside && n_groups <= PB_SCAN_GROUPS && !fp.nrows &&
+                              !(szk_dbg_flags2 & SZ3HIP_DBG2_PACK_SCAN_LAUNCH);
+    uint32_t *gsums = reinterpret_cast<uint32_t *>(group_off + ((n_groups + 2) & ~1ull));  // behind the offsets (same array), 16-byte aligned
+    const uint16_t *scan_in = nullptr;
+    szk_encode_launches = 0;
+    if (seg_bits) {  // segments -> chunk word counts + group sums, all over the chip; the scan then walks one u32 per group
+        const uint64_t n_segs = (n + 255) / 256;
+        hipLaunchKernelGGL(k_seg_chunks, dim3((uint32_t)std::min<uint64_t>(((n_segs + 7) / 8 + 255) / 256, 1024)), dim3(256), 0, s, seg_bits, n_segs, seg_made,
+                           chunk_words, n_chunks, gsums, sub_bits, *layout, scan_in_pack ? 1 : 0);
+        scan_in = reinterpret_cast<const uint16_t *>(gsums);
+    }
+    szk_encode_launches++;  // (the segment pass or the bits pass)
+    if (!scan_in_pack) {
+        hipLaunchKernelGGL(k_scan_groups, dim3(fp.nrows ? 65 : 1), dim3(1024), 0, s, chunk_words, n_chunks, group_off, total_words, *layout, 1, scan_in,
+                           (uint64_t)0, seg_made, fp);
+        szk_encode_launches++;
+    }
     // the packer's workgroups are persistent and split the chunks statically: all of them, the role and the assemble workgroups
     // must be resident together (5 per compute unit at 30 KB of LDS each), or the late ones double the launch's duration
     const uint32_t extra = rb + (asmp ? 32u : 0u);
@@ -6695,13 +6780,12 @@ int szk_launch_encode(const uint16_t *codes, uint64_t n, const uint32_t *d_enc, 
         mp.fuse_flag = mg->fuse_flag;
         const uint32_t pb = pgrid < 2048 - extra ? pgrid : 2048 - extra;
         hipLaunchKernelGGL(k_merge, dim3(rb + pb + (asmp ? ASM_BLOCKS : 0)), dim3(256), 0, s, mp, n, chunk_words, group_off, mode, state, payload, apv, pb, rp);
+        szk_encode_launches++;
     } else
 #else
     if (mg) return -2;  // (no fused stage 1 in this build: nothing hands a merge over)
 #endif
-    if (asmp && !(rp.on && !rp.no_book) && n_chunks >= 4096 && ((asmp->assumed_narrow && !(szk_dbg_flags & SZ3HIP_DBG_PACK_OLD)) || asmp->samp_words)) {
-        // one-byte codes (stage 1's one-launch form assumed them; a probe that says otherwise voids the call) and no book built beside the
-        // packer: the pair-table packer, one 1024-thread workgroup per CU (SZ3HIP_DBG_PACK_OLD: k_pack as before)
+    if (packb) {
         static int n_cu = 0;
         if (!n_cu) {
             int dev = 0;
@@ -6711,29 +6795,33 @@ int szk_launch_encode(const uint16_t *codes, uint64_t n, const uint32_t *d_enc, 
         }
         const uint32_t pb = (uint32_t)n_cu > rb + 1 ? (uint32_t)n_cu - rb : 1u;  // (the role workgroups take a compute unit each)
         const uint32_t split = 1;
-        // (a call that may code with its sampled book is this kernel's whatever the debug flag says: k_pack's one-byte path takes code words
-        // up to 16 bits. Behind the two-launch form of stage 1 — a context's first call — whether it does is known on the device only:
-        // both packers are launched and the one whose case it is not returns at once)
-        uint32_t beside = asmp->samp_words && !asmp->assumed_narrow ? SZK_PACKB_ONLY_SAMPLED : 0u;
 #ifdef SZ3HIP_LAB
         beside |= (szk_dbg_flags & SZ3HIP_DBG_PACK_LAB_NO_STORES) ? SZK_PACKB_LAB_NO_STORES : 0u;   // (lab switches of k_pack_b: see the kernel)
         beside |= (szk_dbg_flags & SZ3HIP_DBG_PACK_LAB_ONE_UNIT) ? SZK_PACKB_LAB_ONE_UNIT : 0u;
 #endif
-        hipLaunchKernelGGL(k_pack_b, dim3(rb + PB_ASM_BLOCKS + pb), dim3(PB_THREADS), 0, s, codes, n, d_enc, chunk_words, group_off, mode, sym_add, state,
-                           payload, apv, pb, split, rp, beside);
+        if (scan_in_pack)
+            hipLaunchKernelGGL(k_pack_b<true>, dim3(rb + PB_ASM_BLOCKS + pb), dim3(PB_THREADS), 0, s, codes, n, d_enc, chunk_words, (const uint64_t *)nullptr, mode,
+                               sym_add, state, payload, apv, pb, split, rp, beside, (const uint32_t *)gsums, (uint32_t)n_groups, group_off, total_words);
+        else
+            hipLaunchKernelGGL(k_pack_b<false>, dim3(rb + PB_ASM_BLOCKS + pb), dim3(PB_THREADS), 0, s, codes, n, d_enc, chunk_words, group_off, mode, sym_add,
+                               state, payload, apv, pb, split, rp, beside, (const uint32_t *)nullptr, 0u, (uint64_t *)nullptr, (uint64_t *)nullptr);
+        szk_encode_launches++;
         if (beside & SZK_PACKB_ONLY_SAMPLED) {
             const uint32_t pb2 = pgrid < 1280 - extra ? pgrid : 1280 - extra;
             hipLaunchKernelGGL((k_pack<ENC_WIN>), dim3(rb + pb2 + (asmp ? ASM_BLOCKS : 0)), dim3(256), 0, s, codes, n, d_enc, info, chunk_words, group_off, mode,
                                sym_add, state, payload, apv, pb2, rp);
+            szk_encode_launches++;
         }
     } else if (mode.pack_wide) {
         const uint32_t pb = pgrid < 768 - extra ? pgrid : 768 - extra;
         hipLaunchKernelGGL((k_pack<2 * ENC_WIN>), dim3(rb + pb + (asmp ? ASM_BLOCKS : 0)), dim3(256), 0, s, codes, n, d_enc, info, chunk_words, group_off, mode,
                            sym_add, state, payload, apv, pb, rp);
+        szk_encode_launches++;
     } else {
         const uint32_t pb = pgrid < 1280 - extra ? pgrid : 1280 - extra;
         hipLaunchKernelGGL((k_pack<ENC_WIN>), dim3(rb + pb + (asmp ? ASM_BLOCKS : 0)), dim3(256), 0, s, codes, n, d_enc, info, chunk_words, group_off, mode,
                            sym_add, state, payload, apv, pb, rp);
+        szk_encode_launches++;
     }
     SZK_CHECK_LAUNCH();
     return 0;
