@@ -243,6 +243,37 @@ int sz3hip_get_sparse_decode(void);
 /* test hook, process-wide and cumulative: decoder units the Huffman stage of the tile / region calls' fast path decoded, and units their
  * streams held (equal where the stage ran densely) */
 void sz3hip_debug_tile_units(uint64_t *decoded, uint64_t *total);
+/* Several tiles of one stream in one call: n boxes of the grid of every 2^level-th point — the screenful of tiles of a
+ * pyramid level, a set of probe boxes — each bit for bit what sz3hip_decompress_tile_to_device and the full decode's slice deliver. The
+ * boxes share what one call pays once: the container's zstd stage and the payload's copy in, one Huffman stage over the UNION of their
+ * decoder units, and one reconstruction's launch sequence in which every launch carries all boxes (the launch count does not grow with n).
+ * Boxes may overlap and repeat. Level 0 is the region decode of n boxes; all boxes of a request have the one level.
+ * sz3hip_box: conf->N entries of lo / ext are used, slowest first, in coordinates of the grid of every 2^level-th point.
+ * sz3hip_tiles_plan_for: a pure function (no device). points: the predicted points, summed over the boxes; scratch_elems: the boxes' level
+ * buffers, one after the other; units_needed: the size of the union of the boxes' unit lists (sz3hip_tile_units_for).
+ * d_outs: a HOST array of n device pointers; box i's array is contiguous, ext extents of T. There are no strided views in this call (the
+ * single-box call has them). Outputs that overlap one another: SZ3HIP_EINVAL.
+ * Errors: n == 0, n > SZ3HIP_MAX_BOXES, a NULL array: SZ3HIP_EINVAL. Every box is validated before anything is launched or written; the first
+ * bad box is refused with the code and wording of sz3hip_decompress_tile_to_device, "box <index>: " in front. An anchor stride that is no power
+ * of two: SZ3HIP_EUNSUPPORTED from the plan. SZ3HIP_FLOAT and SZ3HIP_DOUBLE; the integer element types are SZ3HIP_EUNSUPPORTED.
+ * sz3hip_decompress_tiles_to_device: pointer, stream and synchrony rules are sz3hip_decompress_tile_to_device's; conf comes back as the FULL
+ * array's Config. A container that is no single interpolation stream (or an anchor stride that is no power of two) takes the fallback ONCE: one
+ * full decode into one scratch array of the call, then n gathers. */
+#define SZ3HIP_MAX_BOXES 256
+typedef struct sz3hip_box {
+    uint64_t lo[4], ext[4];
+} sz3hip_box;
+typedef struct sz3hip_tiles_plan {
+    uint32_t n_boxes;
+    int32_t n_levels;        /* interpolation levels that run: the grid's, the same for every box */
+    uint64_t points;         /* predicted points over all passes, summed over the boxes */
+    uint64_t scratch_elems;  /* elements of T the call needs in device memory besides the outputs */
+    uint64_t units_total;    /* decoder units of the stream's code array: ceil(num / 512) */
+    uint64_t units_needed;   /* units in the union of the boxes' unit lists */
+} sz3hip_tiles_plan;
+int sz3hip_tiles_plan_for(const sz3hip_config *conf, int level, const sz3hip_box *boxes, uint32_t n, sz3hip_tiles_plan *out);
+int sz3hip_decompress_tiles_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const sz3hip_box *boxes,
+                                      uint32_t n, void *const *d_outs, void *stream);
 /* (test and measurement hook) the strided gather alone: the view (N extents, element strides) of d_in into the contiguous d_out on stream,
  * integers widened to f64 as the compress call does; asynchronous */
 int sz3hip_debug_gather(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream);
@@ -365,10 +396,20 @@ int sz3hip_decompress_device_region(sz3hip_ctx *ctx, const void *d_payload, size
  * and keeps it; the list travels by one asynchronous copy on `stream` in front of the Huffman stage's launch. */
 int sz3hip_decompress_device_tile(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, const uint64_t *lo, const uint64_t *ext,
                                   void *d_out, void *stream);
+/* the same for n boxes of one level in one call (see sz3hip_tiles_plan_for above): lo / ext of a box hold one entry per extent the payload's
+ * header names; d_outs is a host array of n device pointers, box i's array contiguous. One Huffman stage decodes the union of the boxes' units
+ * (the list form when the union is within the sparse limit, else the dense launch); the boxes' level buffers lie one after the other in the
+ * context's region scratch; the records the reconstruction's workgroups read are built into a pinned array the context keeps and travel by one
+ * asynchronous copy on `stream` in front of the first launch. Calls of one context may follow each other on a stream without a host
+ * synchronisation in between. Any other predictor: SZ3HIP_EUNSUPPORTED, as for the single box. */
+int sz3hip_decompress_device_tiles(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, const sz3hip_box *boxes, uint32_t n,
+                                   void *const *d_outs, void *stream);
+/* test hook, process-wide and cumulative: kernel launches issued by the box reconstructions, single and multi */
+uint64_t sz3hip_debug_region_launches(void);
 /* test hook: the capacity of the context's region scratch, in elements (0 before its first region call) */
 uint64_t sz3hip_debug_region_scratch(const sz3hip_ctx *ctx);
-/* test hook: the number of region decodes of this process that ran over the box's windows (the fast path of either call); a container
- * that went through the full-decode fallback does not count */
+/* test hook: the number of region decodes of this process that ran over the box's windows (the fast path of either call; a multi-box
+ * call counts once, whatever the number of its boxes); a container that went through the full-decode fallback does not count */
 uint64_t sz3hip_debug_region_fast_calls(void);
 
 /* diagnostics of the last compress on this ctx (valid after sz3hip_compress_finish) */

@@ -130,6 +130,17 @@ class _CTilePlan(C.Structure):
     _fields_ = [("region", _CRegionPlan), ("units_total", C.c_uint64), ("units_needed", C.c_uint64)]
 
 
+class _CBox(C.Structure):
+    """sz3hip_box (include/sz3hip.h)"""
+    _fields_ = [("lo", C.c_uint64 * 4), ("ext", C.c_uint64 * 4)]
+
+
+class _CTilesPlan(C.Structure):
+    """sz3hip_tiles_plan (include/sz3hip.h)"""
+    _fields_ = [("n_boxes", C.c_uint32), ("n_levels", C.c_int32), ("points", C.c_uint64), ("scratch_elems", C.c_uint64), ("units_total", C.c_uint64),
+                ("units_needed", C.c_uint64)]
+
+
 class _CVerifyStats(C.Structure):
     """sz3hip_verify_stats (include/sz3hip.h)"""
     _fields_ = ([(k, C.c_uint64) for k in ("n", "n_nonfinite", "n_nonfinite_mismatch", "n_over", "first_over", "argmax")] +
@@ -253,6 +264,14 @@ def lib():
     L.sz3hip_set_sparse_decode.argtypes = [C.c_int]
     L.sz3hip_get_sparse_decode.restype = C.c_int
     L.sz3hip_get_sparse_decode.argtypes = []
+    L.sz3hip_tiles_plan_for.restype = C.c_int
+    L.sz3hip_tiles_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CBox), C.c_uint32, P(_CTilesPlan)]
+    L.sz3hip_decompress_tiles_to_device.restype = C.c_int
+    L.sz3hip_decompress_tiles_to_device.argtypes = [P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_int, P(_CBox), C.c_uint32, P(C.c_void_p), C.c_void_p]
+    L.sz3hip_decompress_device_tiles.restype = C.c_int
+    L.sz3hip_decompress_device_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, P(_CBox), C.c_uint32, P(C.c_void_p), C.c_void_p]
+    L.sz3hip_debug_region_launches.restype = C.c_uint64
+    L.sz3hip_debug_region_launches.argtypes = []
     L.sz3hip_debug_tile_units.restype = None
     L.sz3hip_debug_tile_units.argtypes = [P(C.c_uint64), P(C.c_uint64)]
     L.sz3hip_debug_region_fast_calls.restype = C.c_uint64
@@ -680,6 +699,64 @@ def decompress_tile(blob, dtype, level, lo, shape, out=None, device=None, stream
     return _decompress_partial("decompress_tile", blob, dtype, lambda: (int(level), None, None), shape_of, out, device, stream)
 
 
+def _boxes(N, boxes):
+    """boxes: a sequence of (lo, shape) pairs, N entries each -> (the sz3hip_box array, the shapes)"""
+    boxes = [(tuple(int(v) for v in lo), tuple(int(v) for v in shape)) for lo, shape in boxes]
+    arr = (_CBox * max(len(boxes), 1))()
+    for i, (lo, shape) in enumerate(boxes):
+        if len(lo) != N or len(shape) != N:
+            raise ValueError("box %d: lo and shape need one entry per extent of the array (%d)" % (i, N))
+        if any(v < 0 for v in lo) or any(v < 0 for v in shape):
+            raise ValueError("box %d: lo and shape must not be negative" % i)
+        arr[i].lo[:N] = lo
+        arr[i].ext[:N] = shape
+    return arr, [shape for _, shape in boxes]
+
+
+def tiles_plan(conf, level, boxes):
+    """what one decompress_tiles call for `boxes` — (lo, shape) pairs in coordinates of the grid of every 2**level-th point of conf's array —
+    touches (sz3hip_tiles_plan_for): a dict with n_boxes, n_levels, points and scratch_elems (summed over the boxes), units_total and
+    units_needed (the size of the union of the boxes' unit lists). Needs no device."""
+    arr, shapes = _boxes(conf.N, boxes)
+    plan = _CTilesPlan()
+    _check(lib().sz3hip_tiles_plan_for(C.byref(conf._c), int(level), arr, len(shapes), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k in ("n_boxes", "n_levels", "points", "scratch_elems", "units_total", "units_needed")}
+
+
+def decompress_tiles(blob, dtype, level, boxes, out=None, device=None, stream=None):
+    """Several boxes of the grid of every 2**level-th point of a container in ONE call (sz3hip_decompress_tiles_to_device): box i — a
+    (lo, shape) pair in coarse-grid coordinates — comes out bit for bit as decompress_tile delivers it. The boxes share the container's
+    host stage, one Huffman stage over the union of their units and one reconstruction's launches. Device only: `device=` allocates the
+    tensors, or `out=` is a list of contiguous tensors of the boxes' shapes on one HIP device, none overlapping another. float32 / float64.
+    Returns (list of tensors, Config) — the Config is the FULL array's. `stream` as for decompress."""
+    blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
+    npdt = _np_dtype(dtype)
+    dt = _dtype_id(npdt)
+    if out is None and device is None:
+        raise ValueError("decompress_tiles decodes into device memory: pass device= or out=")
+    if out is not None and not all(_gpu_tensor(t) for t in out):
+        raise ValueError("out must be a list of tensors on a HIP device")
+    call = lib().sz3hip_decompress_tiles_to_device
+    if dt > 1:  # (the library's own refusal, before anything is parsed or allocated)
+        _check(call(C.byref(Config(1)._c), dt, blob.ctypes.data, blob.size, int(level), None, 0, None, None))
+    conf = Config(1)
+    _check(lib().sz3hip_peek_config(C.byref(conf._c), blob.ctypes.data, blob.size))
+    arr, shapes = _boxes(conf.N, boxes)
+    import torch
+    if out is None:
+        out = [torch.empty(shape, dtype=getattr(torch, npdt.name), device=device) for shape in shapes]
+    out = list(out)
+    if len(out) != len(shapes):
+        raise ValueError("out needs one tensor per box (%d)" % len(shapes))
+    for t, shape in zip(out, shapes):
+        if _np_dtype(t.dtype) != npdt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("out must hold contiguous %s tensors of the boxes' shapes" % npdt)
+    ptrs = (C.c_void_p * max(len(out), 1))(*[t.data_ptr() for t in out])
+    handle = _stream_handle(out[0].device, stream) if out else None  # (no box: the library's refusal)
+    _check(call(C.byref(conf._c), dt, blob.ctypes.data, blob.size, int(level), arr, len(shapes), ptrs, handle))
+    return out, conf
+
+
 def decompress_region(blob, dtype, lo, shape, out=None, device=None, stream=None):
     """The box [lo, lo + shape) of a container, bit for bit what ``decompress(blob, dtype, device=...)[0]`` holds there, in work sized to the
     box where the container is a single interpolation stream (sz3hip_decompress_region_to_device). Device only: `device=` allocates a tensor
@@ -852,6 +929,20 @@ class DeviceCompressor:
         if len(lo) != len(shape) or not 1 <= len(lo) <= 4:
             raise ValueError("lo and shape need one entry per extent of the array")
         _check(lib().sz3hip_decompress_device_tile(self._h, d_payload, int(size), int(level), (C.c_uint64 * 4)(*lo), (C.c_uint64 * 4)(*shape), d_out, stream))
+
+    def decompress_tiles(self, d_payload, size, level, boxes, d_outs, stream=0):
+        """several boxes — (lo, shape) pairs in coarse-grid coordinates — of the grid of every 2**level-th point of an interpolation payload
+        in one call; d_outs: one device pointer per box, its array contiguous"""
+        boxes = list(boxes)
+        N = len(boxes[0][0]) if boxes else 1
+        if not 1 <= N <= 4:
+            raise ValueError("lo and shape need one entry per extent of the array")
+        arr, shapes = _boxes(N, boxes)
+        d_outs = [int(p) for p in d_outs]
+        if len(d_outs) != len(shapes):
+            raise ValueError("d_outs needs one pointer per box (%d)" % len(shapes))
+        ptrs = (C.c_void_p * max(len(d_outs), 1))(*d_outs)
+        _check(lib().sz3hip_decompress_device_tiles(self._h, d_payload, int(size), int(level), arr, len(shapes), ptrs, stream))
 
     def region_scratch(self):
         """capacity of the context's region scratch in elements (0 before its first region call)"""

@@ -46,6 +46,11 @@ int szi_fail(int code, const char *fmt, ...) {
     return code;
 }
 #define fail szi_fail
+int szi_fail_box(uint32_t i) {
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    return fail(g_err_code, "box %u: %s", i, msg);
+}
 extern "C" int sz3hip_lab_build(void);
 extern "C" const char *sz3hip_last_error(void) { return g_err; }
 extern "C" int sz3hip_last_error_code(void) { return g_err_code; }
@@ -250,6 +255,9 @@ static void ctx_free(sz3hip_ctx *c) {
     if (c->h_ovf) (void)hipHostFree(c->h_ovf);
     if (c->d_units) (void)hipFree(c->d_units);
     if (c->h_units) (void)hipHostFree(c->h_units);
+    if (c->d_table) (void)hipFree(c->d_table);
+    if (c->h_table) (void)hipHostFree(c->h_table);
+    if (c->ev_table) (void)hipEventDestroy(c->ev_table);
     free(c->unit_bits);
     for (int i = 0; i < ST_COUNT; i++)
         for (int j = 0; j < 2; j++)
@@ -2352,6 +2360,94 @@ extern "C" int sz3hip_tile_plan_for(const sz3hip_config *conf, int level, const 
     out->units_needed = szk_tile_mark_units(&g, bits.data(), ~0ull);
     return 0;
 }
+// ---- several boxes of one level in one request ----
+// The geometries of a request's boxes, every box checked before the first buffer is placed; the boxes' level buffers follow each other in
+// the scratch by a running base (lv[].base becomes the buffer's place in the whole scratch, *scratch_elems the sum). A bad box is refused
+// with the single-box call's code and wording and its index in front. All boxes of a request have the grid's level count, buffer count and
+// pass order.
+static int boxes_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, int level, const sz3hip_box *boxes, uint32_t n,
+                          std::vector<szk_region_geom> &gs, uint64_t *scratch_elems) {
+    gs.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const int rc = region_geometry(N, dims, interp_id, direction, anchor_stride, boxes[i].lo, boxes[i].ext, &gs[i], level);
+        if (rc) return rc == SZ3HIP_EINVAL ? szi_fail_box(i) : rc;
+    }
+    uint64_t base = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        szk_region_geom &g = gs[i];
+        if (g.n_levels != gs[0].n_levels || g.nbuf != gs[0].nbuf || memcmp(g.perm, gs[0].perm, sizeof(g.perm)))
+            return fail(SZ3HIP_EHIP, "box %u: its level count, buffer count or pass order is not the request's", i);
+        for (int b = 0; b < g.nbuf; b++) g.lv[b].base += base;
+        base += g.scratch_elems;
+    }
+    *scratch_elems = base;
+    return 0;
+}
+static int boxes_args(const char *who, const void *boxes, uint32_t n, const void *third, const char *third_name) {
+    if (!boxes || !third) return fail(SZ3HIP_EINVAL, "%s: NULL argument (%s)", who, !boxes ? "boxes" : third_name);
+    if (n == 0 || n > SZ3HIP_MAX_BOXES) return fail(SZ3HIP_EINVAL, "%s: a request holds 1 .. %d boxes (this one %u)", who, SZ3HIP_MAX_BOXES, n);
+    return 0;
+}
+// the outputs of a request: n device pointers, box i's array of prod(ext) elements of tsz bytes; none NULL, no two overlapping
+int szi_boxes_outputs_check(int N, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, size_t tsz) {
+    std::vector<std::pair<uintptr_t, uintptr_t>> r(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!d_outs[i]) return fail(SZ3HIP_EINVAL, "box %u: the output array is NULL", i);
+        uint64_t m = tsz;
+        for (int j = 0; j < N; j++) m *= boxes[i].ext[j];
+        r[i] = {(uintptr_t)d_outs[i], (uintptr_t)d_outs[i] + m};
+    }
+    std::sort(r.begin(), r.end());
+    for (uint32_t i = 1; i < n; i++)
+        if (r[i].first < r[i - 1].second) return fail(SZ3HIP_EINVAL, "the outputs of two boxes overlap");
+    return 0;
+}
+extern "C" int sz3hip_tiles_plan_for(const sz3hip_config *conf, int level, const sz3hip_box *boxes, uint32_t n, sz3hip_tiles_plan *out) {
+    if (!conf) return fail(SZ3HIP_EINVAL, "sz3hip_tiles_plan_for: NULL argument (conf)");
+    int rc = boxes_args("sz3hip_tiles_plan_for", boxes, n, out, "out");
+    if (rc) return rc;
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
+    if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
+    static const int def_anchor[4] = {4096, 128, 32, 16};  // (conf_geometry's)
+    const uint64_t anchor = conf->interpAnchorStride < 0 ? (uint64_t)def_anchor[conf->N - 1] : (uint64_t)conf->interpAnchorStride;
+    uint64_t dims[4] = {0, 0, 0, 0}, num = 1;
+    for (int i = 0; i < conf->N; i++) {
+        dims[i] = conf->dims[i];
+        num *= dims[i];
+    }
+    std::vector<szk_region_geom> gs;
+    memset(out, 0, sizeof(*out));
+    if ((rc = boxes_geometry(conf->N, dims, conf->interpAlgo, conf->interpDirection, anchor, level, boxes, n, gs, &out->scratch_elems))) return rc;
+    out->n_boxes = n;
+    out->n_levels = gs[0].n_levels;
+    out->units_total = units_of(num);
+    if (out->units_total > 0xFFFFFFFFull) return fail(SZ3HIP_EINVAL, "the array has more decoder units than a 32-bit index names");
+    std::vector<uint64_t> bits((size_t)((out->units_total + 63) / 64), 0);
+    for (const szk_region_geom &g : gs) {
+        out->points += g.points;
+        out->units_needed += szk_tile_mark_units(&g, bits.data(), ~0ull);  // (newly set bits only: the sum is the union's size)
+    }
+    return 0;
+}
+// the context's table of a multi-box call: a pinned and a device array of 64-bit words, made by its first such call, grown when a request
+// needs more, kept; and the event that is recorded behind the table's copy
+static int table_reserve(sz3hip_ctx *ctx, uint64_t words) {
+    if (!ctx->ev_table) HIPCHK(hipEventCreateWithFlags(&ctx->ev_table, hipEventDisableTiming));
+    if (words <= ctx->table_cap) return 0;
+    if (ctx->d_table) {
+        HIPCHK(hipDeviceSynchronize());  // (an earlier call's copy and kernels may still read them)
+        (void)hipFree(ctx->d_table);
+    }
+    if (ctx->h_table) (void)hipHostFree(ctx->h_table);  // (also one left alone by a device allocation that failed)
+    ctx->d_table = ctx->h_table = nullptr;
+    ctx->table_cap = 0;
+    ctx->table_pending = false;
+    const uint64_t cap = std::max<uint64_t>(words, 8192);
+    HIPCHK(hipHostMalloc((void **)&ctx->h_table, cap * 8));
+    HIPCHK(hipMalloc((void **)&ctx->d_table, cap * 8));
+    ctx->table_cap = cap;
+    return 0;
+}
 // the context's unit list: a pinned and a device array of max_n / 512 + 1 entries and the host's bit per unit, made by its first tile / region
 // call, kept
 static int tile_units_reserve(sz3hip_ctx *ctx) {
@@ -2390,6 +2486,7 @@ extern "C" uint64_t sz3hip_debug_region_fast_calls(void) { return g_region_fast_
 // ---- the partial request (szi_partial, DESIGN.md sections 11 - 13) on a context ----
 static inline bool is_box(const szi_partial *q) { return q && q->kind == SZI_BOX; }
 static inline bool is_coarse(const szi_partial *q) { return q && q->kind == SZI_COARSE; }
+static inline bool is_boxes(const szi_partial *q) { return q && q->kind == SZI_BOXES; }
 // the context's coarse code array: made by its first coarse call, kept (later calls allocate nothing); then the call's grid against it
 static int coarse_reserve(sz3hip_ctx *ctx, int N, const uint64_t *dims, int level) {
     if (!ctx->d_coarse_codes) {
@@ -2401,10 +2498,33 @@ static int coarse_reserve(sz3hip_ctx *ctx, int N, const uint64_t *dims, int leve
     if (szi_partial_num(&grid, N, dims) > ctx->coarse_codes_cap) return fail(SZ3HIP_EINVAL, "the coarse grid exceeds the context capacity");
     return 0;
 }
-// The reconstruction of an interpolation stream for a request: the whole array, its coarse grid or a box (rg: the box's geometry).
+// A multi-box request on a context, before anything is launched: the boxes' geometries, their outputs, the scratch for the sum of their
+// buffers, the unit list and the table. Then the pinned arrays: an earlier multi-box call's copies of h_units and h_table were queued in
+// front of the event it recorded, so waiting for that event makes both free to write whatever stream that call ran on. (A single-box call
+// writes h_units without this wait: its guarantee is decode_header's synchronise of the call's stream, which covers every earlier call on
+// that stream; a context is not used on two streams at once.)
+static int boxes_prepare(sz3hip_ctx *ctx, int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const szi_partial *part,
+                         std::vector<szk_region_geom> &gs, uint64_t *elems) {
+    int rr = boxes_geometry(N, dims, interp_id, direction, anchor_stride, part->level, part->boxes, part->n_boxes, gs, elems);
+    if (rr || (rr = szi_boxes_outputs_check(N, part->boxes, part->n_boxes, part->d_outs, ctx->dtype == SZ3HIP_FLOAT ? 4 : 8))) return rr;
+    if ((rr = region_reserve(ctx, *elems)) || (rr = tile_units_reserve(ctx)) || (rr = table_reserve(ctx, szk_region_multi_table_words(gs.data(), part->n_boxes)))) return rr;
+    if (ctx->table_pending) {
+        HIPCHK(hipEventSynchronize(ctx->ev_table));
+        ctx->table_pending = false;
+    }
+    return 0;
+}
+// The reconstruction of an interpolation stream for a request: the whole array, its coarse grid, a box (rg: the box's geometry) or several
+// (rg: their geometries, placed in boxes_elems elements of the context's scratch; one fast call whatever their number).
 // The lists as the launchers take them: a payload and offsets into it, or the null base and pointers as offsets.
 static int launch_interp_recon(sz3hip_ctx *ctx, const szk_interp_params *ip, const szi_partial *part, const szk_region_geom *rg, const uint8_t *base,
-                               uint64_t vout_idx, uint64_t vout_val, uint64_t n_vout, void *d_out, hipStream_t s) {
+                               uint64_t vout_idx, uint64_t vout_val, uint64_t n_vout, void *d_out, hipStream_t s, uint64_t boxes_elems = 0) {
+    if (is_boxes(part)) {
+        g_region_fast_calls++;
+        ctx->table_pending = true;  // (the launcher records ev_table behind the table's copy)
+        return szk_launch_interp_decompress_region_multi(ctx->dtype, ip, rg, part->n_boxes, boxes_elems, base, vout_idx, vout_val, n_vout, ctx->d_codes, ctx->d_region,
+                                                         part->d_outs, ctx->h_table, ctx->d_table, ctx->table_cap, ctx->ev_table, s);
+    }
     if (is_box(part)) {
         g_region_fast_calls++;
         return szk_launch_interp_decompress_region(ctx->dtype, ip, rg, base, vout_idx, vout_val, n_vout, ctx->d_codes, ctx->d_region, d_out, s);
@@ -2419,9 +2539,15 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
     szk_region_geom rg;
+    std::vector<szk_region_geom> gs;  // (several boxes: their geometries; d_out is unused)
+    uint64_t boxes_elems = 0;
     if (is_box(part)) {  // (d_out: the box. The windows and the context's scratch, before anything is launched)
         int rr = region_geometry(p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, part->lo, part->ext, &rg, part->level);
         if (rr || (rr = region_reserve(ctx, rg.scratch_elems))) return rr;
+    }
+    if (is_boxes(part)) {
+        int rr = boxes_prepare(ctx, p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, part, gs, &boxes_elems);
+        if (rr) return rr;
     }
     const uint64_t num = szi_partial_num(nullptr, p->N, p->dims);
     if (num > ctx->max_n) return fail(SZ3HIP_EINVAL, "array exceeds the context capacity");
@@ -2445,11 +2571,12 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
     ip.eb = p->eb;
     ip.radius = p->radius;
     // (the lists are the caller's own arrays: handed over as offsets from a null base)
-    if (is_box(part)) {  // (a stock stream's codes come through the stock decoder: every unit)
+    if (is_box(part) || is_boxes(part)) {  // (a stock stream's codes come through the stock decoder: every unit)
         g_tile_units_decoded += units_of(num);
         g_tile_units_total += units_of(num);
     }
-    if (launch_interp_recon(ctx, &ip, part, &rg, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, d_out, s))
+    if (launch_interp_recon(ctx, &ip, part, is_boxes(part) ? gs.data() : &rg, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, d_out, s,
+                            boxes_elems))
         return fail(SZ3HIP_EHIP, "interpolation decoder launch failed");
     uint32_t bad = 0;
     HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
@@ -2546,7 +2673,7 @@ static int decode_header(sz3hip_ctx *ctx, const void *d_payload, size_t payload_
 // DESIGN.md §11; a box of it, §12, or of that grid, §13) share the header's parse and the Huffman stage; they differ in the units a box
 // has decoded and in the reconstruction.
 static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header &h, const szh_offsets &o, const szi_partial *part, void *d_out, hipStream_t s) {
-    const bool region = is_box(part);
+    const bool region = is_box(part), multi = is_boxes(part);
     uint32_t *ovf = reinterpret_cast<uint32_t *>(ctx->d_counters + 12);  // overflow flag of the half-width chain (see below)
     if (is_coarse(part)) {
         if (h.predictor != 1)
@@ -2558,13 +2685,21 @@ static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header 
         if (rr) return rr;
     }
     szk_region_geom rg;
-    if (region) {
+    std::vector<szk_region_geom> gs;  // (several boxes: their geometries; d_out is unused)
+    uint64_t boxes_elems = 0;
+    if (region || multi) {
         if (h.predictor != 1)
             return fail(SZ3HIP_EUNSUPPORTED, "sz3hip_decompress_device_region reads interpolation payloads only (this one's predictor id is %d): a device context has "
                         "no full-size scratch of its own — sz3hip_decompress_region_to_device decodes every container", h.predictor);
         if (h.ndim < 1 || h.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
-        int rr = region_geometry(h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, part->lo, part->ext, &rg, part->level);
-        if (rr || (rr = region_reserve(ctx, rg.scratch_elems)) || (rr = tile_units_reserve(ctx))) return rr;
+        int rr;
+        if (multi) {
+            rr = boxes_prepare(ctx, h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, part, gs, &boxes_elems);
+        } else {
+            rr = region_geometry(h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, part->lo, part->ext, &rg, part->level);
+            if (!rr && !(rr = region_reserve(ctx, rg.scratch_elems))) rr = tile_units_reserve(ctx);
+        }
+        if (rr) return rr;
     }
     const uint8_t *pl = (const uint8_t *)d_payload;
     szk_blk_params bp;
@@ -2639,14 +2774,22 @@ static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header 
     szk_dec_params dp;
     dp.unit_list = nullptr;
     dp.n_list = 0;
-    if (region) {
+    if (region || multi) {
         // the units the tile's passes read a code from (built while the tables' launch runs); few enough: the Huffman stage decodes those alone.
-        // The other units keep what the code array held — the list covers every read
+        // The other units keep what the code array held — the list covers every read. Several boxes: one stage for the union of their units —
+        // every box marks into the one bit array (newly set bits count) with what is left of the limit as its budget
         const uint64_t total = units_of(h.n), limit = sparse_limit(total);
         uint64_t n_list = total;
         if (sz3hip_get_sparse_decode() && total <= ctx->units_cap) {
             memset(ctx->unit_bits, 0, (size_t)((total + 63) / 64) * 8);
-            if (szk_tile_mark_units(&rg, ctx->unit_bits, limit) <= limit) {
+            uint64_t marked = 0;
+            bool within = true;
+            for (uint32_t i = 0, nb = multi ? part->n_boxes : 1; i < nb && within; i++) {
+                const uint64_t left = limit - marked, m = szk_tile_mark_units(multi ? &gs[i] : &rg, ctx->unit_bits, left);
+                within = m <= left;
+                marked += within ? m : 0;
+            }
+            if (within) {
                 n_list = units_from_bits(ctx->unit_bits, total, ctx->h_units, ctx->units_cap);
                 for (uint64_t i = 0; i < n_list; i++)
                     if (ctx->h_units[i] >= total) return fail(SZ3HIP_EHIP, "the tile's unit list names a unit the stream does not have");
@@ -2739,8 +2882,8 @@ static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header 
         ip.beta = h.interp_beta;
         ip.eb = h.eb;
         ip.radius = (int)h.radius;
-        if (!region && !is_coarse(part)) dense2_for(ctx, ip);
-        rc = launch_interp_recon(ctx, &ip, part, &rg, pl, o.vout_idx, o.vout_val, h.n_vout, d_out, s);
+        if (!region && !multi && !is_coarse(part)) dense2_for(ctx, ip);
+        rc = launch_interp_recon(ctx, &ip, part, multi ? gs.data() : &rg, pl, o.vout_idx, o.vout_val, h.n_vout, d_out, s, boxes_elems);
     } else if (h.predictor == 2) {
         // codes -> deltas, then the blocks in anti-diagonal fronts once the side stream has the choices and coefficients
         rc = szk_launch_blk_decompress(ctx->dtype, ctx->d_codes, d_out, &bp, &sc, pl, &h, &o, ctx->d_blk_coef, s, ctx->ev_join);
@@ -2798,6 +2941,21 @@ extern "C" int sz3hip_decompress_device_tile(sz3hip_ctx *ctx, const void *d_payl
     if (!d_payload || !d_out) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_tile: the %s is NULL", !d_payload ? "payload" : "output array");
     return device_box(ctx, d_payload, payload_size, level, lo, ext, d_out, stream);
 }
+// (a box's lo / ext: one entry per extent the payload's header names; every box is checked before anything is launched)
+extern "C" int sz3hip_decompress_device_tiles(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, int level, const sz3hip_box *boxes, uint32_t n,
+                                              void *const *d_outs, void *stream) {
+    if (!ctx) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_tiles: no context");
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
+    int rc = boxes_args("sz3hip_decompress_device_tiles", boxes, n, d_outs, "d_outs");
+    if (rc) return rc;
+    if (!d_payload) return fail(SZ3HIP_EINVAL, "sz3hip_decompress_device_tiles: the payload is NULL");
+    szh_header h;
+    szh_offsets o;
+    if ((rc = decode_header(ctx, d_payload, payload_size, (hipStream_t)stream, h, o))) return rc;
+    szi_partial q = {SZI_BOXES, level, {}, {}, n, boxes, d_outs};
+    return decode_body(ctx, d_payload, h, o, &q, nullptr, (hipStream_t)stream);
+}
+extern "C" uint64_t sz3hip_debug_region_launches(void) { return szk_region_launches(); }
 extern "C" int sz3hip_coarse_dims(const sz3hip_config *conf, int level, uint64_t *dims_out) {
     if (!conf || !dims_out) return fail(SZ3HIP_EINVAL, "sz3hip_coarse_dims: NULL argument");
     if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "coarse level %d is outside 0 .. 30", level);

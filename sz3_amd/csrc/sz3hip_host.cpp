@@ -1764,8 +1764,9 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
     if ((rc = slot_ctx(s, conf->num))) return rc;
     const szi_partial *part = out.part;
     const size_t out_bytes = (size_t)szi_partial_num(part, conf) * tsize;
+    const bool boxes = part && part->kind == SZI_BOXES;  // (the request names its own output arrays: no array of the slot's, nothing to hand out)
     void *dst = part && out.in_place() ? (void *)out.dev : nullptr;  // (a partial decode's contiguous output is written where it lies)
-    if (!dst) {
+    if (!dst && !boxes) {
         if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, out_bytes))) return rc;
         dst = s->dev_in;
     }
@@ -1789,7 +1790,8 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
     if ((rc = stock_huff_run(s, hd, tr, offset, bits, bit_bytes, n))) return rc;
     rc = szi_stock_import(s->ctx, &sp, &g, d_blk, hd.d_em, d_unpred, n_unpred, d_tile_cnt, d_tile_base, d_vidx, d_vval, d_bad, dst, s->stream, part);
     if (rc) return rc;
-    HIPCHK(d2h_out(out, dst, out_bytes));
+    if (boxes) out.delivered = true;  // (szi_stock_import waited for the stream)
+    else HIPCHK(d2h_out(out, dst, out_bytes));
     return 0;
 }
 
@@ -2897,11 +2899,12 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
     if ((rc = slot_ctx(s, conf->num))) return rc;
     const szi_partial *part = is_int ? nullptr : out.part;
     if (part && hdr.predictor != 1) return fail(SZ3HIP_EFORMAT, "the Config names the interpolation stream but the payload's predictor id is %d", (int)hdr.predictor);
-    if (part && part->kind == SZI_BOX && hdr.ndim != (uint32_t)conf->N) return fail(SZ3HIP_EFORMAT, "the payload's extent count does not match the Config");
+    const bool boxes = part && part->kind == SZI_BOXES;  // (the request names its own output arrays: no array of the slot's, nothing to hand out)
+    if (part && (part->kind == SZI_BOX || boxes) && hdr.ndim != (uint32_t)conf->N) return fail(SZ3HIP_EFORMAT, "the payload's extent count does not match the Config");
     const size_t cbytes = (size_t)szi_partial_num(part, conf) * (cdt == SZ3HIP_FLOAT ? 4 : 8);
     // (a device call's contiguous f32 / f64 array is decoded where it lies)
     void *dst = out.in_place() && !is_int ? (void *)out.dev : nullptr;
-    if (!dst) {
+    if (!dst && !boxes) {
         if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, cbytes))) return rc;
         dst = s->dev_in;
     }
@@ -2913,7 +2916,8 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
     if (!is_int) {
         HIPCHK(hipStreamSynchronize(s->stream));
         stamp(out, 2);
-        HIPCHK(d2h_out(out, dst, part ? cbytes : raw_bytes));
+        if (boxes) out.delivered = true;
+        else HIPCHK(d2h_out(out, dst, part ? cbytes : raw_bytes));
     } else if (out.dev) {  // (narrowed straight into the caller's view)
         out.delivered = true;
         if (szk_launch_scatter(dataType, 1, s->dev_in, out.dev, &out.view, s->stream)) return fail(SZ3HIP_EHIP, "integer narrowing kernel failed");
@@ -3255,6 +3259,111 @@ static int partial_to_device(const char *who, sz3hip_config *conf, int dataType,
     if (!dev.view.contig && szk_launch_scatter(dataType, 0, dense, dev.ptr, &dev.view, cs)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
     HIPCHK(hipStreamSynchronize(cs));
     return 0;
+}
+// The multi form: n boxes of one level in one call. What the single form pays per box is paid once: the zstd stage and
+// the payload's copy in, the Huffman stage (the union of the boxes' units), the reconstruction's launch sequence — and, on the fallback, the
+// full decode into the one scratch array, behind which n gathers run. The checks' order is the box kind's above, every box and every output
+// before anything is allocated, launched or written; the outputs are contiguous (no strides in this call).
+static int partial_boxes_to_device(const char *who, sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const sz3hip_box *boxes,
+                                   uint32_t n, void *const *d_outs, void *stream) {
+    if (!dtype_ok(dataType))
+        return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
+    if (dtype_is_int(dataType)) return fail(SZ3HIP_EUNSUPPORTED, "the region decode reads float / double arrays; integer element types are not supported yet");
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
+    if (!conf || !boxes || !d_outs) return fail(SZ3HIP_EINVAL, "%s: NULL argument (%s)", who, !conf ? "conf" : !boxes ? "boxes" : "d_outs");
+    if (n == 0 || n > SZ3HIP_MAX_BOXES) return fail(SZ3HIP_EINVAL, "%s: a request holds 1 .. %d boxes (this one %u)", who, SZ3HIP_MAX_BOXES, n);
+    int rc = sz3hip_peek_config(conf, cmpData, cmpSize);
+    if (rc) return rc;
+    if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
+    const int N = conf->N;
+    for (uint32_t b = 0; b < n; b++)
+        for (int i = 0; i < N; i++) {
+            const uint64_t cd = szi_coarse_extent(conf->dims[i], level), lo = boxes[b].lo[i], ext = boxes[b].ext[i];
+            if (ext == 0) return fail(SZ3HIP_EINVAL, "box %u: the region has extent 0 in dimension %d", b, i);
+            if (lo >= cd || ext > cd - lo)
+                return fail(SZ3HIP_EINVAL, "box %u: the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", b, (unsigned long long)lo, (unsigned long long)lo,
+                            (unsigned long long)ext, i, (unsigned long long)cd);
+        }
+    if (zs::load()) return SZ3HIP_EZSTD;
+    const size_t es = dtype_size(dataType);
+    if ((rc = szi_boxes_outputs_check(N, boxes, n, d_outs, es))) return rc;
+    int device = 0;
+    for (uint32_t b = 0; b < n; b++) {
+        int dv = 0;
+        if ((rc = dev_pointer(d_outs[b], &dv))) return rc;
+        if (b && dv != device) return fail(SZ3HIP_EINVAL, "box %u: its output lies on device %d, box 0's on device %d", b, dv, device);
+        device = dv;
+    }
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(cmpData) + 8;
+    uint64_t payload;
+    memcpy(&payload, p, 8);
+    p += 8;
+    DeviceGuard guard;
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));  // (what the caller queued on the outputs comes first)
+    HostLock lock(conf->openmp);
+    szi_partial q;
+    memset(&q, 0, sizeof(q));
+    q.kind = SZI_BOXES;
+    q.level = level;
+    q.n_boxes = n;
+    q.boxes = boxes;
+    q.d_outs = d_outs;
+    if (!conf->openmp && (conf->cmprAlgo == SZ3HIP_ALGO_HIP_INTERP || conf->cmprAlgo == SZ3HIP_ALGO_INTERP)) {
+        SlotLease lease(device, dtype_compute(dataType));
+        HostSlot *s = lease.s;
+        if (!s->stream) HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        DecodeOut o(nullptr);  // (no host destination and no view: the decoders write the request's arrays)
+        o.dataType = dataType;
+        o.stream = s->stream;
+        o.part = &q;
+        rc = decompress_blob(s, conf, dataType, p, (size_t)payload, o);
+        if (rc != SZ3HIP_EUNSUPPORTED) {
+            if (rc) return rc;
+            if (!o.delivered) return fail(SZ3HIP_EHIP, "the region decode did not deliver its arrays");
+            HIPCHK(hipStreamSynchronize(s->stream));
+            return 0;
+        }
+    }
+    // the full array once, decoded as sz3hip_decompress_to_device does, into a scratch of this call; then every box's view of it
+    struct Scratch {
+        void *p = nullptr;
+        ~Scratch() {
+            if (p) (void)hipFree(p);
+        }
+    } full;
+    if (hipMalloc(&full.p, std::max<size_t>((size_t)conf->num * es, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SZ3HIP_EHIP, "no device memory for the full-size scratch (%zu bytes) this container's region decode needs", (size_t)conf->num * es);
+    }
+    DevArray fd;
+    if ((rc = dev_array(conf, nullptr, full.p, true, &fd))) return rc;
+    if (conf->openmp) rc = decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &fd);
+    else {
+        SlotLease lease(device, dtype_compute(dataType));
+        rc = decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, DecodeOut(nullptr), &fd, 0, conf->dims[0]);
+    }
+    if (rc) return rc;
+    hipStream_t cs = (hipStream_t)stream;
+    for (uint32_t b = 0; b < n; b++) {
+        szi_partial one;
+        memset(&one, 0, sizeof(one));
+        one.kind = SZI_BOX;
+        one.level = level;
+        for (int i = 0; i < N; i++) {
+            one.lo[i] = boxes[b].lo[i];
+            one.ext[i] = boxes[b].ext[i];
+        }
+        szk_view gv;
+        const int64_t corner = partial_view(one, N, one.ext, fd.view, &gv);
+        if (szk_launch_gather(dataType, 0, (const char *)full.p + corner * (int64_t)es, &gv, d_outs[b], nullptr, cs)) return fail(SZ3HIP_EHIP, "gather kernel failed");
+    }
+    HIPCHK(hipStreamSynchronize(cs));
+    return 0;
+}
+extern "C" int sz3hip_decompress_tiles_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const sz3hip_box *boxes,
+                                                 uint32_t n, void *const *d_outs, void *stream) {
+    return partial_boxes_to_device("sz3hip_decompress_tiles_to_device", conf, dataType, cmpData, cmpSize, level, boxes, n, d_outs, stream);
 }
 extern "C" int sz3hip_decompress_coarse_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, void *d_out,
                                                   const int64_t *strides, void *stream) {

@@ -13,6 +13,8 @@
 
 // records code + message for sz3hip_last_error() (thread-local) and returns code
 int szi_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// the error just recorded, again with "box <i>: " in front of its message (a multi-box request names the box it refuses); returns its code
+int szi_fail_box(uint32_t i);
 struct sz3hip_ctx;
 // ---- stock-stream interoperability (sz3hip_stock.hip, sz3hip_stock_host.cpp) ----
 struct szg_geom;
@@ -29,20 +31,37 @@ struct szi_stock_params {  // what InterpolationDecomposition::save holds beside
 //   SZI_COARSE  every 2^level-th point of the array (level >= 1; lo / ext unused)
 //   SZI_BOX     the box [lo, lo + ext) of the grid of every 2^level-th point, in that grid's coordinates, one entry per extent of the
 //               stream, slowest first (level 0: the region decode — the box is one of the array itself)
-enum { SZI_FULL = 0, SZI_COARSE, SZI_BOX };
+//   SZI_BOXES   n_boxes boxes of that grid in one request (lo / ext unused): box i is boxes[i], its array — contiguous, of
+//               its ext extents — is d_outs[i] (device pointers in a host array). The decoders write those arrays themselves: the d_out that
+//               travels beside the request is unused, and a DecodeOut counts as delivered once the decode returns 0
+enum { SZI_FULL = 0, SZI_COARSE, SZI_BOX, SZI_BOXES };
 struct szi_partial {
     int kind, level;
     uint64_t lo[4], ext[4];
+    uint32_t n_boxes;
+    const sz3hip_box *boxes;
+    void *const *d_outs;
 };
 static inline uint64_t szi_coarse_extent(uint64_t d, int level) { return d ? ((d - 1) >> level) + 1 : 0; }
-// the element count of q's output for an array of N extents
+// the element count of q's output for an array of N extents (SZI_BOXES: the sum over the boxes)
 static inline uint64_t szi_partial_num(const szi_partial *q, int N, const uint64_t *dims) {
+    if (q && q->kind == SZI_BOXES) {
+        uint64_t sum = 0;
+        for (uint32_t b = 0; b < q->n_boxes; b++) {
+            uint64_t m = 1;
+            for (int i = 0; i < N; i++) m *= q->boxes[b].ext[i];
+            sum += m;
+        }
+        return sum;
+    }
     uint64_t n = 1;
     for (int i = 0; i < N; i++) n *= !q || q->kind == SZI_FULL ? dims[i] : q->kind == SZI_BOX ? q->ext[i] : szi_coarse_extent(dims[i], q->level);
     return n;
 }
 static inline uint64_t szi_partial_num(const szi_partial *q, const sz3hip_config *conf) { return szi_partial_num(q, conf->N, conf->dims); }
 // sz3hip_decompress_device with a partial request (the host API's slots call it; part null: the full decode)
+// the outputs of an SZI_BOXES request: none NULL, no two of them overlapping (tsz: the element size)
+int szi_boxes_outputs_check(int N, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, size_t tsz);
 int szi_decompress_device_partial(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_partial *part, void *d_out, void *stream);
 // after sz3hip_compress_stage1 chose interpolation (header predictor 1): waits for it, reports its parameters and the number of
 // unpredictable values (the anchor grid included); SZ3HIP_EUNSUPPORTED when stage 1 took another predictor
@@ -122,6 +141,10 @@ struct sz3hip_ctx {
     uint32_t *h_units, *d_units;  // tile / region decode: the decoder units to decode, pinned and on the device (max_n / 512 + 1 entries; made by the first such call, kept)
     uint64_t units_cap;
     uint64_t *unit_bits;          // ... and the host's bit per unit they are built in
+    uint64_t *h_table, *d_table;  // multi-box decode: the records its workgroups read, pinned and on the device (made by the first such call, grown when a request needs more, kept)
+    uint64_t table_cap;           // ... in 64-bit words
+    hipEvent_t ev_table;          // recorded behind the copy of h_table (and of h_units, which the same call queues in front of it): the next multi-box call waits for it before it writes either
+    bool table_pending;
     void *s2_payload;  // stage 2's arguments, kept for the repeat after a mispredicted code-book form
     size_t s2_cap;
     // Two code books: bk[book_idx] is the last one a call of this context completed with (-1: none yet). Stage 2 builds this

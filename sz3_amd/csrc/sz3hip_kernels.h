@@ -417,6 +417,17 @@ uint64_t szk_tile_mark_units(const szk_region_geom *g, uint64_t *bits, uint64_t 
 // ip = the full array's parameters, codes = its per-element codes, scratch = g->scratch_elems elements, d_out = prod(ext) elements, contiguous
 int szk_launch_interp_decompress_region(int dtype, const szk_interp_params *ip, const szk_region_geom *g, const uint8_t *payload, uint64_t vout_idx_off,
                                         uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, void *scratch, void *d_out, hipStream_t s);
+// n boxes of one level of one stream in one launch sequence. gs: the boxes' geometries with lv[].base already the
+// buffer's place in `scratch` (scratch_elems elements); d_outs: n device pointers, box i's array contiguous. The records the workgroups read
+// are built into h_table (pinned) and go to d_table by one copy on s in front of the first launch; `copied` is recorded behind that copy — the
+// caller waits for it before it lets anybody write h_table again. table_words: what both arrays hold, at least szk_region_multi_table_words.
+// -1: the boxes are not one request (level count, buffer count, pass order) or a window leaves its buffer; nothing was launched
+uint64_t szk_region_multi_table_words(const szk_region_geom *gs, uint32_t n);
+int szk_launch_interp_decompress_region_multi(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
+                                              const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
+                                              void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
+                                              hipStream_t s);
+uint64_t szk_region_launches(void);  // test hook: kernel launches the box reconstructions issued so far
 
 int szk_launch_profile_blocks(int dtype, const void *d_in, int N, const uint64_t *dims, uint64_t bs, uint64_t stride, double abseb,
                               uint8_t *d_flags, uint64_t *total_out, hipStream_t s);

@@ -20,6 +20,9 @@
 #include "sz3hip_devutil.h"
 #include "sz3hip_interp_rules.h"
 
+#include <atomic>
+#include <vector>
+
 // ---- host: the windows ----------------------------------------------------------------------------------------------------------------
 static inline uint64_t sub_sat(uint64_t a, uint64_t b) { return a > b ? a - b : 0; }
 
@@ -312,8 +315,9 @@ struct szk_region_pass {
     uint64_t dims[4], off[4], first[4], step[4], cnt[4], wlo[4], boff[4];
     double eb;
 };
-template <typename T, typename IT>
-__device__ __forceinline__ void region_point(T *__restrict__ buf, const uint16_t *__restrict__ codes, const szk_region_pass &p, uint64_t t) {
+// (P: szk_region_pass, or the same fields put together from a shared and a per-box part — szk_region_pass_parts, the multi-box form below)
+template <typename T, typename IT, typename P>
+__device__ __forceinline__ void region_point(T *__restrict__ buf, const uint16_t *__restrict__ codes, const P &p, uint64_t t) {
     IT r = (IT)t;
     uint64_t idx = 0, a = 0, cd = 0;
 #pragma unroll
@@ -356,6 +360,9 @@ __global__ __launch_bounds__(64) void k_region_first(T *__restrict__ buf, const 
 }
 
 // ---- host: the launches ---------------------------------------------------------------------------------------------------------------
+// test hook (sz3hip_debug_region_launches): kernel launches the box reconstructions of this process issued, single and multi
+static std::atomic<uint64_t> g_region_launches{0};
+uint64_t szk_region_launches(void) { return g_region_launches.load(); }
 template <typename T>
 static int run_region(const szk_interp_params &ip, const szk_region_geom &g, const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off,
                       uint64_t n_vout, const uint16_t *codes, T *scratch, T *d_out, hipStream_t s) {
@@ -381,11 +388,15 @@ static int run_region(const szk_interp_params &ip, const szk_region_geom &g, con
         for (int b = 0; b < g.nbuf; b++) rb.base[b] = g.lv[b].base;
         const uint32_t gr = (uint32_t)((n_vout + 255) / 256 < 4096 ? (n_vout + 255) / 256 : 4096);
         hipLaunchKernelGGL((k_region_scatter_raw<T>), dim3(gr), dim3(256), 0, s, payload, vout_idx_off, vout_val_off, n_vout, num, rb, scratch);
+        g_region_launches++;
     }
     if (g.anchor == 0) {  // the first point, when the coarsest window holds it (then it is the buffer's first element)
         bool at0 = true;
         for (int j = 0; j < N; j++) at0 = at0 && g.lv[0].wlo[j] == 0;
-        if (at0) hipLaunchKernelGGL((k_region_first<T>), dim3(1), dim3(64), 0, s, scratch + g.lv[0].base, codes, ip.eb, ip.radius);
+        if (at0) {
+            hipLaunchKernelGGL((k_region_first<T>), dim3(1), dim3(64), 0, s, scratch + g.lv[0].base, codes, ip.eb, ip.radius);
+            g_region_launches++;
+        }
     }
     for (int b = 0; b < g.n_levels; b++) {
         const szk_region_level &lv = g.lv[b];
@@ -406,6 +417,7 @@ static int run_region(const szk_interp_params &ip, const szk_region_geom &g, con
             const uint64_t nb = (rg.total + 255) / 256;
             if (nb > 0x7FFFFFFFull) return -1;
             hipLaunchKernelGGL((k_region_regrid<T>), dim3((uint32_t)nb), dim3(256), 0, s, (const T *)(scratch + up.base), scratch + lv.base, rg);
+            g_region_launches++;
         }
         const int level = g.n_levels - b;  // the level's number on the grid: stride 2^(level - 1); in the full array it is level + shift
         szk_region_pass p;
@@ -435,9 +447,11 @@ static int run_region(const szk_interp_params &ip, const szk_region_geom &g, con
             if (nb > 0x7FFFFFFFull) return -1;
             p.subpass = 0;
             hipLaunchKernelGGL((k_region_pass<T>), dim3((uint32_t)nb), dim3(256), 0, s, scratch + lv.base, codes, p);
+            g_region_launches++;
             if (!p.old_api && p.interp_id == 0) {  // the deferred last point of even-length lines, as in run_interp
                 p.subpass = 1;
                 hipLaunchKernelGGL((k_region_pass<T>), dim3((uint32_t)nb), dim3(256), 0, s, scratch + lv.base, codes, p);
+                g_region_launches++;
             }
         }
     }
@@ -454,6 +468,7 @@ static int run_region(const szk_interp_params &ip, const szk_region_geom &g, con
     }
     v.contig = 0;
     if (szk_launch_gather(sizeof(T) == 4 ? 0 : 1, 0, scratch + fin.base + corner, &v, d_out, nullptr, s)) return -2;
+    g_region_launches++;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
@@ -465,4 +480,424 @@ int szk_launch_interp_decompress_region(int dtype, const szk_interp_params *ip, 
         if (g->full[j] != ip->dims[j] || g->dims[j] != ((ip->dims[j] - 1) >> g->shift) + 1) return -1;
     return dtype == 0 ? run_region<float>(*ip, *g, payload, vout_idx_off, vout_val_off, n_vout, codes, (float *)scratch, (float *)d_out, s)
                       : run_region<double>(*ip, *g, payload, vout_idx_off, vout_val_off, n_vout, codes, (double *)scratch, (double *)d_out, s);
+}
+
+// ---- n boxes of one level of one stream in one launch sequence -------------------------------------------------------
+// The boxes' reconstructions are independent and their launch sequences identical — the level count and the pass order are the grid's, not
+// the box's —, so one sequence serves them all: blockIdx.y is the box, grid.x covers the largest box of the launch, and a workgroup reads its
+// box's record from a table in device memory (a load that is uniform per workgroup) and leaves when it lies beyond its own box's total.
+// What all boxes of a pass share stays a kernel argument; a record holds what differs. Every record is a row of 64-bit words.
+struct szk_region_pass_shared {  // szk_region_pass without ...
+    int N, dir, interp_id, old_api, subpass, radius;
+    uint32_t ls;
+    uint64_t s, bsz;
+    uint64_t dims[4], off[4], step[4];
+    double eb;
+};
+struct szk_region_pass_box {  // ... the box's part: the pass window's lattice, the level's buffer and where that lies in the scratch
+    uint64_t total, belems, base;
+    uint64_t first[4], cnt[4], wlo[4], boff[4];
+};
+// The two parts as region_point reads them. It indexes dims and boff by the pass's axis, a run-time value: an array in registers cannot be
+// indexed so (the whole struct would go to scratch memory), a chain of selects can — and folds away where the index is a constant.
+struct szk_sel4 {
+    uint64_t v[4];
+    __device__ __forceinline__ uint64_t operator[](int i) const { return i == 0 ? v[0] : i == 1 ? v[1] : i == 2 ? v[2] : v[3]; }
+};
+struct szk_region_pass_parts {
+    int N, dir, interp_id, old_api, subpass, radius;
+    uint32_t ls;
+    uint64_t s, bsz, total, belems;
+    szk_sel4 dims, boff;
+    uint64_t off[4], first[4], step[4], cnt[4], wlo[4];
+    double eb;
+};
+struct szk_region_regrid_box {
+    szk_region_regrid g;
+    uint64_t src, dst;  // the two buffers' bases in the scratch
+};
+struct szk_region_first_box {
+    uint64_t total, base;  // total 1: the box's coarsest window holds the origin
+};
+struct szk_region_gather_box {
+    uint64_t total, src;  // points of the box; its corner in the scratch
+    void *dst;
+    uint64_t ext[4], str[4];  // extents in the last N of four places; the finest buffer's element strides
+};
+struct szk_region_scatter_shared {
+    uint64_t full[4];
+    uint32_t nbuf, shift;
+};
+#define SZK_SCATTER_ROW 9  // words per buffer of a box's scatter record: wlo[4], cnt[4], base
+static_assert(sizeof(szk_region_pass_box) == 19 * 8 && sizeof(szk_region_regrid_box) == 19 * 8 && sizeof(szk_region_gather_box) == 11 * 8, "table records are rows of words");
+
+// k_region_scatter_raw per box: every box scans the whole list (as its own call would) and keeps what falls into its windows
+template <typename T>
+__global__ __launch_bounds__(256) void k_region_scatter_raw_multi(const uint8_t *__restrict__ payload, uint64_t idx_off, uint64_t val_off, uint64_t cnt, uint64_t n,
+                                                                  szk_region_scatter_shared g, const uint64_t *__restrict__ tab, T *__restrict__ scratch) {
+    const uint64_t *idx = reinterpret_cast<const uint64_t *>(payload + idx_off);
+    const T *val = reinterpret_cast<const T *>(payload + val_off);
+    const uint64_t *rec = tab + (uint64_t)blockIdx.y * g.nbuf * SZK_SCATTER_ROW;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * 256) {
+        uint64_t r = idx[i];
+        if (r >= n) continue;
+        uint64_t c[4];
+        c[3] = r % g.full[3];
+        r /= g.full[3];
+        c[2] = r % g.full[2];
+        r /= g.full[2];
+        c[1] = r % g.full[1];
+        c[0] = r / g.full[1];
+        if ((c[0] | c[1] | c[2] | c[3]) & ((1ull << g.shift) - 1)) continue;
+#pragma unroll
+        for (int j = 0; j < 4; j++) c[j] >>= g.shift;
+        const uint64_t any = c[0] | c[1] | c[2] | c[3];
+        const uint32_t top = g.nbuf - 1;
+        const uint32_t tz = any ? (uint32_t)(__ffsll((long long)any) - 1) : 64u;
+        const uint32_t b = tz >= top ? 0u : top - tz;
+        const uint32_t ls = top - b;
+        const uint64_t *lv = rec + (uint64_t)b * SZK_SCATTER_ROW;
+        uint64_t o = 0;
+        bool in = true;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint64_t wlo = lv[j], bc = lv[4 + j];
+            const uint64_t q = (c[j] - wlo) >> ls;
+            in = in && c[j] >= wlo && q < bc;
+            o = o * bc + q;
+        }
+        if (in) scratch[lv[8] + o] = val[i];
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(64) void k_region_first_multi(T *__restrict__ scratch, const uint16_t *__restrict__ codes, double eb, int radius,
+                                                           const szk_region_first_box *__restrict__ recs) {
+    const szk_region_first_box &r = recs[blockIdx.y];
+    if (threadIdx.x == 0 && blockIdx.x == 0 && r.total && codes[0]) scratch[r.base] = ref_recover<T>((T)0, codes[0], eb, radius);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_region_regrid_multi(T *__restrict__ scratch, const szk_region_regrid_box *__restrict__ recs) {
+    const szk_region_regrid_box &b = recs[blockIdx.y];
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= b.g.total) return;
+    uint64_t r = t, so = 0, dx = 0;
+    uint64_t m[4];
+#pragma unroll
+    for (int j = 3; j >= 0; j--) {
+        m[j] = r % b.g.ev[j];
+        r /= b.g.ev[j];
+    }
+    bool in = true;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint64_t sq = m[j] + b.g.shift[j];
+        in = in && sq < b.g.scnt[j];
+        so = so * b.g.scnt[j] + sq;
+        dx = dx * b.g.dcnt[j] + 2 * m[j];
+    }
+    if (in) scratch[b.dst + dx] = scratch[b.src + so];
+}
+// the pass of one box is region_point over szk_region_pass put together again from the two parts; IT by the box's own total, as k_region_pass
+// chooses it
+template <typename T>
+__global__ __launch_bounds__(256) void k_region_pass_multi(T *__restrict__ scratch, const uint16_t *__restrict__ codes, szk_region_pass_shared sh,
+                                                           const szk_region_pass_box *__restrict__ recs) {
+    const szk_region_pass_box &b = recs[blockIdx.y];
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t total = b.total;
+    if (t >= total) return;
+    szk_region_pass_parts p;
+    p.N = sh.N;
+    p.dir = sh.dir;
+    p.interp_id = sh.interp_id;
+    p.old_api = sh.old_api;
+    p.subpass = sh.subpass;
+    p.radius = sh.radius;
+    p.ls = sh.ls;
+    p.s = sh.s;
+    p.bsz = sh.bsz;
+    p.total = total;
+    p.belems = b.belems;
+    p.eb = sh.eb;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        p.dims.v[j] = sh.dims[j];
+        p.off[j] = sh.off[j];
+        p.step[j] = sh.step[j];
+        p.first[j] = b.first[j];
+        p.cnt[j] = b.cnt[j];
+        p.wlo[j] = b.wlo[j];
+        p.boff.v[j] = b.boff[j];
+    }
+    if (total <= 0xFFFFFFFFull) region_point<T, uint32_t>(scratch + b.base, codes, p, t);
+    else region_point<T, uint64_t>(scratch + b.base, codes, p, t);
+}
+// box i out of its finest buffer into d_outs[i], contiguous; lanes run along x
+template <typename T>
+__global__ __launch_bounds__(256) void k_region_gather_multi(const T *__restrict__ scratch, const szk_region_gather_box *__restrict__ recs) {
+    const szk_region_gather_box &b = recs[blockIdx.y];
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= b.total) return;
+    uint64_t r = t, so = 0;
+#pragma unroll
+    for (int j = 3; j >= 0; j--) {
+        so += (r % b.ext[j]) * b.str[j];
+        r /= b.ext[j];
+    }
+    static_cast<T *>(b.dst)[t] = scratch[b.src + so];
+}
+
+// words the table of a request of n boxes takes (an upper bound: every box with every record)
+uint64_t szk_region_multi_table_words(const szk_region_geom *gs, uint32_t n) {
+    const uint64_t nb = (uint64_t)gs[0].nbuf, nl = (uint64_t)gs[0].n_levels, N = (uint64_t)gs[0].N;
+    return (uint64_t)n * (nb * SZK_SCATTER_ROW + 2 + nl * 19 + nl * N * 19 + 11);
+}
+
+namespace {
+struct MultiLaunch {
+    int kind;  // 0 scatter, 1 first, 2 regrid, 3 pass, 4 gather
+    uint64_t off;  // the launch's records in the table, in words
+    uint32_t gx;
+    bool twice;    // pass: the deferred points' launch follows
+    szk_region_pass_shared sh;
+};
+}  // namespace
+template <typename T>
+static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
+                            uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, T *scratch, void *const *d_outs,
+                            uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s) {
+    const szk_region_geom &g0 = gs[0];
+    const int N = g0.N, nbuf = g0.nbuf, n_levels = g0.n_levels;
+    uint64_t num = 1, off[4] = {0, 0, 0, 0};
+    for (int j = N - 1; j >= 0; j--) {
+        off[j] = num << g0.shift;
+        num *= g0.full[j];
+    }
+    // every box's buffers inside the scratch, before anything is built
+    for (uint32_t i = 0; i < n; i++)
+        for (int b = 0; b < nbuf; b++)
+            if (gs[i].lv[b].base > scratch_elems || gs[i].lv[b].elems > scratch_elems - gs[i].lv[b].base) return -1;
+    std::vector<MultiLaunch> seq;
+    uint64_t w = 0;  // the table's cursor
+    auto room = [&](uint64_t words) { return words <= table_words && w <= table_words - words; };
+    auto grid_of = [](uint64_t total, uint32_t *gx) {
+        const uint64_t nb = (total + 255) / 256;
+        if (nb > 0x7FFFFFFFull) return false;
+        *gx = (uint32_t)nb;
+        return true;
+    };
+    if (n_vout) {
+        if (!room((uint64_t)n * nbuf * SZK_SCATTER_ROW)) return -1;
+        MultiLaunch l{};
+        l.kind = 0;
+        l.off = w;
+        l.gx = (uint32_t)((n_vout + 255) / 256 < 4096 ? (n_vout + 255) / 256 : 4096);
+        for (uint32_t i = 0; i < n; i++)
+            for (int b = 0; b < nbuf; b++) {
+                uint64_t *row = h_table + w;
+                for (int q = 0; q < 4; q++) {
+                    const int j = q - (4 - N);
+                    row[q] = j >= 0 ? gs[i].lv[b].wlo[j] : 0;
+                    row[4 + q] = j >= 0 ? gs[i].lv[b].cnt[j] : 1;
+                }
+                row[8] = gs[i].lv[b].base;
+                w += SZK_SCATTER_ROW;
+            }
+        seq.push_back(l);
+    }
+    if (g0.anchor == 0) {  // the first point, for the boxes whose coarsest window holds it
+        if (!room((uint64_t)n * 2)) return -1;
+        bool any = false;
+        const uint64_t at = w;
+        for (uint32_t i = 0; i < n; i++) {
+            bool at0 = true;
+            for (int j = 0; j < N; j++) at0 = at0 && gs[i].lv[0].wlo[j] == 0;
+            szk_region_first_box r = {at0 ? 1ull : 0ull, gs[i].lv[0].base};
+            memcpy(h_table + w, &r, sizeof(r));
+            w += 2;
+            any = any || at0;
+        }
+        if (any) {
+            MultiLaunch l{};
+            l.kind = 1;
+            l.off = at;
+            l.gx = 1;
+            seq.push_back(l);
+        } else {
+            w = at;
+        }
+    }
+    for (int b = 0; b < n_levels; b++) {
+        if (b > 0) {
+            if (!room((uint64_t)n * 19)) return -1;
+            MultiLaunch l{};
+            l.kind = 2;
+            l.off = w;
+            uint64_t most = 0;
+            for (uint32_t i = 0; i < n; i++) {
+                const szk_region_level &lv = gs[i].lv[b], &up = gs[i].lv[b - 1];
+                szk_region_regrid_box r;
+                memset(&r, 0, sizeof(r));
+                r.g.total = 1;
+                for (int q = 0; q < 4; q++) {
+                    const int j = q - (4 - N);
+                    r.g.dcnt[q] = j >= 0 ? lv.cnt[j] : 1;
+                    r.g.scnt[q] = j >= 0 ? up.cnt[j] : 1;
+                    r.g.ev[q] = (r.g.dcnt[q] + 1) / 2;
+                    if (j >= 0 && lv.wlo[j] < up.wlo[j]) return -1;
+                    r.g.shift[q] = j >= 0 ? (lv.wlo[j] - up.wlo[j]) / up.s : 0;
+                    r.g.total *= r.g.ev[q];
+                }
+                r.src = up.base;
+                r.dst = lv.base;
+                memcpy(h_table + w, &r, sizeof(r));
+                w += 19;
+                most = r.g.total > most ? r.g.total : most;
+            }
+            if (!grid_of(most, &l.gx)) return -1;
+            if (most) seq.push_back(l);
+            else w = l.off;
+        }
+        const int level = n_levels - b;
+        szk_region_pass_shared sh;
+        memset(&sh, 0, sizeof(sh));
+        sh.N = N;
+        sh.interp_id = ip.interp_id;
+        sh.old_api = N <= 2;
+        sh.radius = ip.radius;
+        sh.s = g0.lv[b].s;
+        sh.ls = (uint32_t)(level - 1);
+        sh.bsz = 32ull * sh.s;
+        sh.eb = szk_interp_level_eb(ip.eb, ip.alpha, ip.beta, level + g0.shift);
+        for (int j = 0; j < N; j++) {
+            sh.dims[j] = g0.dims[j];
+            sh.off[j] = off[j];
+        }
+        for (int k = 0; k < N; k++) {
+            if (!room((uint64_t)n * 19)) return -1;
+            MultiLaunch l{};
+            l.kind = 3;
+            l.off = w;
+            sh.dir = g0.perm[k];
+            uint64_t most = 0;
+            for (uint32_t i = 0; i < n; i++) {
+                const szk_region_level &lv = gs[i].lv[b];
+                szk_region_pass_box r;
+                memset(&r, 0, sizeof(r));
+                uint64_t step[4] = {0, 0, 0, 0};
+                r.total = szk_region_pass_window(&gs[i], b, k, r.first, step, r.cnt);
+                for (int j = 0; j < N; j++) {
+                    if (i == 0) sh.step[j] = step[j];
+                    else if (sh.step[j] != step[j]) return -1;  // (the lattice's steps are the level's and the pass's)
+                    if (r.total && (r.first[j] < lv.wlo[j] || (r.first[j] + (r.cnt[j] - 1) * step[j] - lv.wlo[j]) / lv.s >= lv.cnt[j])) return -1;  // the window lies on the buffer
+                    r.wlo[j] = lv.wlo[j];
+                    r.boff[j] = lv.boff[j];
+                }
+                r.belems = lv.elems;
+                r.base = lv.base;
+                memcpy(h_table + w, &r, sizeof(r));
+                w += 19;
+                most = r.total > most ? r.total : most;
+            }
+            if (!grid_of(most, &l.gx)) return -1;
+            if (most == 0) {  // (no box has a point in this pass)
+                w = l.off;
+                continue;
+            }
+            l.sh = sh;
+            l.twice = !sh.old_api && sh.interp_id == 0;
+            seq.push_back(l);
+        }
+    }
+    {   // the boxes, out of their finest buffers (stride 1)
+        if (!room((uint64_t)n * 11)) return -1;
+        MultiLaunch l{};
+        l.kind = 4;
+        l.off = w;
+        uint64_t most = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const szk_region_geom &g = gs[i];
+            const szk_region_level &fin = g.lv[nbuf - 1];
+            szk_region_gather_box r;
+            memset(&r, 0, sizeof(r));
+            r.total = 1;
+            r.src = fin.base;
+            r.dst = d_outs[i];
+            for (int q = 0; q < 4; q++) {
+                const int j = q - (4 - N);
+                r.ext[q] = j >= 0 ? g.ext[j] : 1;
+                r.str[q] = j >= 0 ? fin.boff[j] : 0;
+                if (j >= 0) {
+                    if (g.lo[j] < fin.wlo[j] || g.lo[j] - fin.wlo[j] + g.ext[j] > fin.cnt[j]) return -1;  // the box lies on the buffer
+                    r.src += (g.lo[j] - fin.wlo[j]) * fin.boff[j];
+                    r.total *= g.ext[j];
+                }
+            }
+            memcpy(h_table + w, &r, sizeof(r));
+            w += 11;
+            most = r.total > most ? r.total : most;
+        }
+        if (!grid_of(most, &l.gx)) return -1;
+        seq.push_back(l);
+    }
+    // the whole table by one copy, in front of the first launch; `copied` tells the next call's build when the pinned array may be rewritten
+    if (hipMemcpyAsync(d_table, h_table, w * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+    if (hipEventRecord(copied, s) != hipSuccess) return -2;
+    szk_region_scatter_shared ss;
+    memset(&ss, 0, sizeof(ss));
+    ss.nbuf = (uint32_t)nbuf;
+    ss.shift = (uint32_t)g0.shift;
+    for (int q = 0; q < 4; q++) ss.full[q] = q - (4 - N) >= 0 ? g0.full[q - (4 - N)] : 1;
+    for (const MultiLaunch &l : seq) {
+        const dim3 grid(l.gx, n);
+        const uint64_t *rec = d_table + l.off;
+        switch (l.kind) {
+        case 0:
+            hipLaunchKernelGGL((k_region_scatter_raw_multi<T>), grid, dim3(256), 0, s, payload, vout_idx_off, vout_val_off, n_vout, num, ss, rec, scratch);
+            break;
+        case 1:
+            hipLaunchKernelGGL((k_region_first_multi<T>), grid, dim3(64), 0, s, scratch, codes, ip.eb, ip.radius, reinterpret_cast<const szk_region_first_box *>(rec));
+            break;
+        case 2:
+            hipLaunchKernelGGL((k_region_regrid_multi<T>), grid, dim3(256), 0, s, scratch, reinterpret_cast<const szk_region_regrid_box *>(rec));
+            break;
+        case 3: {
+            szk_region_pass_shared sh = l.sh;
+            sh.subpass = 0;
+            hipLaunchKernelGGL((k_region_pass_multi<T>), grid, dim3(256), 0, s, scratch, codes, sh, reinterpret_cast<const szk_region_pass_box *>(rec));
+            if (l.twice) {  // the deferred last point of even-length lines, as in run_region
+                sh.subpass = 1;
+                g_region_launches++;
+                hipLaunchKernelGGL((k_region_pass_multi<T>), grid, dim3(256), 0, s, scratch, codes, sh, reinterpret_cast<const szk_region_pass_box *>(rec));
+            }
+            break;
+        }
+        default:
+            hipLaunchKernelGGL((k_region_gather_multi<T>), grid, dim3(256), 0, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_box *>(rec));
+        }
+        g_region_launches++;
+    }
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int szk_launch_interp_decompress_region_multi(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
+                                              const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
+                                              void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
+                                              hipStream_t s) {
+    if (n < 1 || n > 65535 || !gs || !d_outs || !h_table || !d_table) return -1;
+    for (uint32_t i = 0; i < n; i++) {  // one level of one stream: the grid, the level count, the buffer count and the pass order are the request's
+        const szk_region_geom &g = gs[i];
+        if (g.N != ip->N || g.nbuf < 1 || g.shift < 0 || g.shift > 30) return -1;
+        if (g.n_levels != gs[0].n_levels || g.nbuf != gs[0].nbuf || g.shift != gs[0].shift || g.anchor != gs[0].anchor || memcmp(g.perm, gs[0].perm, sizeof(g.perm))) return -1;
+        for (int j = 0; j < ip->N; j++)
+            if (g.full[j] != ip->dims[j] || g.dims[j] != ((ip->dims[j] - 1) >> g.shift) + 1) return -1;
+        for (int b = 0; b < g.nbuf; b++)
+            if (g.lv[b].s != gs[0].lv[b].s) return -1;
+        if (!d_outs[i]) return -1;
+    }
+    return dtype == 0 ? run_region_multi<float>(*ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, (float *)scratch, d_outs, h_table, d_table,
+                                                table_words, copied, s)
+                      : run_region_multi<double>(*ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, (double *)scratch, d_outs, h_table, d_table,
+                                                 table_words, copied, s);
 }
