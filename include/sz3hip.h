@@ -412,6 +412,56 @@ uint64_t sz3hip_debug_region_scratch(const sz3hip_ctx *ctx);
  * call counts once, whatever the number of its boxes); a container that went through the full-decode fallback does not count */
 uint64_t sz3hip_debug_region_fast_calls(void);
 
+/* ---- an opened stream: everything that does not depend on the box is done once ----
+ * A viewer or an analysis asks one stream for many boxes. Open does, once, what every call above pays again: the zstd stage and the payload's
+ * copy in, the header's round trip, the decoder tables and the DENSE Huffman launch over every unit (a stock ALGO_INTERP stream: the stock
+ * decoder). Open may synchronise. When it returns the handle owns what a request reads — the per-element code array (2 bytes per element), the
+ * raw-value lists, the interpolation parameters, a region scratch and the pinned and device tables — and the caller's blob or payload may be
+ * freed or overwritten. A container that is no single interpolation stream (Lorenzo and block streams, ALGO_NOPRED, ALGO_LOSSLESS, the stock
+ * 1-D chain, conf->openmp slabs, pipelined pieces, an anchor stride that is no power of two) takes the full decode ONCE, at open, into an array
+ * the handle keeps (stats.fast == 0); its requests are strided gathers out of that array. Every container the library decodes can be opened.
+ * float / double only: an integer dataType is SZ3HIP_EUNSUPPORTED, with the partial calls' wording.
+ *   sz3hip_stream_open          an SZ3 container in host memory; conf comes back as the full array's Config; device < 0: the calling thread's
+ *                               current device
+ *   sz3hip_stream_open_payload  a device context's payload (SZH1) in device memory; `stream`: what produced the payload is waited for there
+ *   sz3hip_stream_config        the full array's Config (a payload's: extents, error bound and interpolation fields)
+ *   sz3hip_stream_tiles         sz3hip_decompress_device_tiles' semantics exactly — a level, 1 .. SZ3HIP_MAX_BOXES boxes in coarse coordinates,
+ *                               contiguous outputs, every box and output checked before anything is launched or written, the same codes and
+ *                               wording with "box <i>: " in front, overlapping and repeated boxes allowed, level 0 the region decode, the whole
+ *                               grid as a box the coarse decode — but it runs the reconstruction alone: no Huffman stage, no copy of the payload,
+ *                               no device-to-host copy and no host synchronisation (but the wait for the previous request's table copy, and a
+ *                               scratch or table that has to grow). The request's coarsest levels may run in one launch (sz3hip_debug_chain_points).
+ *   sz3hip_stream_close         waits for the handle's outstanding work, then frees everything. NULL is allowed.
+ * A handle serves ONE request at a time: it is not thread-safe (two handles are independent of each other). A request on another HIP stream
+ * than the previous one's is ordered behind it by an event — the scratch and the tables are shared — without a wait on the host. */
+typedef struct sz3hip_stream sz3hip_stream;
+/* (no typedef: the statistics call carries the struct's name, as stat(2) does — write `struct sz3hip_stream_stats`) */
+struct sz3hip_stream_stats {
+    uint32_t fast;                       /* 1: requests run over the boxes' windows; 0: gathers out of the resident full array */
+    uint32_t huffman_stages;             /* Huffman stages behind this handle's codes: 1 after open, for its life — no request adds one (0 on a handle
+                                          * that keeps the full array: the stages of that one full decode are not counted) */
+    uint32_t launches_last_request;      /* kernel launches the last request issued */
+    uint32_t chain_levels_last_request;  /* ... and how many of its coarsest levels ran inside the chain launch (0: chain off or no level fits) */
+    uint64_t units_total;                /* decoder units (512 codes) of the stream */
+    uint64_t requests;                   /* requests served */
+    uint64_t scratch_elems;              /* capacity of the handle's region scratch, in elements */
+    uint64_t resident_bytes;             /* device memory the handle holds: codes, lists, scratch, table (or the full array) */
+    uint32_t n_levels_last_request;      /* levels the last request's reconstruction ran */
+    uint32_t chain_points;               /* the threshold in force at the last request */
+};
+int sz3hip_stream_open(sz3hip_stream **out, sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int device);
+int sz3hip_stream_open_payload(sz3hip_stream **out, int device, int dataType, const void *d_payload, size_t payload_size, void *stream);
+int sz3hip_stream_config(const sz3hip_stream *h, sz3hip_config *conf);
+int sz3hip_stream_tiles(sz3hip_stream *h, int level, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, void *stream);
+int sz3hip_stream_stats(const sz3hip_stream *h, struct sz3hip_stream_stats *st);
+void sz3hip_stream_close(sz3hip_stream *h);
+/* development switch, process-wide: a request of a handle runs its coarsest c levels in ONE launch (one workgroup per box walks first point,
+ * regrids and passes with a barrier between steps), c the largest count such that for every box every pass of those levels has at most
+ * `points` points. 0: off — the request issues exactly the launches sz3hip_decompress_device_tiles issues. Environment twin, read once when
+ * the setter was never called: SZ3HIP_CHAIN_POINTS. The existing calls never take the chain. */
+void sz3hip_debug_chain_points(uint32_t points);
+uint32_t sz3hip_debug_get_chain_points(void);
+
 /* diagnostics of the last compress on this ctx (valid after sz3hip_compress_finish) */
 typedef struct sz3hip_stats {
     uint64_t n, n_value_outliers, n_delta_outliers, n_chunks, bitstream_bytes, payload_bytes;

@@ -141,6 +141,13 @@ class _CTilesPlan(C.Structure):
                 ("units_needed", C.c_uint64)]
 
 
+class _CStreamStats(C.Structure):
+    """struct sz3hip_stream_stats (include/sz3hip.h)"""
+    _fields_ = [("fast", C.c_uint32), ("huffman_stages", C.c_uint32), ("launches_last_request", C.c_uint32), ("chain_levels_last_request", C.c_uint32),
+                ("units_total", C.c_uint64), ("requests", C.c_uint64), ("scratch_elems", C.c_uint64), ("resident_bytes", C.c_uint64),
+                ("n_levels_last_request", C.c_uint32), ("chain_points", C.c_uint32)]
+
+
 class _CVerifyStats(C.Structure):
     """sz3hip_verify_stats (include/sz3hip.h)"""
     _fields_ = ([(k, C.c_uint64) for k in ("n", "n_nonfinite", "n_nonfinite_mismatch", "n_over", "first_over", "argmax")] +
@@ -278,6 +285,22 @@ def lib():
     L.sz3hip_debug_region_fast_calls.argtypes = []
     L.sz3hip_debug_region_scratch.restype = C.c_uint64
     L.sz3hip_debug_region_scratch.argtypes = [C.c_void_p]
+    L.sz3hip_stream_open.restype = C.c_int
+    L.sz3hip_stream_open.argtypes = [P(C.c_void_p), P(_CConfig), C.c_int, C.c_void_p, C.c_size_t, C.c_int]
+    L.sz3hip_stream_open_payload.restype = C.c_int
+    L.sz3hip_stream_open_payload.argtypes = [P(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.sz3hip_stream_config.restype = C.c_int
+    L.sz3hip_stream_config.argtypes = [C.c_void_p, P(_CConfig)]
+    L.sz3hip_stream_tiles.restype = C.c_int
+    L.sz3hip_stream_tiles.argtypes = [C.c_void_p, C.c_int, P(_CBox), C.c_uint32, P(C.c_void_p), C.c_void_p]
+    L.sz3hip_stream_stats.restype = C.c_int
+    L.sz3hip_stream_stats.argtypes = [C.c_void_p, P(_CStreamStats)]
+    L.sz3hip_stream_close.restype = None
+    L.sz3hip_stream_close.argtypes = [C.c_void_p]
+    L.sz3hip_debug_chain_points.restype = None
+    L.sz3hip_debug_chain_points.argtypes = [C.c_uint32]
+    L.sz3hip_debug_get_chain_points.restype = C.c_uint32
+    L.sz3hip_debug_get_chain_points.argtypes = []
     L.sz3hip_verify_device.restype = C.c_int
     L.sz3hip_verify_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), C.c_void_p, P(C.c_int64), C.c_double,
                                        P(_CVerifyStats), C.c_void_p]
@@ -784,6 +807,102 @@ def decompress_coarse(blob, dtype, level, out=None, device=None, stream=None):
     return _decompress_partial("decompress_coarse", blob, dtype, lambda: (int(level),), lambda conf: (coarse_dims(conf, level), (int(level),)), out, device, stream)
 
 
+def set_chain_points(points):
+    """development switch (sz3hip_debug_chain_points): a Stream request runs its coarsest levels — those whose every pass has at most
+    `points` points for every box — in one launch; 0 switches the chain off"""
+    lib().sz3hip_debug_chain_points(int(points))
+
+
+def get_chain_points():
+    return int(lib().sz3hip_debug_get_chain_points())
+
+
+class Stream:
+    """An opened stream (sz3hip_stream_*): open_stream / DeviceCompressor.open_stream do, once, everything of a partial
+    decode that does not depend on the box — the container's host stage, the copy in, the Huffman stage over every unit — and keep the codes
+    resident on the device; tiles / tile / region / coarse are then the reconstruction alone, bit for bit what decompress_tiles delivers.
+    A container that is no single interpolation stream is decoded in full once (stats()["fast"] == 0) and its requests are gathers.
+    One request at a time: a Stream is not thread-safe. Use as a context manager, or close() it."""
+
+    def __init__(self, handle, dtype, device):
+        self._h = handle
+        self.dtype = np.dtype(dtype)
+        self.device = device
+        c = Config(1)
+        _check(lib().sz3hip_stream_config(self._h, C.byref(c._c)))
+        self.conf = c
+
+    def close(self):
+        if self._h:
+            lib().sz3hip_stream_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def stats(self):
+        st = _CStreamStats()
+        _check(lib().sz3hip_stream_stats(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in _CStreamStats._fields_}
+
+    def tiles(self, level, boxes, out=None, stream=None):
+        """boxes — (lo, shape) pairs in coordinates of the grid of every 2**level-th point — in one request; `out`: a list of contiguous
+        tensors of the boxes' shapes on the stream's device, none overlapping another (default: allocated). Asynchronous on `stream`
+        (a torch stream or a raw handle; default: the device's current stream). Returns the list of tensors."""
+        arr, shapes = _boxes(self.conf.N, boxes)
+        import torch
+        if out is None:
+            out = [torch.empty(shape, dtype=getattr(torch, self.dtype.name), device=self.device) for shape in shapes]
+        out = list(out)
+        if len(out) != len(shapes):
+            raise ValueError("out needs one tensor per box (%d)" % len(shapes))
+        for t, shape in zip(out, shapes):
+            if not _gpu_tensor(t) or _np_dtype(t.dtype) != self.dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("out must hold contiguous %s tensors of the boxes' shapes on a HIP device" % self.dtype)
+        ptrs = (C.c_void_p * max(len(out), 1))(*[t.data_ptr() for t in out])
+        _check(lib().sz3hip_stream_tiles(self._h, int(level), arr, len(shapes), ptrs, _stream_handle(self.device, stream)))
+        return out
+
+    def tile(self, level, lo, shape, out=None, stream=None):
+        """one box of the grid of every 2**level-th point (tiles with one box)"""
+        return self.tiles(level, [(lo, shape)], None if out is None else [out], stream)[0]
+
+    def region(self, lo, shape, out=None, stream=None):
+        """one box of the array itself (tile at level 0)"""
+        return self.tile(0, lo, shape, out, stream)
+
+    def coarse(self, level, out=None, stream=None):
+        """every 2**level-th point of the array (the whole grid as one box)"""
+        dims = coarse_dims(self.conf, level)
+        return self.tile(level, (0,) * len(dims), dims, out, stream)
+
+
+def open_stream(blob, dtype, device=None):
+    """Opens a container for many partial decodes (sz3hip_stream_open): returns a Stream. The blob may be freed or overwritten afterwards.
+    `device`: a torch device, its index, or None for the current one. float32 / float64."""
+    blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
+    npdt = _np_dtype(dtype)
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("open_stream decodes into device memory: device must be a HIP device")
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    h = C.c_void_p()
+    conf = Config(1)
+    _check(lib().sz3hip_stream_open(C.byref(h), C.byref(conf._c), _dtype_id(npdt), blob.ctypes.data, blob.size, index))
+    return Stream(h, npdt, torch.device("cuda", index))
+
+
 class VerifyStats(dict):
     """the fields of sz3hip_verify_stats (include/sz3hip.h), as items and as attributes"""
     __getattr__ = dict.__getitem__
@@ -862,6 +981,7 @@ class DeviceCompressor:
         if not self._h:
             raise SZ3HipError(-4, lib().sz3hip_last_error().decode())
         self.max_elems = int(max_elems)
+        self.device = int(device)
 
     def close(self):
         if self._h:
@@ -943,6 +1063,14 @@ class DeviceCompressor:
             raise ValueError("d_outs needs one pointer per box (%d)" % len(shapes))
         ptrs = (C.c_void_p * max(len(d_outs), 1))(*d_outs)
         _check(lib().sz3hip_decompress_device_tiles(self._h, d_payload, int(size), int(level), arr, len(shapes), ptrs, stream))
+
+    def open_stream(self, d_payload, size, stream=0):
+        """Opens a payload of this context's type that lies in device memory (sz3hip_stream_open_payload): returns a Stream that owns
+        everything its requests read — the payload may be freed or overwritten afterwards. `stream`: what produced the payload is waited for there."""
+        import torch
+        h = C.c_void_p()
+        _check(lib().sz3hip_stream_open_payload(C.byref(h), int(self.device), _dtype_id(self.dtype), d_payload, int(size), stream))
+        return Stream(h, self.dtype, torch.device("cuda", int(self.device)))
 
     def region_scratch(self):
         """capacity of the context's region scratch in elements (0 before its first region call)"""

@@ -2388,6 +2388,11 @@ static int boxes_args(const char *who, const void *boxes, uint32_t n, const void
     if (n == 0 || n > SZ3HIP_MAX_BOXES) return fail(SZ3HIP_EINVAL, "%s: a request holds 1 .. %d boxes (this one %u)", who, SZ3HIP_MAX_BOXES, n);
     return 0;
 }
+int szi_boxes_args(const char *who, const void *boxes, uint32_t n, const void *third, const char *third_name) { return boxes_args(who, boxes, n, third, third_name); }
+int szi_boxes_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, int level, const sz3hip_box *boxes, uint32_t n,
+                       std::vector<szk_region_geom> &gs, uint64_t *scratch_elems) {
+    return boxes_geometry(N, dims, interp_id, direction, anchor_stride, level, boxes, n, gs, scratch_elems);
+}
 // the outputs of a request: n device pointers, box i's array of prod(ext) elements of tsz bytes; none NULL, no two overlapping
 int szi_boxes_outputs_check(int N, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, size_t tsz) {
     std::vector<std::pair<uintptr_t, uintptr_t>> r(n);
@@ -2487,6 +2492,54 @@ extern "C" uint64_t sz3hip_debug_region_fast_calls(void) { return g_region_fast_
 static inline bool is_box(const szi_partial *q) { return q && q->kind == SZI_BOX; }
 static inline bool is_coarse(const szi_partial *q) { return q && q->kind == SZI_COARSE; }
 static inline bool is_boxes(const szi_partial *q) { return q && q->kind == SZI_BOXES; }
+static inline bool is_open(const szi_partial *q) { return q && q->kind == SZI_OPEN; }
+void szi_stream_codes_free(szi_stream_codes *c) {
+    if (c->d_codes) (void)hipFree(c->d_codes);
+    if (c->d_vidx) (void)hipFree(c->d_vidx);
+    if (c->d_vval) (void)hipFree(c->d_vval);
+    c->d_codes = nullptr;
+    c->d_vidx = nullptr;
+    c->d_vval = nullptr;
+    c->bytes = 0;
+}
+// SZI_OPEN: what a later reconstruction of this stream reads — the context's code array and the raw-value lists — copied
+// into arrays of their own on s (the decode's caller synchronises before the context's arrays are reused). The lists as launch_interp_recon takes them.
+static int stream_capture(sz3hip_ctx *ctx, const szk_interp_params *ip, szi_stream_codes *c, const uint8_t *base, uint64_t vout_idx, uint64_t vout_val,
+                          uint64_t n_vout, hipStream_t s) {
+    const size_t tsz = ctx->dtype == SZ3HIP_FLOAT ? 4 : 8;
+    memset(c, 0, sizeof(*c));
+    c->ip = *ip;
+    c->ip.n_vout = c->ip.vout_idx = nullptr;
+    c->ip.vout_val = c->ip.dense2 = nullptr;
+    c->ip.far_cnt = nullptr;
+    c->ip.out_cap = c->ip.dense2_elems = 0;
+    c->n = 1;
+    for (int i = 0; i < ip->N; i++) c->n *= ip->dims[i];
+    c->n_vout = n_vout;
+    const size_t cb = (size_t)c->n * 2 + 64, ib = (size_t)n_vout * 8 + 64, vb = (size_t)n_vout * tsz + 64;
+    if (hipMalloc((void **)&c->d_codes, cb) != hipSuccess || hipMalloc((void **)&c->d_vidx, ib) != hipSuccess || hipMalloc(&c->d_vval, vb) != hipSuccess) {
+        (void)hipGetLastError();
+        szi_stream_codes_free(c);
+        return fail(SZ3HIP_EHIP, "no device memory for the opened stream's codes and lists (%zu bytes)", cb + ib + vb);
+    }
+    c->bytes = cb + ib + vb;
+    hipError_t e = hipMemcpyAsync(c->d_codes, ctx->d_codes, (size_t)c->n * 2, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && n_vout) e = hipMemcpyAsync(c->d_vidx, (const void *)((uintptr_t)base + vout_idx), (size_t)n_vout * 8, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && n_vout) e = hipMemcpyAsync(c->d_vval, (const void *)((uintptr_t)base + vout_val), (size_t)n_vout * tsz, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        szi_stream_codes_free(c);
+        return fail(SZ3HIP_EHIP, "copying the opened stream's codes and lists failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+// an opened stream's requests run the windows: the same condition the region decode has (the messages are region_geometry's)
+static int open_check(uint64_t anchor_stride) {
+    if (anchor_stride & (anchor_stride - 1))
+        return fail(SZ3HIP_EUNSUPPORTED, "the region decode needs an anchor stride that is 0 or a power of two (this one is %llu): the levels' strides and the "
+                    "anchor grid do not nest otherwise", (unsigned long long)anchor_stride);
+    return 0;
+}
 // the context's coarse code array: made by its first coarse call, kept (later calls allocate nothing); then the call's grid against it
 static int coarse_reserve(sz3hip_ctx *ctx, int N, const uint64_t *dims, int level) {
     if (!ctx->d_coarse_codes) {
@@ -2519,6 +2572,7 @@ static int boxes_prepare(sz3hip_ctx *ctx, int N, const uint64_t *dims, int inter
 // The lists as the launchers take them: a payload and offsets into it, or the null base and pointers as offsets.
 static int launch_interp_recon(sz3hip_ctx *ctx, const szk_interp_params *ip, const szi_partial *part, const szk_region_geom *rg, const uint8_t *base,
                                uint64_t vout_idx, uint64_t vout_val, uint64_t n_vout, void *d_out, hipStream_t s, uint64_t boxes_elems = 0) {
+    if (is_open(part)) return stream_capture(ctx, ip, part->open, base, vout_idx, vout_val, n_vout, s);
     if (is_boxes(part)) {
         g_region_fast_calls++;
         ctx->table_pending = true;  // (the launcher records ev_table behind the table's copy)
@@ -2549,6 +2603,10 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
         int rr = boxes_prepare(ctx, p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, part, gs, &boxes_elems);
         if (rr) return rr;
     }
+    if (is_open(part)) {
+        int rr = open_check(p->anchor_stride);
+        if (rr) return rr;
+    }
     const uint64_t num = szi_partial_num(nullptr, p->N, p->dims);
     if (num > ctx->max_n) return fail(SZ3HIP_EINVAL, "array exceeds the context capacity");
     if (is_coarse(part)) {  // (d_out: the coarse grid)
@@ -2575,9 +2633,9 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
         g_tile_units_decoded += units_of(num);
         g_tile_units_total += units_of(num);
     }
-    if (launch_interp_recon(ctx, &ip, part, is_boxes(part) ? gs.data() : &rg, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, d_out, s,
-                            boxes_elems))
-        return fail(SZ3HIP_EHIP, "interpolation decoder launch failed");
+    if (int rr = launch_interp_recon(ctx, &ip, part, is_boxes(part) ? gs.data() : &rg, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, d_out, s,
+                                     boxes_elems))
+        return is_open(part) ? rr : fail(SZ3HIP_EHIP, "interpolation decoder launch failed");
     uint32_t bad = 0;
     HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -2682,6 +2740,13 @@ static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header 
         if (h.ndim < 1 || h.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
         if (h.anchor_stride & (h.anchor_stride - 1)) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header (anchor stride %llu is no power of two)", (unsigned long long)h.anchor_stride);
         int rr = coarse_reserve(ctx, 4, h.dims, part->level);
+        if (rr) return rr;
+    }
+    if (is_open(part)) {
+        if (h.predictor != 1)
+            return fail(SZ3HIP_EUNSUPPORTED, "a stream's codes are kept for interpolation payloads only (this one's predictor id is %d)", h.predictor);
+        if (h.ndim < 1 || h.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
+        int rr = open_check(h.anchor_stride);
         if (rr) return rr;
     }
     szk_region_geom rg;
@@ -2882,8 +2947,9 @@ static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header 
         ip.beta = h.interp_beta;
         ip.eb = h.eb;
         ip.radius = (int)h.radius;
-        if (!region && !multi && !is_coarse(part)) dense2_for(ctx, ip);
+        if (!region && !multi && !is_coarse(part) && !is_open(part)) dense2_for(ctx, ip);
         rc = launch_interp_recon(ctx, &ip, part, multi ? gs.data() : &rg, pl, o.vout_idx, o.vout_val, h.n_vout, d_out, s, boxes_elems);
+        if (rc && is_open(part)) return rc;  // (stream_capture's own refusal)
     } else if (h.predictor == 2) {
         // codes -> deltas, then the blocks in anti-diagonal fronts once the side stream has the choices and coefficients
         rc = szk_launch_blk_decompress(ctx->dtype, ctx->d_codes, d_out, &bp, &sc, pl, &h, &o, ctx->d_blk_coef, s, ctx->ev_join);

@@ -1764,7 +1764,7 @@ int stock_decompress_interp(HostSlot *s, const sz3hip_config *conf, int dataType
     if ((rc = slot_ctx(s, conf->num))) return rc;
     const szi_partial *part = out.part;
     const size_t out_bytes = (size_t)szi_partial_num(part, conf) * tsize;
-    const bool boxes = part && part->kind == SZI_BOXES;  // (the request names its own output arrays: no array of the slot's, nothing to hand out)
+    const bool boxes = szi_partial_own_outputs(part);  // (the request names its own output arrays, or none: no array of the slot's, nothing to hand out)
     void *dst = part && out.in_place() ? (void *)out.dev : nullptr;  // (a partial decode's contiguous output is written where it lies)
     if (!dst && !boxes) {
         if ((rc = ensure_dev(&s->dev_in, &s->dev_in_bytes, out_bytes))) return rc;
@@ -2899,7 +2899,7 @@ int decompress_blob(HostSlot *s, const sz3hip_config *conf, int dataType, const 
     if ((rc = slot_ctx(s, conf->num))) return rc;
     const szi_partial *part = is_int ? nullptr : out.part;
     if (part && hdr.predictor != 1) return fail(SZ3HIP_EFORMAT, "the Config names the interpolation stream but the payload's predictor id is %d", (int)hdr.predictor);
-    const bool boxes = part && part->kind == SZI_BOXES;  // (the request names its own output arrays: no array of the slot's, nothing to hand out)
+    const bool boxes = szi_partial_own_outputs(part);  // (the request names its own output arrays, or none: no array of the slot's, nothing to hand out)
     if (part && (part->kind == SZI_BOX || boxes) && hdr.ndim != (uint32_t)conf->N) return fail(SZ3HIP_EFORMAT, "the payload's extent count does not match the Config");
     const size_t cbytes = (size_t)szi_partial_num(part, conf) * (cdt == SZ3HIP_FLOAT ? 4 : 8);
     // (a device call's contiguous f32 / f64 array is decoded where it lies)
@@ -3364,6 +3364,73 @@ static int partial_boxes_to_device(const char *who, sz3hip_config *conf, int dat
 extern "C" int sz3hip_decompress_tiles_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const sz3hip_box *boxes,
                                                  uint32_t n, void *const *d_outs, void *stream) {
     return partial_boxes_to_device("sz3hip_decompress_tiles_to_device", conf, dataType, cmpData, cmpSize, level, boxes, n, d_outs, stream);
+}
+// sz3hip_stream_open's host side: what partial_boxes_to_device does in front of its boxes, once. The fast path is a decode
+// that stops behind its Huffman stage (SZI_OPEN) and leaves the codes and the lists in arrays `codes` then owns; everything else is the one
+// full decode, into an array the caller keeps. The slot is handed back when this returns: the handle holds no context.
+int szi_stream_open_container(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int device, szi_stream_codes *codes, void **d_full, int *fast,
+                              int *huffman) {
+    memset(codes, 0, sizeof(*codes));
+    *d_full = nullptr;
+    *fast = *huffman = 0;
+    if (!dtype_ok(dataType))
+        return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
+    if (dtype_is_int(dataType)) return fail(SZ3HIP_EUNSUPPORTED, "the region decode reads float / double arrays; integer element types are not supported yet");
+    if (!conf || !cmpData) return fail(SZ3HIP_EINVAL, "sz3hip_stream_open: NULL argument (%s)", !conf ? "conf" : "cmpData");
+    int rc = sz3hip_peek_config(conf, cmpData, cmpSize);
+    if (rc) return rc;
+    if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
+    if (zs::load()) return SZ3HIP_EZSTD;
+    const size_t es = dtype_size(dataType);
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(cmpData) + 8;
+    uint64_t payload;
+    memcpy(&payload, p, 8);
+    p += 8;
+    DeviceGuard guard;
+    if (device < 0) device = guard.prev >= 0 ? guard.prev : 0;
+    HIPCHK(hipSetDevice(device));
+    HostLock lock(conf->openmp);
+    if (!conf->openmp && (conf->cmprAlgo == SZ3HIP_ALGO_HIP_INTERP || conf->cmprAlgo == SZ3HIP_ALGO_INTERP)) {
+        SlotLease lease(device, dtype_compute(dataType));
+        HostSlot *s = lease.s;
+        if (!s->stream) HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        szi_partial q;
+        memset(&q, 0, sizeof(q));
+        q.kind = SZI_OPEN;
+        q.open = codes;
+        DecodeOut o(nullptr);  // (no host destination and no view: the decode delivers nothing but the codes)
+        o.dataType = dataType;
+        o.stream = s->stream;
+        o.part = &q;
+        rc = decompress_blob(s, conf, dataType, p, (size_t)payload, o);
+        if (!rc && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(SZ3HIP_EHIP, "the opened stream's decode failed on the device");
+        if (rc) szi_stream_codes_free(codes);
+        if (rc != SZ3HIP_EUNSUPPORTED) {
+            *fast = *huffman = rc ? 0 : 1;
+            return rc;
+        }
+    }
+    // the full array once, decoded as sz3hip_decompress_to_device does, into an array the handle keeps
+    void *full = nullptr;
+    if (hipMalloc(&full, std::max<size_t>((size_t)conf->num * es, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SZ3HIP_EHIP, "no device memory for the full-size array (%zu bytes) this container's opened stream keeps", (size_t)conf->num * es);
+    }
+    DevArray fd;
+    if (!(rc = dev_array(conf, nullptr, full, true, &fd))) {
+        if (conf->openmp) rc = decompress_slabs(conf, dataType, p, (size_t)payload, nullptr, &fd);
+        else {
+            SlotLease lease(device, dtype_compute(dataType));
+            rc = decode_blob_to(lease.s, conf, dataType, p, (size_t)payload, DecodeOut(nullptr), &fd, 0, conf->dims[0]);
+        }
+    }
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(SZ3HIP_EHIP, "the opened stream's full decode failed on the device");
+    if (rc) {
+        (void)hipFree(full);
+        return rc;
+    }
+    *d_full = full;
+    return 0;
 }
 extern "C" int sz3hip_decompress_coarse_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, void *d_out,
                                                   const int64_t *strides, void *stream) {

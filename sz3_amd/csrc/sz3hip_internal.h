@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/sz3hip.h"
 #include "sz3hip_format.h"
 #include "sz3hip_kernels.h"
@@ -34,14 +36,29 @@ struct szi_stock_params {  // what InterpolationDecomposition::save holds beside
 //   SZI_BOXES   n_boxes boxes of that grid in one request (lo / ext unused): box i is boxes[i], its array — contiguous, of
 //               its ext extents — is d_outs[i] (device pointers in a host array). The decoders write those arrays themselves: the d_out that
 //               travels beside the request is unused, and a DecodeOut counts as delivered once the decode returns 0
-enum { SZI_FULL = 0, SZI_COARSE, SZI_BOX, SZI_BOXES };
+//   SZI_OPEN    no point at all: the decode stops behind its Huffman stage (the dense launch; a stock stream: the stock decoder
+//               and k_stock_to_elem) and copies what a later reconstruction reads — the per-element codes, the raw-value lists, the interpolation
+//               parameters — into arrays of their own that `open` then owns. Like SZI_BOXES it takes no output array. SZ3HIP_EUNSUPPORTED where
+//               the stream is no interpolation stream or its anchor stride no power of two
+enum { SZI_FULL = 0, SZI_COARSE, SZI_BOX, SZI_BOXES, SZI_OPEN };
+struct szi_stream_codes {  // what an opened stream keeps of a single interpolation stream (device arrays from hipMalloc; the owner frees them)
+    szk_interp_params ip;  // N, dims, interp_id, direction, anchor_stride, alpha, beta, eb, radius — the rest zero
+    uint16_t *d_codes;     // ip's element count codes
+    uint64_t *d_vidx;      // the raw records: index and value sections, n_vout entries each
+    void *d_vval;
+    uint64_t n, n_vout, bytes;  // bytes: what the three arrays hold
+};
+void szi_stream_codes_free(szi_stream_codes *c);
 struct szi_partial {
     int kind, level;
     uint64_t lo[4], ext[4];
     uint32_t n_boxes;
     const sz3hip_box *boxes;
     void *const *d_outs;
+    szi_stream_codes *open;  // SZI_OPEN
 };
+// a request that names no output array of the slot's (its decoders deliver by themselves, or deliver nothing)
+static inline bool szi_partial_own_outputs(const szi_partial *q) { return q && (q->kind == SZI_BOXES || q->kind == SZI_OPEN); }
 static inline uint64_t szi_coarse_extent(uint64_t d, int level) { return d ? ((d - 1) >> level) + 1 : 0; }
 // the element count of q's output for an array of N extents (SZI_BOXES: the sum over the boxes)
 static inline uint64_t szi_partial_num(const szi_partial *q, int N, const uint64_t *dims) {
@@ -62,6 +79,16 @@ static inline uint64_t szi_partial_num(const szi_partial *q, const sz3hip_config
 // sz3hip_decompress_device with a partial request (the host API's slots call it; part null: the full decode)
 // the outputs of an SZI_BOXES request: none NULL, no two of them overlapping (tsz: the element size)
 int szi_boxes_outputs_check(int N, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, size_t tsz);
+// a request's argument checks and its boxes' geometries as the multi-box calls make them (sz3hip_api.cpp: boxes_args, boxes_geometry), for the
+// opened stream (sz3hip_stream.cpp)
+int szi_boxes_args(const char *who, const void *boxes, uint32_t n, const void *third, const char *third_name);
+int szi_boxes_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, int level, const sz3hip_box *boxes, uint32_t n,
+                       std::vector<szk_region_geom> &gs, uint64_t *scratch_elems);
+// the host side of sz3hip_stream_open (sz3hip_host.cpp: the container, libzstd and the slots live there): the arguments' checks, then either the
+// stream's codes (*fast = 1) or, for a container that is no single interpolation stream, its full decode in *d_full (hipMalloc; the caller owns it).
+// *huffman: Huffman stages run (0: a container without one). conf comes back as the full array's
+int szi_stream_open_container(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int device, szi_stream_codes *codes, void **d_full, int *fast,
+                              int *huffman);
 int szi_decompress_device_partial(sz3hip_ctx *ctx, const void *d_payload, size_t payload_size, const szi_partial *part, void *d_out, void *stream);
 // after sz3hip_compress_stage1 chose interpolation (header predictor 1): waits for it, reports its parameters and the number of
 // unpredictable values (the anchor grid included); SZ3HIP_EUNSUPPORTED when stage 1 took another predictor

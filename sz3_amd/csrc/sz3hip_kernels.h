@@ -427,6 +427,14 @@ int szk_launch_interp_decompress_region_multi(int dtype, const szk_interp_params
                                               const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                               void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
                                               hipStream_t s);
+// the same for an opened stream's request: with chain_points != 0 the coarsest c levels — the largest count such that for
+// every box every pass of those levels has at most chain_points points — run in ONE launch (k_region_chain_multi: one workgroup per box walks
+// first point, regrids and passes, a barrier between steps); chain_points 0: exactly the launches above. *chain_levels: c; *launches: kernel
+// launches issued
+int szk_launch_interp_decompress_region_chain(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
+                                              const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
+                                              void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
+                                              hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches);
 uint64_t szk_region_launches(void);  // test hook: kernel launches the box reconstructions issued so far
 
 int szk_launch_profile_blocks(int dtype, const void *d_in, int N, const uint64_t *dims, uint64_t bs, uint64_t stride, double abseb,

@@ -647,10 +647,90 @@ __global__ __launch_bounds__(256) void k_region_gather_multi(const T *__restrict
     static_cast<T *>(b.dst)[t] = scratch[b.src + so];
 }
 
-// words the table of a request of n boxes takes (an upper bound: every box with every record)
+
+// ---- the coarsest levels of a request in ONE launch ---------------------------------------------------------------------
+// All but the finest one or two levels of a box are a few thousand points each, and every one of them costs a launch or two per pass. Here one
+// workgroup per box (blockIdx.x) walks a step table — first point, regrid, pass, deferred sub-pass — over the request's coarsest levels: each
+// step is a loop t = threadIdx.x, += 1024 over the body of the multi kernel it replaces (the pass: region_point<T, uint32_t> over
+// szk_region_pass_parts, put together as k_region_pass_multi does), so the arithmetic is that path's by construction. A __syncthreads() follows
+// every step and every thread reaches it (no return around it): the only ordering there is. The box's level buffers are written and read by
+// this one workgroup, in place, with plain loads and stores; `scratch` is neither read-only nor __restrict__ here. No waiting between
+// workgroups, no flags, no atomics, no LDS. A step's records are the multi kernels' own, in the request's table: `rec` is box 0's record (box
+// i's follows i records on), `shared` a pass's szk_region_pass_shared (subpass as the step says), both in words from the table's start.
+struct szk_chain_step {
+    uint64_t kind;  // 1 first point, 2 regrid, 3 pass
+    uint64_t subpass;
+    uint64_t rec, shared;
+};
+static_assert(sizeof(szk_chain_step) == 4 * 8 && sizeof(szk_region_pass_shared) == 19 * 8 && sizeof(szk_region_first_box) == 2 * 8, "table records are rows of words");
+template <typename T>
+__global__ __launch_bounds__(1024) void k_region_chain_multi(T *scratch, const uint16_t *__restrict__ codes, double eb0, int radius, const uint64_t *__restrict__ tab,
+                                                             uint64_t steps_off, uint32_t n_steps) {
+    const uint32_t box = blockIdx.x;
+    const szk_chain_step *steps = reinterpret_cast<const szk_chain_step *>(tab + steps_off);
+    for (uint32_t q = 0; q < n_steps; q++) {
+        const szk_chain_step st = steps[q];
+        if (st.kind == 1) {  // k_region_first_multi
+            const szk_region_first_box &r = reinterpret_cast<const szk_region_first_box *>(tab + st.rec)[box];
+            if (threadIdx.x == 0 && r.total && codes[0]) scratch[r.base] = ref_recover<T>((T)0, codes[0], eb0, radius);
+        } else if (st.kind == 2) {  // k_region_regrid_multi
+            const szk_region_regrid_box &b = reinterpret_cast<const szk_region_regrid_box *>(tab + st.rec)[box];
+            for (uint64_t t = threadIdx.x; t < b.g.total; t += 1024) {
+                uint64_t r = t, so = 0, dx = 0;
+                uint64_t m[4];
+#pragma unroll
+                for (int j = 3; j >= 0; j--) {
+                    m[j] = r % b.g.ev[j];
+                    r /= b.g.ev[j];
+                }
+                bool in = true;
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const uint64_t sq = m[j] + b.g.shift[j];
+                    in = in && sq < b.g.scnt[j];
+                    so = so * b.g.scnt[j] + sq;
+                    dx = dx * b.g.dcnt[j] + 2 * m[j];
+                }
+                if (in) scratch[b.dst + dx] = scratch[b.src + so];
+            }
+        } else {  // k_region_pass_multi
+            const szk_region_pass_shared &sh = *reinterpret_cast<const szk_region_pass_shared *>(tab + st.shared);
+            const szk_region_pass_box &b = reinterpret_cast<const szk_region_pass_box *>(tab + st.rec)[box];
+            const uint64_t total = b.total;  // (at most chain_points, a 32-bit number: the host chose the levels so)
+            szk_region_pass_parts p;
+            p.N = sh.N;
+            p.dir = sh.dir;
+            p.interp_id = sh.interp_id;
+            p.old_api = sh.old_api;
+            p.subpass = (int)st.subpass;
+            p.radius = sh.radius;
+            p.ls = sh.ls;
+            p.s = sh.s;
+            p.bsz = sh.bsz;
+            p.total = total;
+            p.belems = b.belems;
+            p.eb = sh.eb;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                p.dims.v[j] = sh.dims[j];
+                p.off[j] = sh.off[j];
+                p.step[j] = sh.step[j];
+                p.first[j] = b.first[j];
+                p.cnt[j] = b.cnt[j];
+                p.wlo[j] = b.wlo[j];
+                p.boff.v[j] = b.boff[j];
+            }
+            T *buf = scratch + b.base;
+            for (uint64_t t = threadIdx.x; t < total; t += 1024) region_point<T, uint32_t>(buf, codes, p, t);
+        }
+        __syncthreads();
+    }
+}
+
+// words the table of a request of n boxes takes (an upper bound: every box with every record; behind them the chain's pass parameters and steps)
 uint64_t szk_region_multi_table_words(const szk_region_geom *gs, uint32_t n) {
     const uint64_t nb = (uint64_t)gs[0].nbuf, nl = (uint64_t)gs[0].n_levels, N = (uint64_t)gs[0].N;
-    return (uint64_t)n * (nb * SZK_SCATTER_ROW + 2 + nl * 19 + nl * N * 19 + 11);
+    return (uint64_t)n * (nb * SZK_SCATTER_ROW + 2 + nl * 19 + nl * N * 19 + 11) + nl * N * 19 + (1 + nl * (1 + 2 * N)) * 4;
 }
 
 namespace {
@@ -660,14 +740,30 @@ struct MultiLaunch {
     uint32_t gx;
     bool twice;    // pass: the deferred points' launch follows
     szk_region_pass_shared sh;
+    bool chained;  // the launch is a step of the chain's one launch instead
 };
 }  // namespace
 template <typename T>
 static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
                             uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, T *scratch, void *const *d_outs,
-                            uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s) {
+                            uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t chain_points = 0,
+                            uint32_t *chain_levels = nullptr, uint32_t *launches = nullptr) {
     const szk_region_geom &g0 = gs[0];
     const int N = g0.N, nbuf = g0.nbuf, n_levels = g0.n_levels;
+    // the chain takes the coarsest c levels: the largest count such that every pass of those levels has at most chain_points points for EVERY box
+    // (the launch sequence is common to all boxes: the largest one decides)
+    int c = 0;
+    for (; chain_points && c < n_levels; c++) {
+        bool fits = true;
+        for (uint32_t i = 0; i < n && fits; i++)
+            for (int k = 0; k < N && fits; k++) {
+                uint64_t first[4], step[4], cnt[4];
+                fits = szk_region_pass_window(&gs[i], c, k, first, step, cnt) <= chain_points;
+            }
+        if (!fits) break;
+    }
+    if (chain_levels) *chain_levels = (uint32_t)c;
+    uint32_t issued = 0;
     uint64_t num = 1, off[4] = {0, 0, 0, 0};
     for (int j = N - 1; j >= 0; j--) {
         off[j] = num << g0.shift;
@@ -722,6 +818,7 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
             l.kind = 1;
             l.off = at;
             l.gx = 1;
+            l.chained = c > 0;
             seq.push_back(l);
         } else {
             w = at;
@@ -755,6 +852,7 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
                 most = r.g.total > most ? r.g.total : most;
             }
             if (!grid_of(most, &l.gx)) return -1;
+            l.chained = b < c;
             if (most) seq.push_back(l);
             else w = l.off;
         }
@@ -806,6 +904,7 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
             }
             l.sh = sh;
             l.twice = !sh.old_api && sh.interp_id == 0;
+            l.chained = b < c;
             seq.push_back(l);
         }
     }
@@ -840,6 +939,34 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
         if (!grid_of(most, &l.gx)) return -1;
         seq.push_back(l);
     }
+    // the chain's steps, behind the boxes' records: the chained launches in their order, a pass's shared part in front of its step(s)
+    uint64_t steps_off = 0;
+    uint32_t n_steps = 0;
+    if (c > 0) {
+        std::vector<szk_chain_step> steps;
+        for (const MultiLaunch &l : seq) {
+            if (!l.chained) continue;
+            szk_chain_step st = {(uint64_t)l.kind, 0, l.off, 0};
+            if (l.kind == 3) {
+                if (!room(19)) return -1;
+                szk_region_pass_shared sh = l.sh;
+                sh.subpass = 0;
+                memcpy(h_table + w, &sh, sizeof(sh));
+                st.shared = w;
+                w += 19;
+            }
+            steps.push_back(st);
+            if (l.kind == 3 && l.twice) {  // the deferred last point of even-length lines: a step of its own, behind a barrier
+                st.subpass = 1;
+                steps.push_back(st);
+            }
+        }
+        if (!room(steps.size() * 4)) return -1;
+        steps_off = w;
+        n_steps = (uint32_t)steps.size();
+        memcpy(h_table + w, steps.data(), steps.size() * sizeof(szk_chain_step));
+        w += steps.size() * 4;
+    }
     // the whole table by one copy, in front of the first launch; `copied` tells the next call's build when the pinned array may be rewritten
     if (hipMemcpyAsync(d_table, h_table, w * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
     if (hipEventRecord(copied, s) != hipSuccess) return -2;
@@ -848,7 +975,17 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
     ss.nbuf = (uint32_t)nbuf;
     ss.shift = (uint32_t)g0.shift;
     for (int q = 0; q < 4; q++) ss.full[q] = q - (4 - N) >= 0 ? g0.full[q - (4 - N)] : 1;
+    bool chain_done = false;
     for (const MultiLaunch &l : seq) {
+        if (l.chained) {  // (the chained launches follow each other in seq: the one launch stands where the first of them stood)
+            if (!chain_done && n_steps) {
+                hipLaunchKernelGGL((k_region_chain_multi<T>), dim3(n), dim3(1024), 0, s, scratch, codes, ip.eb, ip.radius, (const uint64_t *)d_table, steps_off, n_steps);
+                g_region_launches++;
+                issued++;
+            }
+            chain_done = true;
+            continue;
+        }
         const dim3 grid(l.gx, n);
         const uint64_t *rec = d_table + l.off;
         switch (l.kind) {
@@ -868,6 +1005,7 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
             if (l.twice) {  // the deferred last point of even-length lines, as in run_region
                 sh.subpass = 1;
                 g_region_launches++;
+                issued++;
                 hipLaunchKernelGGL((k_region_pass_multi<T>), grid, dim3(256), 0, s, scratch, codes, sh, reinterpret_cast<const szk_region_pass_box *>(rec));
             }
             break;
@@ -876,7 +1014,9 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
             hipLaunchKernelGGL((k_region_gather_multi<T>), grid, dim3(256), 0, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_box *>(rec));
         }
         g_region_launches++;
+        issued++;
     }
+    if (launches) *launches = issued;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
@@ -885,6 +1025,15 @@ int szk_launch_interp_decompress_region_multi(int dtype, const szk_interp_params
                                               const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                               void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
                                               hipStream_t s) {
+    return szk_launch_interp_decompress_region_chain(dtype, ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, d_outs, h_table, d_table,
+                                                     table_words, copied, s, 0, nullptr, nullptr);
+}
+int szk_launch_interp_decompress_region_chain(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
+                                              const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
+                                              void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
+                                              hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches) {
+    if (chain_levels) *chain_levels = 0;
+    if (launches) *launches = 0;
     if (n < 1 || n > 65535 || !gs || !d_outs || !h_table || !d_table) return -1;
     for (uint32_t i = 0; i < n; i++) {  // one level of one stream: the grid, the level count, the buffer count and the pass order are the request's
         const szk_region_geom &g = gs[i];
@@ -897,7 +1046,7 @@ int szk_launch_interp_decompress_region_multi(int dtype, const szk_interp_params
         if (!d_outs[i]) return -1;
     }
     return dtype == 0 ? run_region_multi<float>(*ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, (float *)scratch, d_outs, h_table, d_table,
-                                                table_words, copied, s)
+                                                table_words, copied, s, chain_points, chain_levels, launches)
                       : run_region_multi<double>(*ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, (double *)scratch, d_outs, h_table, d_table,
-                                                 table_words, copied, s);
+                                                 table_words, copied, s, chain_points, chain_levels, launches);
 }

@@ -1,0 +1,351 @@
+// sz3_amd/csrc/sz3hip_stream.cpp — an opened stream: everything of a partial decode that does not depend on the box is done
+// once, at open; a request is the reconstruction alone.
+//
+// Open runs the existing decode chain with the request kind SZI_OPEN (sz3hip_internal.h): the chain stops behind its Huffman stage — the dense
+// launch over every unit; a stock ALGO_INTERP stream: the stock decoder and k_stock_to_elem — and copies the per-element codes and the raw-value
+// lists into arrays of their own. The handle keeps those, the interpolation parameters, a region scratch and the pinned / device tables: a leaner
+// set than a context (no histogram, code books, outlier lists or payload). A container that is no single interpolation stream is decoded in full,
+// once, into an array the handle keeps; its requests are strided gathers.
+// A request (sz3hip_stream_tiles) is boxes_prepare's checks and the multi-box reconstruction (sz3hip_region.hip) against the resident arrays.
+// A handle serves one request at a time; it is not thread-safe.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <vector>
+
+#include "../../include/sz3hip.h"
+#include "sz3hip_format.h"
+#include "sz3hip_internal.h"
+#include "sz3hip_kernels.h"
+
+#define fail szi_fail
+#define HIPCHK(call)                                                                              \
+    do {                                                                                          \
+        hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) return fail(SZ3HIP_EHIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+struct sz3hip_stream {
+    int device = 0, dtype = 0;
+    int N = 0;
+    uint64_t dims[4] = {0, 0, 0, 0}, num = 0;
+    sz3hip_config conf;
+    bool fast = false;
+    szi_stream_codes codes;  // fast: the codes, the lists, the parameters
+    void *d_full = nullptr;  // else: the full decode
+    void *d_region = nullptr;  // the levels' compact buffers of a request's boxes: made by the first request, grown when one needs more, kept
+    uint64_t region_cap = 0;
+    uint64_t *h_table = nullptr, *d_table = nullptr;  // the records a request's workgroups read, pinned and on the device
+    uint64_t table_cap = 0;
+    hipEvent_t ev_table = nullptr;  // recorded behind the table's copy: the next request waits for it before it writes h_table
+    bool table_pending = false;
+    hipEvent_t ev_req = nullptr;  // recorded behind a request's last launch: a request on another stream is ordered behind it (scratch and tables are shared)
+    bool req_pending = false;
+    hipStream_t last_stream = nullptr;
+    uint32_t huffman_stages = 0, launches_last = 0, chain_last = 0, levels_last = 0, chain_points_last = 0;
+    uint64_t requests = 0;
+};
+
+namespace {
+struct DeviceScope {  // the caller's current device is left as it was found
+    int prev = -1;
+    DeviceScope() {
+        if (hipGetDevice(&prev) != hipSuccess) {
+            (void)hipGetLastError();
+            prev = -1;
+        }
+    }
+    ~DeviceScope() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+inline size_t tsize(int dtype) { return dtype == SZ3HIP_FLOAT ? 4 : 8; }
+
+// the chain's threshold (sz3hip_debug_chain_points; -1: SZ3HIP_CHAIN_POINTS decides at the first request). The default is a measurement
+// (DESIGN.md section 15): 0, the chain off
+constexpr uint32_t CHAIN_POINTS_DEFAULT = 0;
+std::atomic<int64_t> g_chain_points{-1};
+
+int dtype_check(int dataType) {
+    if (dataType < 0 || dataType > 9) return fail(SZ3HIP_EUNSUPPORTED, "dataType %d is not one of SZ_FLOAT .. SZ_INT64 (0 .. 9)", dataType);
+    if (dataType > SZ3HIP_DOUBLE) return fail(SZ3HIP_EUNSUPPORTED, "the region decode reads float / double arrays; integer element types are not supported yet");
+    return 0;
+}
+void release(sz3hip_stream *h) {
+    szi_stream_codes_free(&h->codes);
+    if (h->d_full) (void)hipFree(h->d_full);
+    if (h->d_region) (void)hipFree(h->d_region);
+    if (h->d_table) (void)hipFree(h->d_table);
+    if (h->h_table) (void)hipHostFree(h->h_table);
+    if (h->ev_table) (void)hipEventDestroy(h->ev_table);
+    if (h->ev_req) (void)hipEventDestroy(h->ev_req);
+    delete h;
+}
+int events(sz3hip_stream *h) {
+    HIPCHK(hipEventCreateWithFlags(&h->ev_table, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_req, hipEventDisableTiming));
+    return 0;
+}
+// the handle's scratch and table, as a context keeps them (region_reserve, table_reserve of sz3hip_api.cpp): grown when a request needs more
+int region_reserve(sz3hip_stream *h, uint64_t elems) {
+    if (elems <= h->region_cap) return 0;
+    if (h->d_region) {
+        HIPCHK(hipDeviceSynchronize());  // (an earlier request's kernels may still read it)
+        HIPCHK(hipFree(h->d_region));
+    }
+    h->d_region = nullptr;
+    h->region_cap = 0;
+    if (hipMalloc(&h->d_region, elems * tsize(h->dtype) + 64) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_region = nullptr;
+        return fail(SZ3HIP_EHIP, "no device memory for the region decode's scratch (%zu bytes)", (size_t)(elems * tsize(h->dtype)));
+    }
+    h->region_cap = elems;
+    return 0;
+}
+int table_reserve(sz3hip_stream *h, uint64_t words) {
+    if (words <= h->table_cap) return 0;
+    if (h->d_table) {
+        HIPCHK(hipDeviceSynchronize());  // (an earlier request's copy and kernels may still read them)
+        (void)hipFree(h->d_table);
+    }
+    if (h->h_table) (void)hipHostFree(h->h_table);
+    h->d_table = h->h_table = nullptr;
+    h->table_cap = 0;
+    h->table_pending = false;
+    const uint64_t cap = std::max<uint64_t>(words, 8192);
+    HIPCHK(hipHostMalloc((void **)&h->h_table, cap * 8));
+    HIPCHK(hipMalloc((void **)&h->d_table, cap * 8));
+    h->table_cap = cap;
+    return 0;
+}
+// the boxes of a request against the grid of every 2^level-th point, with the multi-box calls' wording (the fallback: no geometry is made)
+int boxes_on_grid(const sz3hip_stream *h, int level, const sz3hip_box *boxes, uint32_t n) {
+    for (uint32_t b = 0; b < n; b++)
+        for (int i = 0; i < h->N; i++) {
+            const uint64_t cd = szi_coarse_extent(h->dims[i], level), lo = boxes[b].lo[i], ext = boxes[b].ext[i];
+            if (ext == 0) return fail(SZ3HIP_EINVAL, "box %u: the region has extent 0 in dimension %d", b, i);
+            if (lo >= cd || ext > cd - lo)
+                return fail(SZ3HIP_EINVAL, "box %u: the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", b, (unsigned long long)lo, (unsigned long long)lo,
+                            (unsigned long long)ext, i, (unsigned long long)cd);
+        }
+    return 0;
+}
+}  // namespace
+
+extern "C" void sz3hip_debug_chain_points(uint32_t points) { g_chain_points.store((int64_t)points); }
+extern "C" uint32_t sz3hip_debug_get_chain_points(void) {
+    if (g_chain_points.load() < 0) {
+        const char *e = getenv("SZ3HIP_CHAIN_POINTS");
+        g_chain_points.store(e && *e ? (int64_t)std::min<unsigned long long>(strtoull(e, nullptr, 10), 0xFFFFFFFFull) : (int64_t)CHAIN_POINTS_DEFAULT);
+    }
+    return (uint32_t)g_chain_points.load();
+}
+
+extern "C" int sz3hip_stream_open(sz3hip_stream **out, sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int device) {
+    if (!out) return fail(SZ3HIP_EINVAL, "sz3hip_stream_open: NULL argument (out)");
+    *out = nullptr;
+    int rc = dtype_check(dataType);
+    if (rc) return rc;
+    sz3hip_stream *h = new sz3hip_stream();
+    memset(&h->codes, 0, sizeof(h->codes));
+    int fast = 0, huffman = 0;
+    DeviceScope scope;
+    if (device < 0) device = scope.prev >= 0 ? scope.prev : 0;
+    if ((rc = szi_stream_open_container(conf, dataType, cmpData, cmpSize, device, &h->codes, &h->d_full, &fast, &huffman))) {
+        release(h);
+        return rc;
+    }
+    h->device = device;
+    h->dtype = dataType;
+    h->conf = *conf;
+    h->fast = fast != 0;
+    h->huffman_stages = (uint32_t)huffman;
+    h->N = conf->N;
+    h->num = conf->num;
+    for (int i = 0; i < conf->N; i++) h->dims[i] = conf->dims[i];
+    if (hipSetDevice(device) != hipSuccess || (rc = events(h))) {
+        release(h);
+        return rc ? rc : fail(SZ3HIP_EHIP, "hipSetDevice(%d) failed", device);
+    }
+    *out = h;
+    return 0;
+}
+
+extern "C" int sz3hip_stream_open_payload(sz3hip_stream **out, int device, int dataType, const void *d_payload, size_t payload_size, void *stream) {
+    if (!out) return fail(SZ3HIP_EINVAL, "sz3hip_stream_open_payload: NULL argument (out)");
+    *out = nullptr;
+    int rc = dtype_check(dataType);
+    if (rc) return rc;
+    if (!d_payload) return fail(SZ3HIP_EINVAL, "sz3hip_stream_open_payload: the payload is NULL");
+    if (payload_size < sizeof(szh_header)) return fail(SZ3HIP_EFORMAT, "payload shorter than its header");
+    DeviceScope scope;
+    if (device < 0) device = scope.prev >= 0 ? scope.prev : 0;
+    HIPCHK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipStreamSynchronize(s));  // (what produced the payload comes first)
+    szh_header hd;
+    HIPCHK(hipMemcpy(&hd, d_payload, sizeof(hd), hipMemcpyDeviceToHost));
+    if (hd.magic != SZH_MAGIC) return fail(SZ3HIP_EFORMAT, "not an SZH1 payload");
+    if (hd.dtype != dataType) return fail(SZ3HIP_EINVAL, "payload data type does not match the requested one");
+    if (hd.n == 0 || hd.ndim < 1 || hd.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
+    // a context for the length of the open: the header's checks, the tables and the Huffman stage are its decode's; it is destroyed before this
+    // returns (the handle keeps the codes and the lists, not the context)
+    sz3hip_ctx *ctx = sz3hip_ctx_create(device, hd.n, dataType);
+    if (!ctx) return sz3hip_last_error_code();
+    sz3hip_stream *h = new sz3hip_stream();
+    memset(&h->codes, 0, sizeof(h->codes));
+    szi_partial q;
+    memset(&q, 0, sizeof(q));
+    q.kind = SZI_OPEN;
+    q.open = &h->codes;
+    rc = szi_decompress_device_partial(ctx, d_payload, payload_size, &q, nullptr, s);
+    if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = fail(SZ3HIP_EHIP, "the opened stream's decode failed on the device");
+    h->fast = rc == 0;
+    h->huffman_stages = rc == 0 ? 1 : 0;
+    if (rc == SZ3HIP_EUNSUPPORTED) {  // no single interpolation stream the windows nest on: the full decode, once, into an array the handle keeps
+        szi_stream_codes_free(&h->codes);
+        rc = 0;
+        if (hipMalloc(&h->d_full, std::max<size_t>((size_t)hd.n * tsize(dataType), 16)) != hipSuccess) {
+            (void)hipGetLastError();
+            h->d_full = nullptr;
+            rc = fail(SZ3HIP_EHIP, "no device memory for the full-size array (%zu bytes) this payload's opened stream keeps", (size_t)hd.n * tsize(dataType));
+        }
+        if (!rc) rc = sz3hip_decompress_device(ctx, d_payload, payload_size, h->d_full, s);
+        if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = fail(SZ3HIP_EHIP, "the opened stream's full decode failed on the device");
+    }
+    sz3hip_ctx_destroy(ctx);
+    if (!rc) rc = events(h);
+    if (rc) {
+        release(h);
+        return rc;
+    }
+    h->device = device;
+    h->dtype = dataType;
+    h->N = (int)hd.ndim;
+    h->num = hd.n;
+    for (int i = 0; i < h->N; i++) h->dims[i] = hd.dims[4 - h->N + i];
+    // the Config a payload implies: the header's extents as they stand (one entry per extent, also of size 1), bound and interpolation fields
+    sz3hip_config_init(&h->conf, h->N, h->dims);
+    h->conf.N = h->N;
+    for (int i = 0; i < 4; i++) h->conf.dims[i] = i < h->N ? h->dims[i] : 0;
+    h->conf.num = hd.n;
+    h->conf.dataType = (uint8_t)dataType;
+    h->conf.cmprAlgo = hd.predictor == 1 ? SZ3HIP_ALGO_HIP_INTERP : SZ3HIP_ALGO_HIP_LORENZO;
+    h->conf.errorBoundMode = SZ3HIP_EB_ABS;
+    h->conf.absErrorBound = hd.eb;
+    h->conf.quantbinCnt = (int32_t)(2 * hd.radius);
+    if (hd.predictor == 1) {
+        h->conf.interpAlgo = (uint8_t)hd.interp_id;
+        h->conf.interpDirection = (uint8_t)hd.interp_dir;
+        h->conf.interpAnchorStride = (int32_t)hd.anchor_stride;
+        h->conf.interpAlpha = hd.interp_alpha;
+        h->conf.interpBeta = hd.interp_beta;
+    }
+    *out = h;
+    return 0;
+}
+
+extern "C" int sz3hip_stream_config(const sz3hip_stream *h, sz3hip_config *conf) {
+    if (!h || !conf) return fail(SZ3HIP_EINVAL, "sz3hip_stream_config: %s", !h ? "no handle" : "NULL argument (conf)");
+    *conf = h->conf;
+    return 0;
+}
+
+extern "C" int sz3hip_stream_stats(const sz3hip_stream *h, struct sz3hip_stream_stats *st) {
+    if (!h || !st) return fail(SZ3HIP_EINVAL, "sz3hip_stream_stats: %s", !h ? "no handle" : "NULL argument (st)");
+    memset(st, 0, sizeof(*st));
+    st->fast = h->fast ? 1 : 0;
+    st->huffman_stages = h->huffman_stages;
+    st->launches_last_request = h->launches_last;
+    st->chain_levels_last_request = h->chain_last;
+    st->units_total = (h->num + SZH_UNIT_SYMS - 1) / SZH_UNIT_SYMS;
+    st->requests = h->requests;
+    st->scratch_elems = h->region_cap;
+    st->resident_bytes = h->codes.bytes + (h->d_full ? std::max<uint64_t>(h->num * tsize(h->dtype), 16) : 0) + (h->d_region ? h->region_cap * tsize(h->dtype) + 64 : 0) +
+                         h->table_cap * 8;
+    st->n_levels_last_request = h->levels_last;
+    st->chain_points = h->chain_points_last;
+    return 0;
+}
+
+extern "C" int sz3hip_stream_tiles(sz3hip_stream *h, int level, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, void *stream) {
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_tiles: no handle");
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
+    int rc = szi_boxes_args("sz3hip_stream_tiles", boxes, n, d_outs, "d_outs");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    if (!h->fast) {  // strided gathers out of the resident array (nothing of it is written after open: no ordering between requests is needed)
+        if ((rc = boxes_on_grid(h, level, boxes, n)) || (rc = szi_boxes_outputs_check(h->N, boxes, n, d_outs, tsize(h->dtype)))) return rc;
+        HIPCHK(hipSetDevice(h->device));
+        uint64_t str[4] = {0, 0, 0, 0}, run = 1;
+        for (int i = h->N - 1; i >= 0; i--) {
+            str[i] = run;
+            run *= h->dims[i];
+        }
+        for (uint32_t b = 0; b < n; b++) {
+            szk_view gv;
+            memset(&gv, 0, sizeof(gv));
+            uint64_t corner = 0;
+            for (int q = 0; q < 4; q++) {
+                const int i = q - (4 - h->N);
+                gv.dims[q] = i >= 0 ? boxes[b].ext[i] : 1;
+                gv.str[q] = i >= 0 && boxes[b].ext[i] > 1 ? (int64_t)(str[i] << level) : 0;
+                if (i >= 0) corner += (boxes[b].lo[i] << level) * str[i];
+            }
+            if (szk_launch_gather(h->dtype, 0, (const char *)h->d_full + corner * tsize(h->dtype), &gv, d_outs[b], nullptr, s)) return fail(SZ3HIP_EHIP, "gather kernel failed");
+        }
+        h->launches_last = n;
+        h->chain_last = h->levels_last = 0;
+        h->chain_points_last = sz3hip_debug_get_chain_points();
+        h->requests++;
+        return 0;
+    }
+    // every box and every output before anything is launched or written (boxes_prepare of sz3hip_api.cpp, on the handle's arrays)
+    const szk_interp_params &ip = h->codes.ip;
+    std::vector<szk_region_geom> gs;
+    uint64_t elems = 0;
+    if ((rc = szi_boxes_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, level, boxes, n, gs, &elems))) return rc;
+    if ((rc = szi_boxes_outputs_check(ip.N, boxes, n, d_outs, tsize(h->dtype)))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = region_reserve(h, elems)) || (rc = table_reserve(h, szk_region_multi_table_words(gs.data(), n)))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    const uint32_t chain_points = sz3hip_debug_get_chain_points();
+    uint32_t chain_levels = 0, launches = 0;
+    h->table_pending = true;  // (the launcher records ev_table behind the table's copy)
+    // (the lists are the handle's own arrays: handed over as offsets from a null base, as a stock stream's are)
+    const int lr = szk_launch_interp_decompress_region_chain(h->dtype, &ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx, (uint64_t)(uintptr_t)h->codes.d_vval,
+                                                             h->codes.n_vout, h->codes.d_codes, h->d_region, d_outs, h->h_table, h->d_table, h->table_cap, h->ev_table, s,
+                                                             chain_points, &chain_levels, &launches);
+    HIPCHK(hipEventRecord(h->ev_req, s));
+    h->req_pending = true;
+    h->last_stream = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's reconstruction could not be launched (%d)", lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = (uint32_t)gs[0].n_levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+extern "C" void sz3hip_stream_close(sz3hip_stream *h) {
+    if (!h) return;
+    DeviceScope scope;
+    if (hipSetDevice(h->device) == hipSuccess) {
+        if (h->req_pending) (void)hipEventSynchronize(h->ev_req);
+        if (h->table_pending) (void)hipEventSynchronize(h->ev_table);
+        // (a fallback handle's gathers carry no event: everything queued on the device)
+        if (!h->fast) (void)hipDeviceSynchronize();
+    }
+    release(h);
+}
