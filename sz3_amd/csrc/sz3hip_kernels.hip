@@ -2127,7 +2127,13 @@ __global__ __launch_bounds__(256) void k_hist_reduce(const uint32_t *__restrict_
 //             merge (every round pairs ALL items below the smallest possible new node), chunked code assignment.
 //   block 1/2 deterministic order of the two outlier lists.
 // Code lengths are limited to 16 bits for alphabets up to 512 symbols (the packer then joins four code words per
-// 64-bit register; the loss is < 0.01 bit/symbol) and to SZH_MAX_LEN = 24 bits otherwise (two per register).
+// 64-bit register) and to SZH_MAX_LEN = 24 bits otherwise (two per register). Where the limit binds, cb_kraft_repair lengthens whole
+// leaves to the limit: next to free when the clamp meets a few rare leaves (a field's tail, the margins' bins), far from the
+// length-limited optimum on deep trees (Fibonacci-like counts: 0.27 % of the stream with five levels clamped, 3.6 % with eleven). The
+// small path therefore measures what the repair cost and, beyond 1 / 2048 of the stream, takes the optimum by package-merge
+// (cb_package_merge: alphabets up to 512 symbols, arrays below 2^28 elements; the loss is then < 0.01 bit/symbol and < 0.2 %). The wide
+// path's 24-bit limit keeps the closed form: 0.12 % on Fibonacci counts three levels too deep. profiles/r16_crafted_codes.txt,
+// tests/test_gpu_crafted_codes.py.
 // ------------------------------------------------------------------------------------------------------------
 #define CB_THREADS 256       // threads of the small-alphabet path
 #define CB_LAUNCH 1024       // threads per workgroup of the launch
@@ -2611,6 +2617,73 @@ __device__ void cb_kraft_repair(uint16_t *pleaf, uint32_t m, uint32_t *s_cnt, ui
     if (t < SZH_MAX_LEN + 2) s_cnt[t] = 0;
     __syncthreads();
     for (uint32_t q = t; q < m; q += NT) atomicAdd(&s_cnt[pleaf[q]], 1u);
+    __syncthreads();
+}
+
+// The length-limited optimum by package-merge (Larmore & Hirschberg, boundary form) for the small path's short alphabets, where the
+// closed form above is far from it (deep trees: Fibonacci-like counts). keys: (weight << 16) | symbol ascending, weights' sum < 2^28
+// (a package holds a leaf once per level: < 16 sums). Level by level, deepest first, the m leaves are merged with the packages — pairs —
+// of the level below: an item's place is its index plus its rank in the other list (leaves in front of packages of equal weight); a bit
+// per place says "leaf". The cheapest 2m - 2 items of the top level are the solution; walking down, every package taken stands for
+// two items of the level below, and a leaf's length is the number of levels that took it — the q cheapest leaves of a level are the
+// ones taken. NT live threads. M: [2m] u32, P: [m] u32, F: [L * ceil(2m / 32)] u32, all LDS. pleaf and s_cnt are rebuilt.
+__device__ void cb_package_merge(const uint64_t *keys, uint32_t m, uint32_t L, uint16_t *pleaf, uint32_t *s_cnt, uint32_t *M, uint32_t *P,
+                                 uint32_t *F, uint32_t NT) {
+    const uint32_t t = threadIdx.x;
+    const uint32_t SW = (2 * m + 31) / 32;
+    for (uint32_t i = t; i < L * SW; i += NT) F[i] = 0;
+    __syncthreads();
+    uint32_t np = 0;
+    for (uint32_t lev = 0; lev < L; lev++) {
+        uint32_t *f = F + lev * SW;
+        for (uint32_t i = t; i < m; i += NT) {
+            const uint32_t w = (uint32_t)(keys[i] >> 16);
+            uint32_t a = 0, b = np;  // packages lighter than the leaf
+            while (a < b) {
+                const uint32_t mid = (a + b) >> 1;
+                if (P[mid] < w) a = mid + 1;
+                else b = mid;
+            }
+            const uint32_t pos = i + a;
+            M[pos] = w;
+            atomicOr(&f[pos >> 5], 1u << (pos & 31u));
+        }
+        for (uint32_t j = t; j < np; j += NT) {
+            const uint32_t w = P[j];
+            uint32_t a = 0, b = m;  // leaves not heavier than the package
+            while (a < b) {
+                const uint32_t mid = (a + b) >> 1;
+                if ((uint32_t)(keys[mid] >> 16) <= w) a = mid + 1;
+                else b = mid;
+            }
+            M[j + a] = w;
+        }
+        __syncthreads();
+        np = (m + np) / 2;
+        for (uint32_t k = t; k < np; k += NT) P[k] = M[2 * k] + M[2 * k + 1];
+        __syncthreads();
+    }
+    if (t == 0) {
+        uint32_t take = 2 * m - 2;
+        for (uint32_t lev = L; lev-- > 0;) {
+            const uint32_t *f = F + lev * SW;
+            uint32_t leaves = 0;
+            for (uint32_t w = 0; w < SW && w * 32 < take; w++) {
+                const uint32_t rem = take - w * 32;
+                leaves += (uint32_t)__popc(rem >= 32 ? f[w] : f[w] & ((1u << rem) - 1u));
+            }
+            M[lev] = leaves;
+            take = 2 * (take - leaves);
+        }
+    }
+    if (t < SZH_MAX_LEN + 2) s_cnt[t] = 0;
+    __syncthreads();
+    for (uint32_t q = t; q < m; q += NT) {
+        uint32_t l = 0;
+        for (uint32_t lev = 0; lev < L; lev++) l += q < M[lev];
+        pleaf[q] = (uint16_t)l;
+        atomicAdd(&s_cnt[l], 1u);
+    }
     __syncthreads();
 }
 
@@ -3165,9 +3238,14 @@ __device__ void cb_small(const uint64_t *__restrict__ hist, const szk_cb_params 
             __syncthreads();
         }
         if (t == 0) p.info->ts[5] = wall_clock64();
-        // 5. leaf lengths (sorted position q), clamp to L, per-length counts
+        // 5. leaf lengths (sorted position q), clamp to L, per-length counts; the unclamped code's bits beside them
+        __shared__ unsigned long long s_bits[2];  // [0] the unclamped code's total bits (depths beyond 2^r count 2^r), [1] the repaired code's
+        if (t < 2) s_bits[t] = 0;
+        __syncthreads();
+        unsigned long long free_bits = 0;
         for (uint32_t q = t; q < m; q += CB_THREADS) {
             uint32_t l = (uint32_t)aux[pleaf[q]] + 1;
+            free_bits += (keys[q] >> 16) * l;
             if (l > L) {
                 l = L;
                 s_over = 1;
@@ -3175,8 +3253,22 @@ __device__ void cb_small(const uint64_t *__restrict__ hist, const szk_cb_params 
             pleaf[q] = (uint16_t)l;
             atomicAdd(&s_cnt[l], 1u);
         }
+        if (free_bits) atomicAdd(&s_bits[0], free_bits);
         __syncthreads();
-        if (s_over) cb_kraft_repair(pleaf, m, s_cnt, L, CB_THREADS, reinterpret_cast<uint64_t *>(cnt_tbl));
+        if (s_over) {
+            cb_kraft_repair(pleaf, m, s_cnt, L, CB_THREADS, reinterpret_cast<uint64_t *>(cnt_tbl));
+            // The closed form is next to free where the clamp met a few rare leaves (a field's tail, the margins' bins): kept whenever it
+            // costs less than 1 / 2048 of the stream. Beyond that (deep trees) short alphabets take the optimum by package-merge.
+            if (L == 16u && m <= CB_SHORT_SYMS && s_total < (1ull << 28)) {
+                unsigned long long bits = 0;
+                for (uint32_t q = t; q < m; q += CB_THREADS) bits += (keys[q] >> 16) * pleaf[q];
+                if (bits) atomicAdd(&s_bits[1], bits);
+                __syncthreads();
+                if ((s_bits[1] - s_bits[0]) * 2048ull > s_bits[0])
+                    cb_package_merge(keys, m, L, pleaf, s_cnt, reinterpret_cast<uint32_t *>(ifreq), reinterpret_cast<uint32_t *>(pint),
+                                     reinterpret_cast<uint32_t *>(aux2), CB_THREADS);
+            }
+        }
         // 6. canonical first code per length
         if (t == 0) {
             uint32_t code = 0;
