@@ -2567,21 +2567,33 @@ static int boxes_prepare(sz3hip_ctx *ctx, int N, const uint64_t *dims, int inter
     }
     return 0;
 }
-// The reconstruction of an interpolation stream for a request: the whole array, its coarse grid, a box (rg: the box's geometry) or several
-// (rg: their geometries, placed in boxes_elems elements of the context's scratch; one fast call whatever their number).
+// A box request (SZI_BOX: one geometry, refused in region_geometry's own words, no table and no wait) or a multi-box one, before anything is
+// launched: gs holds n >= 1 geometries either way and only the launch differs. units: the call runs the Huffman stage over a unit list.
+static int box_request_prepare(sz3hip_ctx *ctx, int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const szi_partial *part, bool units,
+                               std::vector<szk_region_geom> &gs, uint64_t *elems) {
+    if (is_boxes(part)) return boxes_prepare(ctx, N, dims, interp_id, direction, anchor_stride, part, gs, elems);
+    gs.resize(1);
+    int rr = region_geometry(N, dims, interp_id, direction, anchor_stride, part->lo, part->ext, &gs[0], part->level);
+    if (rr) return rr;
+    *elems = gs[0].scratch_elems;
+    if ((rr = region_reserve(ctx, *elems))) return rr;
+    return units ? tile_units_reserve(ctx) : 0;
+}
+// The reconstruction of an interpolation stream for a request: the whole array, its coarse grid, a box (gs: the box's geometry) or several
+// (gs: their geometries, placed in boxes_elems elements of the context's scratch; one fast call whatever their number).
 // The lists as the launchers take them: a payload and offsets into it, or the null base and pointers as offsets.
-static int launch_interp_recon(sz3hip_ctx *ctx, const szk_interp_params *ip, const szi_partial *part, const szk_region_geom *rg, const uint8_t *base,
+static int launch_interp_recon(sz3hip_ctx *ctx, const szk_interp_params *ip, const szi_partial *part, const szk_region_geom *gs, const uint8_t *base,
                                uint64_t vout_idx, uint64_t vout_val, uint64_t n_vout, void *d_out, hipStream_t s, uint64_t boxes_elems = 0) {
     if (is_open(part)) return stream_capture(ctx, ip, part->open, base, vout_idx, vout_val, n_vout, s);
     if (is_boxes(part)) {
         g_region_fast_calls++;
         ctx->table_pending = true;  // (the launcher records ev_table behind the table's copy)
-        return szk_launch_interp_decompress_region_multi(ctx->dtype, ip, rg, part->n_boxes, boxes_elems, base, vout_idx, vout_val, n_vout, ctx->d_codes, ctx->d_region,
-                                                         part->d_outs, ctx->h_table, ctx->d_table, ctx->table_cap, ctx->ev_table, s);
+        return szk_launch_interp_decompress_region_multi(ctx->dtype, ip, gs, part->n_boxes, boxes_elems, base, vout_idx, vout_val, n_vout, ctx->d_codes, ctx->d_region,
+                                                         part->d_outs, ctx->h_table, ctx->d_table, ctx->table_cap, ctx->ev_table, s, 0, nullptr, nullptr);
     }
     if (is_box(part)) {
         g_region_fast_calls++;
-        return szk_launch_interp_decompress_region(ctx->dtype, ip, rg, base, vout_idx, vout_val, n_vout, ctx->d_codes, ctx->d_region, d_out, s);
+        return szk_launch_interp_decompress_region(ctx->dtype, ip, gs, base, vout_idx, vout_val, n_vout, ctx->d_codes, ctx->d_region, d_out, s);
     }
     if (is_coarse(part)) return szk_launch_interp_decompress_coarse(ctx->dtype, ip, part->level, base, vout_idx, vout_val, n_vout, ctx->d_codes, ctx->d_coarse_codes, d_out, s);
     return szk_launch_interp_decompress(ctx->dtype, ip, base, vout_idx, vout_val, n_vout, ctx->d_codes, d_out, s);
@@ -2592,15 +2604,10 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
                      uint32_t *d_bad, void *d_out, void *stream, const szi_partial *part) {
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
-    szk_region_geom rg;
-    std::vector<szk_region_geom> gs;  // (several boxes: their geometries; d_out is unused)
+    std::vector<szk_region_geom> gs;  // (a box: its geometry, d_out is the box; several: theirs, d_out is unused)
     uint64_t boxes_elems = 0;
-    if (is_box(part)) {  // (d_out: the box. The windows and the context's scratch, before anything is launched)
-        int rr = region_geometry(p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, part->lo, part->ext, &rg, part->level);
-        if (rr || (rr = region_reserve(ctx, rg.scratch_elems))) return rr;
-    }
-    if (is_boxes(part)) {
-        int rr = boxes_prepare(ctx, p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, part, gs, &boxes_elems);
+    if (is_box(part) || is_boxes(part)) {  // (the windows and the context's scratch, before anything is launched)
+        int rr = box_request_prepare(ctx, p->N, p->dims, p->interp_id, p->direction, p->anchor_stride, part, false, gs, &boxes_elems);
         if (rr) return rr;
     }
     if (is_open(part)) {
@@ -2633,7 +2640,7 @@ int szi_stock_import(sz3hip_ctx *ctx, const szi_stock_params *p, const szg_geom 
         g_tile_units_decoded += units_of(num);
         g_tile_units_total += units_of(num);
     }
-    if (int rr = launch_interp_recon(ctx, &ip, part, is_boxes(part) ? gs.data() : &rg, nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, d_out, s,
+    if (int rr = launch_interp_recon(ctx, &ip, part, gs.data(), nullptr, (uint64_t)(uintptr_t)d_vout_idx, (uint64_t)(uintptr_t)d_vout_val, n_unpred, d_out, s,
                                      boxes_elems))
         return is_open(part) ? rr : fail(SZ3HIP_EHIP, "interpolation decoder launch failed");
     uint32_t bad = 0;
@@ -2731,7 +2738,7 @@ static int decode_header(sz3hip_ctx *ctx, const void *d_payload, size_t payload_
 // DESIGN.md §11; a box of it, §12, or of that grid, §13) share the header's parse and the Huffman stage; they differ in the units a box
 // has decoded and in the reconstruction.
 static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header &h, const szh_offsets &o, const szi_partial *part, void *d_out, hipStream_t s) {
-    const bool region = is_box(part), multi = is_boxes(part);
+    const bool boxed = is_box(part) || is_boxes(part);  // (one box or several: n >= 1 geometries, gs)
     uint32_t *ovf = reinterpret_cast<uint32_t *>(ctx->d_counters + 12);  // overflow flag of the half-width chain (see below)
     if (is_coarse(part)) {
         if (h.predictor != 1)
@@ -2749,21 +2756,14 @@ static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header 
         int rr = open_check(h.anchor_stride);
         if (rr) return rr;
     }
-    szk_region_geom rg;
-    std::vector<szk_region_geom> gs;  // (several boxes: their geometries; d_out is unused)
+    std::vector<szk_region_geom> gs;  // (a box: its geometry, d_out is the box; several: theirs, d_out is unused)
     uint64_t boxes_elems = 0;
-    if (region || multi) {
+    if (boxed) {
         if (h.predictor != 1)
             return fail(SZ3HIP_EUNSUPPORTED, "sz3hip_decompress_device_region reads interpolation payloads only (this one's predictor id is %d): a device context has "
                         "no full-size scratch of its own — sz3hip_decompress_region_to_device decodes every container", h.predictor);
         if (h.ndim < 1 || h.ndim > 4) return fail(SZ3HIP_EFORMAT, "corrupt SZH1 header");
-        int rr;
-        if (multi) {
-            rr = boxes_prepare(ctx, h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, part, gs, &boxes_elems);
-        } else {
-            rr = region_geometry(h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, part->lo, part->ext, &rg, part->level);
-            if (!rr && !(rr = region_reserve(ctx, rg.scratch_elems))) rr = tile_units_reserve(ctx);
-        }
+        int rr = box_request_prepare(ctx, h.ndim, h.dims + 4 - h.ndim, (int)h.interp_id, (int)h.interp_dir, h.anchor_stride, part, true, gs, &boxes_elems);
         if (rr) return rr;
     }
     const uint8_t *pl = (const uint8_t *)d_payload;
@@ -2839,7 +2839,7 @@ static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header 
     szk_dec_params dp;
     dp.unit_list = nullptr;
     dp.n_list = 0;
-    if (region || multi) {
+    if (boxed) {
         // the units the tile's passes read a code from (built while the tables' launch runs); few enough: the Huffman stage decodes those alone.
         // The other units keep what the code array held — the list covers every read. Several boxes: one stage for the union of their units —
         // every box marks into the one bit array (newly set bits count) with what is left of the limit as its budget
@@ -2849,8 +2849,8 @@ static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header 
             memset(ctx->unit_bits, 0, (size_t)((total + 63) / 64) * 8);
             uint64_t marked = 0;
             bool within = true;
-            for (uint32_t i = 0, nb = multi ? part->n_boxes : 1; i < nb && within; i++) {
-                const uint64_t left = limit - marked, m = szk_tile_mark_units(multi ? &gs[i] : &rg, ctx->unit_bits, left);
+            for (size_t i = 0; i < gs.size() && within; i++) {
+                const uint64_t left = limit - marked, m = szk_tile_mark_units(&gs[i], ctx->unit_bits, left);
                 within = m <= left;
                 marked += within ? m : 0;
             }
@@ -2947,8 +2947,8 @@ static int decode_body(sz3hip_ctx *ctx, const void *d_payload, const szh_header 
         ip.beta = h.interp_beta;
         ip.eb = h.eb;
         ip.radius = (int)h.radius;
-        if (!region && !multi && !is_coarse(part) && !is_open(part)) dense2_for(ctx, ip);
-        rc = launch_interp_recon(ctx, &ip, part, multi ? gs.data() : &rg, pl, o.vout_idx, o.vout_val, h.n_vout, d_out, s, boxes_elems);
+        if (!boxed && !is_coarse(part) && !is_open(part)) dense2_for(ctx, ip);
+        rc = launch_interp_recon(ctx, &ip, part, gs.data(), pl, o.vout_idx, o.vout_val, h.n_vout, d_out, s, boxes_elems);
         if (rc && is_open(part)) return rc;  // (stream_capture's own refusal)
     } else if (h.predictor == 2) {
         // codes -> deltas, then the blocks in anti-diagonal fronts once the side stream has the choices and coefficients

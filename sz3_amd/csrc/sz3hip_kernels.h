@@ -421,21 +421,17 @@ int szk_launch_interp_decompress_region(int dtype, const szk_interp_params *ip, 
 // buffer's place in `scratch` (scratch_elems elements); d_outs: n device pointers, box i's array contiguous. The records the workgroups read
 // are built into h_table (pinned) and go to d_table by one copy on s in front of the first launch; `copied` is recorded behind that copy — the
 // caller waits for it before it lets anybody write h_table again. table_words: what both arrays hold, at least szk_region_multi_table_words.
-// -1: the boxes are not one request (level count, buffer count, pass order) or a window leaves its buffer; nothing was launched
+// -1: the boxes are not one request (level count, buffer count, pass order) or a window leaves its buffer; nothing was launched.
+// chain_points (a context's calls pass 0, an opened stream's requests its threshold): unless 0, the coarsest c levels — the
+// largest count such that for every box every pass of those levels has at most chain_points points — run in ONE launch (k_region_chain_multi:
+// one workgroup per box walks first point, regrids and passes, a barrier between steps). *chain_levels: c; *launches: kernel launches issued
+// (either may be NULL)
 uint64_t szk_region_multi_table_words(const szk_region_geom *gs, uint32_t n);
 int szk_launch_interp_decompress_region_multi(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                               const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                               void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
-                                              hipStream_t s);
-// the same for an opened stream's request: with chain_points != 0 the coarsest c levels — the largest count such that for
-// every box every pass of those levels has at most chain_points points — run in ONE launch (k_region_chain_multi: one workgroup per box walks
-// first point, regrids and passes, a barrier between steps); chain_points 0: exactly the launches above. *chain_levels: c; *launches: kernel
-// launches issued
-int szk_launch_interp_decompress_region_chain(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
-                                              const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
-                                              void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
                                               hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches);
-uint64_t szk_region_launches(void);  // test hook: kernel launches the box reconstructions issued so far
+uint64_t szk_region_launches(void);  // test hook: kernel launches the box reconstructions issued so far, single and multi
 
 int szk_launch_profile_blocks(int dtype, const void *d_in, int N, const uint64_t *dims, uint64_t bs, uint64_t stride, double abseb,
                               uint8_t *d_flags, uint64_t *total_out, hipStream_t s);

@@ -232,19 +232,31 @@ uint64_t szk_region_pass_window(const szk_region_geom *g, int b, int k, uint64_t
 }
 
 // ---- kernels --------------------------------------------------------------------------------------------------------------------------
-// the buffers of all levels, extents in the last N of four places (1 in front), as the coarse decode's geometry has them
-struct szk_region_bufs {
+// Every step of a box's reconstruction — raw records, first point, regrid, pass — has ONE device body; the kernels of the three forms are
+// wrappers that say where the step's record comes from: kernel arguments (the single-box call), a table row chosen by blockIdx.y (the
+// multi-box call), a step of the chain's table (section 15).
+//
+// The raw records. One level buffer of a box as the scatter sees it, extents in the last N of four places (1 in front), as the coarse
+// decode's geometry has them: a row of words. The single call passes its box's rows as a kernel argument, the multi call keeps every box's
+// in its table.
+struct szk_region_scatter_row {
+    uint64_t wlo[4], cnt[4], base;
+};
+struct szk_region_scatter_shared {
     uint64_t full[4];
-    uint64_t wlo[SZK_REGION_MAX_LEVELS][4], cnt[SZK_REGION_MAX_LEVELS][4], base[SZK_REGION_MAX_LEVELS];
     uint32_t nbuf;
     uint32_t shift;  // a tile of level k: wlo / cnt are coarse coordinates, a record's are the full array's — off the coarse grid it is dropped
 };
+struct szk_region_bufs {
+    szk_region_scatter_shared sh;
+    szk_region_scatter_row row[SZK_REGION_MAX_LEVELS];
+};
 // k_scatter_raw for the region: a record goes into the buffer of the level that predicts its point — the largest stride that divides all
 // its coordinates, capped at the coarsest level (whose buffer also holds the anchors / the first point) — and is dropped outside that
-// buffer's window
+// buffer's window. rows: the box's nbuf rows
 template <typename T>
-__global__ __launch_bounds__(256) void k_region_scatter_raw(const uint8_t *__restrict__ payload, uint64_t idx_off, uint64_t val_off, uint64_t cnt, uint64_t n,
-                                                            szk_region_bufs g, T *__restrict__ scratch) {
+__device__ __forceinline__ void region_scatter_records(const uint8_t *__restrict__ payload, uint64_t idx_off, uint64_t val_off, uint64_t cnt, uint64_t n,
+                                                       const szk_region_scatter_shared &g, const szk_region_scatter_row *__restrict__ rows, T *__restrict__ scratch) {
     const uint64_t *idx = reinterpret_cast<const uint64_t *>(payload + idx_off);
     const T *val = reinterpret_cast<const T *>(payload + val_off);
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * 256) {
@@ -265,16 +277,23 @@ __global__ __launch_bounds__(256) void k_region_scatter_raw(const uint8_t *__res
         const uint32_t tz = any ? (uint32_t)(__ffsll((long long)any) - 1) : 64u;
         const uint32_t b = tz >= top ? 0u : top - tz;
         const uint32_t ls = top - b;
+        const szk_region_scatter_row &lv = rows[b];
         uint64_t o = 0;
         bool in = true;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const uint64_t q = (c[j] - g.wlo[b][j]) >> ls;
-            in = in && c[j] >= g.wlo[b][j] && q < g.cnt[b][j];
-            o = o * g.cnt[b][j] + q;
+            const uint64_t wlo = lv.wlo[j], bc = lv.cnt[j];
+            const uint64_t q = (c[j] - wlo) >> ls;
+            in = in && c[j] >= wlo && q < bc;
+            o = o * bc + q;
         }
-        if (in) scratch[g.base[b] + o] = val[i];
+        if (in) scratch[lv.base + o] = val[i];
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_region_scatter_raw(const uint8_t *__restrict__ payload, uint64_t idx_off, uint64_t val_off, uint64_t cnt, uint64_t n,
+                                                            szk_region_bufs g, T *__restrict__ scratch) {
+    region_scatter_records<T>(payload, idx_off, val_off, cnt, n, g.sh, g.row, scratch);
 }
 
 // the points of level 2 s's buffer (src) that lie on level s's buffer (dst): its even positions (dst's low corner is a multiple of 2 s).
@@ -286,9 +305,7 @@ struct szk_region_regrid {
     uint64_t total;
 };
 template <typename T>
-__global__ __launch_bounds__(256) void k_region_regrid(const T *__restrict__ src, T *__restrict__ dst, szk_region_regrid p) {
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= p.total) return;
+__device__ __forceinline__ void region_regrid_point(const T *src, T *dst, const szk_region_regrid &p, uint64_t t) {
     uint64_t r = t, so = 0, dx = 0;
     uint64_t m[4];
 #pragma unroll
@@ -305,6 +322,11 @@ __global__ __launch_bounds__(256) void k_region_regrid(const T *__restrict__ src
         dx = dx * p.dcnt[j] + 2 * m[j];
     }
     if (in) dst[dx] = src[so];
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_region_regrid(const T *__restrict__ src, T *__restrict__ dst, szk_region_regrid p) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < p.total) region_regrid_point<T>(src, dst, p, t);
 }
 
 // one directional pass over its window. first / step / cnt: the window's lattice (full coordinates); wlo / boff: the level's buffer.
@@ -346,140 +368,25 @@ __device__ __forceinline__ void region_point(T *__restrict__ buf, const uint16_t
     const int code = codes[idx];
     if (code) *d = ref_recover<T>(pred, code, p.eb, p.radius);  // code 0: raw value already scattered in place
 }
+// point t of a pass of p.total points, t < p.total: the index type by the total (a uniform branch; up to 2^32 points every count fits 32 bits too)
+template <typename T, typename P>
+__device__ __forceinline__ void region_pass_point(T *__restrict__ buf, const uint16_t *__restrict__ codes, const P &p, uint64_t t) {
+    if (p.total <= 0xFFFFFFFFull) region_point<T, uint32_t>(buf, codes, p, t);
+    else region_point<T, uint64_t>(buf, codes, p, t);
+}
 template <typename T>
 __global__ __launch_bounds__(256) void k_region_pass(T *__restrict__ buf, const uint16_t *__restrict__ codes, szk_region_pass p) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= p.total) return;
-    if (p.total <= 0xFFFFFFFFull) region_point<T, uint32_t>(buf, codes, p, t);  // (uniform branch; then every count fits 32 bits too)
-    else region_point<T, uint64_t>(buf, codes, p, t);
+    if (t < p.total) region_pass_point<T>(buf, codes, p, t);
 }
-// without anchors the first element is predicted by 0 (k_interp_first_dec)
+// without anchors the first element is predicted by 0 (k_interp_first_dec); first: the coarsest buffer's first element
+template <typename T>
+__device__ __forceinline__ void region_first_point(T *first, const uint16_t *__restrict__ codes, double eb, int radius) {
+    if (codes[0]) *first = ref_recover<T>((T)0, codes[0], eb, radius);
+}
 template <typename T>
 __global__ __launch_bounds__(64) void k_region_first(T *__restrict__ buf, const uint16_t *__restrict__ codes, double eb, int radius) {
-    if (threadIdx.x == 0 && blockIdx.x == 0 && codes[0]) buf[0] = ref_recover<T>((T)0, codes[0], eb, radius);
-}
-
-// ---- host: the launches ---------------------------------------------------------------------------------------------------------------
-// test hook (sz3hip_debug_region_launches): kernel launches the box reconstructions of this process issued, single and multi
-static std::atomic<uint64_t> g_region_launches{0};
-uint64_t szk_region_launches(void) { return g_region_launches.load(); }
-template <typename T>
-static int run_region(const szk_interp_params &ip, const szk_region_geom &g, const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off,
-                      uint64_t n_vout, const uint16_t *codes, T *scratch, T *d_out, hipStream_t s) {
-    const int N = g.N;
-    uint64_t num = 1, off[4] = {0, 0, 0, 0};  // off: a step of the (coarse) grid in the FULL code array
-    for (int j = N - 1; j >= 0; j--) {
-        off[j] = num << g.shift;
-        num *= g.full[j];
-    }
-    if (n_vout) {
-        szk_region_bufs rb;
-        memset(&rb, 0, sizeof(rb));
-        rb.nbuf = (uint32_t)g.nbuf;
-        rb.shift = (uint32_t)g.shift;
-        for (int i = 0; i < 4; i++) {
-            const int j = i - (4 - N);
-            rb.full[i] = j >= 0 ? g.full[j] : 1;
-            for (int b = 0; b < g.nbuf; b++) {
-                rb.wlo[b][i] = j >= 0 ? g.lv[b].wlo[j] : 0;
-                rb.cnt[b][i] = j >= 0 ? g.lv[b].cnt[j] : 1;
-            }
-        }
-        for (int b = 0; b < g.nbuf; b++) rb.base[b] = g.lv[b].base;
-        const uint32_t gr = (uint32_t)((n_vout + 255) / 256 < 4096 ? (n_vout + 255) / 256 : 4096);
-        hipLaunchKernelGGL((k_region_scatter_raw<T>), dim3(gr), dim3(256), 0, s, payload, vout_idx_off, vout_val_off, n_vout, num, rb, scratch);
-        g_region_launches++;
-    }
-    if (g.anchor == 0) {  // the first point, when the coarsest window holds it (then it is the buffer's first element)
-        bool at0 = true;
-        for (int j = 0; j < N; j++) at0 = at0 && g.lv[0].wlo[j] == 0;
-        if (at0) {
-            hipLaunchKernelGGL((k_region_first<T>), dim3(1), dim3(64), 0, s, scratch + g.lv[0].base, codes, ip.eb, ip.radius);
-            g_region_launches++;
-        }
-    }
-    for (int b = 0; b < g.n_levels; b++) {
-        const szk_region_level &lv = g.lv[b];
-        if (b > 0) {
-            const szk_region_level &up = g.lv[b - 1];
-            szk_region_regrid rg;
-            memset(&rg, 0, sizeof(rg));
-            rg.total = 1;
-            for (int i = 0; i < 4; i++) {
-                const int j = i - (4 - N);
-                rg.dcnt[i] = j >= 0 ? lv.cnt[j] : 1;
-                rg.scnt[i] = j >= 0 ? up.cnt[j] : 1;
-                rg.ev[i] = (rg.dcnt[i] + 1) / 2;
-                if (j >= 0 && lv.wlo[j] < up.wlo[j]) return -1;
-                rg.shift[i] = j >= 0 ? (lv.wlo[j] - up.wlo[j]) / up.s : 0;
-                rg.total *= rg.ev[i];
-            }
-            const uint64_t nb = (rg.total + 255) / 256;
-            if (nb > 0x7FFFFFFFull) return -1;
-            hipLaunchKernelGGL((k_region_regrid<T>), dim3((uint32_t)nb), dim3(256), 0, s, (const T *)(scratch + up.base), scratch + lv.base, rg);
-            g_region_launches++;
-        }
-        const int level = g.n_levels - b;  // the level's number on the grid: stride 2^(level - 1); in the full array it is level + shift
-        szk_region_pass p;
-        memset(&p, 0, sizeof(p));
-        p.N = N;
-        p.interp_id = ip.interp_id;
-        p.old_api = N <= 2;
-        p.radius = ip.radius;
-        p.s = lv.s;
-        p.ls = (uint32_t)(level - 1);
-        p.bsz = 32ull * lv.s;
-        p.belems = lv.elems;
-        p.eb = szk_interp_level_eb(ip.eb, ip.alpha, ip.beta, level + g.shift);
-        for (int j = 0; j < N; j++) {
-            p.dims[j] = g.dims[j];
-            p.off[j] = off[j];
-            p.wlo[j] = lv.wlo[j];
-            p.boff[j] = lv.boff[j];
-        }
-        for (int k = 0; k < N; k++) {
-            p.dir = g.perm[k];
-            p.total = szk_region_pass_window(&g, b, k, p.first, p.step, p.cnt);
-            if (p.total == 0) continue;
-            for (int j = 0; j < N; j++)  // the window lies on the buffer
-                if (p.first[j] < lv.wlo[j] || (p.first[j] + (p.cnt[j] - 1) * p.step[j] - lv.wlo[j]) / lv.s >= lv.cnt[j]) return -1;
-            const uint64_t nb = (p.total + 255) / 256;
-            if (nb > 0x7FFFFFFFull) return -1;
-            p.subpass = 0;
-            hipLaunchKernelGGL((k_region_pass<T>), dim3((uint32_t)nb), dim3(256), 0, s, scratch + lv.base, codes, p);
-            g_region_launches++;
-            if (!p.old_api && p.interp_id == 0) {  // the deferred last point of even-length lines, as in run_interp
-                p.subpass = 1;
-                hipLaunchKernelGGL((k_region_pass<T>), dim3((uint32_t)nb), dim3(256), 0, s, scratch + lv.base, codes, p);
-                g_region_launches++;
-            }
-        }
-    }
-    // the box, out of the finest buffer (stride 1)
-    const szk_region_level &fin = g.lv[g.nbuf - 1];
-    szk_view v;
-    memset(&v, 0, sizeof(v));
-    uint64_t corner = 0;
-    for (int i = 0; i < 4; i++) {
-        const int j = i - (4 - N);
-        v.dims[i] = j >= 0 ? g.ext[j] : 1;
-        v.str[i] = j >= 0 ? (int64_t)fin.boff[j] : 0;
-        if (j >= 0) corner += (g.lo[j] - fin.wlo[j]) * fin.boff[j];
-    }
-    v.contig = 0;
-    if (szk_launch_gather(sizeof(T) == 4 ? 0 : 1, 0, scratch + fin.base + corner, &v, d_out, nullptr, s)) return -2;
-    g_region_launches++;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
-int szk_launch_interp_decompress_region(int dtype, const szk_interp_params *ip, const szk_region_geom *g, const uint8_t *payload, uint64_t vout_idx_off,
-                                        uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, void *scratch, void *d_out, hipStream_t s) {
-    if (g->N != ip->N || g->nbuf < 1 || g->shift < 0 || g->shift > 30) return -1;
-    for (int j = 0; j < ip->N; j++)
-        if (g->full[j] != ip->dims[j] || g->dims[j] != ((ip->dims[j] - 1) >> g->shift) + 1) return -1;
-    return dtype == 0 ? run_region<float>(*ip, *g, payload, vout_idx_off, vout_val_off, n_vout, codes, (float *)scratch, (float *)d_out, s)
-                      : run_region<double>(*ip, *g, payload, vout_idx_off, vout_val_off, n_vout, codes, (double *)scratch, (double *)d_out, s);
+    if (threadIdx.x == 0 && blockIdx.x == 0) region_first_point<T>(buf, codes, eb, radius);
 }
 
 // ---- n boxes of one level of one stream in one launch sequence -------------------------------------------------------
@@ -512,6 +419,37 @@ struct szk_region_pass_parts {
     uint64_t off[4], first[4], step[4], cnt[4], wlo[4];
     double eb;
 };
+__host__ __device__ __forceinline__ uint64_t *szk_words(uint64_t (&a)[4]) { return a; }
+__host__ __device__ __forceinline__ uint64_t *szk_words(szk_sel4 &a) { return a.v; }
+// the two parts put together, sub-pass `subpass`. P: szk_region_pass_parts — a workgroup of the multi kernels and of the chain, from its
+// box's record — or szk_region_pass — the host, for the single call's kernel argument
+template <typename P>
+__host__ __device__ __forceinline__ P region_pass_join(const szk_region_pass_shared &sh, const szk_region_pass_box &b, int subpass) {
+    P p;
+    p.N = sh.N;
+    p.dir = sh.dir;
+    p.interp_id = sh.interp_id;
+    p.old_api = sh.old_api;
+    p.subpass = subpass;
+    p.radius = sh.radius;
+    p.ls = sh.ls;
+    p.s = sh.s;
+    p.bsz = sh.bsz;
+    p.total = b.total;
+    p.belems = b.belems;
+    p.eb = sh.eb;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        szk_words(p.dims)[j] = sh.dims[j];
+        p.off[j] = sh.off[j];
+        p.step[j] = sh.step[j];
+        p.first[j] = b.first[j];
+        p.cnt[j] = b.cnt[j];
+        p.wlo[j] = b.wlo[j];
+        szk_words(p.boff)[j] = b.boff[j];
+    }
+    return p;
+}
 struct szk_region_regrid_box {
     szk_region_regrid g;
     uint64_t src, dst;  // the two buffers' bases in the scratch
@@ -524,113 +462,37 @@ struct szk_region_gather_box {
     void *dst;
     uint64_t ext[4], str[4];  // extents in the last N of four places; the finest buffer's element strides
 };
-struct szk_region_scatter_shared {
-    uint64_t full[4];
-    uint32_t nbuf, shift;
-};
-#define SZK_SCATTER_ROW 9  // words per buffer of a box's scatter record: wlo[4], cnt[4], base
-static_assert(sizeof(szk_region_pass_box) == 19 * 8 && sizeof(szk_region_regrid_box) == 19 * 8 && sizeof(szk_region_gather_box) == 11 * 8, "table records are rows of words");
+#define SZK_WORDS(R) ((uint64_t)(sizeof(R) / 8))  // a record in the table
+static_assert(sizeof(szk_region_scatter_row) == 9 * 8 && sizeof(szk_region_pass_box) == 19 * 8 && sizeof(szk_region_regrid_box) == 19 * 8 &&
+                  sizeof(szk_region_gather_box) == 11 * 8,
+              "table records are rows of words");
 
 // k_region_scatter_raw per box: every box scans the whole list (as its own call would) and keeps what falls into its windows
 template <typename T>
 __global__ __launch_bounds__(256) void k_region_scatter_raw_multi(const uint8_t *__restrict__ payload, uint64_t idx_off, uint64_t val_off, uint64_t cnt, uint64_t n,
                                                                   szk_region_scatter_shared g, const uint64_t *__restrict__ tab, T *__restrict__ scratch) {
-    const uint64_t *idx = reinterpret_cast<const uint64_t *>(payload + idx_off);
-    const T *val = reinterpret_cast<const T *>(payload + val_off);
-    const uint64_t *rec = tab + (uint64_t)blockIdx.y * g.nbuf * SZK_SCATTER_ROW;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (uint64_t)gridDim.x * 256) {
-        uint64_t r = idx[i];
-        if (r >= n) continue;
-        uint64_t c[4];
-        c[3] = r % g.full[3];
-        r /= g.full[3];
-        c[2] = r % g.full[2];
-        r /= g.full[2];
-        c[1] = r % g.full[1];
-        c[0] = r / g.full[1];
-        if ((c[0] | c[1] | c[2] | c[3]) & ((1ull << g.shift) - 1)) continue;
-#pragma unroll
-        for (int j = 0; j < 4; j++) c[j] >>= g.shift;
-        const uint64_t any = c[0] | c[1] | c[2] | c[3];
-        const uint32_t top = g.nbuf - 1;
-        const uint32_t tz = any ? (uint32_t)(__ffsll((long long)any) - 1) : 64u;
-        const uint32_t b = tz >= top ? 0u : top - tz;
-        const uint32_t ls = top - b;
-        const uint64_t *lv = rec + (uint64_t)b * SZK_SCATTER_ROW;
-        uint64_t o = 0;
-        bool in = true;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint64_t wlo = lv[j], bc = lv[4 + j];
-            const uint64_t q = (c[j] - wlo) >> ls;
-            in = in && c[j] >= wlo && q < bc;
-            o = o * bc + q;
-        }
-        if (in) scratch[lv[8] + o] = val[i];
-    }
+    region_scatter_records<T>(payload, idx_off, val_off, cnt, n, g, reinterpret_cast<const szk_region_scatter_row *>(tab) + (uint64_t)blockIdx.y * g.nbuf, scratch);
 }
 template <typename T>
 __global__ __launch_bounds__(64) void k_region_first_multi(T *__restrict__ scratch, const uint16_t *__restrict__ codes, double eb, int radius,
                                                            const szk_region_first_box *__restrict__ recs) {
     const szk_region_first_box &r = recs[blockIdx.y];
-    if (threadIdx.x == 0 && blockIdx.x == 0 && r.total && codes[0]) scratch[r.base] = ref_recover<T>((T)0, codes[0], eb, radius);
+    if (threadIdx.x == 0 && blockIdx.x == 0 && r.total) region_first_point<T>(scratch + r.base, codes, eb, radius);
 }
 template <typename T>
 __global__ __launch_bounds__(256) void k_region_regrid_multi(T *__restrict__ scratch, const szk_region_regrid_box *__restrict__ recs) {
     const szk_region_regrid_box &b = recs[blockIdx.y];
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= b.g.total) return;
-    uint64_t r = t, so = 0, dx = 0;
-    uint64_t m[4];
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-        m[j] = r % b.g.ev[j];
-        r /= b.g.ev[j];
-    }
-    bool in = true;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const uint64_t sq = m[j] + b.g.shift[j];
-        in = in && sq < b.g.scnt[j];
-        so = so * b.g.scnt[j] + sq;
-        dx = dx * b.g.dcnt[j] + 2 * m[j];
-    }
-    if (in) scratch[b.dst + dx] = scratch[b.src + so];
+    if (t < b.g.total) region_regrid_point<T>(scratch + b.src, scratch + b.dst, b.g, t);
 }
-// the pass of one box is region_point over szk_region_pass put together again from the two parts; IT by the box's own total, as k_region_pass
-// chooses it
 template <typename T>
 __global__ __launch_bounds__(256) void k_region_pass_multi(T *__restrict__ scratch, const uint16_t *__restrict__ codes, szk_region_pass_shared sh,
                                                            const szk_region_pass_box *__restrict__ recs) {
     const szk_region_pass_box &b = recs[blockIdx.y];
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint64_t total = b.total;
-    if (t >= total) return;
-    szk_region_pass_parts p;
-    p.N = sh.N;
-    p.dir = sh.dir;
-    p.interp_id = sh.interp_id;
-    p.old_api = sh.old_api;
-    p.subpass = sh.subpass;
-    p.radius = sh.radius;
-    p.ls = sh.ls;
-    p.s = sh.s;
-    p.bsz = sh.bsz;
-    p.total = total;
-    p.belems = b.belems;
-    p.eb = sh.eb;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        p.dims.v[j] = sh.dims[j];
-        p.off[j] = sh.off[j];
-        p.step[j] = sh.step[j];
-        p.first[j] = b.first[j];
-        p.cnt[j] = b.cnt[j];
-        p.wlo[j] = b.wlo[j];
-        p.boff.v[j] = b.boff[j];
-    }
-    if (total <= 0xFFFFFFFFull) region_point<T, uint32_t>(scratch + b.base, codes, p, t);
-    else region_point<T, uint64_t>(scratch + b.base, codes, p, t);
+    if (t >= b.total) return;
+    const szk_region_pass_parts p = region_pass_join<szk_region_pass_parts>(sh, b, sh.subpass);
+    region_pass_point<T>(scratch + b.base, codes, p, t);
 }
 // box i out of its finest buffer into d_outs[i], contiguous; lanes run along x
 template <typename T>
@@ -647,16 +509,15 @@ __global__ __launch_bounds__(256) void k_region_gather_multi(const T *__restrict
     static_cast<T *>(b.dst)[t] = scratch[b.src + so];
 }
 
-
 // ---- the coarsest levels of a request in ONE launch ---------------------------------------------------------------------
 // All but the finest one or two levels of a box are a few thousand points each, and every one of them costs a launch or two per pass. Here one
 // workgroup per box (blockIdx.x) walks a step table — first point, regrid, pass, deferred sub-pass — over the request's coarsest levels: each
-// step is a loop t = threadIdx.x, += 1024 over the body of the multi kernel it replaces (the pass: region_point<T, uint32_t> over
-// szk_region_pass_parts, put together as k_region_pass_multi does), so the arithmetic is that path's by construction. A __syncthreads() follows
-// every step and every thread reaches it (no return around it): the only ordering there is. The box's level buffers are written and read by
-// this one workgroup, in place, with plain loads and stores; `scratch` is neither read-only nor __restrict__ here. No waiting between
-// workgroups, no flags, no atomics, no LDS. A step's records are the multi kernels' own, in the request's table: `rec` is box 0's record (box
-// i's follows i records on), `shared` a pass's szk_region_pass_shared (subpass as the step says), both in words from the table's start.
+// step is a loop t = threadIdx.x, += 1024 over the body the multi kernel it replaces calls (the pass: region_point<T, uint32_t> over
+// region_pass_join's szk_region_pass_parts). A __syncthreads() follows every step and every thread reaches it (no return around it): the only
+// ordering there is. The box's level buffers are written and read by this one workgroup, in place, with plain loads and stores; `scratch`
+// is neither read-only nor __restrict__ here. No waiting between workgroups, no flags, no atomics, no LDS. A step's records are the multi
+// kernels' own, in the request's table: `rec` is box 0's record (box i's follows i records on), `shared` a pass's szk_region_pass_shared
+// (subpass as the step says), both in words from the table's start.
 struct szk_chain_step {
     uint64_t kind;  // 1 first point, 2 regrid, 3 pass
     uint64_t subpass;
@@ -672,65 +533,209 @@ __global__ __launch_bounds__(1024) void k_region_chain_multi(T *scratch, const u
         const szk_chain_step st = steps[q];
         if (st.kind == 1) {  // k_region_first_multi
             const szk_region_first_box &r = reinterpret_cast<const szk_region_first_box *>(tab + st.rec)[box];
-            if (threadIdx.x == 0 && r.total && codes[0]) scratch[r.base] = ref_recover<T>((T)0, codes[0], eb0, radius);
+            if (threadIdx.x == 0 && r.total) region_first_point<T>(scratch + r.base, codes, eb0, radius);
         } else if (st.kind == 2) {  // k_region_regrid_multi
             const szk_region_regrid_box &b = reinterpret_cast<const szk_region_regrid_box *>(tab + st.rec)[box];
-            for (uint64_t t = threadIdx.x; t < b.g.total; t += 1024) {
-                uint64_t r = t, so = 0, dx = 0;
-                uint64_t m[4];
-#pragma unroll
-                for (int j = 3; j >= 0; j--) {
-                    m[j] = r % b.g.ev[j];
-                    r /= b.g.ev[j];
-                }
-                bool in = true;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const uint64_t sq = m[j] + b.g.shift[j];
-                    in = in && sq < b.g.scnt[j];
-                    so = so * b.g.scnt[j] + sq;
-                    dx = dx * b.g.dcnt[j] + 2 * m[j];
-                }
-                if (in) scratch[b.dst + dx] = scratch[b.src + so];
-            }
-        } else {  // k_region_pass_multi
-            const szk_region_pass_shared &sh = *reinterpret_cast<const szk_region_pass_shared *>(tab + st.shared);
+            for (uint64_t t = threadIdx.x; t < b.g.total; t += 1024) region_regrid_point<T>(scratch + b.src, scratch + b.dst, b.g, t);
+        } else {  // k_region_pass_multi; a pass's total is at most chain_points, a 32-bit number: the host chose the levels so
             const szk_region_pass_box &b = reinterpret_cast<const szk_region_pass_box *>(tab + st.rec)[box];
-            const uint64_t total = b.total;  // (at most chain_points, a 32-bit number: the host chose the levels so)
-            szk_region_pass_parts p;
-            p.N = sh.N;
-            p.dir = sh.dir;
-            p.interp_id = sh.interp_id;
-            p.old_api = sh.old_api;
-            p.subpass = (int)st.subpass;
-            p.radius = sh.radius;
-            p.ls = sh.ls;
-            p.s = sh.s;
-            p.bsz = sh.bsz;
-            p.total = total;
-            p.belems = b.belems;
-            p.eb = sh.eb;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                p.dims.v[j] = sh.dims[j];
-                p.off[j] = sh.off[j];
-                p.step[j] = sh.step[j];
-                p.first[j] = b.first[j];
-                p.cnt[j] = b.cnt[j];
-                p.wlo[j] = b.wlo[j];
-                p.boff.v[j] = b.boff[j];
-            }
+            const szk_region_pass_parts p = region_pass_join<szk_region_pass_parts>(*reinterpret_cast<const szk_region_pass_shared *>(tab + st.shared), b, (int)st.subpass);
             T *buf = scratch + b.base;
-            for (uint64_t t = threadIdx.x; t < total; t += 1024) region_point<T, uint32_t>(buf, codes, p, t);
+            for (uint64_t t = threadIdx.x; t < p.total; t += 1024) region_point<T, uint32_t>(buf, codes, p, t);
         }
         __syncthreads();
     }
 }
 
+// ---- host: a step's records from a box's geometry -------------------------------------------------------------------------------------------
+// One builder per record, used by the single-box and the multi-box driver alike; a builder that can refuse returns -1 and holds that
+// refusal's only copy. Four-place arrays hold the N extents in their last places, as the kernels read them.
+//
+// a step of the (coarse) grid along each dimension in the FULL code array; returns the full array's element count
+static uint64_t region_code_steps(const szk_region_geom &g, uint64_t *off) {
+    uint64_t num = 1;
+    for (int j = 3; j >= 0; j--) {
+        off[j] = j < g.N ? num << g.shift : 0;
+        if (j < g.N) num *= g.full[j];
+    }
+    return num;
+}
+// workgroups of 256 threads over `total` points; false: more than a grid's 31 bits
+static bool region_grid(uint64_t total, uint32_t *gx) {
+    const uint64_t nb = (total + 255) / 256;
+    if (nb > 0x7FFFFFFFull) return false;
+    *gx = (uint32_t)nb;
+    return true;
+}
+static uint32_t region_scatter_grid(uint64_t n_vout) { return (uint32_t)((n_vout + 255) / 256 < 4096 ? (n_vout + 255) / 256 : 4096); }
+// the raw records: what the boxes of a request share, and a box's nbuf rows
+static void region_scatter_shared(const szk_region_geom &g, szk_region_scatter_shared *sh) {
+    memset(sh, 0, sizeof(*sh));
+    sh->nbuf = (uint32_t)g.nbuf;
+    sh->shift = (uint32_t)g.shift;
+    for (int q = 0; q < 4; q++) sh->full[q] = q - (4 - g.N) >= 0 ? g.full[q - (4 - g.N)] : 1;
+}
+static void region_scatter_rows(const szk_region_geom &g, szk_region_scatter_row *rows) {
+    for (int b = 0; b < g.nbuf; b++) {
+        for (int q = 0; q < 4; q++) {
+            const int j = q - (4 - g.N);
+            rows[b].wlo[q] = j >= 0 ? g.lv[b].wlo[j] : 0;
+            rows[b].cnt[q] = j >= 0 ? g.lv[b].cnt[j] : 1;
+        }
+        rows[b].base = g.lv[b].base;
+    }
+}
+// the first point runs for a box whose coarsest window holds the origin (then it is that buffer's first element)
+static szk_region_first_box region_first_record(const szk_region_geom &g) {
+    bool at0 = true;
+    for (int j = 0; j < g.N; j++) at0 = at0 && g.lv[0].wlo[j] == 0;
+    return {at0 ? 1ull : 0ull, g.lv[0].base};
+}
+// level b >= 1 from level b - 1. -1: level b's buffer starts below the one it is filled from
+static int region_regrid_record(const szk_region_geom &g, int b, szk_region_regrid_box *r) {
+    const szk_region_level &lv = g.lv[b], &up = g.lv[b - 1];
+    memset(r, 0, sizeof(*r));
+    r->g.total = 1;
+    for (int q = 0; q < 4; q++) {
+        const int j = q - (4 - g.N);
+        r->g.dcnt[q] = j >= 0 ? lv.cnt[j] : 1;
+        r->g.scnt[q] = j >= 0 ? up.cnt[j] : 1;
+        r->g.ev[q] = (r->g.dcnt[q] + 1) / 2;
+        if (j >= 0 && lv.wlo[j] < up.wlo[j]) return -1;
+        r->g.shift[q] = j >= 0 ? (lv.wlo[j] - up.wlo[j]) / up.s : 0;
+        r->g.total *= r->g.ev[q];
+    }
+    r->src = up.base;
+    r->dst = lv.base;
+    return 0;
+}
+// what the passes of level b share (the boxes of a request too: these are the grid's); a pass adds its axis and its lattice's steps
+static void region_pass_level(const szk_interp_params &ip, const szk_region_geom &g, int b, szk_region_pass_shared *sh) {
+    const int level = g.n_levels - b;  // the level's number on the grid: stride 2^(level - 1); in the full array it is level + shift
+    memset(sh, 0, sizeof(*sh));
+    sh->N = g.N;
+    sh->interp_id = ip.interp_id;
+    sh->old_api = g.N <= 2;
+    sh->radius = ip.radius;
+    sh->s = g.lv[b].s;
+    sh->ls = (uint32_t)(level - 1);
+    sh->bsz = 32ull * sh->s;
+    sh->eb = szk_interp_level_eb(ip.eb, ip.alpha, ip.beta, level + g.shift);
+    region_code_steps(g, sh->off);
+    for (int j = 0; j < g.N; j++) sh->dims[j] = g.dims[j];
+}
+// linear mode for N >= 3 defers the last point of even-length lines, as run_interp does: the pass is launched a second time with subpass 1
+static bool region_pass_twice(const szk_region_pass_shared &sh) { return !sh.old_api && sh.interp_id == 0; }
+// pass k of level b of one box: the axis and the steps into sh, the box's part into r. -1: the window does not lie on the level's buffer
+static int region_pass_records(const szk_region_geom &g, int b, int k, szk_region_pass_shared *sh, szk_region_pass_box *r) {
+    const szk_region_level &lv = g.lv[b];
+    memset(r, 0, sizeof(*r));
+    sh->dir = g.perm[k];
+    r->total = szk_region_pass_window(&g, b, k, r->first, sh->step, r->cnt);
+    for (int j = 0; j < g.N; j++) {
+        if (r->total && (r->first[j] < lv.wlo[j] || (r->first[j] + (r->cnt[j] - 1) * sh->step[j] - lv.wlo[j]) / lv.s >= lv.cnt[j])) return -1;
+        r->wlo[j] = lv.wlo[j];
+        r->boff[j] = lv.boff[j];
+    }
+    r->belems = lv.elems;
+    r->base = lv.base;
+    return 0;
+}
+// the box, out of the finest buffer (stride 1). -1: the box does not lie on that buffer
+static int region_gather_record(const szk_region_geom &g, void *dst, szk_region_gather_box *r) {
+    const szk_region_level &fin = g.lv[g.nbuf - 1];
+    memset(r, 0, sizeof(*r));
+    r->total = 1;
+    r->src = fin.base;
+    r->dst = dst;
+    for (int q = 0; q < 4; q++) {
+        const int j = q - (4 - g.N);
+        r->ext[q] = j >= 0 ? g.ext[j] : 1;
+        r->str[q] = j >= 0 ? fin.boff[j] : 0;
+        if (j < 0) continue;
+        if (g.lo[j] < fin.wlo[j] || g.lo[j] - fin.wlo[j] + g.ext[j] > fin.cnt[j]) return -1;
+        r->src += (g.lo[j] - fin.wlo[j]) * fin.boff[j];
+        r->total *= g.ext[j];
+    }
+    return 0;
+}
+
+// ---- host: the launches ---------------------------------------------------------------------------------------------------------------
+// test hook (sz3hip_debug_region_launches): kernel launches the box reconstructions of this process issued, single and multi. Every launch
+// is counted here, and for the request where the driver keeps a count (*issued)
+static std::atomic<uint64_t> g_region_launches{0};
+uint64_t szk_region_launches(void) { return g_region_launches.load(); }
+static void region_count(uint32_t *issued) {
+    g_region_launches++;
+    if (issued) ++*issued;
+}
+template <typename... KA, typename... A>
+static void region_launch(uint32_t *issued, void (*kernel)(KA...), dim3 grid, uint32_t block, hipStream_t s, const A &...args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(block), 0, s, args...);
+    region_count(issued);
+}
+
+template <typename T>
+static int run_region(const szk_interp_params &ip, const szk_region_geom &g, const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off,
+                      uint64_t n_vout, const uint16_t *codes, T *scratch, T *d_out, hipStream_t s) {
+    uint32_t gx;
+    if (n_vout) {
+        uint64_t off[4];
+        szk_region_bufs rb;
+        memset(&rb, 0, sizeof(rb));
+        region_scatter_shared(g, &rb.sh);
+        region_scatter_rows(g, rb.row);
+        region_launch(nullptr, k_region_scatter_raw<T>, dim3(region_scatter_grid(n_vout)), 256, s, payload, vout_idx_off, vout_val_off, n_vout, region_code_steps(g, off), rb,
+                      scratch);
+    }
+    if (g.anchor == 0 && region_first_record(g).total) region_launch(nullptr, k_region_first<T>, dim3(1), 64, s, scratch + g.lv[0].base, codes, ip.eb, ip.radius);
+    for (int b = 0; b < g.n_levels; b++) {
+        if (b > 0) {
+            szk_region_regrid_box r;
+            if (region_regrid_record(g, b, &r) || !region_grid(r.g.total, &gx)) return -1;
+            region_launch(nullptr, k_region_regrid<T>, dim3(gx), 256, s, (const T *)(scratch + r.src), scratch + r.dst, r.g);
+        }
+        szk_region_pass_shared sh;
+        region_pass_level(ip, g, b, &sh);
+        for (int k = 0; k < g.N; k++) {
+            szk_region_pass_box pb;
+            if (region_pass_records(g, b, k, &sh, &pb)) return -1;
+            if (pb.total == 0) continue;
+            if (!region_grid(pb.total, &gx)) return -1;
+            for (int sub = 0; sub < (region_pass_twice(sh) ? 2 : 1); sub++)
+                region_launch(nullptr, k_region_pass<T>, dim3(gx), 256, s, scratch + pb.base, codes, region_pass_join<szk_region_pass>(sh, pb, sub));
+        }
+    }
+    szk_region_gather_box gb;
+    if (region_gather_record(g, d_out, &gb)) return -1;
+    szk_view v;
+    memset(&v, 0, sizeof(v));
+    for (int q = 0; q < 4; q++) {
+        v.dims[q] = gb.ext[q];
+        v.str[q] = (int64_t)gb.str[q];
+    }
+    v.contig = 0;
+    if (szk_launch_gather(sizeof(T) == 4 ? 0 : 1, 0, scratch + gb.src, &v, d_out, nullptr, s)) return -2;
+    region_count(nullptr);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int szk_launch_interp_decompress_region(int dtype, const szk_interp_params *ip, const szk_region_geom *g, const uint8_t *payload, uint64_t vout_idx_off,
+                                        uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, void *scratch, void *d_out, hipStream_t s) {
+    if (g->N != ip->N || g->nbuf < 1 || g->shift < 0 || g->shift > 30) return -1;
+    for (int j = 0; j < ip->N; j++)
+        if (g->full[j] != ip->dims[j] || g->dims[j] != ((ip->dims[j] - 1) >> g->shift) + 1) return -1;
+    return dtype == 0 ? run_region<float>(*ip, *g, payload, vout_idx_off, vout_val_off, n_vout, codes, (float *)scratch, (float *)d_out, s)
+                      : run_region<double>(*ip, *g, payload, vout_idx_off, vout_val_off, n_vout, codes, (double *)scratch, (double *)d_out, s);
+}
+
 // words the table of a request of n boxes takes (an upper bound: every box with every record; behind them the chain's pass parameters and steps)
 uint64_t szk_region_multi_table_words(const szk_region_geom *gs, uint32_t n) {
     const uint64_t nb = (uint64_t)gs[0].nbuf, nl = (uint64_t)gs[0].n_levels, N = (uint64_t)gs[0].N;
-    return (uint64_t)n * (nb * SZK_SCATTER_ROW + 2 + nl * 19 + nl * N * 19 + 11) + nl * N * 19 + (1 + nl * (1 + 2 * N)) * 4;
+    return (uint64_t)n * (nb * SZK_WORDS(szk_region_scatter_row) + SZK_WORDS(szk_region_first_box) + nl * SZK_WORDS(szk_region_regrid_box) +
+                          nl * N * SZK_WORDS(szk_region_pass_box) + SZK_WORDS(szk_region_gather_box)) +
+           nl * N * SZK_WORDS(szk_region_pass_shared) + (1 + nl * (1 + 2 * N)) * SZK_WORDS(szk_chain_step);
 }
 
 namespace {
@@ -746,8 +751,8 @@ struct MultiLaunch {
 template <typename T>
 static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
                             uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, T *scratch, void *const *d_outs,
-                            uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t chain_points = 0,
-                            uint32_t *chain_levels = nullptr, uint32_t *launches = nullptr) {
+                            uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t chain_points,
+                            uint32_t *chain_levels, uint32_t *launches) {
     const szk_region_geom &g0 = gs[0];
     const int N = g0.N, nbuf = g0.nbuf, n_levels = g0.n_levels;
     // the chain takes the coarsest c levels: the largest count such that every pass of those levels has at most chain_points points for EVERY box
@@ -763,12 +768,6 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
         if (!fits) break;
     }
     if (chain_levels) *chain_levels = (uint32_t)c;
-    uint32_t issued = 0;
-    uint64_t num = 1, off[4] = {0, 0, 0, 0};
-    for (int j = N - 1; j >= 0; j--) {
-        off[j] = num << g0.shift;
-        num *= g0.full[j];
-    }
     // every box's buffers inside the scratch, before anything is built
     for (uint32_t i = 0; i < n; i++)
         for (int b = 0; b < nbuf; b++)
@@ -776,167 +775,90 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
     std::vector<MultiLaunch> seq;
     uint64_t w = 0;  // the table's cursor
     auto room = [&](uint64_t words) { return words <= table_words && w <= table_words - words; };
-    auto grid_of = [](uint64_t total, uint32_t *gx) {
-        const uint64_t nb = (total + 255) / 256;
-        if (nb > 0x7FFFFFFFull) return false;
-        *gx = (uint32_t)nb;
-        return true;
+    auto put = [&](const void *rec, size_t bytes) {
+        memcpy(h_table + w, rec, bytes);
+        w += bytes / 8;
     };
+    // a launch of `kind` whose records start at the cursor, room for `words` per box provided
+    auto launch_at = [&](int kind, uint64_t words, MultiLaunch *l) {
+        *l = MultiLaunch{};
+        l->kind = kind;
+        l->off = w;
+        return room((uint64_t)n * words);
+    };
+    MultiLaunch l;
     if (n_vout) {
-        if (!room((uint64_t)n * nbuf * SZK_SCATTER_ROW)) return -1;
-        MultiLaunch l{};
-        l.kind = 0;
-        l.off = w;
-        l.gx = (uint32_t)((n_vout + 255) / 256 < 4096 ? (n_vout + 255) / 256 : 4096);
-        for (uint32_t i = 0; i < n; i++)
-            for (int b = 0; b < nbuf; b++) {
-                uint64_t *row = h_table + w;
-                for (int q = 0; q < 4; q++) {
-                    const int j = q - (4 - N);
-                    row[q] = j >= 0 ? gs[i].lv[b].wlo[j] : 0;
-                    row[4 + q] = j >= 0 ? gs[i].lv[b].cnt[j] : 1;
-                }
-                row[8] = gs[i].lv[b].base;
-                w += SZK_SCATTER_ROW;
-            }
+        if (!launch_at(0, nbuf * SZK_WORDS(szk_region_scatter_row), &l)) return -1;
+        l.gx = region_scatter_grid(n_vout);
+        for (uint32_t i = 0; i < n; i++) {
+            szk_region_scatter_row rows[SZK_REGION_MAX_LEVELS];
+            region_scatter_rows(gs[i], rows);
+            put(rows, nbuf * sizeof(rows[0]));
+        }
         seq.push_back(l);
     }
     if (g0.anchor == 0) {  // the first point, for the boxes whose coarsest window holds it
-        if (!room((uint64_t)n * 2)) return -1;
+        if (!launch_at(1, SZK_WORDS(szk_region_first_box), &l)) return -1;
         bool any = false;
-        const uint64_t at = w;
         for (uint32_t i = 0; i < n; i++) {
-            bool at0 = true;
-            for (int j = 0; j < N; j++) at0 = at0 && gs[i].lv[0].wlo[j] == 0;
-            szk_region_first_box r = {at0 ? 1ull : 0ull, gs[i].lv[0].base};
-            memcpy(h_table + w, &r, sizeof(r));
-            w += 2;
-            any = any || at0;
+            const szk_region_first_box r = region_first_record(gs[i]);
+            put(&r, sizeof(r));
+            any = any || r.total;
         }
-        if (any) {
-            MultiLaunch l{};
-            l.kind = 1;
-            l.off = at;
-            l.gx = 1;
-            l.chained = c > 0;
-            seq.push_back(l);
-        } else {
-            w = at;
-        }
+        l.gx = 1;
+        l.chained = c > 0;
+        if (any) seq.push_back(l);
+        else w = l.off;
     }
     for (int b = 0; b < n_levels; b++) {
+        uint64_t most = 0;
         if (b > 0) {
-            if (!room((uint64_t)n * 19)) return -1;
-            MultiLaunch l{};
-            l.kind = 2;
-            l.off = w;
-            uint64_t most = 0;
+            if (!launch_at(2, SZK_WORDS(szk_region_regrid_box), &l)) return -1;
             for (uint32_t i = 0; i < n; i++) {
-                const szk_region_level &lv = gs[i].lv[b], &up = gs[i].lv[b - 1];
                 szk_region_regrid_box r;
-                memset(&r, 0, sizeof(r));
-                r.g.total = 1;
-                for (int q = 0; q < 4; q++) {
-                    const int j = q - (4 - N);
-                    r.g.dcnt[q] = j >= 0 ? lv.cnt[j] : 1;
-                    r.g.scnt[q] = j >= 0 ? up.cnt[j] : 1;
-                    r.g.ev[q] = (r.g.dcnt[q] + 1) / 2;
-                    if (j >= 0 && lv.wlo[j] < up.wlo[j]) return -1;
-                    r.g.shift[q] = j >= 0 ? (lv.wlo[j] - up.wlo[j]) / up.s : 0;
-                    r.g.total *= r.g.ev[q];
-                }
-                r.src = up.base;
-                r.dst = lv.base;
-                memcpy(h_table + w, &r, sizeof(r));
-                w += 19;
+                if (region_regrid_record(gs[i], b, &r)) return -1;
+                put(&r, sizeof(r));
                 most = r.g.total > most ? r.g.total : most;
             }
-            if (!grid_of(most, &l.gx)) return -1;
+            if (!region_grid(most, &l.gx)) return -1;
             l.chained = b < c;
             if (most) seq.push_back(l);
             else w = l.off;
         }
-        const int level = n_levels - b;
         szk_region_pass_shared sh;
-        memset(&sh, 0, sizeof(sh));
-        sh.N = N;
-        sh.interp_id = ip.interp_id;
-        sh.old_api = N <= 2;
-        sh.radius = ip.radius;
-        sh.s = g0.lv[b].s;
-        sh.ls = (uint32_t)(level - 1);
-        sh.bsz = 32ull * sh.s;
-        sh.eb = szk_interp_level_eb(ip.eb, ip.alpha, ip.beta, level + g0.shift);
-        for (int j = 0; j < N; j++) {
-            sh.dims[j] = g0.dims[j];
-            sh.off[j] = off[j];
-        }
+        region_pass_level(ip, g0, b, &sh);
         for (int k = 0; k < N; k++) {
-            if (!room((uint64_t)n * 19)) return -1;
-            MultiLaunch l{};
-            l.kind = 3;
-            l.off = w;
-            sh.dir = g0.perm[k];
-            uint64_t most = 0;
+            if (!launch_at(3, SZK_WORDS(szk_region_pass_box), &l)) return -1;
+            most = 0;
             for (uint32_t i = 0; i < n; i++) {
-                const szk_region_level &lv = gs[i].lv[b];
+                szk_region_pass_shared si = sh;
                 szk_region_pass_box r;
-                memset(&r, 0, sizeof(r));
-                uint64_t step[4] = {0, 0, 0, 0};
-                r.total = szk_region_pass_window(&gs[i], b, k, r.first, step, r.cnt);
-                for (int j = 0; j < N; j++) {
-                    if (i == 0) sh.step[j] = step[j];
-                    else if (sh.step[j] != step[j]) return -1;  // (the lattice's steps are the level's and the pass's)
-                    if (r.total && (r.first[j] < lv.wlo[j] || (r.first[j] + (r.cnt[j] - 1) * step[j] - lv.wlo[j]) / lv.s >= lv.cnt[j])) return -1;  // the window lies on the buffer
-                    r.wlo[j] = lv.wlo[j];
-                    r.boff[j] = lv.boff[j];
-                }
-                r.belems = lv.elems;
-                r.base = lv.base;
-                memcpy(h_table + w, &r, sizeof(r));
-                w += 19;
+                if (region_pass_records(gs[i], b, k, i ? &si : &sh, &r)) return -1;
+                if (i && memcmp(si.step, sh.step, sizeof(sh.step))) return -1;  // (the lattice's steps are the level's and the pass's)
+                put(&r, sizeof(r));
                 most = r.total > most ? r.total : most;
             }
-            if (!grid_of(most, &l.gx)) return -1;
+            if (!region_grid(most, &l.gx)) return -1;
             if (most == 0) {  // (no box has a point in this pass)
                 w = l.off;
                 continue;
             }
             l.sh = sh;
-            l.twice = !sh.old_api && sh.interp_id == 0;
+            l.twice = region_pass_twice(sh);
             l.chained = b < c;
             seq.push_back(l);
         }
     }
-    {   // the boxes, out of their finest buffers (stride 1)
-        if (!room((uint64_t)n * 11)) return -1;
-        MultiLaunch l{};
-        l.kind = 4;
-        l.off = w;
+    {
+        if (!launch_at(4, SZK_WORDS(szk_region_gather_box), &l)) return -1;
         uint64_t most = 0;
         for (uint32_t i = 0; i < n; i++) {
-            const szk_region_geom &g = gs[i];
-            const szk_region_level &fin = g.lv[nbuf - 1];
             szk_region_gather_box r;
-            memset(&r, 0, sizeof(r));
-            r.total = 1;
-            r.src = fin.base;
-            r.dst = d_outs[i];
-            for (int q = 0; q < 4; q++) {
-                const int j = q - (4 - N);
-                r.ext[q] = j >= 0 ? g.ext[j] : 1;
-                r.str[q] = j >= 0 ? fin.boff[j] : 0;
-                if (j >= 0) {
-                    if (g.lo[j] < fin.wlo[j] || g.lo[j] - fin.wlo[j] + g.ext[j] > fin.cnt[j]) return -1;  // the box lies on the buffer
-                    r.src += (g.lo[j] - fin.wlo[j]) * fin.boff[j];
-                    r.total *= g.ext[j];
-                }
-            }
-            memcpy(h_table + w, &r, sizeof(r));
-            w += 11;
+            if (region_gather_record(gs[i], d_outs[i], &r)) return -1;
+            put(&r, sizeof(r));
             most = r.total > most ? r.total : most;
         }
-        if (!grid_of(most, &l.gx)) return -1;
+        if (!region_grid(most, &l.gx)) return -1;
         seq.push_back(l);
     }
     // the chain's steps, behind the boxes' records: the chained launches in their order, a pass's shared part in front of its step(s)
@@ -944,77 +866,63 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
     uint32_t n_steps = 0;
     if (c > 0) {
         std::vector<szk_chain_step> steps;
-        for (const MultiLaunch &l : seq) {
-            if (!l.chained) continue;
-            szk_chain_step st = {(uint64_t)l.kind, 0, l.off, 0};
-            if (l.kind == 3) {
-                if (!room(19)) return -1;
-                szk_region_pass_shared sh = l.sh;
-                sh.subpass = 0;
-                memcpy(h_table + w, &sh, sizeof(sh));
+        for (const MultiLaunch &cl : seq) {
+            if (!cl.chained) continue;
+            szk_chain_step st = {(uint64_t)cl.kind, 0, cl.off, 0};
+            if (cl.kind == 3) {
+                if (!room(SZK_WORDS(szk_region_pass_shared))) return -1;
                 st.shared = w;
-                w += 19;
+                put(&cl.sh, sizeof(cl.sh));
             }
             steps.push_back(st);
-            if (l.kind == 3 && l.twice) {  // the deferred last point of even-length lines: a step of its own, behind a barrier
+            if (cl.kind == 3 && cl.twice) {  // the deferred last point of even-length lines: a step of its own, behind a barrier
                 st.subpass = 1;
                 steps.push_back(st);
             }
         }
-        if (!room(steps.size() * 4)) return -1;
+        if (!room(steps.size() * SZK_WORDS(szk_chain_step))) return -1;
         steps_off = w;
         n_steps = (uint32_t)steps.size();
-        memcpy(h_table + w, steps.data(), steps.size() * sizeof(szk_chain_step));
-        w += steps.size() * 4;
+        put(steps.data(), steps.size() * sizeof(szk_chain_step));
     }
     // the whole table by one copy, in front of the first launch; `copied` tells the next call's build when the pinned array may be rewritten
     if (hipMemcpyAsync(d_table, h_table, w * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
     if (hipEventRecord(copied, s) != hipSuccess) return -2;
     szk_region_scatter_shared ss;
-    memset(&ss, 0, sizeof(ss));
-    ss.nbuf = (uint32_t)nbuf;
-    ss.shift = (uint32_t)g0.shift;
-    for (int q = 0; q < 4; q++) ss.full[q] = q - (4 - N) >= 0 ? g0.full[q - (4 - N)] : 1;
+    region_scatter_shared(g0, &ss);
+    uint64_t off[4];
+    const uint64_t num = region_code_steps(g0, off);
+    uint32_t issued = 0;
     bool chain_done = false;
-    for (const MultiLaunch &l : seq) {
-        if (l.chained) {  // (the chained launches follow each other in seq: the one launch stands where the first of them stood)
-            if (!chain_done && n_steps) {
-                hipLaunchKernelGGL((k_region_chain_multi<T>), dim3(n), dim3(1024), 0, s, scratch, codes, ip.eb, ip.radius, (const uint64_t *)d_table, steps_off, n_steps);
-                g_region_launches++;
-                issued++;
-            }
+    for (const MultiLaunch &ml : seq) {
+        if (ml.chained) {  // (the chained launches follow each other in seq: the one launch stands where the first of them stood)
+            if (!chain_done && n_steps)
+                region_launch(&issued, k_region_chain_multi<T>, dim3(n), 1024, s, scratch, codes, ip.eb, ip.radius, (const uint64_t *)d_table, steps_off, n_steps);
             chain_done = true;
             continue;
         }
-        const dim3 grid(l.gx, n);
-        const uint64_t *rec = d_table + l.off;
-        switch (l.kind) {
+        const dim3 grid(ml.gx, n);
+        const uint64_t *rec = d_table + ml.off;
+        switch (ml.kind) {
         case 0:
-            hipLaunchKernelGGL((k_region_scatter_raw_multi<T>), grid, dim3(256), 0, s, payload, vout_idx_off, vout_val_off, n_vout, num, ss, rec, scratch);
+            region_launch(&issued, k_region_scatter_raw_multi<T>, grid, 256, s, payload, vout_idx_off, vout_val_off, n_vout, num, ss, rec, scratch);
             break;
         case 1:
-            hipLaunchKernelGGL((k_region_first_multi<T>), grid, dim3(64), 0, s, scratch, codes, ip.eb, ip.radius, reinterpret_cast<const szk_region_first_box *>(rec));
+            region_launch(&issued, k_region_first_multi<T>, grid, 64, s, scratch, codes, ip.eb, ip.radius, reinterpret_cast<const szk_region_first_box *>(rec));
             break;
         case 2:
-            hipLaunchKernelGGL((k_region_regrid_multi<T>), grid, dim3(256), 0, s, scratch, reinterpret_cast<const szk_region_regrid_box *>(rec));
+            region_launch(&issued, k_region_regrid_multi<T>, grid, 256, s, scratch, reinterpret_cast<const szk_region_regrid_box *>(rec));
             break;
-        case 3: {
-            szk_region_pass_shared sh = l.sh;
-            sh.subpass = 0;
-            hipLaunchKernelGGL((k_region_pass_multi<T>), grid, dim3(256), 0, s, scratch, codes, sh, reinterpret_cast<const szk_region_pass_box *>(rec));
-            if (l.twice) {  // the deferred last point of even-length lines, as in run_region
-                sh.subpass = 1;
-                g_region_launches++;
-                issued++;
-                hipLaunchKernelGGL((k_region_pass_multi<T>), grid, dim3(256), 0, s, scratch, codes, sh, reinterpret_cast<const szk_region_pass_box *>(rec));
+        case 3:
+            for (int sub = 0; sub < (ml.twice ? 2 : 1); sub++) {  // (the deferred last point of even-length lines, as in run_region)
+                szk_region_pass_shared sh = ml.sh;
+                sh.subpass = sub;
+                region_launch(&issued, k_region_pass_multi<T>, grid, 256, s, scratch, codes, sh, reinterpret_cast<const szk_region_pass_box *>(rec));
             }
             break;
-        }
         default:
-            hipLaunchKernelGGL((k_region_gather_multi<T>), grid, dim3(256), 0, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_box *>(rec));
+            region_launch(&issued, k_region_gather_multi<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_box *>(rec));
         }
-        g_region_launches++;
-        issued++;
     }
     if (launches) *launches = issued;
     hipError_t e = hipGetLastError();
@@ -1022,13 +930,6 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
 }
 
 int szk_launch_interp_decompress_region_multi(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
-                                              const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
-                                              void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
-                                              hipStream_t s) {
-    return szk_launch_interp_decompress_region_chain(dtype, ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, d_outs, h_table, d_table,
-                                                     table_words, copied, s, 0, nullptr, nullptr);
-}
-int szk_launch_interp_decompress_region_chain(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                               const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                               void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
                                               hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches) {

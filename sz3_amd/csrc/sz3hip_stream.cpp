@@ -323,7 +323,7 @@ extern "C" int sz3hip_stream_tiles(sz3hip_stream *h, int level, const sz3hip_box
     uint32_t chain_levels = 0, launches = 0;
     h->table_pending = true;  // (the launcher records ev_table behind the table's copy)
     // (the lists are the handle's own arrays: handed over as offsets from a null base, as a stock stream's are)
-    const int lr = szk_launch_interp_decompress_region_chain(h->dtype, &ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx, (uint64_t)(uintptr_t)h->codes.d_vval,
+    const int lr = szk_launch_interp_decompress_region_multi(h->dtype, &ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx, (uint64_t)(uintptr_t)h->codes.d_vval,
                                                              h->codes.n_vout, h->codes.d_codes, h->d_region, d_outs, h->h_table, h->d_table, h->table_cap, h->ev_table, s,
                                                              chain_points, &chain_levels, &launches);
     HIPCHK(hipEventRecord(h->ev_req, s));

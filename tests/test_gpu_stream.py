@@ -204,6 +204,53 @@ def test_chain_at_every_split(shape, dtype, interp, chain):
                     assert c_whole < n_levels, "the finest level of the whole grid has more than 8192 points in a pass"
 
 
+FORMS = [(shape, dtype, (("interpAlgo", interp),)) for shape, dtype in (((1000,), "float32"), ((33, 70), "float64"), ((9, 12, 17, 20), "float32")) for interp in (0, 1)]
+FORMS.append(((33, 70), "float32", (("quantbinCnt", 256), ("interpAnchorStride", 0))))  # (spiky: raw records, and no anchors: the first point)
+FORM_IDS = ["%s-%s-%s" % ("x".join(map(str, f[0])), f[1], "-".join("%s%s" % q for q in f[2])) for f in FORMS]
+
+
+@pytest.mark.parametrize("shape,dtype,kw", FORMS, ids=FORM_IDS)
+def test_four_forms_of_one_request(shape, dtype, kw, chain):
+    """The box reconstruction's three kernel forms run one device body per step; the same request through all four ways to reach them — the
+    context's single-box call box by box, its multi-box call, the handle with the chain off, the handle with every level in the chain — gives
+    the same bytes, the full decode's, in 1-D, 2-D and 4-D (the chain's other tests are 3-D). The spiky 2-D case has raw records inside and
+    outside the boxes and no anchors: the scatter and the first-point body."""
+    spikes = "interpAnchorStride" in dict(kw)
+    a = spiky(shape=shape)[0] if spikes else smooth(shape, dtype)
+    conf = conf_for(a.shape, **dict(kw))
+    dc, pl, size, full = device_payload(a, conf)
+    s = torch.cuda.current_stream().cuda_stream
+    dt = getattr(torch, a.dtype.name)
+    if spikes:
+        assert int((raw(full).view(np.float32) == 1e6).sum()) > 0, "the field's spikes are raw records"
+    with dc.open_stream(pl.data_ptr(), size, s) as st:
+        assert st.stats()["fast"] == 1
+        for k in (0, 1):
+            bx = request(coarse_shape(a.shape, k))
+            n_levels = sz3_amd.tiles_plan(conf, k, bx)["n_levels"]
+            forms = {}
+            single = [torch.full(tuple(ext), SENTINEL, dtype=dt, device=DEV) for _, ext in bx]
+            for (lo, ext), o in zip(bx, single):
+                dc.decompress_tile(pl.data_ptr(), size, k, lo, ext, o.data_ptr(), s)
+            forms["single-box calls"] = single
+            multi = [torch.full(tuple(ext), SENTINEL, dtype=dt, device=DEV) for _, ext in bx]
+            dc.decompress_tiles(pl.data_ptr(), size, k, bx, [o.data_ptr() for o in multi], s)
+            forms["multi-box call"] = multi
+            chain(0)
+            forms["handle, chain off"] = ask(st, k, bx)
+            assert st.stats()["chain_levels_last_request"] == 0
+            chain(1 << 31)
+            forms["handle, all in the chain"] = ask(st, k, bx)
+            assert st.stats()["chain_levels_last_request"] == n_levels == st.stats()["n_levels_last_request"]
+            torch.cuda.synchronize()
+            for name, outs in forms.items():
+                same(outs, full, k, bx, name)
+            for name, outs in forms.items():
+                for i, (got, want) in enumerate(zip(outs, single)):
+                    assert np.array_equal(raw(got), raw(want)), "%s, level %d: box %d differs from the single-box call's" % (name, k, i)
+    dc.close()
+
+
 # ---- 3. the launch count -------------------------------------------------------------------------------------------------------------------
 def test_launch_count(chain):
     shape = (65, 47, 130)
