@@ -455,6 +455,44 @@ int sz3hip_stream_config(const sz3hip_stream *h, sz3hip_config *conf);
 int sz3hip_stream_tiles(sz3hip_stream *h, int level, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, void *stream);
 int sz3hip_stream_stats(const sz3hip_stream *h, struct sz3hip_stream_stats *st);
 void sz3hip_stream_close(sz3hip_stream *h);
+/* ---- a frame in one request: boxes of SEVERAL levels, into strided views ----
+ * A level-of-detail frame wants fine tiles near the focus and coarse ones elsewhere, each written where the viewer shows it — a rectangle of
+ * its atlas or screen buffer. sz3hip_stream_request takes 1 .. SZ3HIP_MAX_BOXES boxes that each name their own level and their own output
+ * view. Every box is bit for bit what sz3hip_stream_tiles delivers for that box at that level — the full decode's slice — written through
+ * the view. The rest is sz3hip_stream_tiles' contract: overlapping and repeated boxes are allowed; every box and every output is checked
+ * before anything is launched or written, with the existing codes and wording and "box <i>: " in front; no Huffman stage, no copy of the
+ * payload, no device-to-host copy, no host synchronisation beyond a tiles request's waits, the same event ordering between requests on
+ * different HIP streams. float / double handles only (there are no others). reserved != 0: SZ3HIP_EINVAL.
+ * One launch sequence serves the whole request: the boxes are aligned by ARRAY level (a tile's grid level l is the array's level l + k), so
+ * the request issues the launches of its finest level alone, whatever the number of boxes and of levels
+ * (stats: launches_last_request; n_levels_last_request: the array levels that sequence ran). A request whose boxes all have ONE level issues
+ * exactly the launches sz3hip_stream_tiles issues for them — the chain launch included where sz3hip_debug_chain_points says so — with the
+ * strided gather in the gather's place. A request of two or more distinct levels does NOT take the chain: chain_levels_last_request is 0.
+ * A handle that keeps the full array (stats.fast == 0) serves the request by one strided gather launch out of that array.
+ * Views: strides are in elements, slowest first, one per extent of the box; all zero means contiguous. Dimensions of extent 1 are ignored.
+ * Over the others a stride must be positive and the view nested in row-major order: strides[j] >= ext[j'] * strides[j'] for the next counted
+ * dimension j'. A negative, zero or permuted stride is SZ3HIP_EINVAL, and the message says which. Two outputs of one request are accepted when
+ * their byte hulls are disjoint, or when both have the same strides, nested over all their dimensions, and the element distance of their
+ * origins decomposes without remainder into offsets o[j] along those strides with o[j] + ext_b[j] <= strides[j-1] / strides[j] for j >= 1 and
+ * o[j] >= ext_a[j] for some j: two rectangles of one atlas that do not meet. Anything else: SZ3HIP_EINVAL ("box i: the output overlaps box
+ * j's, or cannot be shown not to").
+ * sz3hip_request_plan_for: a pure function (no device), the request's checks — all but whether a pointer is device memory — and what it
+ * touches: points and scratch_elems are the sums of the boxes' sz3hip_tile_plan_for figures, n_levels the array levels the merged sequence
+ * runs (the finest box's own level count). dataType: the element size of the views; an integer type is SZ3HIP_EUNSUPPORTED. */
+typedef struct sz3hip_tile_req {
+    int32_t level;        /* 0 .. 30: the box lies on the grid of every 2^level-th point */
+    uint32_t reserved;    /* 0 */
+    sz3hip_box box;       /* in that grid's coordinates, slowest first, N entries used */
+    void *d_out;          /* device pointer: the view's element [0, .., 0] */
+    int64_t strides[4];   /* element strides of the view, slowest first, N entries used; all zero: contiguous */
+} sz3hip_tile_req;
+typedef struct sz3hip_request_plan {
+    uint32_t n;
+    int32_t finest_level, coarsest_level, n_levels;
+    uint64_t points, scratch_elems;
+} sz3hip_request_plan;
+int sz3hip_request_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, sz3hip_request_plan *out);
+int sz3hip_stream_request(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, void *stream);
 /* development switch, process-wide: a request of a handle runs its coarsest c levels in ONE launch (one workgroup per box walks first point,
  * regrids and passes with a barrier between steps), c the largest count such that for every box every pass of those levels has at most
  * `points` points. 0: off — the request issues exactly the launches sz3hip_decompress_device_tiles issues. Environment twin, read once when

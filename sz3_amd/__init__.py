@@ -84,6 +84,7 @@ class Dbg2(enum.IntFlag):
     """The second word of development switches (sz3hip_debug_flags2): enum sz3hip_dbg2 of include/sz3hip_debug.h without the
     SZ3HIP_DBG2_ prefix, same values. One bit, one meaning."""
     PACK_SCAN_LAUNCH = 1
+    REQUEST_BY_LEVEL = 2
 
 
 class SZ3HipError(RuntimeError):
@@ -139,6 +140,17 @@ class _CTilesPlan(C.Structure):
     """sz3hip_tiles_plan (include/sz3hip.h)"""
     _fields_ = [("n_boxes", C.c_uint32), ("n_levels", C.c_int32), ("points", C.c_uint64), ("scratch_elems", C.c_uint64), ("units_total", C.c_uint64),
                 ("units_needed", C.c_uint64)]
+
+
+class _CTileReq(C.Structure):
+    """sz3hip_tile_req (include/sz3hip.h)"""
+    _fields_ = [("level", C.c_int32), ("reserved", C.c_uint32), ("box", _CBox), ("d_out", C.c_void_p), ("strides", C.c_int64 * 4)]
+
+
+class _CRequestPlan(C.Structure):
+    """sz3hip_request_plan (include/sz3hip.h)"""
+    _fields_ = [("n", C.c_uint32), ("finest_level", C.c_int32), ("coarsest_level", C.c_int32), ("n_levels", C.c_int32), ("points", C.c_uint64),
+                ("scratch_elems", C.c_uint64)]
 
 
 class _CStreamStats(C.Structure):
@@ -295,6 +307,10 @@ def lib():
     L.sz3hip_stream_tiles.argtypes = [C.c_void_p, C.c_int, P(_CBox), C.c_uint32, P(C.c_void_p), C.c_void_p]
     L.sz3hip_stream_stats.restype = C.c_int
     L.sz3hip_stream_stats.argtypes = [C.c_void_p, P(_CStreamStats)]
+    L.sz3hip_stream_request.restype = C.c_int
+    L.sz3hip_stream_request.argtypes = [C.c_void_p, P(_CTileReq), C.c_uint32, C.c_void_p]
+    L.sz3hip_request_plan_for.restype = C.c_int
+    L.sz3hip_request_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CRequestPlan)]
     L.sz3hip_stream_close.restype = None
     L.sz3hip_stream_close.argtypes = [C.c_void_p]
     L.sz3hip_debug_chain_points.restype = None
@@ -807,6 +823,37 @@ def decompress_coarse(blob, dtype, level, out=None, device=None, stream=None):
     return _decompress_partial("decompress_coarse", blob, dtype, lambda: (int(level),), lambda conf: (coarse_dims(conf, level), (int(level),)), out, device, stream)
 
 
+def request_plan(conf, dtype, items):
+    """what one Stream.request for `items` touches (sz3hip_request_plan_for), without a device. `items` have Stream.request's form: (level, lo,
+    shape) or (level, lo, shape, out), lo / shape in coordinates of the grid of every 2**level-th point of conf's array. Of a tensor `out` the
+    plan reads the address and the element strides only (its shape and dtype are checked as request checks them); an item without one is
+    given a contiguous placeholder that overlaps no other. The request's own checks run, views and overlaps included. Returns a dict with n,
+    finest_level, coarsest_level, n_levels (the array levels the one merged launch sequence runs), points and scratch_elems (summed over
+    the boxes)."""
+    items = [tuple(it) for it in items]
+    if any(len(it) not in (3, 4) for it in items):
+        raise ValueError("an item is (level, lo, shape) or (level, lo, shape, out)")
+    npdt = _np_dtype(dtype)
+    arr, shapes = _boxes(conf.N, [(it[1], it[2]) for it in items])
+    reqs = (_CTileReq * max(len(items), 1))()
+    at = 1 << 40  # (placeholders: never read, never written)
+    for i, (it, shape) in enumerate(zip(items, shapes)):
+        reqs[i].level = int(it[0])
+        reqs[i].box = arr[i]
+        t = it[3] if len(it) == 4 else None
+        if t is not None:
+            if _np_dtype(t.dtype) != npdt or tuple(t.shape) != shape:
+                raise ValueError("item %d: out must be a %s tensor of the box's shape %s" % (i, npdt, shape))
+            reqs[i].d_out = t.data_ptr()
+            reqs[i].strides[:conf.N] = [int(v) for v in t.stride()]
+        else:
+            reqs[i].d_out = at
+            at += (int(np.prod(shape, dtype=np.uint64)) * npdt.itemsize + 255) & ~255
+    plan = _CRequestPlan()
+    _check(lib().sz3hip_request_plan_for(C.byref(conf._c), _dtype_id(npdt), reqs, len(items), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k, _ in _CRequestPlan._fields_}
+
+
 def set_chain_points(points):
     """development switch (sz3hip_debug_chain_points): a Stream request runs its coarsest levels — those whose every pass has at most
     `points` points for every box — in one launch; 0 switches the chain off"""
@@ -820,7 +867,8 @@ def get_chain_points():
 class Stream:
     """An opened stream (sz3hip_stream_*): open_stream / DeviceCompressor.open_stream do, once, everything of a partial
     decode that does not depend on the box — the container's host stage, the copy in, the Huffman stage over every unit — and keep the codes
-    resident on the device; tiles / tile / region / coarse are then the reconstruction alone, bit for bit what decompress_tiles delivers.
+    resident on the device; tiles / tile / region / coarse are then the reconstruction alone, bit for bit what decompress_tiles delivers;
+    request takes boxes of several levels, each into a view of its own, in one launch sequence (section 16).
     A container that is no single interpolation stream is decoded in full once (stats()["fast"] == 0) and its requests are gathers.
     One request at a time: a Stream is not thread-safe. Use as a context manager, or close() it."""
 
@@ -872,6 +920,32 @@ class Stream:
         ptrs = (C.c_void_p * max(len(out), 1))(*[t.data_ptr() for t in out])
         _check(lib().sz3hip_stream_tiles(self._h, int(level), arr, len(shapes), ptrs, _stream_handle(self.device, stream)))
         return out
+
+    def request(self, items, stream=None):
+        """boxes of SEVERAL levels in one request (sz3hip_stream_request): `items` are (level, lo, shape) or
+        (level, lo, shape, out) — lo / shape in coordinates of the grid of every 2**level-th point; `out` any view of that shape and the
+        stream's dtype on its device, its element strides taken from the tensor: a rectangle of an atlas, a view with a step along x.
+        Missing outputs are allocated. One launch sequence serves all boxes, whatever their levels. Asynchronous on `stream`, as tiles.
+        Returns the list of tensors."""
+        items = [tuple(it) for it in items]
+        if any(len(it) not in (3, 4) for it in items):
+            raise ValueError("an item is (level, lo, shape) or (level, lo, shape, out)")
+        N = self.conf.N
+        arr, shapes = _boxes(N, [(it[1], it[2]) for it in items])
+        import torch
+        reqs = (_CTileReq * max(len(items), 1))()
+        outs = []
+        for i, (it, shape) in enumerate(zip(items, shapes)):
+            t = it[3] if len(it) == 4 and it[3] is not None else torch.empty(shape, dtype=getattr(torch, self.dtype.name), device=self.device)
+            if not _gpu_tensor(t) or _np_dtype(t.dtype) != self.dtype or tuple(t.shape) != shape or t.device != self.device:
+                raise ValueError("item %d: out must be a %s tensor of the box's shape %s on %s" % (i, self.dtype, shape, self.device))
+            outs.append(t)
+            reqs[i].level = int(it[0])
+            reqs[i].box = arr[i]
+            reqs[i].d_out = t.data_ptr()
+            reqs[i].strides[:N] = [int(v) for v in t.stride()]
+        _check(lib().sz3hip_stream_request(self._h, reqs, len(items), _stream_handle(self.device, stream)))
+        return outs
 
     def tile(self, level, lo, shape, out=None, stream=None):
         """one box of the grid of every 2**level-th point (tiles with one box)"""

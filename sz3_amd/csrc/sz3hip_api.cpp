@@ -2393,6 +2393,32 @@ int szi_boxes_geometry(int N, const uint64_t *dims, int interp_id, int direction
                        std::vector<szk_region_geom> &gs, uint64_t *scratch_elems) {
     return boxes_geometry(N, dims, interp_id, direction, anchor_stride, level, boxes, n, gs, scratch_elems);
 }
+// the boxes of a request of several levels: box i on the grid of its own level; the checks, codes and wording are
+// boxes_geometry's, the running base too. The boxes' level counts differ: the launcher aligns them by array level.
+int szi_request_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const sz3hip_tile_req *reqs, uint32_t n,
+                         std::vector<szk_region_geom> &gs, uint64_t *scratch_elems) {
+    gs.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const int rc = region_geometry(N, dims, interp_id, direction, anchor_stride, reqs[i].box.lo, reqs[i].box.ext, &gs[i], reqs[i].level);
+        if (rc) return rc == SZ3HIP_EINVAL ? szi_fail_box(i) : rc;
+    }
+    uint64_t base = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        szk_region_geom &g = gs[i];
+        for (int b = 0; b < g.nbuf; b++) g.lv[b].base += base;
+        base += g.scratch_elems;
+    }
+    *scratch_elems = base;
+    return 0;
+}
+int szi_request_geometry_conf(const sz3hip_config *conf, const sz3hip_tile_req *reqs, uint32_t n, std::vector<szk_region_geom> &gs, uint64_t *scratch_elems) {
+    if (conf->N < 1 || conf->N > 4) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", (int)conf->N);
+    static const int def_anchor[4] = {4096, 128, 32, 16};  // (conf_geometry's)
+    const uint64_t anchor = conf->interpAnchorStride < 0 ? (uint64_t)def_anchor[conf->N - 1] : (uint64_t)conf->interpAnchorStride;
+    uint64_t dims[4] = {0, 0, 0, 0};
+    for (int i = 0; i < conf->N; i++) dims[i] = conf->dims[i];
+    return szi_request_geometry(conf->N, dims, conf->interpAlgo, conf->interpDirection, anchor, reqs, n, gs, scratch_elems);
+}
 // the outputs of a request: n device pointers, box i's array of prod(ext) elements of tsz bytes; none NULL, no two overlapping
 int szi_boxes_outputs_check(int N, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, size_t tsz) {
     std::vector<std::pair<uintptr_t, uintptr_t>> r(n);

@@ -84,6 +84,11 @@ int szi_boxes_outputs_check(int N, const sz3hip_box *boxes, uint32_t n, void *co
 int szi_boxes_args(const char *who, const void *boxes, uint32_t n, const void *third, const char *third_name);
 int szi_boxes_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, int level, const sz3hip_box *boxes, uint32_t n,
                        std::vector<szk_region_geom> &gs, uint64_t *scratch_elems);
+// the geometries of a request whose boxes name their own levels (sz3hip_stream_request, sz3hip_request_plan_for): boxes_geometry's checks and
+// wording per box, the buffers one after the other in the scratch; _conf: from a Config, as the plan functions read it
+int szi_request_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const sz3hip_tile_req *reqs, uint32_t n,
+                         std::vector<szk_region_geom> &gs, uint64_t *scratch_elems);
+int szi_request_geometry_conf(const sz3hip_config *conf, const sz3hip_tile_req *reqs, uint32_t n, std::vector<szk_region_geom> &gs, uint64_t *scratch_elems);
 // the host side of sz3hip_stream_open (sz3hip_host.cpp: the container, libzstd and the slots live there): the arguments' checks, then either the
 // stream's codes (*fast = 1) or, for a container that is no single interpolation stream, its full decode in *d_full (hipMalloc; the caller owns it).
 // *huffman: Huffman stages run (0: a container without one). conf comes back as the full array's

@@ -431,6 +431,33 @@ int szk_launch_interp_decompress_region_multi(int dtype, const szk_interp_params
                                               const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                               void *scratch, void *const *d_outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied,
                                               hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches);
+// boxes of SEVERAL levels of one stream in one launch sequence, into strided views. gs[i]: box i's geometry at ITS level
+// (gs[i].shift), lv[].base already the buffer's place in `scratch`; outs[i]: where box i goes. The boxes are aligned by array level: one
+// scatter, one first point, per array level from the top down to the finest requested one a regrid and the N passes, one strided gather —
+// the launch count is the finest level's own, whatever the number of boxes and levels. *levels: the array levels that sequence ran.
+// A request whose boxes all have ONE level is szk_launch_interp_decompress_region_multi's sequence exactly (chain_points as there) with the
+// strided gather in the gather's place; two or more levels never take the chain (*chain_levels 0). Where the alignment does not hold
+// (n_levels + shift differs between two boxes that run levels — no stream this library decodes does that) the request runs level group by
+// level group over the one-level sequence. Table, `copied` and the return values are the multi call's.
+struct szk_region_out {
+    void *dst;        // the view's element [0, .., 0]
+    int64_t str[4];   // element strides, slowest first, N entries used (those of extent-1 dimensions are not read)
+};
+struct szk_region_gather_strided_box {  // a record of k_region_gather_strided: extents in the last N of four places (1 in front)
+    uint64_t total, src;  // points of the box; its corner, in elements from the source array's start
+    void *dst;
+    uint64_t ext[4], str[4];  // the source's element strides
+    int64_t dstr[4];          // the destination's
+};
+uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n);
+int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
+                                                const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
+                                                void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,
+                                                hipEvent_t copied, hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches, uint32_t *levels);
+// n strided boxes of one array into n strided views in one launch (the gather of szk_launch_gather with a strided destination, per box): recs
+// are copied through h_table into d_table (n * 15 words) in front of the launch, `copied` recorded behind the copy
+int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gather_strided_box *recs, uint32_t n, uint64_t *h_table, uint64_t *d_table,
+                            uint64_t table_words, hipEvent_t copied, hipStream_t s);
 uint64_t szk_region_launches(void);  // test hook: kernel launches the box reconstructions issued so far, single and multi
 
 int szk_launch_profile_blocks(int dtype, const void *d_in, int N, const uint64_t *dims, uint64_t bs, uint64_t stride, double abseb,

@@ -20,6 +20,7 @@
 #include "sz3hip_devutil.h"
 #include "sz3hip_interp_rules.h"
 
+#include <algorithm>
 #include <atomic>
 #include <vector>
 
@@ -509,6 +510,86 @@ __global__ __launch_bounds__(256) void k_region_gather_multi(const T *__restrict
     static_cast<T *>(b.dst)[t] = scratch[b.src + so];
 }
 
+// ---- boxes of SEVERAL levels in one launch sequence --------------------------------------------------------------------
+// A tile of level k is the region problem on the grid of every 2^k-th point, and its grid level l is the array's level l + k; for every box
+// that runs levels at all n_levels + shift is the array's level count. So the boxes of a mixed request are aligned by ARRAY level: in the
+// launch of array level A - b every box works on ITS buffer b (lv[b], stride 2^(nbuf - 1 - b) on its own grid), and a box of fewer than b + 1
+// levels has finished — its record carries total 0. What the multi form passes as a kernel argument common to all boxes and the box's level
+// decides — s, ls, bsz, off, dims, step; nbuf, shift — moves into the box's record; what an array level decides stays an argument. The
+// bodies are the ones above.
+struct szk_region_scatter_box {
+    uint64_t rows;         // the box's nbuf rows (szk_region_scatter_row), in words from the table's start
+    uint32_t nbuf, shift;
+};
+struct szk_region_pass_level {  // what all boxes share at an array level: szk_region_pass_shared without what the box's level decides
+    int N, dir, interp_id, old_api, subpass, radius;
+    double eb;
+};
+struct szk_region_pass_mixed_box {
+    uint64_t s, ls, bsz;
+    uint64_t dims[4], off[4], step[4];
+    szk_region_pass_box box;
+};
+static_assert(sizeof(szk_region_scatter_box) == 2 * 8 && sizeof(szk_region_pass_mixed_box) == 34 * 8 && sizeof(szk_region_gather_strided_box) == 15 * 8 &&
+                  sizeof(szk_region_pass_level) == 4 * 8,
+              "table records are rows of words");
+template <typename T>
+__global__ __launch_bounds__(256) void k_region_scatter_raw_mixed(const uint8_t *__restrict__ payload, uint64_t idx_off, uint64_t val_off, uint64_t cnt, uint64_t n,
+                                                                  szk_sel4 full, const uint64_t *__restrict__ tab, const szk_region_scatter_box *__restrict__ recs,
+                                                                  T *__restrict__ scratch) {
+    const szk_region_scatter_box &r = recs[blockIdx.y];
+    szk_region_scatter_shared g;
+#pragma unroll
+    for (int j = 0; j < 4; j++) g.full[j] = full.v[j];
+    g.nbuf = r.nbuf;
+    g.shift = r.shift;
+    region_scatter_records<T>(payload, idx_off, val_off, cnt, n, g, reinterpret_cast<const szk_region_scatter_row *>(tab + r.rows), scratch);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_region_pass_mixed(T *__restrict__ scratch, const uint16_t *__restrict__ codes, szk_region_pass_level lvl,
+                                                           const szk_region_pass_mixed_box *__restrict__ recs) {
+    const szk_region_pass_mixed_box &r = recs[blockIdx.y];
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= r.box.total) return;  // (also every workgroup of a box that has finished: total 0)
+    szk_region_pass_shared sh;
+    sh.N = lvl.N;
+    sh.dir = lvl.dir;
+    sh.interp_id = lvl.interp_id;
+    sh.old_api = lvl.old_api;
+    sh.subpass = lvl.subpass;
+    sh.radius = lvl.radius;
+    sh.ls = (uint32_t)r.ls;
+    sh.s = r.s;
+    sh.bsz = r.bsz;
+    sh.eb = lvl.eb;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        sh.dims[j] = r.dims[j];
+        sh.off[j] = r.off[j];
+        sh.step[j] = r.step[j];
+    }
+    const szk_region_pass_parts p = region_pass_join<szk_region_pass_parts>(sh, r.box, lvl.subpass);
+    region_pass_point<T>(scratch + r.box.base, codes, p, t);
+}
+// k_region_gather_multi with the destination's element strides in the record: box i out of `src` (the scratch: its finest buffer; a handle
+// that keeps the full array: that array, str the strides of its every 2^level-th point) into the view at b.dst; lanes run along x
+template <typename T>
+__global__ __launch_bounds__(256) void k_region_gather_strided(const T *__restrict__ src, const szk_region_gather_strided_box *__restrict__ recs) {
+    const szk_region_gather_strided_box &b = recs[blockIdx.y];
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= b.total) return;
+    uint64_t r = t, so = 0;
+    int64_t dx = 0;
+#pragma unroll
+    for (int j = 3; j >= 0; j--) {
+        const uint64_t q = r % b.ext[j];
+        so += q * b.str[j];
+        dx += (int64_t)q * b.dstr[j];
+        r /= b.ext[j];
+    }
+    static_cast<T *>(b.dst)[dx] = src[b.src + so];
+}
+
 // ---- the coarsest levels of a request in ONE launch ---------------------------------------------------------------------
 // All but the finest one or two levels of a box are a few thousand points each, and every one of them costs a launch or two per pass. Here one
 // workgroup per box (blockIdx.x) walks a step table — first point, regrid, pass, deferred sub-pass — over the request's coarsest levels: each
@@ -659,6 +740,50 @@ static int region_gather_record(const szk_region_geom &g, void *dst, szk_region_
     }
     return 0;
 }
+// the same into a strided view: the gather record and the destination's element strides (none for a dimension of extent 1)
+static int region_gather_strided_record(const szk_region_geom &g, const szk_region_out &out, szk_region_gather_strided_box *r) {
+    szk_region_gather_box c;
+    if (region_gather_record(g, out.dst, &c)) return -1;
+    memset(r, 0, sizeof(*r));
+    r->total = c.total;
+    r->src = c.src;
+    r->dst = c.dst;
+    for (int q = 0; q < 4; q++) {
+        const int j = q - (4 - g.N);
+        r->ext[q] = c.ext[q];
+        r->str[q] = c.str[q];
+        r->dstr[q] = j >= 0 && g.ext[j] > 1 ? out.str[j] : 0;
+    }
+    return 0;
+}
+// a box's gather record as its launch reads it — into the view *out, or (out null) into the contiguous array dst — as words; *total: the box's points
+static int region_gather_words(const szk_region_geom &g, void *dst, const szk_region_out *out, uint64_t *rec, uint64_t *total) {
+    szk_region_gather_box c;
+    szk_region_gather_strided_box v;
+    if (out ? region_gather_strided_record(g, *out, &v) : region_gather_record(g, dst, &c)) return -1;
+    if (out) memcpy(rec, &v, sizeof(v));
+    else memcpy(rec, &c, sizeof(c));
+    *total = out ? v.total : c.total;
+    return 0;
+}
+// a box's part of a pass at array level A - b as the mixed form keeps it: what the box's level decides, and the multi form's record. A box of
+// fewer than b + 1 levels has finished: a record of zeros (total 0). sh: the level's shared part as the box sees it (eb, dir: the array level's)
+static int region_pass_mixed_record(const szk_interp_params &ip, const szk_region_geom &g, int b, int k, szk_region_pass_shared *sh, szk_region_pass_mixed_box *r) {
+    memset(r, 0, sizeof(*r));
+    memset(sh, 0, sizeof(*sh));
+    if (b >= g.n_levels) return 0;
+    region_pass_level(ip, g, b, sh);
+    if (region_pass_records(g, b, k, sh, &r->box)) return -1;
+    r->s = sh->s;
+    r->ls = sh->ls;
+    r->bsz = sh->bsz;
+    for (int j = 0; j < 4; j++) {
+        r->dims[j] = sh->dims[j];
+        r->off[j] = sh->off[j];
+        r->step[j] = sh->step[j];
+    }
+    return 0;
+}
 
 // ---- host: the launches ---------------------------------------------------------------------------------------------------------------
 // test hook (sz3hip_debug_region_launches): kernel launches the box reconstructions of this process issued, single and multi. Every launch
@@ -752,7 +877,7 @@ template <typename T>
 static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
                             uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, T *scratch, void *const *d_outs,
                             uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t chain_points,
-                            uint32_t *chain_levels, uint32_t *launches) {
+                            uint32_t *chain_levels, uint32_t *launches, const szk_region_out *outs = nullptr) {  // (outs: strided views instead of d_outs)
     const szk_region_geom &g0 = gs[0];
     const int N = g0.N, nbuf = g0.nbuf, n_levels = g0.n_levels;
     // the chain takes the coarsest c levels: the largest count such that every pass of those levels has at most chain_points points for EVERY box
@@ -850,13 +975,14 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
         }
     }
     {
-        if (!launch_at(4, SZK_WORDS(szk_region_gather_box), &l)) return -1;
+        const uint64_t words = outs ? SZK_WORDS(szk_region_gather_strided_box) : SZK_WORDS(szk_region_gather_box);  // (the form is the request's, chosen once)
+        if (!launch_at(4, words, &l)) return -1;
         uint64_t most = 0;
         for (uint32_t i = 0; i < n; i++) {
-            szk_region_gather_box r;
-            if (region_gather_record(gs[i], d_outs[i], &r)) return -1;
-            put(&r, sizeof(r));
-            most = r.total > most ? r.total : most;
+            uint64_t rec[SZK_WORDS(szk_region_gather_strided_box)], total;
+            if (region_gather_words(gs[i], outs ? nullptr : d_outs[i], outs ? &outs[i] : nullptr, rec, &total)) return -1;
+            put(rec, words * 8);
+            most = std::max(most, total);
         }
         if (!region_grid(most, &l.gx)) return -1;
         seq.push_back(l);
@@ -921,7 +1047,8 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
             }
             break;
         default:
-            region_launch(&issued, k_region_gather_multi<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_box *>(rec));
+            if (outs) region_launch(&issued, k_region_gather_strided<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_strided_box *>(rec));
+            else region_launch(&issued, k_region_gather_multi<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_box *>(rec));
         }
     }
     if (launches) *launches = issued;
@@ -950,4 +1077,269 @@ int szk_launch_interp_decompress_region_multi(int dtype, const szk_interp_params
                                                 table_words, copied, s, chain_points, chain_levels, launches)
                       : run_region_multi<double>(*ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, (double *)scratch, d_outs, h_table, d_table,
                                                  table_words, copied, s, chain_points, chain_levels, launches);
+}
+
+// ---- boxes of several levels in one request ------------------------------------------------------------------------
+namespace {
+struct MixedLaunch {
+    int kind;      // 0 scatter, 1 first, 2 regrid, 3 pass, 4 gather
+    uint64_t off;  // the launch's records in the table, in words
+    uint32_t gx;
+    bool twice;
+    szk_region_pass_level lvl;
+};
+// the array's level count as the boxes that run levels see it; false: two of them disagree (or differ in pass order), the sequence cannot be merged
+bool request_aligned(const szk_region_geom *gs, uint32_t n) {
+    int A = -1;
+    for (uint32_t i = 0; i < n; i++) {
+        if (memcmp(gs[i].perm, gs[0].perm, sizeof(gs[0].perm))) return false;
+        if (gs[i].n_levels == 0) continue;
+        if (A >= 0 && gs[i].n_levels + gs[i].shift != A) return false;
+        A = gs[i].n_levels + gs[i].shift;
+    }
+    return true;
+}
+}  // namespace
+uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n) {
+    uint64_t nl = 0, kinds = 0, words = 0;
+    const uint64_t N = (uint64_t)gs[0].N;
+    for (uint32_t i = 0; i < n; i++) {
+        nl = std::max<uint64_t>(nl, (uint64_t)gs[i].n_levels);
+        kinds |= 1ull << gs[i].shift;
+    }
+    for (uint32_t i = 0; i < n; i++)
+        words += (uint64_t)gs[i].nbuf * SZK_WORDS(szk_region_scatter_row) + SZK_WORDS(szk_region_scatter_box) + SZK_WORDS(szk_region_first_box) +
+                 nl * SZK_WORDS(szk_region_regrid_box) + nl * N * SZK_WORDS(szk_region_pass_mixed_box) + SZK_WORDS(szk_region_gather_strided_box);
+    // (one level, or level group by level group: the one-level sequence's chain parts, once per level)
+    return words + (uint64_t)__builtin_popcountll(kinds) * (nl * N * SZK_WORDS(szk_region_pass_shared) + (1 + nl * (1 + 2 * N)) * SZK_WORDS(szk_chain_step));
+}
+template <typename T>
+static int run_region_mixed(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
+                            uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, T *scratch, const szk_region_out *outs,
+                            uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t *launches, uint32_t *levels) {
+    const int N = gs[0].N;
+    int n_levels = 0;  // the array levels the sequence runs: the finest box's own count
+    for (uint32_t i = 0; i < n; i++) {
+        n_levels = std::max(n_levels, gs[i].n_levels);
+        for (int b = 0; b < gs[i].nbuf; b++)
+            if (gs[i].lv[b].base > scratch_elems || gs[i].lv[b].elems > scratch_elems - gs[i].lv[b].base) return -1;
+    }
+    if (levels) *levels = (uint32_t)n_levels;
+    std::vector<MixedLaunch> seq;
+    uint64_t w = 0;
+    auto room = [&](uint64_t words) { return words <= table_words && w <= table_words - words; };
+    auto put = [&](const void *rec, size_t bytes) {
+        memcpy(h_table + w, rec, bytes);
+        w += bytes / 8;
+    };
+    auto launch_at = [&](int kind, uint64_t words, MixedLaunch *l) {
+        *l = MixedLaunch{};
+        l->kind = kind;
+        l->off = w;
+        return room((uint64_t)n * words);
+    };
+    MixedLaunch l;
+    if (n_vout) {  // every box's rows, then the boxes' records
+        std::vector<szk_region_scatter_box> recs(n);
+        for (uint32_t i = 0; i < n; i++) {
+            szk_region_scatter_row rows[SZK_REGION_MAX_LEVELS];
+            if (!room((uint64_t)gs[i].nbuf * SZK_WORDS(szk_region_scatter_row))) return -1;
+            region_scatter_rows(gs[i], rows);
+            recs[i] = {w, (uint32_t)gs[i].nbuf, (uint32_t)gs[i].shift};
+            put(rows, gs[i].nbuf * sizeof(rows[0]));
+        }
+        if (!launch_at(0, SZK_WORDS(szk_region_scatter_box), &l)) return -1;
+        put(recs.data(), n * sizeof(recs[0]));
+        l.gx = region_scatter_grid(n_vout);
+        seq.push_back(l);
+    }
+    {  // the first point: per box (a box whose every grid point is an anchor has none, whatever the others have)
+        if (!launch_at(1, SZK_WORDS(szk_region_first_box), &l)) return -1;
+        bool any = false;
+        for (uint32_t i = 0; i < n; i++) {
+            szk_region_first_box r = region_first_record(gs[i]);
+            if (gs[i].anchor != 0) r.total = 0;
+            put(&r, sizeof(r));
+            any = any || r.total;
+        }
+        l.gx = 1;
+        if (any) seq.push_back(l);
+        else w = l.off;
+    }
+    for (int b = 0; b < n_levels; b++) {
+        uint64_t most = 0;
+        if (b > 0) {
+            if (!launch_at(2, SZK_WORDS(szk_region_regrid_box), &l)) return -1;
+            for (uint32_t i = 0; i < n; i++) {
+                szk_region_regrid_box r;
+                memset(&r, 0, sizeof(r));
+                if (b < gs[i].n_levels && region_regrid_record(gs[i], b, &r)) return -1;
+                put(&r, sizeof(r));
+                most = std::max(most, r.g.total);
+            }
+            if (!region_grid(most, &l.gx)) return -1;
+            if (most) seq.push_back(l);
+            else w = l.off;
+        }
+        for (int k = 0; k < N; k++) {
+            if (!launch_at(3, SZK_WORDS(szk_region_pass_mixed_box), &l)) return -1;
+            most = 0;
+            bool have = false;
+            szk_region_pass_shared ref;
+            for (uint32_t i = 0; i < n; i++) {
+                szk_region_pass_shared sh;
+                szk_region_pass_mixed_box r;
+                if (region_pass_mixed_record(ip, gs[i], b, k, &sh, &r)) return -1;
+                put(&r, sizeof(r));
+                if (b >= gs[i].n_levels) continue;
+                // (what stays a kernel argument is the array level's: the same for every box that runs it)
+                // (-4, before anything is copied or launched: the caller then serves the request level group by level group)
+                if (have && (sh.dir != ref.dir || sh.old_api != ref.old_api || sh.interp_id != ref.interp_id || memcmp(&sh.eb, &ref.eb, sizeof(sh.eb)))) return -4;
+                if (!have) ref = sh;
+                have = true;
+                most = std::max(most, r.box.total);
+            }
+            if (!region_grid(most, &l.gx)) return -1;
+            if (most == 0) {
+                w = l.off;
+                continue;
+            }
+            l.lvl = szk_region_pass_level{ref.N, ref.dir, ref.interp_id, ref.old_api, 0, ref.radius, ref.eb};
+            l.twice = region_pass_twice(ref);
+            seq.push_back(l);
+        }
+    }
+    {
+        if (!launch_at(4, SZK_WORDS(szk_region_gather_strided_box), &l)) return -1;
+        uint64_t most = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            szk_region_gather_strided_box r;
+            if (region_gather_strided_record(gs[i], outs[i], &r)) return -1;
+            put(&r, sizeof(r));
+            most = std::max(most, r.total);
+        }
+        if (!region_grid(most, &l.gx)) return -1;
+        seq.push_back(l);
+    }
+    if (hipMemcpyAsync(d_table, h_table, w * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+    if (hipEventRecord(copied, s) != hipSuccess) return -2;
+    szk_sel4 full;
+    for (int q = 0; q < 4; q++) full.v[q] = q - (4 - N) >= 0 ? gs[0].full[q - (4 - N)] : 1;
+    uint64_t off[4];
+    const uint64_t num = region_code_steps(gs[0], off);
+    uint32_t issued = 0;
+    for (const MixedLaunch &ml : seq) {
+        const dim3 grid(ml.gx, n);
+        const uint64_t *rec = d_table + ml.off;
+        switch (ml.kind) {
+        case 0:
+            region_launch(&issued, k_region_scatter_raw_mixed<T>, grid, 256, s, payload, vout_idx_off, vout_val_off, n_vout, num, full, (const uint64_t *)d_table,
+                          reinterpret_cast<const szk_region_scatter_box *>(rec), scratch);
+            break;
+        case 1:
+            region_launch(&issued, k_region_first_multi<T>, grid, 64, s, scratch, codes, ip.eb, ip.radius, reinterpret_cast<const szk_region_first_box *>(rec));
+            break;
+        case 2:
+            region_launch(&issued, k_region_regrid_multi<T>, grid, 256, s, scratch, reinterpret_cast<const szk_region_regrid_box *>(rec));
+            break;
+        case 3:
+            for (int sub = 0; sub < (ml.twice ? 2 : 1); sub++) {
+                szk_region_pass_level lvl = ml.lvl;
+                lvl.subpass = sub;
+                region_launch(&issued, k_region_pass_mixed<T>, grid, 256, s, scratch, codes, lvl, reinterpret_cast<const szk_region_pass_mixed_box *>(rec));
+            }
+            break;
+        default:
+            region_launch(&issued, k_region_gather_strided<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_strided_box *>(rec));
+        }
+    }
+    if (launches) *launches = issued;
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+template <typename T>
+static int run_region_request(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
+                              uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, T *scratch, const szk_region_out *outs,
+                              uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t chain_points,
+                              uint32_t *chain_levels, uint32_t *launches, uint32_t *levels) {
+    bool one = true;
+    for (uint32_t i = 1; i < n; i++) one = one && gs[i].shift == gs[0].shift;
+    if (one) {  // the one-level sequence, the chain included
+        if (levels) *levels = (uint32_t)gs[0].n_levels;
+        return run_region_multi<T>(ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, nullptr, h_table, d_table, table_words, copied, s,
+                                   chain_points, chain_levels, launches, outs);
+    }
+    if (request_aligned(gs, n) && !(szk_dbg_flags2 & SZ3HIP_DBG2_REQUEST_BY_LEVEL)) {
+        const int rc = run_region_mixed<T>(ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, outs, h_table, d_table, table_words,
+                                           copied, s, launches, levels);
+        if (rc != -4) return rc;  // (-4: a pass's arguments are not one for all boxes; nothing was copied or launched)
+    }
+    // level group by level group, every group with a stretch of the table of its own (no wait between the groups' copies)
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return gs[a].shift < gs[b].shift; });
+    uint64_t used = 0;
+    uint32_t total = 0, most_levels = 0;
+    for (uint32_t at = 0; at < n;) {
+        std::vector<szk_region_geom> gg;
+        std::vector<szk_region_out> oo;
+        for (; at < n && (gg.empty() || gs[order[at]].shift == gg[0].shift); at++) {
+            gg.push_back(gs[order[at]]);
+            oo.push_back(outs[order[at]]);
+        }
+        const uint64_t need = szk_region_request_table_words(gg.data(), (uint32_t)gg.size());
+        if (need > table_words || used > table_words - need) return -1;
+        uint32_t issued = 0;
+        const int rc = run_region_multi<T>(ip, gg.data(), (uint32_t)gg.size(), scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, nullptr,
+                                           h_table + used, d_table + used, need, copied, s, 0, nullptr, &issued, oo.data());
+        if (rc) return rc;
+        used += need;
+        total += issued;
+        most_levels = std::max(most_levels, (uint32_t)gg[0].n_levels);
+    }
+    if (launches) *launches = total;
+    if (levels) *levels = most_levels;
+    return 0;
+}
+
+int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
+                                                const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
+                                                void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,
+                                                hipEvent_t copied, hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches, uint32_t *levels) {
+    if (chain_levels) *chain_levels = 0;
+    if (launches) *launches = 0;
+    if (levels) *levels = 0;
+    if (n < 1 || n > 65535 || !gs || !outs || !h_table || !d_table) return -1;
+    for (uint32_t i = 0; i < n; i++) {  // one stream: every box on the grid of its own level
+        const szk_region_geom &g = gs[i];
+        if (g.N != ip->N || g.nbuf < 1 || g.nbuf > SZK_REGION_MAX_LEVELS || g.n_levels < 0 || g.n_levels > g.nbuf || g.shift < 0 || g.shift > 30) return -1;
+        for (int j = 0; j < ip->N; j++)
+            if (g.full[j] != ip->dims[j] || g.dims[j] != ((ip->dims[j] - 1) >> g.shift) + 1) return -1;
+        if (!outs[i].dst) return -1;
+        if (g.shift == gs[0].shift) {  // (the one-level sequence's conditions, for the boxes of a level)
+            if (g.n_levels != gs[0].n_levels || g.nbuf != gs[0].nbuf || g.anchor != gs[0].anchor) return -1;
+        }
+    }
+    return dtype == 0 ? run_region_request<float>(*ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, (float *)scratch, outs, h_table, d_table,
+                                                  table_words, copied, s, chain_points, chain_levels, launches, levels)
+                      : run_region_request<double>(*ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, (double *)scratch, outs, h_table, d_table,
+                                                   table_words, copied, s, chain_points, chain_levels, launches, levels);
+}
+
+int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gather_strided_box *recs, uint32_t n, uint64_t *h_table, uint64_t *d_table,
+                            uint64_t table_words, hipEvent_t copied, hipStream_t s) {
+    if (n < 1 || n > 65535 || !d_src || !recs || !h_table || !d_table || (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box) > table_words) return -1;
+    uint64_t most = 0;
+    for (uint32_t i = 0; i < n; i++) most = std::max(most, recs[i].total);
+    uint32_t gx;
+    if (!region_grid(most, &gx)) return -1;
+    memcpy(h_table, recs, (size_t)n * sizeof(recs[0]));
+    if (hipMemcpyAsync(d_table, h_table, (size_t)n * sizeof(recs[0]), hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+    if (hipEventRecord(copied, s) != hipSuccess) return -2;
+    const szk_region_gather_strided_box *d_recs = reinterpret_cast<const szk_region_gather_strided_box *>(d_table);
+    if (dtype == 0) region_launch(nullptr, k_region_gather_strided<float>, dim3(gx, n), 256, s, (const float *)d_src, d_recs);
+    else region_launch(nullptr, k_region_gather_strided<double>, dim3(gx, n), 256, s, (const double *)d_src, d_recs);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
 }

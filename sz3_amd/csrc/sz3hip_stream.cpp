@@ -7,6 +7,8 @@
 // set than a context (no histogram, code books, outlier lists or payload). A container that is no single interpolation stream is decoded in full,
 // once, into an array the handle keeps; its requests are strided gathers.
 // A request (sz3hip_stream_tiles) is boxes_prepare's checks and the multi-box reconstruction (sz3hip_region.hip) against the resident arrays.
+// sz3hip_stream_request takes boxes of several levels, each into a strided view of its own: the views' checks are here,
+// the one launch sequence aligned by array level in sz3hip_region.hip.
 // A handle serves one request at a time; it is not thread-safe.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -333,6 +335,193 @@ extern "C" int sz3hip_stream_tiles(sz3hip_stream *h, int level, const sz3hip_box
     h->launches_last = launches;
     h->chain_last = chain_levels;
     h->levels_last = (uint32_t)gs[0].n_levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+// ---- boxes of several levels in one request, into strided views ----------------------------------------------------------
+namespace {
+struct ReqView {
+    uintptr_t lo, hi;  // the byte hull
+    int64_t str[4];    // element strides as the kernels read them: the caller's, or the contiguous ones
+    bool atlas;        // the caller's strides are positive and nested over ALL N dimensions: the view may be a rectangle of an atlas
+};
+// what comes before any geometry: the arguments, every box's reserved word and output pointer
+int request_args(const char *who, const sz3hip_tile_req *reqs, uint32_t n) {
+    int rc = szi_boxes_args(who, reqs, n, reqs, "reqs");
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n; i++) {
+        if (reqs[i].reserved) return fail(SZ3HIP_EINVAL, "box %u: the reserved word is %u, not 0", i, reqs[i].reserved);
+        if (!reqs[i].d_out) return fail(SZ3HIP_EINVAL, "box %u: the output array is NULL", i);
+    }
+    return 0;
+}
+// every view by itself, then every pair (the boxes' extents are checked by now: none is 0)
+int request_views(int N, const sz3hip_tile_req *reqs, uint32_t n, size_t tsz, std::vector<ReqView> &vs) {
+    vs.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const sz3hip_tile_req &q = reqs[i];
+        ReqView &v = vs[i];
+        bool given = false;
+        for (int j = 0; j < N; j++) given = given || q.strides[j] != 0;
+        uint64_t span = 0;  // the last element's distance from the first
+        if (!given) {
+            uint64_t run = 1;
+            for (int j = N - 1; j >= 0; j--) {
+                v.str[j] = (int64_t)run;
+                run *= q.box.ext[j];
+            }
+            span = run - 1;
+            v.atlas = false;
+        } else {
+            int inner = -1;  // the next counted dimension
+            v.atlas = true;
+            for (int j = N - 1; j >= 0; j--) {
+                const int64_t st = q.strides[j];
+                v.str[j] = st;
+                if (j < N - 1 && (st <= 0 || q.strides[j + 1] <= 0 || (uint64_t)st / (uint64_t)q.strides[j + 1] < q.box.ext[j + 1])) v.atlas = false;
+                if (st <= 0) v.atlas = false;
+                if (q.box.ext[j] == 1) continue;
+                if (st < 0) return fail(SZ3HIP_EINVAL, "box %u: the view's stride of dimension %d is negative (%lld)", i, j, (long long)st);
+                if (st == 0) return fail(SZ3HIP_EINVAL, "box %u: the view's stride of dimension %d is zero", i, j);
+                if ((uint64_t)st > (1ull << 56) / q.box.ext[j])  // (the hull's byte count stays far inside 64 bits)
+                    return fail(SZ3HIP_EINVAL, "box %u: the view's stride of dimension %d is too large (%lld)", i, j, (long long)st);
+                if (inner >= 0 && (uint64_t)st / (uint64_t)q.strides[inner] < q.box.ext[inner])
+                    return fail(SZ3HIP_EINVAL, "box %u: the view's strides are permuted or overlap: dimension %d's (%lld) is below %llu * dimension %d's (%lld); a view is nested in row-major order",
+                                i, j, (long long)st, (unsigned long long)q.box.ext[inner], inner, (long long)q.strides[inner]);
+                span += (q.box.ext[j] - 1) * (uint64_t)st;
+                inner = j;
+            }
+        }
+        v.lo = (uintptr_t)q.d_out;
+        // (span < 4 * 2^56 elements: the byte count cannot wrap; the hull's end could, for a pointer near the top of the address space)
+        if ((span + 1) * tsz > UINTPTR_MAX - v.lo) return fail(SZ3HIP_EINVAL, "box %u: the view runs past the end of the address space", i);
+        v.hi = v.lo + (uintptr_t)((span + 1) * tsz);
+    }
+    for (uint32_t i = 1; i < n; i++)
+        for (uint32_t k = 0; k < i; k++) {
+            if (vs[i].hi <= vs[k].lo || vs[k].hi <= vs[i].lo) continue;  // disjoint hulls
+            bool apart = false;
+            if (vs[i].atlas && vs[k].atlas && !memcmp(vs[i].str, vs[k].str, N * sizeof(int64_t))) {  // two rectangles of one atlas?
+                const uint32_t a = vs[i].lo >= vs[k].lo ? k : i, b = a == i ? k : i;  // b's origin is not below a's
+                uint64_t d = (uint64_t)(vs[b].lo - vs[a].lo);
+                bool fits = d % tsz == 0;
+                d /= tsz;
+                for (int j = 0; j < N && fits; j++) {
+                    const uint64_t st = (uint64_t)vs[a].str[j], o = d / st;
+                    d -= o * st;
+                    if (j >= 1 && o + reqs[b].box.ext[j] > (uint64_t)vs[a].str[j - 1] / st) fits = false;
+                    if (o >= reqs[a].box.ext[j]) apart = true;
+                }
+                apart = apart && fits && d == 0;
+            }
+            if (!apart) return fail(SZ3HIP_EINVAL, "box %u: the output overlaps box %u's, or cannot be shown not to", i, k);
+        }
+    return 0;
+}
+}  // namespace
+
+extern "C" int sz3hip_request_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, sz3hip_request_plan *out) {
+    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_request_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
+    int rc = dtype_check(dataType);
+    if (rc || (rc = request_args("sz3hip_request_plan_for", reqs, n))) return rc;
+    std::vector<szk_region_geom> gs;
+    std::vector<ReqView> vs;
+    memset(out, 0, sizeof(*out));
+    if ((rc = szi_request_geometry_conf(conf, reqs, n, gs, &out->scratch_elems)) || (rc = request_views(conf->N, reqs, n, tsize(dataType), vs))) return rc;
+    out->n = n;
+    out->finest_level = out->coarsest_level = reqs[0].level;
+    for (uint32_t i = 0; i < n; i++) {
+        out->finest_level = std::min(out->finest_level, reqs[i].level);
+        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
+        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
+        out->points += gs[i].points;
+    }
+    return 0;
+}
+
+extern "C" int sz3hip_stream_request(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, void *stream) {
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_request: no handle");
+    int rc = request_args("sz3hip_stream_request", reqs, n);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    std::vector<ReqView> vs;
+    std::vector<szk_region_geom> gs;
+    uint64_t elems = 0, words = 0;
+    std::vector<szk_region_gather_strided_box> full_recs;  // a handle that keeps the full array
+    if (!h->fast) {
+        for (uint32_t b = 0; b < n; b++) {
+            if (reqs[b].level < 0 || reqs[b].level > 30) return fail(SZ3HIP_EINVAL, "box %u: tile level %d is outside 0 .. 30", b, reqs[b].level);
+            for (int i = 0; i < h->N; i++) {  // (boxes_on_grid's checks and wording, on the grid of the box's own level)
+                const uint64_t cd = szi_coarse_extent(h->dims[i], reqs[b].level), lo = reqs[b].box.lo[i], ext = reqs[b].box.ext[i];
+                if (ext == 0) return fail(SZ3HIP_EINVAL, "box %u: the region has extent 0 in dimension %d", b, i);
+                if (lo >= cd || ext > cd - lo)
+                    return fail(SZ3HIP_EINVAL, "box %u: the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", b, (unsigned long long)lo, (unsigned long long)lo,
+                                (unsigned long long)ext, i, (unsigned long long)cd);
+            }
+        }
+        if ((rc = request_views(h->N, reqs, n, tsize(h->dtype), vs))) return rc;
+        // per box the view of the resident array whose strides are multiplied by 2^level, into the caller's view
+        uint64_t str[4] = {0, 0, 0, 0}, run = 1;
+        for (int i = h->N - 1; i >= 0; i--) {
+            str[i] = run;
+            run *= h->dims[i];
+        }
+        full_recs.resize(n);
+        for (uint32_t b = 0; b < n; b++) {
+            szk_region_gather_strided_box &r = full_recs[b];
+            memset(&r, 0, sizeof(r));
+            r.total = 1;
+            r.dst = reqs[b].d_out;
+            for (int q = 0; q < 4; q++) {
+                const int i = q - (4 - h->N);
+                r.ext[q] = i >= 0 ? reqs[b].box.ext[i] : 1;
+                r.str[q] = i >= 0 && r.ext[q] > 1 ? str[i] << reqs[b].level : 0;
+                r.dstr[q] = i >= 0 && r.ext[q] > 1 ? vs[b].str[i] : 0;
+                r.total *= r.ext[q];
+                if (i >= 0) r.src += (reqs[b].box.lo[i] << reqs[b].level) * str[i];
+            }
+        }
+        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
+    } else {
+        const szk_interp_params &ip = h->codes.ip;
+        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
+        if ((rc = request_views(ip.N, reqs, n, tsize(h->dtype), vs))) return rc;
+        words = szk_region_request_table_words(gs.data(), n);
+    }
+    HIPCHK(hipSetDevice(h->device));
+    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    const uint32_t chain_points = sz3hip_debug_get_chain_points();
+    uint32_t chain_levels = 0, launches = 0, levels = 0;
+    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
+    int lr;
+    if (!h->fast) {
+        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s);
+        launches = 1;
+    } else {
+        std::vector<szk_region_out> outs(n);
+        for (uint32_t i = 0; i < n; i++) {
+            outs[i].dst = reqs[i].d_out;
+            for (int j = 0; j < 4; j++) outs[i].str[j] = j < h->codes.ip.N ? vs[i].str[j] : 0;
+        }
+        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
+                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, outs.data(), h->h_table,
+                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels);
+    }
+    HIPCHK(hipEventRecord(h->ev_req, s));
+    h->req_pending = true;
+    h->last_stream = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's reconstruction could not be launched (%d)", lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = levels;
     h->chain_points_last = chain_points;
     h->requests++;
     return 0;
