@@ -493,6 +493,63 @@ typedef struct sz3hip_request_plan {
 } sz3hip_request_plan;
 int sz3hip_request_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, sz3hip_request_plan *out);
 int sz3hip_stream_request(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, void *stream);
+/* ---- numbers about boxes, no output: per-box min, max, moments and histogram ----
+ * An analysis that stays on one stream usually wants numbers about boxes — a brick's value range, a region's mean and variance, where the
+ * maximum sits, a histogram — not the arrays. sz3hip_stream_reduce takes 1 .. SZ3HIP_MAX_BOXES boxes that each name their own level, as
+ * sz3hip_stream_request does (coordinates, checks, codes and wording are that call's, "box <i>: " in front; repeated and overlapping boxes
+ * are allowed; everything is checked before anything is launched or written), and runs the same launch sequence with a reduction and a
+ * final fold in the strided gather's place: stats.launches_last_request is the same boxes' sz3hip_stream_request's, plus one. Nothing of a
+ * box is written but its results, in DEVICE memory: d_stats[i] for box i, and row i of d_hist — n * (nbins + 2) counts, slot 0 = under,
+ * slot nbins + 1 = over; ignored and allowed NULL when opts is NULL or nbins is 0. The call zeroes d_hist itself, on `stream`. No
+ * device-to-host copy, no host synchronisation beyond a request's own waits; the ordering between requests is the existing one.
+ * What is reduced: exactly the values sz3hip_stream_request would deliver for the box, each as x = (double)v.
+ *   non-finite   a NaN or +-Inf point is counted in n_nonfinite and left out of everything else (sz3hip_verify_device's rule)
+ *   min, argmin  argmin is the smallest box-local row-major index at which no finite point is smaller, min the value AT that index
+ *                (-0.0 and +0.0 tie: the report carries that element's sign); max / argmax symmetric; nothing finite: NaN and n
+ *   shift        K: the box's point of index 0 if finite, else 0.0
+ *   sum, sum_sq  of x - K and (x - K)^2 over the finite points, each difference and square rounded once, added in a fixed order
+ *   mean         K + sum / m, m = (double)(n - n_nonfinite);  variance  (sum_sq - sum * sum / m) / m  (the population's); IEEE double,
+ *                no fused multiply-add; m = 0: both NaN
+ *   histogram    scale = (double)nbins / (hi - lo), computed once on the host; a finite x goes to slot 0 if x < lo, to slot nbins + 1 if
+ *                x >= hi, else to slot 1 + min((uint64_t)((x - lo) * scale), nbins - 1). A row sums to n - n_nonfinite.
+ * Which points form a partial sum and the order of every fold depend on the box's point count ALONE (chunks of 4096 consecutive row-major
+ * indices): every field is reproducible bit for bit, whatever the request's other boxes, the handle's kind or the device, and
+ * sz3hip_stream_reduce is bit-identical to sz3hip_reduce_device over the same values.
+ * Errors (SZ3HIP_EINVAL): nbins > SZ3HIP_MAX_BINS; nbins > 0 with lo or hi not finite or hi <= lo; opts->reserved or a request's reserved
+ * not 0; d_stats NULL; d_hist NULL with nbins > 0; and sz3hip_stream_request's for the boxes. Integer types: SZ3HIP_EUNSUPPORTED.
+ * sz3hip_reduce_device: the same reduction of ONE plain view in device memory into one sz3hip_box_stats and one histogram row (what a
+ * handle that keeps the full array runs). N, dims, strides and the pointer's rules are sz3hip_verify_device's; float / double only. It is
+ * asynchronous on `stream`; the partial records live in a per-device workspace the library keeps, calls are ordered by an event.
+ * sz3hip_reduce_plan_for: a pure function (no device) with sz3hip_stream_reduce's checks. points, n_levels and the two level fields are
+ * sz3hip_request_plan_for's; partials: the partial records (the sum of the boxes' ceil(points / 4096)); scratch_elems: the level buffers
+ * plus the room of those records, in elements of dataType; hist_words = n * (nbins + 2). */
+#define SZ3HIP_MAX_BINS 1024
+typedef struct sz3hip_reduce_req {
+    int32_t level;        /* 0 .. 30: the box lies on the grid of every 2^level-th point */
+    uint32_t reserved;    /* 0 */
+    sz3hip_box box;       /* in that grid's coordinates, slowest first, N entries used */
+} sz3hip_reduce_req;
+typedef struct sz3hip_reduce_opts {
+    uint32_t nbins, reserved;  /* nbins 0: no histogram */
+    double lo, hi;
+} sz3hip_reduce_opts;
+typedef struct sz3hip_box_stats {            /* 88 bytes, eleven 64-bit words */
+    uint64_t n, n_nonfinite, argmin, argmax; /* points of the box; NaN / +-Inf among them; box-local row-major indices */
+    double min, max;                         /* over the finite points; NaN when there is none (then argmin = argmax = n) */
+    double shift, sum, sum_sq;               /* K; sum of (v - K); sum of (v - K)^2, over the finite points */
+    double mean, variance;                   /* K + sum / m;  (sum_sq - sum * sum / m) / m;  m = (double)(n - n_nonfinite) */
+} sz3hip_box_stats;
+typedef struct sz3hip_reduce_plan {
+    uint32_t n;
+    int32_t finest_level, coarsest_level, n_levels;
+    uint64_t points, scratch_elems, partials, hist_words;
+} sz3hip_reduce_plan;
+int sz3hip_reduce_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_reduce_req *reqs, uint32_t n, const sz3hip_reduce_opts *opts,
+                           sz3hip_reduce_plan *out);
+int sz3hip_stream_reduce(sz3hip_stream *h, const sz3hip_reduce_req *reqs, uint32_t n, const sz3hip_reduce_opts *opts, sz3hip_box_stats *d_stats,
+                         uint64_t *d_hist, void *stream);
+int sz3hip_reduce_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_reduce_opts *opts,
+                         sz3hip_box_stats *d_stats, uint64_t *d_hist, void *stream);
 /* development switch, process-wide: a request of a handle runs its coarsest c levels in ONE launch (one workgroup per box walks first point,
  * regrids and passes with a barrier between steps), c the largest count such that for every box every pass of those levels has at most
  * `points` points. 0: off — the request issues exactly the launches sz3hip_decompress_device_tiles issues. Environment twin, read once when

@@ -153,6 +153,28 @@ class _CRequestPlan(C.Structure):
                 ("scratch_elems", C.c_uint64)]
 
 
+class _CReduceReq(C.Structure):
+    # sz3hip_reduce_req (include/sz3hip.h)
+    _fields_ = [("level", C.c_int32), ("reserved", C.c_uint32), ("box", _CBox)]
+
+
+class _CReduceOpts(C.Structure):
+    # sz3hip_reduce_opts
+    _fields_ = [("nbins", C.c_uint32), ("reserved", C.c_uint32), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class _CBoxStats(C.Structure):
+    # sz3hip_box_stats: eleven 64-bit words
+    _fields_ = ([(k, C.c_uint64) for k in ("n", "n_nonfinite", "argmin", "argmax")] +
+                [(k, C.c_double) for k in ("min", "max", "shift", "sum", "sum_sq", "mean", "variance")])
+
+
+class _CReducePlan(C.Structure):
+    # sz3hip_reduce_plan
+    _fields_ = [("n", C.c_uint32), ("finest_level", C.c_int32), ("coarsest_level", C.c_int32), ("n_levels", C.c_int32), ("points", C.c_uint64),
+                ("scratch_elems", C.c_uint64), ("partials", C.c_uint64), ("hist_words", C.c_uint64)]
+
+
 class _CStreamStats(C.Structure):
     """struct sz3hip_stream_stats (include/sz3hip.h)"""
     _fields_ = [("fast", C.c_uint32), ("huffman_stages", C.c_uint32), ("launches_last_request", C.c_uint32), ("chain_levels_last_request", C.c_uint32),
@@ -309,6 +331,12 @@ def lib():
     L.sz3hip_stream_stats.argtypes = [C.c_void_p, P(_CStreamStats)]
     L.sz3hip_stream_request.restype = C.c_int
     L.sz3hip_stream_request.argtypes = [C.c_void_p, P(_CTileReq), C.c_uint32, C.c_void_p]
+    L.sz3hip_reduce_plan_for.restype = C.c_int
+    L.sz3hip_reduce_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CReduceReq), C.c_uint32, P(_CReduceOpts), P(_CReducePlan)]
+    L.sz3hip_stream_reduce.restype = C.c_int
+    L.sz3hip_stream_reduce.argtypes = [C.c_void_p, P(_CReduceReq), C.c_uint32, P(_CReduceOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sz3hip_reduce_device.restype = C.c_int
+    L.sz3hip_reduce_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CReduceOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     L.sz3hip_request_plan_for.restype = C.c_int
     L.sz3hip_request_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CRequestPlan)]
     L.sz3hip_stream_close.restype = None
@@ -854,6 +882,89 @@ def request_plan(conf, dtype, items):
     return {k: int(getattr(plan, k)) for k, _ in _CRequestPlan._fields_}
 
 
+BOX_STATS_DTYPE = np.dtype([(k, np.uint64 if t is C.c_uint64 else np.float64) for k, t in _CBoxStats._fields_])
+
+
+class ReduceResult:
+    """what a reduction leaves in DEVICE memory: `stats`, an (n, 11) int64 tensor whose rows are sz3hip_box_stats records (raw words), and
+    `hist`, an (n, bins + 2) int64 tensor of counts (slot 0 under, slot bins + 1 over; None without a histogram). Nothing here waits for the
+    device; numpy() does: it synchronises and returns (structured array with the struct's field names, histogram as uint64 or None)."""
+
+    def __init__(self, stats, hist, bins):
+        self.stats = stats
+        self.hist = hist
+        self.bins = bins
+
+    def numpy(self):
+        st = self.stats.cpu().numpy().view(BOX_STATS_DTYPE).reshape(-1)  # (the copy to the host is the synchronisation)
+        return st, None if self.hist is None else self.hist.cpu().numpy().view(np.uint64)
+
+
+def _reduce_opts(bins, lo, hi):
+    o = _CReduceOpts()
+    o.nbins = int(bins)
+    o.lo = float(lo)
+    o.hi = float(hi)
+    return o
+
+
+def _reduce_reqs(N, items):
+    items = [tuple(it) for it in items]
+    if any(len(it) != 3 for it in items):
+        raise ValueError("an item is (level, lo, shape)")
+    arr, _ = _boxes(N, [(it[1], it[2]) for it in items])
+    reqs = (_CReduceReq * max(len(items), 1))()
+    for i, it in enumerate(items):
+        reqs[i].level = int(it[0])
+        reqs[i].box = arr[i]
+    return reqs, len(items)
+
+
+def _reduce_result(n, bins, device):
+    import torch
+    stats = torch.empty((n, C.sizeof(_CBoxStats) // 8), dtype=torch.int64, device=device)
+    hist = torch.empty((n, int(bins) + 2), dtype=torch.int64, device=device) if int(bins) > 0 else None
+    return ReduceResult(stats, hist, int(bins))
+
+
+def reduce_plan(conf, dtype, items, bins=0, lo=0.0, hi=0.0):
+    """what one Stream.reduce for `items` — (level, lo, shape) — touches (sz3hip_reduce_plan_for), without a device: the reduce call's own
+    checks run. Returns a dict with n, finest_level, coarsest_level, n_levels, points, scratch_elems (the level buffers and the partial
+    records' room), partials (one per 4096 points of a box) and hist_words."""
+    reqs, n = _reduce_reqs(conf.N, items)
+    opts = _reduce_opts(bins, lo, hi)
+    plan = _CReducePlan()
+    _check(lib().sz3hip_reduce_plan_for(C.byref(conf._c), _dtype_id(_np_dtype(dtype)), reqs, n, C.byref(opts), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k, _ in _CReducePlan._fields_}
+
+
+def reduce_stats(tensor, bins=0, lo=0.0, hi=0.0, stream=None):
+    """min, max, their places, shifted moments and (bins > 0) a histogram over [lo, hi) of one float32 / float64 torch tensor on a HIP device
+    (sz3hip_reduce_device): the reduction Stream.reduce runs per box, over a plain view — any strides that are not negative, size-1
+    dimensions dropped, at most 4 left; indices are row-major over the tensor's shape. Asynchronous on `stream`; returns a ReduceResult
+    of one row."""
+    if not _is_tensor(tensor):
+        raise TypeError("reduce_stats takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
+    if not _gpu_tensor(tensor):
+        raise ValueError("reduce_stats: the tensor must be on a HIP device (it is on %s)" % tensor.device)
+    name = str(tensor.dtype).replace("torch.", "")
+    if name not in _SZ_TYPES:
+        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
+    if tensor.numel() == 0:
+        raise ValueError("reduce_stats: the tensor is empty")
+    keep = [i for i, d in enumerate(tensor.shape) if int(d) != 1]
+    if len(keep) > 4:
+        raise ValueError("reduce_stats: %d dimensions above size 1 (at most 4 are supported)" % len(keep))
+    dims = [int(tensor.shape[i]) for i in keep] or [1]
+    strides = [int(tensor.stride(i)) for i in keep] or [1]
+    N = len(dims)
+    res = _reduce_result(1, bins, tensor.device)
+    opts = _reduce_opts(bins, lo, hi)
+    _check(lib().sz3hip_reduce_device(_SZ_TYPES[name], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*strides), C.byref(opts),
+                                      res.stats.data_ptr(), None if res.hist is None else res.hist.data_ptr(), _stream_handle(tensor.device, stream)))
+    return res
+
+
 def set_chain_points(points):
     """development switch (sz3hip_debug_chain_points): a Stream request runs its coarsest levels — those whose every pass has at most
     `points` points for every box — in one launch; 0 switches the chain off"""
@@ -946,6 +1057,18 @@ class Stream:
             reqs[i].strides[:N] = [int(v) for v in t.stride()]
         _check(lib().sz3hip_stream_request(self._h, reqs, len(items), _stream_handle(self.device, stream)))
         return outs
+
+    def reduce(self, items, bins=0, lo=0.0, hi=0.0, stream=None):
+        """numbers about boxes, no output arrays (sz3hip_stream_reduce): `items` are (level, lo, shape) as request's.
+        Per box n, n_nonfinite, argmin, argmax, min, max, shift, sum, sum_sq, mean, variance over exactly the values request would deliver,
+        and with bins > 0 a histogram over [lo, hi) with an under and an over slot. The request's launch sequence with a reduction in the
+        gather's place; bit-reproducible. Asynchronous on `stream`, as tiles; returns a ReduceResult (device tensors; .numpy() waits)."""
+        reqs, n = _reduce_reqs(self.conf.N, items)
+        res = _reduce_result(max(n, 1), bins, self.device)
+        opts = _reduce_opts(bins, lo, hi)
+        _check(lib().sz3hip_stream_reduce(self._h, reqs, n, C.byref(opts), res.stats.data_ptr(), None if res.hist is None else res.hist.data_ptr(),
+                                          _stream_handle(self.device, stream)))
+        return res
 
     def tile(self, level, lo, shape, out=None, stream=None):
         """one box of the grid of every 2**level-th point (tiles with one box)"""

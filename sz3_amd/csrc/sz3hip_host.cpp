@@ -2583,6 +2583,14 @@ int dev_array(const sz3hip_config *c, const int64_t *strides, const void *ptr, b
 }
 }  // namespace
 
+int szi_dev_view_strides(int N, const uint64_t *dims, const int64_t *strides, uint64_t *str_out) {
+    szk_view v;
+    const int rc = dev_view(N, dims, strides, false, &v);
+    for (int i = 0; i < N && !rc; i++) str_out[i] = (uint64_t)v.str[4 - N + i];
+    return rc;
+}
+int szi_dev_pointer(const void *ptr, int *device) { return dev_pointer(ptr, device); }
+
 extern "C" int sz3hip_debug_gather(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream) {
     if (!dtype_ok(dataType) || N < 1 || N > 4) return fail(SZ3HIP_EINVAL, "bad arguments");
     sz3hip_config c;

@@ -89,6 +89,12 @@ int szi_boxes_geometry(int N, const uint64_t *dims, int interp_id, int direction
 int szi_request_geometry(int N, const uint64_t *dims, int interp_id, int direction, uint64_t anchor_stride, const sz3hip_tile_req *reqs, uint32_t n,
                          std::vector<szk_region_geom> &gs, uint64_t *scratch_elems);
 int szi_request_geometry_conf(const sz3hip_config *conf, const sz3hip_tile_req *reqs, uint32_t n, std::vector<szk_region_geom> &gs, uint64_t *scratch_elems);
+// a strided gather's record over a plain view (sz3hip_stream.cpp): a fallback handle's boxes, sz3hip_reduce_device's view
+void szi_view_record(int N, const uint64_t *ext, const uint64_t *str, uint64_t corner, void *dst, const int64_t *dstr, struct szk_region_gather_strided_box *r);
+// sz3hip_verify_device's rules for a caller's view and pointer (sz3hip_host.cpp: dev_view, dev_pointer): the view's element strides (NULL:
+// contiguous), the device that owns the memory
+int szi_dev_view_strides(int N, const uint64_t *dims, const int64_t *strides, uint64_t *str_out);
+int szi_dev_pointer(const void *ptr, int *device);
 // the host side of sz3hip_stream_open (sz3hip_host.cpp: the container, libzstd and the slots live there): the arguments' checks, then either the
 // stream's codes (*fast = 1) or, for a container that is no single interpolation stream, its full decode in *d_full (hipMalloc; the caller owns it).
 // *huffman: Huffman stages run (0: a container without one). conf comes back as the full array's

@@ -449,15 +449,51 @@ struct szk_region_gather_strided_box {  // a record of k_region_gather_strided: 
     uint64_t ext[4], str[4];  // the source's element strides
     int64_t dstr[4];          // the destination's
 };
+// ---- a reduction in the gather's place (kernels: sz3hip_reduce.hip) ----
+// A box's record is the strided gather's own (built by the same builders); a reducing request carries in its `dst` word SZK_REDUCE_DST(the
+// index of the box's first partial record, the box's index in the request: its d_stats entry and histogram row — the records of a request
+// served level group by level group are not in the request's order) and does not read `dstr`. The partition rule: chunk c of a box is its row-major indices [c * SZK_REDUCE_CHUNK,
+// min(total, (c + 1) * SZK_REDUCE_CHUNK)), one workgroup and one partial record per chunk; every fold's order depends on `total` alone.
+#define SZK_REDUCE_CHUNK 4096
+#define SZK_REDUCE_DST(part, box) ((uint64_t)(part) | ((uint64_t)(box) << 40))
+#define SZK_REDUCE_DST_PART(w) ((w) & ((1ull << 40) - 1))
+#define SZK_REDUCE_DST_BOX(w) ((w) >> 40)
+__host__ __device__ static inline uint64_t szk_reduce_chunks(uint64_t total) { return (total + SZK_REDUCE_CHUNK - 1) / SZK_REDUCE_CHUNK; }
+struct szk_reduce_part {  // a chunk's record, 8 words: counts, (value, index) pairs with box-local indices (~0: none), the two shifted sums
+    uint64_t n_fin, n_nonfinite, argmin, argmax;
+    double mn, mx, sum, sum_sq;
+};
+struct szk_reduce_hist {  // nbins 0: no histogram
+    uint32_t nbins, pad;
+    double lo, hi, scale;
+};
+// where a reducing request's results go instead of the boxes' views. partials: room for the sum of the boxes' szk_reduce_chunks records
+// (the handle's scratch, behind the level buffers); d_stats: n sz3hip_box_stats (11 words each); d_hist: n rows of nbins + 2 counts, zeroed
+// by the caller in front
+struct szk_region_sink {
+    szk_reduce_part *partials;
+    void *d_stats;
+    uint64_t *d_hist;
+    szk_reduce_hist hist;
+};
+// the two launches over n records in device memory (one box: by value, rec_by_value non-null and d_recs null). gx: the largest box's chunks
+int szk_launch_region_reduce(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
+                             uint32_t n, uint64_t most_total, const szk_region_sink *sink, hipStream_t s);
+int szk_launch_region_reduce_final(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value, uint32_t n,
+                                   const szk_region_sink *sink, hipStream_t s);
 uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n);
+// sink non-null: the request reduces (outs[i].dst: box i's SZK_REDUCE_DST word, cast; the strides are not read) — reduce and final stand
+// in the strided gather's place, *launches is the request's count plus one
 int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                                 const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                                 void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,
-                                                hipEvent_t copied, hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches, uint32_t *levels);
+                                                hipEvent_t copied, hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches, uint32_t *levels,
+                                                const szk_region_sink *sink = nullptr);
 // n strided boxes of one array into n strided views in one launch (the gather of szk_launch_gather with a strided destination, per box): recs
-// are copied through h_table into d_table (n * 15 words) in front of the launch, `copied` recorded behind the copy
+// are copied through h_table into d_table (n * 15 words) in front of the launch, `copied` recorded behind the copy. sink non-null: the boxes are
+// reduced instead (recs[i].dst: box i's SZK_REDUCE_DST word), two launches
 int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gather_strided_box *recs, uint32_t n, uint64_t *h_table, uint64_t *d_table,
-                            uint64_t table_words, hipEvent_t copied, hipStream_t s);
+                            uint64_t table_words, hipEvent_t copied, hipStream_t s, const szk_region_sink *sink = nullptr);
 uint64_t szk_region_launches(void);  // test hook: kernel launches the box reconstructions issued so far, single and multi
 
 int szk_launch_profile_blocks(int dtype, const void *d_in, int N, const uint64_t *dims, uint64_t bs, uint64_t stride, double abseb,

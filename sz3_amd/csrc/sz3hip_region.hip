@@ -800,6 +800,20 @@ static void region_launch(uint32_t *issued, void (*kernel)(KA...), dim3 grid, ui
     region_count(issued);
 }
 
+// a reducing request's launches in the gather's place: the reduction over the boxes' records, then — unless the caller
+// issues it once for several groups — the final
+template <typename T>
+static int region_sink_launch(uint32_t *issued, const T *src, const szk_region_gather_strided_box *d_recs, uint32_t n, uint64_t most, const szk_region_sink *sink,
+                              bool with_final, hipStream_t s) {
+    const int dtype = sizeof(T) == 4 ? 0 : 1;
+    if (szk_launch_region_reduce(dtype, src, d_recs, nullptr, n, most, sink, s)) return -2;
+    region_count(issued);
+    if (!with_final) return 0;
+    if (szk_launch_region_reduce_final(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
+    region_count(issued);
+    return 0;
+}
+
 template <typename T>
 static int run_region(const szk_interp_params &ip, const szk_region_geom &g, const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off,
                       uint64_t n_vout, const uint16_t *codes, T *scratch, T *d_out, hipStream_t s) {
@@ -871,13 +885,15 @@ struct MultiLaunch {
     bool twice;    // pass: the deferred points' launch follows
     szk_region_pass_shared sh;
     bool chained;  // the launch is a step of the chain's one launch instead
+    uint64_t most;  // gather: the largest box's points
 };
 }  // namespace
 template <typename T>
 static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
                             uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, T *scratch, void *const *d_outs,
                             uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t chain_points,
-                            uint32_t *chain_levels, uint32_t *launches, const szk_region_out *outs = nullptr) {  // (outs: strided views instead of d_outs)
+                            uint32_t *chain_levels, uint32_t *launches, const szk_region_out *outs = nullptr,  // (outs: strided views instead of d_outs)
+                            const szk_region_sink *sink = nullptr, bool sink_final = true) {  // (sink: the boxes are reduced, not delivered)
     const szk_region_geom &g0 = gs[0];
     const int N = g0.N, nbuf = g0.nbuf, n_levels = g0.n_levels;
     // the chain takes the coarsest c levels: the largest count such that every pass of those levels has at most chain_points points for EVERY box
@@ -985,6 +1001,7 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
             most = std::max(most, total);
         }
         if (!region_grid(most, &l.gx)) return -1;
+        l.most = most;
         seq.push_back(l);
     }
     // the chain's steps, behind the boxes' records: the chained launches in their order, a pass's shared part in front of its step(s)
@@ -1047,7 +1064,9 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
             }
             break;
         default:
-            if (outs) region_launch(&issued, k_region_gather_strided<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_strided_box *>(rec));
+            if (sink) {
+                if (!outs || region_sink_launch<T>(&issued, scratch, reinterpret_cast<const szk_region_gather_strided_box *>(rec), n, ml.most, sink, sink_final, s)) return -2;
+            } else if (outs) region_launch(&issued, k_region_gather_strided<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_strided_box *>(rec));
             else region_launch(&issued, k_region_gather_multi<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_box *>(rec));
         }
     }
@@ -1087,6 +1106,7 @@ struct MixedLaunch {
     uint32_t gx;
     bool twice;
     szk_region_pass_level lvl;
+    uint64_t most;  // gather: the largest box's points
 };
 // the array's level count as the boxes that run levels see it; false: two of them disagree (or differ in pass order), the sequence cannot be merged
 bool request_aligned(const szk_region_geom *gs, uint32_t n) {
@@ -1116,7 +1136,8 @@ uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n) {
 template <typename T>
 static int run_region_mixed(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
                             uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, T *scratch, const szk_region_out *outs,
-                            uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t *launches, uint32_t *levels) {
+                            uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t *launches, uint32_t *levels,
+                            const szk_region_sink *sink) {
     const int N = gs[0].N;
     int n_levels = 0;  // the array levels the sequence runs: the finest box's own count
     for (uint32_t i = 0; i < n; i++) {
@@ -1219,6 +1240,7 @@ static int run_region_mixed(const szk_interp_params &ip, const szk_region_geom *
             most = std::max(most, r.total);
         }
         if (!region_grid(most, &l.gx)) return -1;
+        l.most = most;
         seq.push_back(l);
     }
     if (hipMemcpyAsync(d_table, h_table, w * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
@@ -1250,7 +1272,9 @@ static int run_region_mixed(const szk_interp_params &ip, const szk_region_geom *
             }
             break;
         default:
-            region_launch(&issued, k_region_gather_strided<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_strided_box *>(rec));
+            if (sink) {
+                if (region_sink_launch<T>(&issued, scratch, reinterpret_cast<const szk_region_gather_strided_box *>(rec), n, ml.most, sink, true, s)) return -2;
+            } else region_launch(&issued, k_region_gather_strided<T>, grid, 256, s, (const T *)scratch, reinterpret_cast<const szk_region_gather_strided_box *>(rec));
         }
     }
     if (launches) *launches = issued;
@@ -1262,17 +1286,17 @@ template <typename T>
 static int run_region_request(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
                               uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes, T *scratch, const szk_region_out *outs,
                               uint64_t *h_table, uint64_t *d_table, uint64_t table_words, hipEvent_t copied, hipStream_t s, uint32_t chain_points,
-                              uint32_t *chain_levels, uint32_t *launches, uint32_t *levels) {
+                              uint32_t *chain_levels, uint32_t *launches, uint32_t *levels, const szk_region_sink *sink) {
     bool one = true;
     for (uint32_t i = 1; i < n; i++) one = one && gs[i].shift == gs[0].shift;
     if (one) {  // the one-level sequence, the chain included
         if (levels) *levels = (uint32_t)gs[0].n_levels;
         return run_region_multi<T>(ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, nullptr, h_table, d_table, table_words, copied, s,
-                                   chain_points, chain_levels, launches, outs);
+                                   chain_points, chain_levels, launches, outs, sink);
     }
     if (request_aligned(gs, n) && !(szk_dbg_flags2 & SZ3HIP_DBG2_REQUEST_BY_LEVEL)) {
         const int rc = run_region_mixed<T>(ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, outs, h_table, d_table, table_words,
-                                           copied, s, launches, levels);
+                                           copied, s, launches, levels, sink);
         if (rc != -4) return rc;  // (-4: a pass's arguments are not one for all boxes; nothing was copied or launched)
     }
     // level group by level group, every group with a stretch of the table of its own (no wait between the groups' copies)
@@ -1292,11 +1316,25 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
         if (need > table_words || used > table_words - need) return -1;
         uint32_t issued = 0;
         const int rc = run_region_multi<T>(ip, gg.data(), (uint32_t)gg.size(), scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, nullptr,
-                                           h_table + used, d_table + used, need, copied, s, 0, nullptr, &issued, oo.data());
+                                           h_table + used, d_table + used, need, copied, s, 0, nullptr, &issued, oo.data(), sink, false);
         if (rc) return rc;
         used += need;
         total += issued;
         most_levels = std::max(most_levels, (uint32_t)gg[0].n_levels);
+    }
+    if (sink) {  // ONE final for the request: the boxes' records once more, in the request's order, behind the groups' stretches
+        const uint64_t need = (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box);
+        if (need > table_words || used > table_words - need) return -1;
+        for (uint32_t i = 0; i < n; i++) {
+            szk_region_gather_strided_box r;
+            if (region_gather_strided_record(gs[i], outs[i], &r)) return -1;
+            memcpy(h_table + used + (uint64_t)i * SZK_WORDS(szk_region_gather_strided_box), &r, sizeof(r));
+        }
+        if (hipMemcpyAsync(d_table + used, h_table + used, need * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+        if (hipEventRecord(copied, s) != hipSuccess) return -2;
+        if (szk_launch_region_reduce_final(sizeof(T) == 4 ? 0 : 1, scratch, reinterpret_cast<const szk_region_gather_strided_box *>(d_table + used), nullptr, n, sink, s))
+            return -2;
+        region_count(&total);
     }
     if (launches) *launches = total;
     if (levels) *levels = most_levels;
@@ -1306,29 +1344,31 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
 int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                                 const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                                 void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,
-                                                hipEvent_t copied, hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches, uint32_t *levels) {
+                                                hipEvent_t copied, hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches, uint32_t *levels,
+                                                const szk_region_sink *sink) {
     if (chain_levels) *chain_levels = 0;
     if (launches) *launches = 0;
     if (levels) *levels = 0;
+    if (sink && (!sink->partials || !sink->d_stats || (sink->hist.nbins && !sink->d_hist))) return -1;
     if (n < 1 || n > 65535 || !gs || !outs || !h_table || !d_table) return -1;
     for (uint32_t i = 0; i < n; i++) {  // one stream: every box on the grid of its own level
         const szk_region_geom &g = gs[i];
         if (g.N != ip->N || g.nbuf < 1 || g.nbuf > SZK_REGION_MAX_LEVELS || g.n_levels < 0 || g.n_levels > g.nbuf || g.shift < 0 || g.shift > 30) return -1;
         for (int j = 0; j < ip->N; j++)
             if (g.full[j] != ip->dims[j] || g.dims[j] != ((ip->dims[j] - 1) >> g.shift) + 1) return -1;
-        if (!outs[i].dst) return -1;
+        if (!sink && !outs[i].dst) return -1;
         if (g.shift == gs[0].shift) {  // (the one-level sequence's conditions, for the boxes of a level)
             if (g.n_levels != gs[0].n_levels || g.nbuf != gs[0].nbuf || g.anchor != gs[0].anchor) return -1;
         }
     }
     return dtype == 0 ? run_region_request<float>(*ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, (float *)scratch, outs, h_table, d_table,
-                                                  table_words, copied, s, chain_points, chain_levels, launches, levels)
+                                                  table_words, copied, s, chain_points, chain_levels, launches, levels, sink)
                       : run_region_request<double>(*ip, gs, n, scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, (double *)scratch, outs, h_table, d_table,
-                                                   table_words, copied, s, chain_points, chain_levels, launches, levels);
+                                                   table_words, copied, s, chain_points, chain_levels, launches, levels, sink);
 }
 
 int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gather_strided_box *recs, uint32_t n, uint64_t *h_table, uint64_t *d_table,
-                            uint64_t table_words, hipEvent_t copied, hipStream_t s) {
+                            uint64_t table_words, hipEvent_t copied, hipStream_t s, const szk_region_sink *sink) {
     if (n < 1 || n > 65535 || !d_src || !recs || !h_table || !d_table || (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box) > table_words) return -1;
     uint64_t most = 0;
     for (uint32_t i = 0; i < n; i++) most = std::max(most, recs[i].total);
@@ -1338,6 +1378,9 @@ int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gathe
     if (hipMemcpyAsync(d_table, h_table, (size_t)n * sizeof(recs[0]), hipMemcpyHostToDevice, s) != hipSuccess) return -2;
     if (hipEventRecord(copied, s) != hipSuccess) return -2;
     const szk_region_gather_strided_box *d_recs = reinterpret_cast<const szk_region_gather_strided_box *>(d_table);
+    if (sink)
+        return dtype == 0 ? region_sink_launch<float>(nullptr, (const float *)d_src, d_recs, n, most, sink, true, s)
+                          : region_sink_launch<double>(nullptr, (const double *)d_src, d_recs, n, most, sink, true, s);
     if (dtype == 0) region_launch(nullptr, k_region_gather_strided<float>, dim3(gx, n), 256, s, (const float *)d_src, d_recs);
     else region_launch(nullptr, k_region_gather_strided<double>, dim3(gx, n), 256, s, (const double *)d_src, d_recs);
     hipError_t e = hipGetLastError();

@@ -9,14 +9,22 @@
 // A request (sz3hip_stream_tiles) is boxes_prepare's checks and the multi-box reconstruction (sz3hip_region.hip) against the resident arrays.
 // sz3hip_stream_request takes boxes of several levels, each into a strided view of its own: the views' checks are here,
 // the one launch sequence aligned by array level in sz3hip_region.hip.
+// sz3hip_stream_reduce takes the same boxes without views and leaves numbers about them in device memory: the request's
+// geometry and sequence with a reduction and its final fold (sz3hip_reduce.hip) in the gather's place; sz3hip_reduce_device is that reduction
+// over one plain view.
 // A handle serves one request at a time; it is not thread-safe.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <math.h>
+
 #include <algorithm>
 #include <atomic>
+#include <map>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "../../include/sz3hip.h"
@@ -422,6 +430,49 @@ int request_views(int N, const sz3hip_tile_req *reqs, uint32_t n, size_t tsz, st
 }
 }  // namespace
 
+namespace {
+// a handle that keeps the full array: every box on the grid of its own level (boxes_on_grid's checks and wording)
+int full_boxes_check(const sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n) {
+    for (uint32_t b = 0; b < n; b++) {
+        if (reqs[b].level < 0 || reqs[b].level > 30) return fail(SZ3HIP_EINVAL, "box %u: tile level %d is outside 0 .. 30", b, reqs[b].level);
+        for (int i = 0; i < h->N; i++) {
+            const uint64_t cd = szi_coarse_extent(h->dims[i], reqs[b].level), lo = reqs[b].box.lo[i], ext = reqs[b].box.ext[i];
+            if (ext == 0) return fail(SZ3HIP_EINVAL, "box %u: the region has extent 0 in dimension %d", b, i);
+            if (lo >= cd || ext > cd - lo)
+                return fail(SZ3HIP_EINVAL, "box %u: the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", b, (unsigned long long)lo, (unsigned long long)lo,
+                            (unsigned long long)ext, i, (unsigned long long)cd);
+        }
+    }
+    return 0;
+}
+// ... and its record: the view of the resident array whose strides are multiplied by 2^level, into the caller's view (dstr null: no view — a
+// reducing request)
+void full_record(const sz3hip_stream *h, const sz3hip_tile_req &q, const int64_t *dstr, szk_region_gather_strided_box *r) {
+    uint64_t str[4] = {0, 0, 0, 0}, corner = 0, run = 1;
+    for (int i = h->N - 1; i >= 0; i--) {
+        corner += (q.box.lo[i] << q.level) * run;
+        str[i] = run << q.level;
+        run *= h->dims[i];
+    }
+    szi_view_record(h->N, q.box.ext, str, corner, q.d_out, dstr, r);
+}
+}  // namespace
+
+// a strided gather's record over a plain view: N extents, the source's element strides and corner, the destination and its strides (null: none)
+void szi_view_record(int N, const uint64_t *ext, const uint64_t *str, uint64_t corner, void *dst, const int64_t *dstr, szk_region_gather_strided_box *r) {
+    memset(r, 0, sizeof(*r));
+    r->total = 1;
+    r->src = corner;
+    r->dst = dst;
+    for (int q = 0; q < 4; q++) {
+        const int i = q - (4 - N);
+        r->ext[q] = i >= 0 ? ext[i] : 1;
+        r->str[q] = i >= 0 && r->ext[q] > 1 ? str[i] : 0;
+        r->dstr[q] = i >= 0 && r->ext[q] > 1 && dstr ? dstr[i] : 0;
+        r->total *= r->ext[q];
+    }
+}
+
 extern "C" int sz3hip_request_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, sz3hip_request_plan *out) {
     if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_request_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
     int rc = dtype_check(dataType);
@@ -452,38 +503,9 @@ extern "C" int sz3hip_stream_request(sz3hip_stream *h, const sz3hip_tile_req *re
     uint64_t elems = 0, words = 0;
     std::vector<szk_region_gather_strided_box> full_recs;  // a handle that keeps the full array
     if (!h->fast) {
-        for (uint32_t b = 0; b < n; b++) {
-            if (reqs[b].level < 0 || reqs[b].level > 30) return fail(SZ3HIP_EINVAL, "box %u: tile level %d is outside 0 .. 30", b, reqs[b].level);
-            for (int i = 0; i < h->N; i++) {  // (boxes_on_grid's checks and wording, on the grid of the box's own level)
-                const uint64_t cd = szi_coarse_extent(h->dims[i], reqs[b].level), lo = reqs[b].box.lo[i], ext = reqs[b].box.ext[i];
-                if (ext == 0) return fail(SZ3HIP_EINVAL, "box %u: the region has extent 0 in dimension %d", b, i);
-                if (lo >= cd || ext > cd - lo)
-                    return fail(SZ3HIP_EINVAL, "box %u: the region [%llu, %llu + %llu) leaves dimension %d (extent %llu)", b, (unsigned long long)lo, (unsigned long long)lo,
-                                (unsigned long long)ext, i, (unsigned long long)cd);
-            }
-        }
-        if ((rc = request_views(h->N, reqs, n, tsize(h->dtype), vs))) return rc;
-        // per box the view of the resident array whose strides are multiplied by 2^level, into the caller's view
-        uint64_t str[4] = {0, 0, 0, 0}, run = 1;
-        for (int i = h->N - 1; i >= 0; i--) {
-            str[i] = run;
-            run *= h->dims[i];
-        }
+        if ((rc = full_boxes_check(h, reqs, n)) || (rc = request_views(h->N, reqs, n, tsize(h->dtype), vs))) return rc;
         full_recs.resize(n);
-        for (uint32_t b = 0; b < n; b++) {
-            szk_region_gather_strided_box &r = full_recs[b];
-            memset(&r, 0, sizeof(r));
-            r.total = 1;
-            r.dst = reqs[b].d_out;
-            for (int q = 0; q < 4; q++) {
-                const int i = q - (4 - h->N);
-                r.ext[q] = i >= 0 ? reqs[b].box.ext[i] : 1;
-                r.str[q] = i >= 0 && r.ext[q] > 1 ? str[i] << reqs[b].level : 0;
-                r.dstr[q] = i >= 0 && r.ext[q] > 1 ? vs[b].str[i] : 0;
-                r.total *= r.ext[q];
-                if (i >= 0) r.src += (reqs[b].box.lo[i] << reqs[b].level) * str[i];
-            }
-        }
+        for (uint32_t b = 0; b < n; b++) full_record(h, reqs[b], vs[b].str, &full_recs[b]);
         words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
     } else {
         const szk_interp_params &ip = h->codes.ip;
@@ -524,6 +546,217 @@ extern "C" int sz3hip_stream_request(sz3hip_stream *h, const sz3hip_tile_req *re
     h->levels_last = levels;
     h->chain_points_last = chain_points;
     h->requests++;
+    return 0;
+}
+
+// ---- numbers about boxes, no output --------------------------------------------------------------------------------------
+namespace {
+// the arguments before any geometry; the boxes as a request's (no view), so that the request's checks and geometry serve as they are
+int reduce_args(const char *who, const sz3hip_reduce_req *reqs, uint32_t n, const void *third, const char *third_name, std::vector<sz3hip_tile_req> &tr) {
+    int rc = szi_boxes_args(who, reqs, n, third, third_name);
+    if (rc) return rc;
+    tr.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (reqs[i].reserved) return fail(SZ3HIP_EINVAL, "box %u: the reserved word is %u, not 0", i, reqs[i].reserved);
+        memset(&tr[i], 0, sizeof(tr[i]));
+        tr[i].level = reqs[i].level;
+        tr[i].box = reqs[i].box;
+    }
+    return 0;
+}
+int reduce_opts(const sz3hip_reduce_opts *opts, const uint64_t *d_hist, bool need_hist, szk_reduce_hist *hh) {
+    memset(hh, 0, sizeof(*hh));
+    if (!opts) return 0;
+    if (opts->reserved) return fail(SZ3HIP_EINVAL, "the options' reserved word is %u, not 0", opts->reserved);
+    if (opts->nbins > SZ3HIP_MAX_BINS) return fail(SZ3HIP_EINVAL, "the histogram has %u bins: at most %d are supported", opts->nbins, SZ3HIP_MAX_BINS);
+    if (opts->nbins == 0) return 0;
+    if (!(fabs(opts->lo) < INFINITY) || !(fabs(opts->hi) < INFINITY)) return fail(SZ3HIP_EINVAL, "the histogram's range [%g, %g) is not finite", opts->lo, opts->hi);
+    if (!(opts->hi > opts->lo)) return fail(SZ3HIP_EINVAL, "the histogram's range [%g, %g) is empty: hi must be above lo", opts->lo, opts->hi);
+    if (need_hist && !d_hist) return fail(SZ3HIP_EINVAL, "the histogram's array (d_hist) is NULL with %u bins", opts->nbins);
+    hh->nbins = opts->nbins;
+    hh->lo = opts->lo;
+    hh->hi = opts->hi;
+    hh->scale = (double)opts->nbins / (opts->hi - opts->lo);
+    return 0;
+}
+// the partial records lie behind the level buffers, on an 8-byte boundary: where they start and what the scratch holds then, in elements
+uint64_t reduce_part_base(uint64_t elems, size_t tsz) { return tsz == 4 ? (elems + 1) & ~1ull : elems; }
+uint64_t reduce_scratch_elems(uint64_t elems, uint64_t partials, size_t tsz) { return reduce_part_base(elems, tsz) + partials * (sizeof(szk_reduce_part) / tsz); }
+// box i's first partial record (the request's order), the records' number
+uint64_t reduce_partials(const sz3hip_tile_req *tr, uint32_t n, int N, std::vector<uint64_t> *first) {
+    uint64_t at = 0;
+    if (first) first->resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        uint64_t total = 1;
+        for (int j = 0; j < N; j++) total *= tr[i].box.ext[j];
+        if (first) (*first)[i] = at;
+        at += szk_reduce_chunks(total);
+    }
+    return at;
+}
+
+// sz3hip_reduce_device's workspace, one per device: the partial records (grown when a view needs more) and the event that orders a call
+// behind the previous one on another stream
+struct ReduceWs {
+    std::mutex mu;
+    szk_reduce_part *d_partials = nullptr;
+    uint64_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    hipStream_t last = nullptr;
+};
+std::mutex g_reduce_mu;
+std::map<int, std::unique_ptr<ReduceWs>> g_reduce_ws;
+ReduceWs *reduce_ws(int device) {
+    std::lock_guard<std::mutex> l(g_reduce_mu);
+    auto &p = g_reduce_ws[device];
+    if (!p) p.reset(new ReduceWs);
+    return p.get();
+}
+}  // namespace
+
+extern "C" int sz3hip_reduce_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_reduce_req *reqs, uint32_t n, const sz3hip_reduce_opts *opts,
+                                      sz3hip_reduce_plan *out) {
+    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_reduce_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
+    int rc = dtype_check(dataType);
+    std::vector<sz3hip_tile_req> tr;
+    szk_reduce_hist hh;
+    if (rc || (rc = reduce_args("sz3hip_reduce_plan_for", reqs, n, reqs, "reqs", tr)) || (rc = reduce_opts(opts, nullptr, false, &hh))) return rc;
+    std::vector<szk_region_geom> gs;
+    uint64_t elems = 0;
+    memset(out, 0, sizeof(*out));
+    if ((rc = szi_request_geometry_conf(conf, tr.data(), n, gs, &elems))) return rc;
+    out->n = n;
+    out->finest_level = out->coarsest_level = reqs[0].level;
+    for (uint32_t i = 0; i < n; i++) {
+        out->finest_level = std::min(out->finest_level, reqs[i].level);
+        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
+        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
+        out->points += gs[i].points;
+    }
+    out->partials = reduce_partials(tr.data(), n, conf->N, nullptr);
+    out->scratch_elems = reduce_scratch_elems(elems, out->partials, tsize(dataType));
+    out->hist_words = (uint64_t)n * (hh.nbins ? hh.nbins + 2 : 0);
+    return 0;
+}
+
+extern "C" int sz3hip_stream_reduce(sz3hip_stream *h, const sz3hip_reduce_req *reqs, uint32_t n, const sz3hip_reduce_opts *opts, sz3hip_box_stats *d_stats,
+                                    uint64_t *d_hist, void *stream) {
+    if (!d_stats) return fail(SZ3HIP_EINVAL, "sz3hip_stream_reduce: NULL argument (d_stats)");
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_reduce: no handle");
+    std::vector<sz3hip_tile_req> tr;
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    int rc = reduce_args("sz3hip_stream_reduce", reqs, n, d_stats, "d_stats", tr);
+    if (rc || (rc = reduce_opts(opts, d_hist, true, &sink.hist))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    std::vector<szk_region_geom> gs;
+    std::vector<uint64_t> first;
+    uint64_t elems = 0, words = 0;
+    const int N = h->fast ? h->codes.ip.N : h->N;
+    if (!h->fast) {
+        if ((rc = full_boxes_check(h, tr.data(), n))) return rc;
+        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
+    } else {
+        const szk_interp_params &ip = h->codes.ip;
+        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, tr.data(), n, gs, &elems))) return rc;
+        // (behind a request's table: the boxes' records once more, for the final of a request served level group by level group)
+        words = szk_region_request_table_words(gs.data(), n) + (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
+    }
+    const uint64_t partials = reduce_partials(tr.data(), n, N, &first);
+    if (partials >= (1ull << 40)) return fail(SZ3HIP_EINVAL, "the boxes hold too many points for one reducing request");
+    for (uint32_t i = 0; i < n; i++) tr[i].d_out = (void *)(uintptr_t)SZK_REDUCE_DST(first[i], i);  // (a reducing request's `dst` word)
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = region_reserve(h, reduce_scratch_elems(elems, partials, tsize(h->dtype)))) || (rc = table_reserve(h, words))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    sink.partials = reinterpret_cast<szk_reduce_part *>((char *)h->d_region + reduce_part_base(elems, tsize(h->dtype)) * tsize(h->dtype));
+    sink.d_stats = d_stats;
+    sink.d_hist = sink.hist.nbins ? d_hist : nullptr;
+    if (sink.hist.nbins) HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)n * (sink.hist.nbins + 2) * 8, s));
+    const uint32_t chain_points = sz3hip_debug_get_chain_points();
+    uint32_t chain_levels = 0, launches = 0, levels = 0;
+    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
+    int lr;
+    if (!h->fast) {
+        std::vector<szk_region_gather_strided_box> full_recs(n);
+        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
+        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
+        launches = 2;
+    } else {
+        std::vector<szk_region_out> outs(n);
+        for (uint32_t i = 0; i < n; i++) {
+            memset(&outs[i], 0, sizeof(outs[i]));
+            outs[i].dst = tr[i].d_out;
+        }
+        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
+                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, outs.data(), h->h_table,
+                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
+    }
+    HIPCHK(hipEventRecord(h->ev_req, s));
+    h->req_pending = true;
+    h->last_stream = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's reduction could not be launched (%d)", lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+extern "C" int sz3hip_reduce_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_reduce_opts *opts,
+                                    sz3hip_box_stats *d_stats, uint64_t *d_hist, void *stream) {
+    int rc = dtype_check(dataType);
+    if (rc) return rc;
+    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++)
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+    if (!d_stats) return fail(SZ3HIP_EINVAL, "sz3hip_reduce_device: NULL argument (d_stats)");
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    if ((rc = reduce_opts(opts, d_hist, true, &sink.hist))) return rc;
+    uint64_t str[4] = {0, 0, 0, 0};
+    int dev = 0;
+    if ((rc = szi_dev_view_strides(N, dims, strides, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
+    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    szk_region_gather_strided_box rec;
+    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);  // (dst word 0: the view's first partial record)
+    const uint64_t partials = szk_reduce_chunks(rec.total);
+    if (partials >= (1ull << 40)) return fail(SZ3HIP_EINVAL, "the view holds too many points for one reduction");
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    HIPCHK(hipSetDevice(dev));
+    ReduceWs *w = reduce_ws(dev);
+    std::lock_guard<std::mutex> lock(w->mu);
+    if (!w->ev) HIPCHK(hipEventCreateWithFlags(&w->ev, hipEventDisableTiming));
+    if (partials > w->cap) {
+        if (w->d_partials) {
+            HIPCHK(hipDeviceSynchronize());  // (an earlier call's kernels may still use them)
+            (void)hipFree(w->d_partials);
+        }
+        w->d_partials = nullptr;
+        w->cap = 0;
+        w->pending = false;
+        const uint64_t cap = std::max<uint64_t>(partials, 4096);
+        HIPCHK(hipMalloc((void **)&w->d_partials, cap * sizeof(szk_reduce_part)));
+        w->cap = cap;
+    }
+    if (w->pending && s != w->last) HIPCHK(hipStreamWaitEvent(s, w->ev, 0));
+    sink.partials = w->d_partials;
+    sink.d_stats = d_stats;
+    sink.d_hist = sink.hist.nbins ? d_hist : nullptr;
+    if (sink.hist.nbins) HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)(sink.hist.nbins + 2) * 8, s));
+    int lr = szk_launch_region_reduce(dataType, d_in, nullptr, &rec, 1, rec.total, &sink, s);
+    if (!lr) lr = szk_launch_region_reduce_final(dataType, d_in, nullptr, &rec, 1, &sink, s);
+    HIPCHK(hipEventRecord(w->ev, s));
+    w->pending = true;
+    w->last = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the reduction could not be launched (%d)", lr);
     return 0;
 }
 
