@@ -550,6 +550,64 @@ int sz3hip_stream_reduce(sz3hip_stream *h, const sz3hip_reduce_req *reqs, uint32
                          uint64_t *d_hist, void *stream);
 int sz3hip_reduce_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_reduce_opts *opts,
                          sz3hip_box_stats *d_stats, uint64_t *d_hist, void *stream);
+/* ---- the points of boxes whose values lie in a range ----
+ * Where in a box do the values lie in [lo, hi]: the cells an isosurface passes through, the candidates above a threshold, the points below
+ * a floor, the NaNs. sz3hip_stream_select takes 1 .. SZ3HIP_MAX_BOXES boxes that each name their own level, as sz3hip_stream_request does
+ * (coordinates, checks, codes and wording are that call's, "box <i>: " in front; repeated and overlapping boxes are allowed; everything is
+ * checked before anything is launched or written), and runs the same launch sequence with three launches in the strided gather's place — a
+ * count per chunk, a scan per box, the write: stats.launches_last_request is the same boxes' sz3hip_stream_request's, plus two (a handle
+ * that keeps the full array: three). It counts as a request in sz3hip_stream_stats.
+ * What is tested: exactly the values sz3hip_stream_request would deliver for the box, each as x = (double)v. A point is selected when
+ * lo <= x && x <= hi; with SZ3HIP_SELECT_INVERT a point that is not NaN is selected when that is false. +-Inf are ordinary values (lo = hi
+ * = +Inf selects the +Inf points), -0.0 and +0.0 compare equal, lo > hi is a valid empty range, a NaN point is selected only under
+ * SZ3HIP_SELECT_NAN. The comparison is in double: a float 0.1f lies above a lo of 0.1.
+ * What is written, all of it DEVICE memory: d_heads[i] = { n: the box's points, count: the selected ones, written = min(count, capacity),
+ * capacity }; d_index[0 .. written): the `written` SMALLEST selected box-local row-major indices, ascending; d_value[r]: the raw bytes of
+ * the point at d_index[r] (NaN payloads and zero signs kept; NULL: indices only). Elements from `written` on are not touched. count >
+ * capacity is not an error: the caller reads the head and calls again. capacity 0 with both pointers NULL counts only. No device-to-host
+ * copy, no host synchronisation beyond a request's own waits; the ordering between requests is the existing one.
+ * The result depends on the box's values alone — not on the grid, on n, on the request's other boxes, on the handle's kind or on the
+ * device: chunks of 4096 consecutive row-major indices are counted, a box's counts are scanned, and a hit's place is its chunk's offset
+ * plus the hits in front of it in the chunk. No flags, no atomics. sz3hip_stream_select is byte-identical to sz3hip_select_device over
+ * the same values.
+ * Errors (SZ3HIP_EINVAL): opts NULL; lo or hi NaN; flags beyond the two; opts->reserved or a request's reserved not 0; d_heads NULL;
+ * capacity > 0 with d_index NULL; d_value non-NULL with capacity 0; two boxes' output ranges overlapping ("box i: the output overlaps box
+ * j's" — ranges of non-zero capacity, index against index and value against value); and sz3hip_stream_request's for the boxes. Integer
+ * types: SZ3HIP_EUNSUPPORTED.
+ * sz3hip_select_device: the same selection of ONE plain view in device memory (what a handle that keeps the full array runs). N, dims,
+ * strides and the pointer's rules are sz3hip_verify_device's; float / double only. Asynchronous on `stream`; the chunk records live in the
+ * per-device workspace sz3hip_reduce_device keeps, calls are ordered by its event.
+ * sz3hip_select_plan_for: a pure function (no device) with sz3hip_stream_select's checks. points, n_levels and the two level fields are
+ * sz3hip_request_plan_for's; partials: the chunk records (the sum of the boxes' ceil(points / 4096)); scratch_elems: the level buffers plus
+ * the room of those records (8 bytes each, on an 8-byte boundary), in elements of dataType. */
+#define SZ3HIP_SELECT_INVERT 1u   /* select the points that are NOT in [lo, hi]; a NaN point is still not selected */
+#define SZ3HIP_SELECT_NAN    2u   /* NaN points are selected too (alone: with lo > hi and no INVERT) */
+typedef struct sz3hip_select_req {   /* 96 bytes */
+    int32_t level;        /* 0 .. 30: the box lies on the grid of every 2^level-th point */
+    uint32_t reserved;    /* 0 */
+    sz3hip_box box;       /* in that grid's coordinates, slowest first, N entries used */
+    uint64_t *d_index;    /* device: capacity box-local row-major indices, ascending */
+    void *d_value;        /* device: capacity elements of the stream's type, the points' raw bytes; NULL: indices only */
+    uint64_t capacity;    /* 0 with both pointers NULL: count only */
+} sz3hip_select_req;
+typedef struct sz3hip_select_opts {  /* 24 bytes */
+    double lo, hi;
+    uint32_t flags, reserved;
+} sz3hip_select_opts;
+typedef struct sz3hip_select_head {  /* 32 bytes */
+    uint64_t n, count, written, capacity;
+} sz3hip_select_head;
+typedef struct sz3hip_select_plan {  /* 40 bytes */
+    uint32_t n;
+    int32_t finest_level, coarsest_level, n_levels;
+    uint64_t points, scratch_elems, partials;
+} sz3hip_select_plan;
+int sz3hip_select_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_select_req *reqs, uint32_t n, const sz3hip_select_opts *opts,
+                           sz3hip_select_plan *out);
+int sz3hip_stream_select(sz3hip_stream *h, const sz3hip_select_req *reqs, uint32_t n, const sz3hip_select_opts *opts, sz3hip_select_head *d_heads,
+                         void *stream);
+int sz3hip_select_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_select_opts *opts,
+                         uint64_t *d_index, void *d_value, uint64_t capacity, sz3hip_select_head *d_head, void *stream);
 /* development switch, process-wide: a request of a handle runs its coarsest c levels in ONE launch (one workgroup per box walks first point,
  * regrids and passes with a barrier between steps), c the largest count such that for every box every pass of those levels has at most
  * `points` points. 0: off — the request issues exactly the launches sz3hip_decompress_device_tiles issues. Environment twin, read once when

@@ -175,6 +175,27 @@ class _CReducePlan(C.Structure):
                 ("scratch_elems", C.c_uint64), ("partials", C.c_uint64), ("hist_words", C.c_uint64)]
 
 
+class _CSelectReq(C.Structure):
+    # sz3hip_select_req (include/sz3hip.h)
+    _fields_ = [("level", C.c_int32), ("reserved", C.c_uint32), ("box", _CBox), ("d_index", C.c_void_p), ("d_value", C.c_void_p), ("capacity", C.c_uint64)]
+
+
+class _CSelectOpts(C.Structure):
+    # sz3hip_select_opts
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _CSelectHead(C.Structure):
+    # sz3hip_select_head: four 64-bit words
+    _fields_ = [(k, C.c_uint64) for k in ("n", "count", "written", "capacity")]
+
+
+class _CSelectPlan(C.Structure):
+    # sz3hip_select_plan
+    _fields_ = [("n", C.c_uint32), ("finest_level", C.c_int32), ("coarsest_level", C.c_int32), ("n_levels", C.c_int32), ("points", C.c_uint64),
+                ("scratch_elems", C.c_uint64), ("partials", C.c_uint64)]
+
+
 class _CStreamStats(C.Structure):
     """struct sz3hip_stream_stats (include/sz3hip.h)"""
     _fields_ = [("fast", C.c_uint32), ("huffman_stages", C.c_uint32), ("launches_last_request", C.c_uint32), ("chain_levels_last_request", C.c_uint32),
@@ -337,6 +358,13 @@ def lib():
     L.sz3hip_stream_reduce.argtypes = [C.c_void_p, P(_CReduceReq), C.c_uint32, P(_CReduceOpts), C.c_void_p, C.c_void_p, C.c_void_p]
     L.sz3hip_reduce_device.restype = C.c_int
     L.sz3hip_reduce_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CReduceOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sz3hip_select_plan_for.restype = C.c_int
+    L.sz3hip_select_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CSelectReq), C.c_uint32, P(_CSelectOpts), P(_CSelectPlan)]
+    L.sz3hip_stream_select.restype = C.c_int
+    L.sz3hip_stream_select.argtypes = [C.c_void_p, P(_CSelectReq), C.c_uint32, P(_CSelectOpts), C.c_void_p, C.c_void_p]
+    L.sz3hip_select_device.restype = C.c_int
+    L.sz3hip_select_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CSelectOpts), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                       C.c_void_p]
     L.sz3hip_request_plan_for.restype = C.c_int
     L.sz3hip_request_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CRequestPlan)]
     L.sz3hip_stream_close.restype = None
@@ -965,6 +993,120 @@ def reduce_stats(tensor, bins=0, lo=0.0, hi=0.0, stream=None):
     return res
 
 
+SELECT_INVERT = 1  # SZ3HIP_SELECT_INVERT
+SELECT_NAN = 2     # SZ3HIP_SELECT_NAN
+
+
+class SelectResult:
+    """what a selection leaves in DEVICE memory: `heads`, an (n, 4) int64 tensor whose rows are sz3hip_select_head records (n, count,
+    written, capacity); `index`, a list of int64 tensors of the boxes' capacities (box-local row-major indices, ascending; only the first
+    `written` are set); `value`, the same in the array's dtype (the points' raw bytes) or None. Nothing here waits for the device; numpy()
+    does: it synchronises and returns per box (count, index[:written], value[:written] or None)."""
+
+    def __init__(self, heads, index, value):
+        self.heads = heads
+        self.index = index
+        self.value = value
+
+    def numpy(self):
+        heads = self.heads.cpu().numpy()  # (the copy to the host is the synchronisation)
+        out = []
+        for i, ix in enumerate(self.index):
+            written = int(heads[i, 2])
+            out.append((int(heads[i, 1]), ix[:written].cpu().numpy(), None if self.value is None else self.value[i][:written].cpu().numpy()))
+        return out
+
+
+def _select_opts(lo, hi, invert, nan):
+    o = _CSelectOpts()
+    o.lo = float(lo)
+    o.hi = float(hi)
+    o.flags = (SELECT_INVERT if invert else 0) | (SELECT_NAN if nan else 0)
+    return o
+
+
+def _select_caps(capacity, n):
+    caps = [int(capacity)] * n if isinstance(capacity, (int, np.integer)) else [int(c) for c in capacity]
+    if len(caps) != n:
+        raise ValueError("capacity is an int or one per item (%d)" % n)
+    if any(c < 0 for c in caps):
+        raise ValueError("a capacity is negative")
+    return caps
+
+
+def _select_reqs(N, items, caps=None, index=None, value=None):
+    items = [tuple(it) for it in items]
+    if any(len(it) != 3 for it in items):
+        raise ValueError("an item is (level, lo, shape)")
+    arr, _ = _boxes(N, [(it[1], it[2]) for it in items])
+    reqs = (_CSelectReq * max(len(items), 1))()
+    for i, it in enumerate(items):
+        reqs[i].level = int(it[0])
+        reqs[i].box = arr[i]
+        if caps is not None:
+            reqs[i].capacity = caps[i]
+        if index is not None and caps[i]:
+            reqs[i].d_index = index[i].data_ptr()
+            reqs[i].d_value = value[i].data_ptr() if value is not None else None
+    return reqs, len(items)
+
+
+def _select_result(caps, values, dtype, device):
+    import torch
+    heads = torch.empty((max(len(caps), 1), C.sizeof(_CSelectHead) // 8), dtype=torch.int64, device=device)
+    index = [torch.empty((c,), dtype=torch.int64, device=device) for c in caps]
+    value = [torch.empty((c,), dtype=dtype, device=device) for c in caps] if values else None
+    return SelectResult(heads, index, value)
+
+
+def select_plan(conf, dtype, items, lo=0.0, hi=0.0, capacity=0, invert=False, nan=False):
+    """what one Stream.select for `items` — (level, lo, shape) — touches (sz3hip_select_plan_for), without a device: the select call's own
+    checks run (the outputs are laid out one behind the other, index and value apart). Returns a dict with n, finest_level,
+    coarsest_level, n_levels, points, scratch_elems (the level buffers and the chunk records' room) and partials (one per 4096 points of a
+    box)."""
+    items = [tuple(it) for it in items]
+    caps = _select_caps(capacity, len(items))
+    reqs, n = _select_reqs(conf.N, items, caps)
+    at = 1 << 20
+    for i in range(n):  # (stand-in addresses: the plan checks the outputs' rules, not whether they are device memory)
+        if caps[i]:
+            reqs[i].d_index = at
+            at += caps[i] * 8
+    opts = _select_opts(lo, hi, invert, nan)
+    plan = _CSelectPlan()
+    _check(lib().sz3hip_select_plan_for(C.byref(conf._c), _dtype_id(_np_dtype(dtype)), reqs, n, C.byref(opts), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k, _ in _CSelectPlan._fields_}
+
+
+def select_points(tensor, lo, hi, capacity, invert=False, nan=False, values=True, stream=None):
+    """the points of one float32 / float64 torch tensor on a HIP device whose values lie in [lo, hi] (sz3hip_select_device): the selection
+    Stream.select runs per box, over a plain view — any strides that are not negative, size-1 dimensions dropped, at most 4 left; indices
+    are row-major over the tensor's shape. invert: the points outside the range; nan: NaN points too. Asynchronous on `stream`; returns a
+    SelectResult of one box."""
+    if not _is_tensor(tensor):
+        raise TypeError("select_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
+    if not _gpu_tensor(tensor):
+        raise ValueError("select_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
+    name = str(tensor.dtype).replace("torch.", "")
+    if name not in _SZ_TYPES:
+        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
+    if tensor.numel() == 0:
+        raise ValueError("select_points: the tensor is empty")
+    keep = [i for i, d in enumerate(tensor.shape) if int(d) != 1]
+    if len(keep) > 4:
+        raise ValueError("select_points: %d dimensions above size 1 (at most 4 are supported)" % len(keep))
+    dims = [int(tensor.shape[i]) for i in keep] or [1]
+    strides = [int(tensor.stride(i)) for i in keep] or [1]
+    N = len(dims)
+    caps = _select_caps(capacity, 1)
+    res = _select_result(caps, values, tensor.dtype, tensor.device)
+    opts = _select_opts(lo, hi, invert, nan)
+    _check(lib().sz3hip_select_device(_SZ_TYPES[name], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*strides), C.byref(opts),
+                                      res.index[0].data_ptr() if caps[0] else None, res.value[0].data_ptr() if values and caps[0] else None, caps[0],
+                                      res.heads.data_ptr(), _stream_handle(tensor.device, stream)))
+    return res
+
+
 def set_chain_points(points):
     """development switch (sz3hip_debug_chain_points): a Stream request runs its coarsest levels — those whose every pass has at most
     `points` points for every box — in one launch; 0 switches the chain off"""
@@ -1068,6 +1210,22 @@ class Stream:
         opts = _reduce_opts(bins, lo, hi)
         _check(lib().sz3hip_stream_reduce(self._h, reqs, n, C.byref(opts), res.stats.data_ptr(), None if res.hist is None else res.hist.data_ptr(),
                                           _stream_handle(self.device, stream)))
+        return res
+
+    def select(self, items, lo, hi, capacity, invert=False, nan=False, values=True, stream=None):
+        """where in boxes the values lie in [lo, hi] (sz3hip_stream_select): `items` are (level, lo, shape) as
+        request's; `capacity` an int or one per item. Per box the count of selected points and the `capacity` smallest selected box-local
+        row-major indices, ascending, with (values) the points' raw values — over exactly the values request would deliver, compared as
+        doubles. invert: the points that are not in the range; nan: NaN points too. The request's launch sequence with count, scan and
+        write in the gather's place; deterministic. Asynchronous on `stream`, as tiles; returns a SelectResult (device tensors; .numpy()
+        waits)."""
+        import torch
+        items = [tuple(it) for it in items]
+        caps = _select_caps(capacity, len(items))
+        res = _select_result(caps, values, getattr(torch, self.dtype.name), self.device)
+        reqs, n = _select_reqs(self.conf.N, items, caps, res.index, res.value)
+        opts = _select_opts(lo, hi, invert, nan)
+        _check(lib().sz3hip_stream_select(self._h, reqs, n, C.byref(opts), res.heads.data_ptr(), _stream_handle(self.device, stream)))
         return res
 
     def tile(self, level, lo, shape, out=None, stream=None):

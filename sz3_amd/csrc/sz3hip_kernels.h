@@ -470,12 +470,34 @@ struct szk_reduce_hist {  // nbins 0: no histogram
 // where a reducing request's results go instead of the boxes' views. partials: room for the sum of the boxes' szk_reduce_chunks records
 // (the handle's scratch, behind the level buffers); d_stats: n sz3hip_box_stats (11 words each); d_hist: n rows of nbins + 2 counts, zeroed
 // by the caller in front
+// kind SZK_SINK_SELECT (kernels: sz3hip_select.hip): the points of the boxes whose values pass sel — sel_counts: one
+// 64-bit word per chunk, the room of the sum of the boxes' szk_reduce_chunks (hit counts, then exclusive offsets in place); sel_heads: n
+// sz3hip_select_head; sel_outs: HOST, SZK_SELECT_OUT_WORDS words per box in the request's order (d_index, d_value, capacity) — the
+// launchers put them into the table behind the boxes' records, where the scan and the write read box i's at words 3 i ..
+#define SZK_SINK_REDUCE 0
+#define SZK_SINK_SELECT 1
+#define SZK_SELECT_OUT_WORDS 3
+struct szk_select_opts {
+    double lo, hi;
+    uint32_t flags, pad;  // SZ3HIP_SELECT_*
+};
 struct szk_region_sink {
     szk_reduce_part *partials;
     void *d_stats;
     uint64_t *d_hist;
     szk_reduce_hist hist;
+    int kind;
+    uint64_t *sel_counts;
+    void *sel_heads;
+    const uint64_t *sel_outs;
+    szk_select_opts sel;
 };
+// the selection's launches over n records in device memory, the boxes' outputs behind them (one box: by value, with sink->sel_outs' three
+// words as arguments): the count; then scan and write (two launches)
+int szk_launch_region_select_count(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
+                                   uint32_t n, uint64_t most_total, const szk_region_sink *sink, hipStream_t s);
+int szk_launch_region_select_place(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
+                                   uint32_t n, uint64_t most_total, const szk_region_sink *sink, hipStream_t s);
 // the two launches over n records in device memory (one box: by value, rec_by_value non-null and d_recs null). gx: the largest box's chunks
 int szk_launch_region_reduce(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
                              uint32_t n, uint64_t most_total, const szk_region_sink *sink, hipStream_t s);
@@ -483,7 +505,8 @@ int szk_launch_region_reduce_final(int dtype, const void *d_src, const struct sz
                                    const szk_region_sink *sink, hipStream_t s);
 uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n);
 // sink non-null: the request reduces (outs[i].dst: box i's SZK_REDUCE_DST word, cast; the strides are not read) — reduce and final stand
-// in the strided gather's place, *launches is the request's count plus one
+// in the strided gather's place, *launches is the request's count plus one; a selecting sink (kind SZK_SINK_SELECT): count, scan and write,
+// the request's count plus two, table_words with room for n * SZK_SELECT_OUT_WORDS more
 int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                                 const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                                 void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,
@@ -491,7 +514,8 @@ int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_para
                                                 const szk_region_sink *sink = nullptr);
 // n strided boxes of one array into n strided views in one launch (the gather of szk_launch_gather with a strided destination, per box): recs
 // are copied through h_table into d_table (n * 15 words) in front of the launch, `copied` recorded behind the copy. sink non-null: the boxes are
-// reduced instead (recs[i].dst: box i's SZK_REDUCE_DST word), two launches
+// reduced instead (recs[i].dst: box i's SZK_REDUCE_DST word), two launches — or selected, three launches, the boxes' outputs (n * 3 words)
+// behind the records in the same copy
 int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gather_strided_box *recs, uint32_t n, uint64_t *h_table, uint64_t *d_table,
                             uint64_t table_words, hipEvent_t copied, hipStream_t s, const szk_region_sink *sink = nullptr);
 uint64_t szk_region_launches(void);  // test hook: kernel launches the box reconstructions issued so far, single and multi

@@ -800,12 +800,31 @@ static void region_launch(uint32_t *issued, void (*kernel)(KA...), dim3 grid, ui
     region_count(issued);
 }
 
+// a selecting request's outputs ride in the table's one copy, directly behind the n boxes' records at the cursor *w (any other sink: nothing)
+static bool region_sink_tail(const szk_region_sink *sink, uint32_t n, uint64_t *h_table, uint64_t *w, uint64_t table_words) {
+    if (!sink || sink->kind != SZK_SINK_SELECT) return true;
+    const uint64_t words = (uint64_t)n * SZK_SELECT_OUT_WORDS;
+    if (!sink->sel_outs || words > table_words || *w > table_words - words) return false;
+    memcpy(h_table + *w, sink->sel_outs, words * 8);
+    *w += words;
+    return true;
+}
+
 // a reducing request's launches in the gather's place: the reduction over the boxes' records, then — unless the caller
 // issues it once for several groups — the final
 template <typename T>
 static int region_sink_launch(uint32_t *issued, const T *src, const szk_region_gather_strided_box *d_recs, uint32_t n, uint64_t most, const szk_region_sink *sink,
                               bool with_final, hipStream_t s) {
     const int dtype = sizeof(T) == 4 ? 0 : 1;
+    if (sink->kind == SZK_SINK_SELECT) {  // (the count, then — once per request — scan and write)
+        if (szk_launch_region_select_count(dtype, src, d_recs, nullptr, n, most, sink, s)) return -2;
+        region_count(issued);
+        if (!with_final) return 0;
+        if (szk_launch_region_select_place(dtype, src, d_recs, nullptr, n, most, sink, s)) return -2;
+        region_count(issued);
+        region_count(issued);
+        return 0;
+    }
     if (szk_launch_region_reduce(dtype, src, d_recs, nullptr, n, most, sink, s)) return -2;
     region_count(issued);
     if (!with_final) return 0;
@@ -1003,6 +1022,7 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
         if (!region_grid(most, &l.gx)) return -1;
         l.most = most;
         seq.push_back(l);
+        if (sink_final && !region_sink_tail(sink, n, h_table, &w, table_words)) return -1;
     }
     // the chain's steps, behind the boxes' records: the chained launches in their order, a pass's shared part in front of its step(s)
     uint64_t steps_off = 0;
@@ -1242,6 +1262,7 @@ static int run_region_mixed(const szk_interp_params &ip, const szk_region_geom *
         if (!region_grid(most, &l.gx)) return -1;
         l.most = most;
         seq.push_back(l);
+        if (!region_sink_tail(sink, n, h_table, &w, table_words)) return -1;
     }
     if (hipMemcpyAsync(d_table, h_table, w * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
     if (hipEventRecord(copied, s) != hipSuccess) return -2;
@@ -1323,17 +1344,24 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
         most_levels = std::max(most_levels, (uint32_t)gg[0].n_levels);
     }
     if (sink) {  // ONE final for the request: the boxes' records once more, in the request's order, behind the groups' stretches
-        const uint64_t need = (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box);
+        uint64_t need = (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box), most = 0;
         if (need > table_words || used > table_words - need) return -1;
         for (uint32_t i = 0; i < n; i++) {
             szk_region_gather_strided_box r;
             if (region_gather_strided_record(gs[i], outs[i], &r)) return -1;
             memcpy(h_table + used + (uint64_t)i * SZK_WORDS(szk_region_gather_strided_box), &r, sizeof(r));
+            most = std::max(most, r.total);
         }
+        need += used;  // (the cursor behind the records; a selection's outputs follow them)
+        if (!region_sink_tail(sink, n, h_table, &need, table_words)) return -1;
+        need -= used;
         if (hipMemcpyAsync(d_table + used, h_table + used, need * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
         if (hipEventRecord(copied, s) != hipSuccess) return -2;
-        if (szk_launch_region_reduce_final(sizeof(T) == 4 ? 0 : 1, scratch, reinterpret_cast<const szk_region_gather_strided_box *>(d_table + used), nullptr, n, sink, s))
-            return -2;
+        const szk_region_gather_strided_box *d_recs = reinterpret_cast<const szk_region_gather_strided_box *>(d_table + used);
+        if (sink->kind == SZK_SINK_SELECT) {  // (the groups counted; scan and write once, over all boxes)
+            if (szk_launch_region_select_place(sizeof(T) == 4 ? 0 : 1, scratch, d_recs, nullptr, n, most, sink, s)) return -2;
+            region_count(&total);
+        } else if (szk_launch_region_reduce_final(sizeof(T) == 4 ? 0 : 1, scratch, d_recs, nullptr, n, sink, s)) return -2;
         region_count(&total);
     }
     if (launches) *launches = total;
@@ -1349,7 +1377,9 @@ int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_para
     if (chain_levels) *chain_levels = 0;
     if (launches) *launches = 0;
     if (levels) *levels = 0;
-    if (sink && (!sink->partials || !sink->d_stats || (sink->hist.nbins && !sink->d_hist))) return -1;
+    if (sink && sink->kind == SZK_SINK_SELECT) {
+        if (!sink->sel_counts || !sink->sel_heads || !sink->sel_outs) return -1;
+    } else if (sink && (!sink->partials || !sink->d_stats || (sink->hist.nbins && !sink->d_hist))) return -1;
     if (n < 1 || n > 65535 || !gs || !outs || !h_table || !d_table) return -1;
     for (uint32_t i = 0; i < n; i++) {  // one stream: every box on the grid of its own level
         const szk_region_geom &g = gs[i];
@@ -1375,7 +1405,9 @@ int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gathe
     uint32_t gx;
     if (!region_grid(most, &gx)) return -1;
     memcpy(h_table, recs, (size_t)n * sizeof(recs[0]));
-    if (hipMemcpyAsync(d_table, h_table, (size_t)n * sizeof(recs[0]), hipMemcpyHostToDevice, s) != hipSuccess) return -2;
+    uint64_t w = (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box);
+    if (!region_sink_tail(sink, n, h_table, &w, table_words)) return -1;
+    if (hipMemcpyAsync(d_table, h_table, w * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
     if (hipEventRecord(copied, s) != hipSuccess) return -2;
     const szk_region_gather_strided_box *d_recs = reinterpret_cast<const szk_region_gather_strided_box *>(d_table);
     if (sink)

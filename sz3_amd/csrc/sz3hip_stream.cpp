@@ -12,9 +12,13 @@
 // sz3hip_stream_reduce takes the same boxes without views and leaves numbers about them in device memory: the request's
 // geometry and sequence with a reduction and its final fold (sz3hip_reduce.hip) in the gather's place; sz3hip_reduce_device is that reduction
 // over one plain view.
+// sz3hip_stream_select takes the boxes with an index and a value array each and leaves where their values lie in a
+// range: the same geometry and sequence with a count, a scan and the write (sz3hip_select.hip) in the gather's place; sz3hip_select_device is
+// that selection over one plain view.
 // A handle serves one request at a time; it is not thread-safe.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -757,6 +761,209 @@ extern "C" int sz3hip_reduce_device(int dataType, int N, const uint64_t *dims, c
     w->pending = true;
     w->last = s;
     if (lr) return fail(SZ3HIP_EHIP, "the reduction could not be launched (%d)", lr);
+    return 0;
+}
+
+// ---- the points of boxes whose values lie in a range -----------------------------------------------------------------------
+namespace {
+int select_opts(const sz3hip_select_opts *opts, szk_select_opts *so) {
+    memset(so, 0, sizeof(*so));
+    if (!opts) return fail(SZ3HIP_EINVAL, "NULL argument (opts): a selection needs its range");
+    if (opts->reserved) return fail(SZ3HIP_EINVAL, "the options' reserved word is %u, not 0", opts->reserved);
+    if (opts->flags & ~(SZ3HIP_SELECT_INVERT | SZ3HIP_SELECT_NAN)) return fail(SZ3HIP_EINVAL, "the options' flags (0x%x) hold bits beyond SZ3HIP_SELECT_INVERT | SZ3HIP_SELECT_NAN", opts->flags);
+    if (opts->lo != opts->lo || opts->hi != opts->hi) return fail(SZ3HIP_EINVAL, "the range's %s is NaN", opts->lo != opts->lo ? "lo" : "hi");
+    so->lo = opts->lo;
+    so->hi = opts->hi;
+    so->flags = opts->flags;
+    return 0;
+}
+// one output's rules (prefix: "box <i>: " or nothing)
+int select_out(const char *prefix, const uint64_t *d_index, const void *d_value, uint64_t capacity, size_t tsz) {
+    if (capacity > 0 && !d_index) return fail(SZ3HIP_EINVAL, "%sd_index is NULL with a capacity of %llu", prefix, (unsigned long long)capacity);
+    if (capacity == 0 && d_value) return fail(SZ3HIP_EINVAL, "%sd_value is given with a capacity of 0", prefix);
+    if (capacity > (1ull << 56)) return fail(SZ3HIP_EINVAL, "%sthe capacity (%llu) is too large", prefix, (unsigned long long)capacity);
+    if ((uintptr_t)d_index % 8 || (uintptr_t)d_value % tsz) return fail(SZ3HIP_EINVAL, "%san output is not aligned to its element size", prefix);
+    return 0;
+}
+// the arguments before any geometry: the boxes as a request's (no view), the outputs' rules, no two outputs of one kind meeting
+int select_args(const char *who, const sz3hip_select_req *reqs, uint32_t n, size_t tsz, std::vector<sz3hip_tile_req> &tr) {
+    int rc = szi_boxes_args(who, reqs, n, reqs, "reqs");
+    if (rc) return rc;
+    tr.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        char prefix[32];
+        snprintf(prefix, sizeof(prefix), "box %u: ", i);
+        if (reqs[i].reserved) return fail(SZ3HIP_EINVAL, "box %u: the reserved word is %u, not 0", i, reqs[i].reserved);
+        if ((rc = select_out(prefix, reqs[i].d_index, reqs[i].d_value, reqs[i].capacity, tsz))) return rc;
+        memset(&tr[i], 0, sizeof(tr[i]));
+        tr[i].level = reqs[i].level;
+        tr[i].box = reqs[i].box;
+    }
+    for (uint32_t i = 1; i < n; i++)
+        for (uint32_t k = 0; k < i && reqs[i].capacity; k++) {
+            if (!reqs[k].capacity) continue;
+            const uintptr_t ai = (uintptr_t)reqs[i].d_index, ak = (uintptr_t)reqs[k].d_index, vi = (uintptr_t)reqs[i].d_value, vk = (uintptr_t)reqs[k].d_value;
+            const bool index_meet = ai < ak + reqs[k].capacity * 8 && ak < ai + reqs[i].capacity * 8;
+            const bool value_meet = vi && vk && vi < vk + reqs[k].capacity * tsz && vk < vi + reqs[i].capacity * tsz;
+            if (index_meet || value_meet) return fail(SZ3HIP_EINVAL, "box %u: the output overlaps box %u's (%s)", i, k, index_meet ? "d_index" : "d_value");
+        }
+    return 0;
+}
+// the chunk records (one 64-bit word each) lie behind the level buffers, on an 8-byte boundary, as a reduce's partials do
+uint64_t select_scratch_elems(uint64_t elems, uint64_t partials, size_t tsz) { return reduce_part_base(elems, tsz) + partials * (8 / tsz); }
+}  // namespace
+
+extern "C" int sz3hip_select_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_select_req *reqs, uint32_t n, const sz3hip_select_opts *opts,
+                                      sz3hip_select_plan *out) {
+    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_select_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
+    int rc = dtype_check(dataType);
+    std::vector<sz3hip_tile_req> tr;
+    szk_select_opts so;
+    if (rc || (rc = select_args("sz3hip_select_plan_for", reqs, n, tsize(dataType), tr)) || (rc = select_opts(opts, &so))) return rc;
+    std::vector<szk_region_geom> gs;
+    uint64_t elems = 0;
+    memset(out, 0, sizeof(*out));
+    if ((rc = szi_request_geometry_conf(conf, tr.data(), n, gs, &elems))) return rc;
+    out->n = n;
+    out->finest_level = out->coarsest_level = reqs[0].level;
+    for (uint32_t i = 0; i < n; i++) {
+        out->finest_level = std::min(out->finest_level, reqs[i].level);
+        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
+        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
+        out->points += gs[i].points;
+    }
+    out->partials = reduce_partials(tr.data(), n, conf->N, nullptr);
+    out->scratch_elems = select_scratch_elems(elems, out->partials, tsize(dataType));
+    return 0;
+}
+
+extern "C" int sz3hip_stream_select(sz3hip_stream *h, const sz3hip_select_req *reqs, uint32_t n, const sz3hip_select_opts *opts, sz3hip_select_head *d_heads,
+                                    void *stream) {
+    if (!d_heads) return fail(SZ3HIP_EINVAL, "sz3hip_stream_select: NULL argument (d_heads)");
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_select: no handle");
+    std::vector<sz3hip_tile_req> tr;
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    sink.kind = SZK_SINK_SELECT;
+    int rc = select_args("sz3hip_stream_select", reqs, n, tsize(h->dtype), tr);
+    if (rc || (rc = select_opts(opts, &sink.sel))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    std::vector<szk_region_geom> gs;
+    std::vector<uint64_t> first;
+    uint64_t elems = 0, words = 0;
+    const int N = h->fast ? h->codes.ip.N : h->N;
+    // (behind the boxes' records: every box's d_index, d_value and capacity, in the table's one copy)
+    const uint64_t tail = (uint64_t)n * SZK_SELECT_OUT_WORDS;
+    if (!h->fast) {
+        if ((rc = full_boxes_check(h, tr.data(), n))) return rc;
+        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
+    } else {
+        const szk_interp_params &ip = h->codes.ip;
+        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, tr.data(), n, gs, &elems))) return rc;
+        // (behind a request's table: the boxes' records once more, for scan and write of a request served level group by level group)
+        words = szk_region_request_table_words(gs.data(), n) + (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
+    }
+    const uint64_t partials = reduce_partials(tr.data(), n, N, &first);
+    if (partials >= (1ull << 40)) return fail(SZ3HIP_EINVAL, "the boxes hold too many points for one selecting request");
+    std::vector<uint64_t> outs(tail);
+    for (uint32_t i = 0; i < n; i++) {
+        tr[i].d_out = (void *)(uintptr_t)SZK_REDUCE_DST(first[i], i);  // (the `dst` word, as a reducing request's)
+        outs[i * SZK_SELECT_OUT_WORDS] = (uint64_t)(uintptr_t)reqs[i].d_index;
+        outs[i * SZK_SELECT_OUT_WORDS + 1] = (uint64_t)(uintptr_t)reqs[i].d_value;
+        outs[i * SZK_SELECT_OUT_WORDS + 2] = reqs[i].capacity;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = region_reserve(h, select_scratch_elems(elems, partials, tsize(h->dtype)))) || (rc = table_reserve(h, words))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    sink.sel_counts = reinterpret_cast<uint64_t *>((char *)h->d_region + reduce_part_base(elems, tsize(h->dtype)) * tsize(h->dtype));
+    sink.sel_heads = d_heads;
+    sink.sel_outs = outs.data();
+    const uint32_t chain_points = sz3hip_debug_get_chain_points();
+    uint32_t chain_levels = 0, launches = 0, levels = 0;
+    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
+    int lr;
+    if (!h->fast) {
+        std::vector<szk_region_gather_strided_box> full_recs(n);
+        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
+        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
+        launches = 3;
+    } else {
+        std::vector<szk_region_out> ro(n);
+        for (uint32_t i = 0; i < n; i++) {
+            memset(&ro[i], 0, sizeof(ro[i]));
+            ro[i].dst = tr[i].d_out;
+        }
+        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
+                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, ro.data(), h->h_table,
+                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
+    }
+    HIPCHK(hipEventRecord(h->ev_req, s));
+    h->req_pending = true;
+    h->last_stream = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's selection could not be launched (%d)", lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+extern "C" int sz3hip_select_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_select_opts *opts,
+                                    uint64_t *d_index, void *d_value, uint64_t capacity, sz3hip_select_head *d_head, void *stream) {
+    int rc = dtype_check(dataType);
+    if (rc) return rc;
+    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++)
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+    if (!d_head) return fail(SZ3HIP_EINVAL, "sz3hip_select_device: NULL argument (d_head)");
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    sink.kind = SZK_SINK_SELECT;
+    if ((rc = select_opts(opts, &sink.sel)) || (rc = select_out("", d_index, d_value, capacity, tsize(dataType)))) return rc;
+    uint64_t str[4] = {0, 0, 0, 0};
+    int dev = 0;
+    if ((rc = szi_dev_view_strides(N, dims, strides, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
+    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    szk_region_gather_strided_box rec;
+    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);  // (dst word 0: the view's first chunk record)
+    const uint64_t partials = szk_reduce_chunks(rec.total);
+    if (partials >= (1ull << 40)) return fail(SZ3HIP_EINVAL, "the view holds too many points for one selection");
+    const uint64_t parts = (partials * 8 + sizeof(szk_reduce_part) - 1) / sizeof(szk_reduce_part);  // (the workspace counts reduce records)
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    HIPCHK(hipSetDevice(dev));
+    ReduceWs *w = reduce_ws(dev);
+    std::lock_guard<std::mutex> lock(w->mu);
+    if (!w->ev) HIPCHK(hipEventCreateWithFlags(&w->ev, hipEventDisableTiming));
+    if (parts > w->cap) {
+        if (w->d_partials) {
+            HIPCHK(hipDeviceSynchronize());  // (an earlier call's kernels may still use them)
+            (void)hipFree(w->d_partials);
+        }
+        w->d_partials = nullptr;
+        w->cap = 0;
+        w->pending = false;
+        const uint64_t cap = std::max<uint64_t>(parts, 4096);
+        HIPCHK(hipMalloc((void **)&w->d_partials, cap * sizeof(szk_reduce_part)));
+        w->cap = cap;
+    }
+    if (w->pending && s != w->last) HIPCHK(hipStreamWaitEvent(s, w->ev, 0));
+    const uint64_t out3[SZK_SELECT_OUT_WORDS] = {(uint64_t)(uintptr_t)d_index, (uint64_t)(uintptr_t)d_value, capacity};
+    sink.sel_counts = reinterpret_cast<uint64_t *>(w->d_partials);
+    sink.sel_heads = d_head;
+    sink.sel_outs = out3;
+    int lr = szk_launch_region_select_count(dataType, d_in, nullptr, &rec, 1, rec.total, &sink, s);
+    if (!lr) lr = szk_launch_region_select_place(dataType, d_in, nullptr, &rec, 1, rec.total, &sink, s);
+    HIPCHK(hipEventRecord(w->ev, s));
+    w->pending = true;
+    w->last = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the selection could not be launched (%d)", lr);
     return 0;
 }
 
