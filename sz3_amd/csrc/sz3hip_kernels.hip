@@ -4663,9 +4663,9 @@ __global__ __launch_bounds__(256) void k_pack(const uint16_t *__restrict__ codes
 // The packer of ONE-BYTE codes (round 6). k_pack spends ~14 vector instructions per symbol (two LDS lookups, the joins of code words
 // into pairs, quads and octets, the emission): it is bound by their issue, not by the 1.5 bytes per symbol it moves. Here a lane
 // looks up PAIRS of codes: a 128 x 128 table over the byte values t in [64, 192) (deltas -63 .. +64 around the mode of a one-byte
-// stream, byte 127; 64 KB of LDS: entry = (code words of t0 and t1 joined) << 5 | their length, 0 when one of them has no code word
-// or the two take more than 27 bits) — one lookup and one shift per TWO symbols. A workgroup is 1024 threads (16 waves share the
-// table: 64 KB + 16 stages of 4 KB, one workgroup per CU); a wave works in units of four chunks: the codes of the unit being packed
+// stream, byte 127; rows padded to PB_PAIR_STRIDE words, 66.5 KB of LDS: entry = (code words of t0 and t1 joined) << 5 | their length,
+// 0 when one of them has no code word or the two take more than 27 bits) — one lookup and one shift per TWO symbols. A workgroup is
+// 1024 threads (16 waves share the table: 66.5 KB + 16 stages of 4 KB, one workgroup per CU); a wave works in units of four chunks: the codes of the unit being packed
 // and of the next one are in registers, the unit's fast-tier chunks share the stage and leave it in one copy-out of 16 bytes per lane.
 //   fast tier (wave-uniform test): every byte of the chunk inside the window, every pair in the table, every lane's two octets <= 64 bits:
 //     8 lookups, 2 emissions of 3 ds_or each;
@@ -4679,6 +4679,12 @@ __global__ __launch_bounds__(256) void k_pack(const uint16_t *__restrict__ codes
 #define PB_THREADS 1024u
 #define PB_WAVES (PB_THREADS / WAVE)
 #define PB_ASM_BLOCKS 32u
+// The pair table's row stride in words: row t1 & 127, column t0 & 127, the columns from 128 on are padding that is never addressed.
+// Odd, so that the rows start in different LDS banks, and below 256, so that it is a byte of packb_chunk's dot product.
+#ifndef PB_PAIR_STRIDE
+#define PB_PAIR_STRIDE 133u
+#endif
+static_assert(PB_PAIR_STRIDE % 2u == 1u && PB_PAIR_STRIDE >= 129u && PB_PAIR_STRIDE <= 255u, "odd, a row holds the 128 window bytes, a byte of the dot product");
 // The stage is an array of 64-bit words whose HIGH half is the earlier 32-bit word of the stream: a left-aligned 64-bit string at bit
 // position pos lands in two of them — two 64-bit LDS atomics instead of three 32-bit ones.
 __device__ __forceinline__ void packb_emit(uint64_t *stage, uint64_t val, uint32_t len, uint32_t pos) {  // val: len bits, right-aligned, 1 <= len <= 64
@@ -4701,10 +4707,13 @@ __device__ __forceinline__ uint32_t packb_chunk(const uint4 &cw, const uint32_t 
         uint32_t e[8];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            // entry of the pair (t0, t1): index (t1 & 127) << 7 | ((t0 ^ t1) & 127) — the XOR spreads the lookups over the LDS banks (the bank
-            // of a 32-bit LDS read is the index's low five bits — the chip's 64 banks serve its 64- and 128-bit reads: with t0 alone a smooth field's symbols, a dozen values around the mode, meet in a dozen banks)
-            const uint32_t m = w[k] & 0x7F7F7F7Fu, x = m ^ (m >> 8), m1 = m >> 16, x1 = x >> 16;
-            const uint32_t a0 = ((x & 0x7Fu) << 2) | ((m & 0x7F00u) << 1), a1 = ((x1 & 0x7Fu) << 2) | ((m1 & 0x7F00u) << 1);
+            // entry of the pair (t0, t1): index (t0 & 127) + PB_PAIR_STRIDE * (t1 & 127), one v_dot4_u32_u8 per pair on the masked word
+            // (unique: t0 & 127 < 128 <= the stride; at most 127 + 127 * stride < 128 * stride, whatever the bytes). The odd stride spreads
+            // the lookups over the LDS banks (the bank of a 32-bit LDS read is the index's low five bits — the chip's 64 banks serve its
+            // 64- and 128-bit reads: with rows of 128 a smooth field's symbols, a dozen values around the mode, meet in a dozen banks)
+            const uint32_t m = w[k] & 0x7F7F7F7Fu;
+            const uint32_t a0 = __builtin_amdgcn_udot4(m, PB_PAIR_STRIDE << 8 | 1u, 0u, false) << 2;
+            const uint32_t a1 = __builtin_amdgcn_udot4(m, (PB_PAIR_STRIDE << 8 | 1u) << 16, 0u, false) << 2;
             e[2 * k] = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(s_pair) + a0);
             e[2 * k + 1] = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(s_pair) + a1);
         }
@@ -4799,13 +4808,16 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
     constexpr uint32_t PB_BATCH = 4;                                    // chunks of a work unit
     constexpr int UNIT_STAGE = PB_BATCH * 128 + 8;                      // 64-bit words: four fast-tier chunks of at most 64 lanes x 128 bits, + the same slack (a multiple of 16 bytes)
     static_assert(2 * UNIT_STAGE >= STAGE_WORDS && UNIT_STAGE % 2 == 0, "the unit's stage also holds one chunk of the slow tiers");
-    __shared__ __align__(16) uint32_t s_pair[128 * 128];
+    __shared__ __align__(16) uint32_t s_pair[PB_PAIR_STRIDE * 128];
     __shared__ uint32_t s_enc8[256];  // code word by byte value ...
     __shared__ uint8_t s_plen8[256];  // ... and its length
     __shared__ __align__(16) uint64_t s_stage[PB_WAVES][UNIT_STAGE];
     __shared__ __align__(16) uint32_t s_goff[SCAN ? PB_SCAN_GROUPS : 4u];  // SCAN: the groups' exclusive word offsets
     __shared__ uint32_t s_gw[PB_WAVES];                                     // ... and the waves' partial sums
     __shared__ uint64_t s_total;
+    // (one workgroup per compute unit; 1 KB beside the arrays above for what the role and assembly bodies declare themselves)
+    static_assert(sizeof(s_pair) + sizeof(s_enc8) + sizeof(s_plen8) + sizeof(s_stage) + sizeof(s_goff) + sizeof(s_gw) + sizeof(s_total) + 1024 <= 160 * 1024,
+                  "k_pack_b's LDS must fit one compute unit");
     // the thread's four group sums (groups 4 * threadIdx.x ...; zero past the last group: the words behind it are whatever was there)
     auto load_sums = [&]() -> uint4 {
         const uint32_t g0 = 4u * threadIdx.x;
@@ -5014,12 +5026,12 @@ __global__ __launch_bounds__(PB_THREADS) void k_pack_b(const uint16_t *__restric
             if (threadIdx.x == PB_THREADS - 1u) *total_w = (uint64_t)run + g_mine;
         }
     }
-    for (uint32_t i = threadIdx.x; i < 128u * 128u; i += PB_THREADS) {
-        const uint32_t i1 = i >> 7, i0 = (i & 127u) ^ i1;        // window indices t & 127 of the first and the second symbol (the table is swizzled: packb_chunk)
-        const uint32_t t0 = i0 < 64u ? i0 + 128u : i0, t1 = i1 < 64u ? i1 + 128u : i1;  // byte values in [64, 192)
+    for (uint32_t i = threadIdx.x; i < PB_PAIR_STRIDE * 128u; i += PB_THREADS) {
+        const uint32_t i1 = i / PB_PAIR_STRIDE, i0 = i - i1 * PB_PAIR_STRIDE;  // window indices t & 127 of the second and the first symbol (packb_chunk's index); i0 >= 128: the row's padding
+        const uint32_t t0 = i0 < 64u ? i0 + 128u : i0 & 127u, t1 = i1 < 64u ? i1 + 128u : i1;  // byte values in [64, 192)
         const uint32_t l0 = s_plen8[t0], l1 = s_plen8[t1];
         const uint32_t len = l0 + l1;
-        s_pair[i] = (l0 && l1 && len <= 27u) ? ((((s_enc8[t0] << l1) | s_enc8[t1]) << 5) | len) : 0u;
+        s_pair[i] = (i0 < 128u && l0 && l1 && len <= 27u) ? ((((s_enc8[t0] << l1) | s_enc8[t1]) << 5) | len) : 0u;  // (0: no entry)
     }
     __syncthreads();
     if (SCAN) ra.go = s_goff[((unit < n_units ? unit : n_units - 1) * PB_BATCH) / PACK_GROUP];
