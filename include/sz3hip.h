@@ -706,6 +706,9 @@ int sz3hip_debug_copy_codes(sz3hip_ctx *ctx, uint16_t *host_codes, uint64_t n);
 /* test hook: which chain the last sz3hip_decompress_device took: out4[0] half-width intermediates, [1] rows that cross chunk
  * boundaries (carry pass), [2] calls left before the half-width chain is tried again after an overflow, [3] reserved */
 int sz3hip_debug_decode_info(sz3hip_ctx *ctx, uint32_t *out4);
+/* the last stock Huffman decode of this process: *passes = restart-point passes launched (0 if none),
+   *route = 0 device, 1 host by the switch, 2 host after the pass cap, 3 single symbol (no bit stream) */
+void sz3hip_debug_stock_huffman(int *passes, int *route);
 /* test hook: non-zero routes every shape through the generic (any-shape) stage-1 kernel instead of the tuned one */
 void sz3hip_debug_force_generic(int on);
 /* development switches (bit mask, process-wide; 0 = product behaviour): an OR of enum sz3hip_dbg, sz3hip_debug.h, which says what each bit gates */

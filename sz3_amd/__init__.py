@@ -336,6 +336,8 @@ def lib():
     L.sz3hip_debug_region_launches.argtypes = []
     L.sz3hip_debug_tile_units.restype = None
     L.sz3hip_debug_tile_units.argtypes = [P(C.c_uint64), P(C.c_uint64)]
+    L.sz3hip_debug_stock_huffman.restype = None
+    L.sz3hip_debug_stock_huffman.argtypes = [P(C.c_int), P(C.c_int)]
     L.sz3hip_debug_region_fast_calls.restype = C.c_uint64
     L.sz3hip_debug_region_fast_calls.argtypes = []
     L.sz3hip_debug_region_scratch.restype = C.c_uint64
@@ -754,6 +756,14 @@ def debug_tile_units():
     d, t = C.c_uint64(0), C.c_uint64(0)
     lib().sz3hip_debug_tile_units(C.byref(d), C.byref(t))
     return int(d.value), int(t.value)
+
+
+def debug_stock_huffman():
+    """(passes, route) of this process's last stock Huffman decode: restart-point passes launched on the device (0 if none), and
+    route 0 device, 1 host by SZ3HIP_STOCK_HOST_HUFFMAN, 2 host after the pass cap, 3 single symbol (no bit stream)"""
+    p, r = C.c_int(0), C.c_int(0)
+    lib().sz3hip_debug_stock_huffman(C.byref(p), C.byref(r))
+    return int(p.value), int(r.value)
 
 
 def _decompress_partial(name, blob, dtype, probe_args, shape_of, out, device, stream):

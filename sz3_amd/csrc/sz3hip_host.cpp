@@ -1318,7 +1318,15 @@ static void stock_huff_ask(DevArena &ar, StockHuffDev &h, uint64_t n, uint64_t b
     ar.ask(&h.d_count, (size_t)(nsub + 2) * 4);
     ar.ask(&h.d_flags, 64);
 }
-static int stock_huff_run(HostSlot *s, const StockHuffDev &h, const stock::Tree &tr, int32_t offset, const uint8_t *bits, uint64_t bit_bytes, uint64_t n) {
+// what the last stock_huff_run of this process did (sz3hip_debug_stock_huffman): restart-point passes launched, and the route taken
+static std::atomic<int> g_stock_huff_passes{0}, g_stock_huff_route{0};
+extern "C" void sz3hip_debug_stock_huffman(int *passes, int *route) {
+    if (passes) *passes = g_stock_huff_passes.load(std::memory_order_relaxed);
+    if (route) *route = g_stock_huff_route.load(std::memory_order_relaxed);
+}
+// route: 0 device, 1 host by the switch, 2 host after the pass cap, 3 single symbol
+static int stock_huff_body(HostSlot *s, const StockHuffDev &h, const stock::Tree &tr, int32_t offset, const uint8_t *bits, uint64_t bit_bytes, uint64_t n, int &passes,
+                           int &route) {
     std::vector<uint16_t> em_host;
     const uint32_t nc = (uint32_t)tr.t.size();
     auto on_host = [&]() -> int {
@@ -1329,6 +1337,7 @@ static int stock_huff_run(HostSlot *s, const StockHuffDev &h, const stock::Tree 
         return 0;
     };
     if (tr.t[0]) {  // a single symbol: no bits at all (encoder/HuffmanEncoder.hpp:233-237)
+        route = 3;
         const int32_t v = tr.C[0] + offset;
         if (v < 0 || v > 65535) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (symbol)");
         em_host.assign((size_t)n, (uint16_t)v);
@@ -1336,7 +1345,10 @@ static int stock_huff_run(HostSlot *s, const StockHuffDev &h, const stock::Tree 
         HIPCHK(hipStreamSynchronize(s->stream));
         return 0;
     }
-    if (stock_host_huffman()) return on_host();
+    if (stock_host_huffman()) {
+        route = 1;
+        return on_host();
+    }
     std::vector<uint32_t> lut;
     stock::make_lut(tr, lut);
     HIPCHK(hipMemsetAsync(h.d_bits + (bit_bytes & ~(uint64_t)3), 0, 16, s->stream));  // (the last word's tail reads as zeros)
@@ -1347,12 +1359,21 @@ static int stock_huff_run(HostSlot *s, const StockHuffDev &h, const stock::Tree 
     HIPCHK(hipMemcpyAsync(h.d_t, tr.t.data(), nc, hipMemcpyHostToDevice, s->stream));
     HIPCHK(hipMemcpyAsync(h.d_lut, lut.data(), 4096 * 4, hipMemcpyHostToDevice, s->stream));
     szk_stock_tree_dev td{h.d_L, h.d_R, h.d_C, h.d_t, h.d_lut, nc, offset};
-    int passes = 0;
     const int rd = szk_launch_stock_huff_decode(&td, (const uint32_t *)h.d_bits, bit_bytes, n, h.d_start, h.d_last, h.d_next, h.d_base, h.d_count, h.d_flags, h.d_em, &passes, s->stream);
-    if (rd == -4) return on_host();  // the restart points did not settle within the pass cap: the bit-serial walk on the host
+    if (rd == -4) {  // the restart points did not settle within the pass cap: the bit-serial walk on the host
+        route = 2;
+        return on_host();
+    }
     if (rd == -3) return fail(SZ3HIP_EFORMAT, "corrupt stock stream (bit stream)");
     if (rd) return fail(SZ3HIP_EHIP, "stock stream: device Huffman decoder failed (%d)", rd);
     return 0;
+}
+static int stock_huff_run(HostSlot *s, const StockHuffDev &h, const stock::Tree &tr, int32_t offset, const uint8_t *bits, uint64_t bit_bytes, uint64_t n) {
+    int passes = 0, route = 0;
+    const int rc = stock_huff_body(s, h, tr, offset, bits, bit_bytes, n, passes, route);
+    g_stock_huff_passes.store(passes, std::memory_order_relaxed);
+    g_stock_huff_route.store(route, std::memory_order_relaxed);
+    return rc;
 }
 // A stock ALGO_NOPRED stream (SZDispatcher.hpp:92-93 -> api/impl/SZAlgoNopred.hpp:26-34): quantizer, tree, codes — value = recover(0, code)
 int stock_decompress_nopred(HostSlot *s, const sz3hip_config *conf, int dataType, const unsigned char *p, size_t payload, DecodeOut &out) {
