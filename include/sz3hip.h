@@ -608,6 +608,58 @@ int sz3hip_stream_select(sz3hip_stream *h, const sz3hip_select_req *reqs, uint32
                          void *stream);
 int sz3hip_select_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_select_opts *opts,
                          uint64_t *d_index, void *d_value, uint64_t capacity, sz3hip_select_head *d_head, void *stream);
+/* ---- texels out of a request: boxes mapped to u8 / u16 / f16 / f32 / RGBA8 ----
+ * What a renderer uploads from a frame is not raw f32 / f64 values but texels: 8- or 16-bit codes of a value window, half floats, or RGBA8
+ * out of a transfer function. sz3hip_stream_map takes sz3hip_stream_request's own requests (the same struct, rules, codes and wording, "box
+ * <i>: " in front; repeated and overlapping boxes are allowed; everything is checked before anything is launched or written) and runs the
+ * same launch sequence with ONE mapping launch in the strided gather's place: stats.launches_last_request is the same boxes'
+ * sz3hip_stream_request's (a handle that keeps the full array: 1). It counts as a request in sz3hip_stream_stats.
+ * The views: d_out and strides describe a view of OUTPUT elements (1, 2, 2, 4 or 4 bytes); d_out must be aligned to the output element; the
+ * output-overlap rule is the request's, evaluated with the output element's size.
+ * What is mapped: exactly the values sz3hip_stream_request would deliver for the box, each as x = (double)v.
+ *   U8, U16, LUT32: with M = 255, 65535 or lut_n - 1 and scale = (double)(M + 1) / (hi - lo), computed once on the host, a NaN point becomes
+ *     nan_code, any other code = x < lo ? 0 : x >= hi ? M : min((uint64_t)((x - lo) * scale), M), in IEEE double without a fused multiply-add:
+ *     sz3hip_stream_reduce's histogram rule with nbins = M + 1 and the two outer slots folded into the end codes — a texel's code is the bin
+ *     the reduce counts the point in. +-Inf are ordinary values (-Inf -> 0, +Inf -> M); -0.0 equals +0.0. U8 and U16 store the code, LUT32
+ *     stores d_lut[code] (a NaN point: nan_code itself, the raw texel).
+ *   F16: (half)(float)x, both conversions rounding to nearest even — the two-step rounding is the definition; overflow gives +-Inf, half
+ *     denormals are kept, a NaN stays a NaN (payload and sign unspecified).
+ *   F32: (float)x; for a float handle the request's bytes, NaN payloads included.
+ * The result at a point depends on that point's value and the options alone: sz3hip_stream_map is byte-identical to sz3hip_map_device over
+ * the same values, on every route. No byte outside the boxes' views is written or read. No device-to-host copy, no host synchronisation
+ * beyond a request's own waits; the ordering between requests is the existing one.
+ * Errors (SZ3HIP_EINVAL): opts NULL; out_type not one of the five; flags or reserved not 0; for U8 / U16 / LUT32 lo or hi not finite, hi <=
+ * lo or hi - lo not finite; nan_code above 255 (U8) or 65535 (U16); lut_n outside 2 .. SZ3HIP_MAX_LUT, d_lut NULL or not 4-byte aligned
+ * (LUT32); lut_n or d_lut set for U8 / U16; lo, hi, nan_code, lut_n or d_lut not 0 / NULL for F16 / F32; an output not aligned to its
+ * element; and sz3hip_stream_request's for the boxes and views. Integer types: SZ3HIP_EUNSUPPORTED.
+ * sz3hip_map_device: the same mapping of ONE plain view in device memory into one output view (what a handle that keeps the full array
+ * runs, in one launch). N, dims, strides_in and d_in's rules are sz3hip_reduce_device's; strides_out are the request's view rules (NULL or
+ * all 0: contiguous). Asynchronous on `stream`; no workspace.
+ * sz3hip_map_plan_for: a pure function (no device) with sz3hip_stream_map's checks. points, n_levels, the two level fields and
+ * scratch_elems are sz3hip_request_plan_for's; out_elem_bytes is the output element's size. */
+#define SZ3HIP_MAP_U8    1   /* 1 byte:  code of the window, M = 255   */
+#define SZ3HIP_MAP_U16   2   /* 2 bytes: code of the window, M = 65535 */
+#define SZ3HIP_MAP_F16   3   /* 2 bytes: IEEE half, (half)(float)x, round to nearest even both times */
+#define SZ3HIP_MAP_F32   4   /* 4 bytes: (float)x — an f64 handle's values narrowed; an f32 handle's unchanged */
+#define SZ3HIP_MAP_LUT32 5   /* 4 bytes: d_lut[code], M = lut_n - 1 — RGBA8 out of a transfer function */
+#define SZ3HIP_MAX_LUT 1024
+typedef struct sz3hip_map_opts {      /* 48 bytes */
+    double lo, hi;                    /* the window (U8, U16, LUT32); 0, 0 otherwise */
+    uint32_t out_type, flags;         /* SZ3HIP_MAP_*; flags 0 */
+    uint32_t nan_code, lut_n;         /* what a NaN point becomes (U8: <= 255, U16: <= 65535, LUT32: the raw 32-bit texel); 2 .. SZ3HIP_MAX_LUT for LUT32, else 0 */
+    const void *d_lut;                /* device, lut_n 32-bit entries, 4-byte aligned; NULL unless LUT32 */
+    uint64_t reserved;                /* 0 */
+} sz3hip_map_opts;
+typedef struct sz3hip_map_plan {      /* 40 bytes */
+    uint32_t n;
+    int32_t finest_level, coarsest_level, n_levels;
+    uint64_t points, scratch_elems, out_elem_bytes;
+} sz3hip_map_plan;
+int sz3hip_map_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_map_opts *opts,
+                        sz3hip_map_plan *out);
+int sz3hip_stream_map(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_map_opts *opts, void *stream);
+int sz3hip_map_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_map_opts *opts,
+                      void *d_out, const int64_t *strides_out, void *stream);
 /* development switch, process-wide: a request of a handle runs its coarsest c levels in ONE launch (one workgroup per box walks first point,
  * regrids and passes with a barrier between steps), c the largest count such that for every box every pass of those levels has at most
  * `points` points. 0: off — the request issues exactly the launches sz3hip_decompress_device_tiles issues. Environment twin, read once when

@@ -95,7 +95,8 @@ enum sz3hip_dbg {
 /* The second word, sz3hip_debug_flags2(): one bit, one meaning. 0 in production. */
 enum sz3hip_dbg2 {
     SZ3HIP_DBG2_PACK_SCAN_LAUNCH = 1,      /* szk_launch_encode: the offset scan of the sampled stage 2 in a launch of its own (k_scan_groups) where k_pack_b would scan the groups' sums itself */
-    SZ3HIP_DBG2_REQUEST_BY_LEVEL = 2       /* run_region_request: a request of several levels runs level group by level group over the one-level sequence (the route of a request whose boxes do not align by array level), not as one merged sequence */
+    SZ3HIP_DBG2_REQUEST_BY_LEVEL = 2,      /* run_region_request: a request of several levels runs level group by level group over the one-level sequence (the route of a request whose boxes do not align by array level), not as one merged sequence */
+    SZ3HIP_DBG2_MAP_PLAIN_STORES = 4       /* szk_launch_region_map: one-byte and two-byte texels by a thread per point (k_region_map), not by the form in which a lane maps four / two consecutive x points and issues one 32-bit store (k_region_map_packed) */
 };
 
 #endif

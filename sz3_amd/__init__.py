@@ -85,6 +85,7 @@ class Dbg2(enum.IntFlag):
     SZ3HIP_DBG2_ prefix, same values. One bit, one meaning."""
     PACK_SCAN_LAUNCH = 1
     REQUEST_BY_LEVEL = 2
+    MAP_PLAIN_STORES = 4
 
 
 class SZ3HipError(RuntimeError):
@@ -194,6 +195,18 @@ class _CSelectPlan(C.Structure):
     # sz3hip_select_plan
     _fields_ = [("n", C.c_uint32), ("finest_level", C.c_int32), ("coarsest_level", C.c_int32), ("n_levels", C.c_int32), ("points", C.c_uint64),
                 ("scratch_elems", C.c_uint64), ("partials", C.c_uint64)]
+
+
+class _CMapOpts(C.Structure):
+    # sz3hip_map_opts: 48 bytes
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("out_type", C.c_uint32), ("flags", C.c_uint32), ("nan_code", C.c_uint32), ("lut_n", C.c_uint32),
+                ("d_lut", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+class _CMapPlan(C.Structure):
+    # sz3hip_map_plan
+    _fields_ = [("n", C.c_uint32), ("finest_level", C.c_int32), ("coarsest_level", C.c_int32), ("n_levels", C.c_int32), ("points", C.c_uint64),
+                ("scratch_elems", C.c_uint64), ("out_elem_bytes", C.c_uint64)]
 
 
 class _CStreamStats(C.Structure):
@@ -367,6 +380,12 @@ def lib():
     L.sz3hip_select_device.restype = C.c_int
     L.sz3hip_select_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CSelectOpts), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                        C.c_void_p]
+    L.sz3hip_map_plan_for.restype = C.c_int
+    L.sz3hip_map_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CMapOpts), P(_CMapPlan)]
+    L.sz3hip_stream_map.restype = C.c_int
+    L.sz3hip_stream_map.argtypes = [C.c_void_p, P(_CTileReq), C.c_uint32, P(_CMapOpts), C.c_void_p]
+    L.sz3hip_map_device.restype = C.c_int
+    L.sz3hip_map_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CMapOpts), C.c_void_p, P(C.c_int64), C.c_void_p]
     L.sz3hip_request_plan_for.restype = C.c_int
     L.sz3hip_request_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CRequestPlan)]
     L.sz3hip_stream_close.restype = None
@@ -1117,6 +1136,122 @@ def select_points(tensor, lo, hi, capacity, invert=False, nan=False, values=True
     return res
 
 
+MAP_U8, MAP_U16, MAP_F16, MAP_F32, MAP_LUT32 = 1, 2, 3, 4, 5  # SZ3HIP_MAP_*
+MAX_LUT = 1024  # SZ3HIP_MAX_LUT
+# out_type name -> (SZ3HIP_MAP_*, the out tensor's dtype name). torch's uint16 has too few operations to be a working storage type (no
+# fill, no indexing, no comparison on every build this package meets): U16 texels live in int16 tensors, the same two bytes; LUT32's
+# RGBA8 texels in int32 tensors.
+_MAP_TYPES = {"u8": (MAP_U8, "uint8"), "u16": (MAP_U16, "int16"), "f16": (MAP_F16, "float16"), "f32": (MAP_F32, "float32"), "lut32": (MAP_LUT32, "int32")}
+
+
+def _map_type(out_type):
+    if isinstance(out_type, str) and out_type.lower() in _MAP_TYPES:
+        return _MAP_TYPES[out_type.lower()]
+    for code, name in _MAP_TYPES.values():
+        if not isinstance(out_type, str) and int(out_type) == code:
+            return code, name
+    raise ValueError("out_type is one of 'u8', 'u16', 'f16', 'f32', 'lut32' (got %r)" % (out_type,))
+
+
+def _map_opts(code, lo, hi, nan_code, lut):
+    """the options struct; `lut`: an int32 torch tensor on a HIP device holding the table's 32-bit entries (kept alive by the caller for the call)"""
+    o = _CMapOpts()
+    o.lo = float(lo)
+    o.hi = float(hi)
+    o.out_type = code
+    o.nan_code = int(nan_code) & 0xFFFFFFFF
+    if lut is not None:
+        if not _gpu_tensor(lut) or str(lut.dtype) != "torch.int32" or lut.dim() != 1 or not lut.is_contiguous():
+            raise ValueError("lut must be a contiguous 1-D int32 tensor on a HIP device")
+        o.lut_n = int(lut.numel())
+        o.d_lut = lut.data_ptr()
+    return o
+
+
+def _map_reqs(N, items, shapes, arr, name, device, alloc):
+    """the request structs over out tensors of dtype `name` (uint8 / int16 / float16 / float32 / int32); alloc: missing outputs are allocated
+    (else given placeholders that overlap no other, for the plan)"""
+    import sys
+    torch = sys.modules.get("torch")
+    itemsize = np.dtype(name).itemsize
+    reqs = (_CTileReq * max(len(items), 1))()
+    outs = []
+    at = 1 << 40
+    for i, (it, shape) in enumerate(zip(items, shapes)):
+        t = it[3] if len(it) == 4 else None
+        if t is None and alloc:
+            t = torch.empty(shape, dtype=getattr(torch, name), device=device)
+        reqs[i].level = int(it[0])
+        reqs[i].box = arr[i]
+        if t is not None:
+            if str(t.dtype) != "torch." + name or tuple(t.shape) != shape or (alloc and (not _gpu_tensor(t) or t.device != device)):
+                raise ValueError("item %d: out must be a %s tensor of the box's shape %s%s" % (i, name, shape, " on %s" % device if alloc else ""))
+            reqs[i].d_out = t.data_ptr()
+            reqs[i].strides[:N] = [int(v) for v in t.stride()]
+        else:
+            reqs[i].d_out = at
+            at += (int(np.prod(shape, dtype=np.uint64)) * itemsize + 255) & ~255
+        outs.append(t)
+    return reqs, outs
+
+
+def map_plan(conf, dtype, items, out_type, lo=0.0, hi=0.0, nan_code=0, lut=None):
+    """what one Stream.map for `items` touches (sz3hip_map_plan_for), without a device: `items` are Stream.map's — (level, lo, shape) or
+    (level, lo, shape, out) — and the map call's own checks run, views and overlaps in OUTPUT elements included. `lut`: an int32 tensor, or
+    for the plan an int (the entry count; the table's address is then a placeholder). Returns a dict with request_plan's fields and
+    out_elem_bytes."""
+    items = [tuple(it) for it in items]
+    if any(len(it) not in (3, 4) for it in items):
+        raise ValueError("an item is (level, lo, shape) or (level, lo, shape, out)")
+    code, name = _map_type(out_type)
+    arr, shapes = _boxes(conf.N, [(it[1], it[2]) for it in items])
+    reqs, _ = _map_reqs(conf.N, items, shapes, arr, name, None, False)
+    if isinstance(lut, int):
+        opts = _map_opts(code, lo, hi, nan_code, None)
+        opts.lut_n = lut
+        opts.d_lut = 1 << 39
+    else:
+        opts = _map_opts(code, lo, hi, nan_code, lut)
+    plan = _CMapPlan()
+    _check(lib().sz3hip_map_plan_for(C.byref(conf._c), _dtype_id(_np_dtype(dtype)), reqs, len(items), C.byref(opts), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k, _ in _CMapPlan._fields_}
+
+
+def map_points(tensor, out_type, lo=0.0, hi=0.0, nan_code=0, lut=None, out=None, stream=None):
+    """texels of one float32 / float64 torch tensor on a HIP device (sz3hip_map_device): the mapping Stream.map runs per box, over a plain
+    view — any strides that are not negative, at most 4 dimensions above size 1. out_type: "u8" / "u16" (codes of the window [lo, hi), a
+    NaN point becomes nan_code), "f16", "f32", or "lut32" (lut[code], `lut` an int32 tensor of 2 .. 1024 entries on the device; a NaN
+    point becomes nan_code itself). `out`: a tensor of the input's shape and of dtype uint8 / int16 (u16's two bytes: torch's uint16 is
+    not a working storage type) / float16 / float32 / int32, any view whose strides nest in row-major order (default: allocated,
+    contiguous). Asynchronous on `stream`; returns `out`."""
+    if not _is_tensor(tensor):
+        raise TypeError("map_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
+    if not _gpu_tensor(tensor):
+        raise ValueError("map_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
+    tname = str(tensor.dtype).replace("torch.", "")
+    if tname not in _SZ_TYPES:
+        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
+    if tensor.numel() == 0:
+        raise ValueError("map_points: the tensor is empty")
+    import torch
+    code, name = _map_type(out_type)
+    if out is None:
+        out = torch.empty(tuple(tensor.shape), dtype=getattr(torch, name), device=tensor.device)
+    if not _gpu_tensor(out) or str(out.dtype) != "torch." + name or tuple(out.shape) != tuple(tensor.shape) or out.device != tensor.device:
+        raise ValueError("map_points: out must be a %s tensor of the input's shape %s on %s" % (name, tuple(tensor.shape), tensor.device))
+    keep = [i for i, d in enumerate(tensor.shape) if int(d) != 1]
+    if len(keep) > 4:
+        raise ValueError("map_points: %d dimensions above size 1 (at most 4 are supported)" % len(keep))
+    dims = [int(tensor.shape[i]) for i in keep] or [1]
+    sin = [int(tensor.stride(i)) for i in keep] or [1]
+    sout = [int(out.stride(i)) for i in keep] or [1]
+    N = len(dims)
+    opts = _map_opts(code, lo, hi, nan_code, lut)
+    _check(lib().sz3hip_map_device(_SZ_TYPES[tname], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*sin), C.byref(opts), out.data_ptr(),
+                                   (C.c_int64 * N)(*sout), _stream_handle(tensor.device, stream)))
+    return out
+
+
 def set_chain_points(points):
     """development switch (sz3hip_debug_chain_points): a Stream request runs its coarsest levels — those whose every pass has at most
     `points` points for every box — in one launch; 0 switches the chain off"""
@@ -1237,6 +1372,25 @@ class Stream:
         opts = _select_opts(lo, hi, invert, nan)
         _check(lib().sz3hip_stream_select(self._h, reqs, n, C.byref(opts), res.heads.data_ptr(), _stream_handle(self.device, stream)))
         return res
+
+    def map(self, items, out_type, lo=0.0, hi=0.0, nan_code=0, lut=None, stream=None):
+        """texels out of boxes (sz3hip_stream_map): `items` are request's — (level, lo, shape) or (level, lo, shape,
+        out) — with `out` a view of OUTPUT elements: dtype uint8 ("u8"), int16 ("u16": the code's two bytes, torch's uint16 is not a
+        working storage type), float16 ("f16"), float32 ("f32") or int32 ("lut32": RGBA8 out of `lut`, an int32 tensor of 2 .. 1024
+        entries on the device). Codes are those of the window [lo, hi) — the bin Stream.reduce would count the point in, the outer slots
+        folded into the end codes; a NaN point becomes nan_code. The request's launch sequence with one mapping launch in the gather's
+        place. Missing outputs are allocated. Asynchronous on `stream`, as tiles. Returns the list of tensors."""
+        items = [tuple(it) for it in items]
+        if any(len(it) not in (3, 4) for it in items):
+            raise ValueError("an item is (level, lo, shape) or (level, lo, shape, out)")
+        items = [it if len(it) == 3 or it[3] is not None else it[:3] for it in items]
+        code, name = _map_type(out_type)
+        N = self.conf.N
+        arr, shapes = _boxes(N, [(it[1], it[2]) for it in items])
+        reqs, outs = _map_reqs(N, items, shapes, arr, name, self.device, True)
+        opts = _map_opts(code, lo, hi, nan_code, lut)
+        _check(lib().sz3hip_stream_map(self._h, reqs, len(items), C.byref(opts), _stream_handle(self.device, stream)))
+        return outs
 
     def tile(self, level, lo, shape, out=None, stream=None):
         """one box of the grid of every 2**level-th point (tiles with one box)"""

@@ -474,13 +474,32 @@ struct szk_reduce_hist {  // nbins 0: no histogram
 // 64-bit word per chunk, the room of the sum of the boxes' szk_reduce_chunks (hit counts, then exclusive offsets in place); sel_heads: n
 // sz3hip_select_head; sel_outs: HOST, SZK_SELECT_OUT_WORDS words per box in the request's order (d_index, d_value, capacity) — the
 // launchers put them into the table behind the boxes' records, where the scan and the write read box i's at words 3 i ..
+// kind SZK_SINK_MAP (kernels: sz3hip_map.hip): the boxes' values mapped to texels, ONE launch in the gather's place on
+// every route. Unlike the other two sinks it reads the records' real `dst` and `dstr` (in OUTPUT elements). map: the options with scale and M
+// worked out on the host; map_threads: the lanes the largest box needs in the form the launcher takes (szk_map_threads over the boxes' extents)
 #define SZK_SINK_REDUCE 0
 #define SZK_SINK_SELECT 1
+#define SZK_SINK_MAP 2
 #define SZK_SELECT_OUT_WORDS 3
 struct szk_select_opts {
     double lo, hi;
     uint32_t flags, pad;  // SZ3HIP_SELECT_*
 };
+struct szk_map_opts {
+    double lo, hi, scale;             // scale = (double)(M + 1) / (hi - lo)
+    uint32_t out_type, M;             // SZ3HIP_MAP_*; the last code
+    uint32_t nan_code, lut_n;
+    const uint32_t *d_lut;            // device, lut_n entries (LUT32)
+};
+// a texel's bytes (SZ3HIP_MAP_U8: 1; _U16, _F16: 2; _F32, _LUT32: 4)
+__host__ __device__ static inline uint32_t szk_map_out_bytes(uint32_t out_type) { return out_type == 1 ? 1u : out_type == 2 || out_type == 3 ? 2u : 4u; }
+// the packed form (one- and two-byte texels): a row of ext_x texels is cut at the destination's 4-byte boundaries; a row has at most this
+// many pieces, whatever its head's alignment, and a lane takes one piece
+__host__ __device__ static inline uint64_t szk_map_row_units(uint64_t ext_x, uint32_t out_bytes) { return (ext_x * out_bytes + 3) / 4 + 1; }
+// the lanes a box of `total` points and x extent ext_x needs: packed (the view's x stride is 1 or not read) rows * units, else a lane per point
+__host__ __device__ static inline uint64_t szk_map_threads(uint64_t total, uint64_t ext_x, int64_t dstr_x, uint32_t out_bytes, bool packed) {
+    return packed && out_bytes < 4 && (dstr_x == 1 || ext_x == 1) ? total / ext_x * szk_map_row_units(ext_x, out_bytes) : total;
+}
 struct szk_region_sink {
     szk_reduce_part *partials;
     void *d_stats;
@@ -491,7 +510,13 @@ struct szk_region_sink {
     void *sel_heads;
     const uint64_t *sel_outs;
     szk_select_opts sel;
+    szk_map_opts map;
+    uint64_t map_threads;
+    bool map_packed;
 };
+// the mapping's one launch over n records in device memory (one box: by value)
+int szk_launch_region_map(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
+                          uint32_t n, const szk_region_sink *sink, hipStream_t s);
 // the selection's launches over n records in device memory, the boxes' outputs behind them (one box: by value, with sink->sel_outs' three
 // words as arguments): the count; then scan and write (two launches)
 int szk_launch_region_select_count(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
@@ -506,7 +531,8 @@ int szk_launch_region_reduce_final(int dtype, const void *d_src, const struct sz
 uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n);
 // sink non-null: the request reduces (outs[i].dst: box i's SZK_REDUCE_DST word, cast; the strides are not read) — reduce and final stand
 // in the strided gather's place, *launches is the request's count plus one; a selecting sink (kind SZK_SINK_SELECT): count, scan and write,
-// the request's count plus two, table_words with room for n * SZK_SELECT_OUT_WORDS more
+// the request's count plus two, table_words with room for n * SZK_SELECT_OUT_WORDS more; a mapping sink (kind SZK_SINK_MAP): outs are the
+// real views in output elements, one launch, the request's count
 int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                                 const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                                 void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,

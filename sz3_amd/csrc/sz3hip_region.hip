@@ -816,6 +816,11 @@ template <typename T>
 static int region_sink_launch(uint32_t *issued, const T *src, const szk_region_gather_strided_box *d_recs, uint32_t n, uint64_t most, const szk_region_sink *sink,
                               bool with_final, hipStream_t s) {
     const int dtype = sizeof(T) == 4 ? 0 : 1;
+    if (sink->kind == SZK_SINK_MAP) {  // (one launch, per group where the request runs group by group; no final)
+        if (szk_launch_region_map(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
+        region_count(issued);
+        return 0;
+    }
     if (sink->kind == SZK_SINK_SELECT) {  // (the count, then — once per request — scan and write)
         if (szk_launch_region_select_count(dtype, src, d_recs, nullptr, n, most, sink, s)) return -2;
         region_count(issued);
@@ -1343,7 +1348,7 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
         total += issued;
         most_levels = std::max(most_levels, (uint32_t)gg[0].n_levels);
     }
-    if (sink) {  // ONE final for the request: the boxes' records once more, in the request's order, behind the groups' stretches
+    if (sink && sink->kind != SZK_SINK_MAP) {  // ONE final for the request: the boxes' records once more, in the request's order, behind the groups' stretches
         uint64_t need = (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box), most = 0;
         if (need > table_words || used > table_words - need) return -1;
         for (uint32_t i = 0; i < n; i++) {
@@ -1377,7 +1382,10 @@ int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_para
     if (chain_levels) *chain_levels = 0;
     if (launches) *launches = 0;
     if (levels) *levels = 0;
-    if (sink && sink->kind == SZK_SINK_SELECT) {
+    if (sink && sink->kind == SZK_SINK_MAP) {  // (the views are real: every box's destination)
+        for (uint32_t i = 0; outs && i < n; i++)
+            if (!outs[i].dst) return -1;
+    } else if (sink && sink->kind == SZK_SINK_SELECT) {
         if (!sink->sel_counts || !sink->sel_heads || !sink->sel_outs) return -1;
     } else if (sink && (!sink->partials || !sink->d_stats || (sink->hist.nbins && !sink->d_hist))) return -1;
     if (n < 1 || n > 65535 || !gs || !outs || !h_table || !d_table) return -1;

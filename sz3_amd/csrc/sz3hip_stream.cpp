@@ -15,6 +15,8 @@
 // sz3hip_stream_select takes the boxes with an index and a value array each and leaves where their values lie in a
 // range: the same geometry and sequence with a count, a scan and the write (sz3hip_select.hip) in the gather's place; sz3hip_select_device is
 // that selection over one plain view.
+// sz3hip_stream_map takes the request's own boxes and views, the views in OUTPUT elements, and leaves texels: the same
+// geometry and sequence with one mapping launch (sz3hip_map.hip) in the gather's place; sz3hip_map_device is that mapping over one plain view.
 // A handle serves one request at a time; it is not thread-safe.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -964,6 +966,184 @@ extern "C" int sz3hip_select_device(int dataType, int N, const uint64_t *dims, c
     w->pending = true;
     w->last = s;
     if (lr) return fail(SZ3HIP_EHIP, "the selection could not be launched (%d)", lr);
+    return 0;
+}
+
+// ---- texels out of a request: boxes mapped to u8 / u16 / f16 / f32 / RGBA8 --------------------------------------------------
+namespace {
+int map_opts_check(const sz3hip_map_opts *opts, szk_map_opts *mo) {
+    memset(mo, 0, sizeof(*mo));
+    if (!opts) return fail(SZ3HIP_EINVAL, "NULL argument (opts): a mapping needs its output type");
+    if (opts->out_type < SZ3HIP_MAP_U8 || opts->out_type > SZ3HIP_MAP_LUT32)
+        return fail(SZ3HIP_EINVAL, "the options' out_type (%u) is not one of SZ3HIP_MAP_U8 .. SZ3HIP_MAP_LUT32 (1 .. 5)", opts->out_type);
+    if (opts->flags) return fail(SZ3HIP_EINVAL, "the options' flags are 0x%x, not 0", opts->flags);
+    if (opts->reserved) return fail(SZ3HIP_EINVAL, "the options' reserved word is %llu, not 0", (unsigned long long)opts->reserved);
+    const uint32_t t = opts->out_type;
+    if (t == SZ3HIP_MAP_F16 || t == SZ3HIP_MAP_F32) {
+        if (opts->lo != 0.0 || opts->hi != 0.0 || opts->nan_code || opts->lut_n || opts->d_lut)  // (a NaN is not 0 either)
+            return fail(SZ3HIP_EINVAL, "the options hold a window, a nan_code or a table: SZ3HIP_MAP_F16 / SZ3HIP_MAP_F32 take none (lo, hi, nan_code, lut_n 0 and d_lut NULL)");
+        mo->out_type = t;
+        return 0;
+    }
+    if (!(fabs(opts->lo) < INFINITY) || !(fabs(opts->hi) < INFINITY)) return fail(SZ3HIP_EINVAL, "the window [%g, %g) is not finite", opts->lo, opts->hi);
+    if (!(opts->hi > opts->lo)) return fail(SZ3HIP_EINVAL, "the window [%g, %g) is empty: hi must be above lo", opts->lo, opts->hi);
+    if (!(fabs(opts->hi - opts->lo) < INFINITY)) return fail(SZ3HIP_EINVAL, "the window [%g, %g) is too wide: hi - lo is not finite", opts->lo, opts->hi);
+    uint32_t M;
+    if (t == SZ3HIP_MAP_LUT32) {
+        if (opts->lut_n < 2 || opts->lut_n > SZ3HIP_MAX_LUT) return fail(SZ3HIP_EINVAL, "the table has %u entries: 2 .. %d are supported", opts->lut_n, SZ3HIP_MAX_LUT);
+        if (!opts->d_lut) return fail(SZ3HIP_EINVAL, "the table (d_lut) is NULL");
+        if ((uintptr_t)opts->d_lut % 4) return fail(SZ3HIP_EINVAL, "the table (d_lut) is not aligned to its 4-byte entries");
+        M = opts->lut_n - 1;
+    } else {
+        if (opts->lut_n || opts->d_lut) return fail(SZ3HIP_EINVAL, "the options hold a table: only SZ3HIP_MAP_LUT32 takes one (lut_n 0 and d_lut NULL)");
+        M = t == SZ3HIP_MAP_U8 ? 255u : 65535u;
+        if (opts->nan_code > M) return fail(SZ3HIP_EINVAL, "nan_code (%u) is beyond the output's range (0 .. %u)", opts->nan_code, M);
+    }
+    mo->lo = opts->lo;
+    mo->hi = opts->hi;
+    mo->scale = (double)(M + 1) / (opts->hi - opts->lo);
+    mo->out_type = t;
+    mo->M = M;
+    mo->nan_code = opts->nan_code;
+    mo->lut_n = opts->lut_n;
+    mo->d_lut = static_cast<const uint32_t *>(opts->d_lut);
+    return 0;
+}
+// every output aligned to the output element; the views and their overlaps by the request's rule with that element's size
+int map_views(int N, const sz3hip_tile_req *reqs, uint32_t n, size_t osz, std::vector<ReqView> &vs) {
+    for (uint32_t i = 0; i < n; i++)
+        if ((uintptr_t)reqs[i].d_out % osz) return fail(SZ3HIP_EINVAL, "box %u: the output is not aligned to its element size (%zu bytes)", i, osz);
+    return request_views(N, reqs, n, osz, vs);
+}
+// the sink of a mapping call: the form (packed unless the development switch asks for a thread per point) and the lanes of the largest box
+void map_sink(szk_region_sink *sink, int N, const sz3hip_tile_req *reqs, uint32_t n, const std::vector<ReqView> &vs) {
+    sink->kind = SZK_SINK_MAP;
+    sink->map_packed = !(szk_dbg_flags2 & SZ3HIP_DBG2_MAP_PLAIN_STORES);
+    const uint32_t ob = szk_map_out_bytes(sink->map.out_type);
+    sink->map_threads = 1;
+    for (uint32_t i = 0; i < n; i++) {
+        uint64_t total = 1;
+        for (int j = 0; j < N; j++) total *= reqs[i].box.ext[j];
+        sink->map_threads = std::max(sink->map_threads, szk_map_threads(total, reqs[i].box.ext[N - 1], vs[i].str[N - 1], ob, sink->map_packed));
+    }
+}
+}  // namespace
+
+extern "C" int sz3hip_map_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_map_opts *opts,
+                                   sz3hip_map_plan *out) {
+    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_map_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
+    int rc = dtype_check(dataType);
+    szk_map_opts mo;
+    if (rc || (rc = request_args("sz3hip_map_plan_for", reqs, n)) || (rc = map_opts_check(opts, &mo))) return rc;
+    std::vector<szk_region_geom> gs;
+    std::vector<ReqView> vs;
+    memset(out, 0, sizeof(*out));
+    const size_t osz = szk_map_out_bytes(mo.out_type);
+    if ((rc = szi_request_geometry_conf(conf, reqs, n, gs, &out->scratch_elems)) || (rc = map_views(conf->N, reqs, n, osz, vs))) return rc;
+    out->n = n;
+    out->finest_level = out->coarsest_level = reqs[0].level;
+    for (uint32_t i = 0; i < n; i++) {
+        out->finest_level = std::min(out->finest_level, reqs[i].level);
+        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
+        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
+        out->points += gs[i].points;
+    }
+    out->out_elem_bytes = osz;
+    return 0;
+}
+
+extern "C" int sz3hip_stream_map(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_map_opts *opts, void *stream) {
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_map: no handle");
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    int rc = request_args("sz3hip_stream_map", reqs, n);
+    if (rc || (rc = map_opts_check(opts, &sink.map))) return rc;
+    const size_t osz = szk_map_out_bytes(sink.map.out_type);
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    std::vector<ReqView> vs;
+    std::vector<szk_region_geom> gs;
+    uint64_t elems = 0, words = 0;
+    const int N = h->fast ? h->codes.ip.N : h->N;
+    if (!h->fast) {
+        if ((rc = full_boxes_check(h, reqs, n)) || (rc = map_views(N, reqs, n, osz, vs))) return rc;
+        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
+    } else {
+        const szk_interp_params &ip = h->codes.ip;
+        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
+        if ((rc = map_views(N, reqs, n, osz, vs))) return rc;
+        words = szk_region_request_table_words(gs.data(), n);
+    }
+    map_sink(&sink, N, reqs, n, vs);
+    HIPCHK(hipSetDevice(h->device));
+    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    const uint32_t chain_points = sz3hip_debug_get_chain_points();
+    uint32_t chain_levels = 0, launches = 0, levels = 0;
+    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
+    int lr;
+    if (!h->fast) {
+        std::vector<szk_region_gather_strided_box> full_recs(n);
+        for (uint32_t b = 0; b < n; b++) full_record(h, reqs[b], vs[b].str, &full_recs[b]);
+        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
+        launches = 1;
+    } else {
+        std::vector<szk_region_out> outs(n);
+        for (uint32_t i = 0; i < n; i++) {
+            outs[i].dst = reqs[i].d_out;
+            for (int j = 0; j < 4; j++) outs[i].str[j] = j < N ? vs[i].str[j] : 0;
+        }
+        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
+                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, outs.data(), h->h_table,
+                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
+    }
+    HIPCHK(hipEventRecord(h->ev_req, s));
+    h->req_pending = true;
+    h->last_stream = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's mapping could not be launched (%d)", lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+extern "C" int sz3hip_map_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_map_opts *opts,
+                                 void *d_out, const int64_t *strides_out, void *stream) {
+    int rc = dtype_check(dataType);
+    if (rc) return rc;
+    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++)
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+    if (!d_out) return fail(SZ3HIP_EINVAL, "sz3hip_map_device: NULL argument (d_out)");
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    if ((rc = map_opts_check(opts, &sink.map))) return rc;
+    uint64_t str[4] = {0, 0, 0, 0};
+    int dev = 0;
+    if ((rc = szi_dev_view_strides(N, dims, strides_in, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
+    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    sz3hip_tile_req q;  // the output as a request's view of the whole array
+    memset(&q, 0, sizeof(q));
+    for (int i = 0; i < N; i++) {
+        q.box.ext[i] = dims[i];
+        q.strides[i] = strides_out ? strides_out[i] : 0;
+    }
+    q.d_out = d_out;
+    std::vector<ReqView> vs;
+    if ((rc = map_views(N, &q, 1, szk_map_out_bytes(sink.map.out_type), vs))) return rc;
+    map_sink(&sink, N, &q, 1, vs);
+    szk_region_gather_strided_box rec;
+    szi_view_record(N, dims, str, 0, d_out, vs[0].str, &rec);
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    HIPCHK(hipSetDevice(dev));
+    if (szk_launch_region_map(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the mapping could not be launched");
     return 0;
 }
 
