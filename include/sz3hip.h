@@ -660,6 +660,69 @@ int sz3hip_map_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_ti
 int sz3hip_stream_map(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_map_opts *opts, void *stream);
 int sz3hip_map_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_map_opts *opts,
                       void *d_out, const int64_t *strides_out, void *stream);
+/* ---- boxes sampled at fractional positions: nearest and linear ----
+ * An oblique slice plane, a tile resampled to a screen's resolution, values at probe or particle positions: none of them lies on a box's
+ * own lattice. sz3hip_stream_sample takes 1 .. SZ3HIP_MAX_BOXES boxes that each name their own level, as sz3hip_stream_request does
+ * (geometry, codes and wording are that call's, "box <i>: " in front; repeated and overlapping boxes are allowed; everything is checked
+ * before anything is launched or written), each with queries of its own, and runs the same launch sequence with ONE sampling launch in the
+ * strided gather's place: stats.launches_last_request is the same boxes' sz3hip_stream_request's (a handle that keeps the full array: 1).
+ * It counts as a request in sz3hip_stream_stats. The values sampled are exactly those the request would deliver for the box.
+ * Coordinates: a coordinate is box-local, in the box's level grid: c_j == q is box point q along dimension j, 0 .. ext_j - 1. All N
+ *   dimensions are given, those of extent 1 too. Each coordinate is converted to double exactly.
+ *   Points form (d_coords non-NULL): n_points * N coordinates of coord_type, query-major, slowest dimension first.
+ *   Lattice form (d_coords NULL): query r = (i0 * counts[1] + i1) * counts[2] + i2 has
+ *     c_j = ((origin[j] + (double)i0 * steps[0][j]) + (double)i1 * steps[1][j]) + (double)i2 * steps[2][j],
+ *   evaluated in double, in that order, without a fused multiply-add.
+ * Which queries are answered: a query is inside when every 0 <= c_j && c_j <= ext_j - 1 (so -0.0 is inside). A query with a NaN
+ *   coordinate always yields (T)fill; an outside query yields (T)fill — unless SZ3HIP_SAMPLE_CLAMP is set: then each non-NaN coordinate is
+ *   first clamped into [0, ext_j - 1], +-Inf to the ends.
+ * NEAREST: i_j = min((uint64_t)floor(c_j + 0.5), ext_j - 1); the output is that point's raw bytes — no arithmetic, NaN payloads kept.
+ * LINEAR: per dimension i = floor(c) and f = c - i. f == 0: the dimension contributes the value at i alone and i + 1 has no influence —
+ *   a grid point reproduces the point's value exactly, next to an Inf or NaN neighbour too, and c = ext - 1 reads nothing outside the box.
+ *   Otherwise (1.0 - f) * a + f * b in double: two multiplies and an add. The fold runs the fastest dimension first, then each slower
+ *   one; the result is rounded once to T. NaN and Inf in a contributing corner propagate by IEEE rules.
+ * The output depends on the box's values, the query and the options alone — not on the route, the grid, the other boxes or the handle's
+ * kind: sz3hip_stream_sample is byte-identical to sz3hip_sample_device over the same values. No device-to-host copy, no host
+ * synchronisation beyond a request's own waits; the ordering between requests is the existing one.
+ * Errors (SZ3HIP_EINVAL): opts NULL; filter, coord_type or flags out of range; the options' reserved word not 0 (fill is not checked: any
+ * double); d_out NULL or not aligned to T; n_points 0 or above 2^31; points form: d_coords not aligned to its type, or any of counts /
+ * origin / steps not zero; lattice form: a count of 0, counts' product != n_points, or a non-finite origin / steps entry among the N
+ * used; two boxes' output ranges overlapping ("box i: the output overlaps box j's"); and sz3hip_stream_request's for the boxes.
+ * Integer types: SZ3HIP_EUNSUPPORTED. A refused call launches and writes nothing, and the handle serves the next request.
+ * sz3hip_sample_device: the same sampling of ONE plain view in device memory (what a handle that keeps the full array runs, in one
+ * launch): N, dims, strides and d_in's rules are sz3hip_reduce_device's; the view is the box, query->level, reserved and box must be
+ * zero. Asynchronous on `stream`; no workspace.
+ * sz3hip_sample_plan_for: a pure function (no device) with sz3hip_stream_sample's checks. Its fields are sz3hip_request_plan_for's, plus
+ * queries, the sum of n_points. */
+#define SZ3HIP_SAMPLE_NEAREST 0u
+#define SZ3HIP_SAMPLE_LINEAR  1u
+#define SZ3HIP_SAMPLE_CLAMP   1u      /* flags */
+typedef struct sz3hip_sample_req {    /* 248 bytes */
+    int32_t level;          /* 0 .. 30: the box lies on the grid of every 2^level-th point */
+    uint32_t reserved;      /* 0 */
+    sz3hip_box box;         /* in that grid's coordinates, slowest first, N entries used */
+    const void *d_coords;   /* device: n_points * N coordinates, query-major, slowest dimension first; NULL: the lattice form */
+    void *d_out;            /* device: n_points elements of the stream's type, contiguous */
+    uint64_t n_points;      /* 1 .. 2^31 */
+    uint64_t counts[3];     /* lattice form: queries along its three axes, slowest first, each >= 1, product == n_points */
+    double origin[4];       /* lattice form: N entries used */
+    double steps[3][4];     /* lattice form: axis a's step, N entries used */
+} sz3hip_sample_req;
+typedef struct sz3hip_sample_opts {   /* 24 bytes */
+    uint32_t filter, coord_type;      /* SZ3HIP_SAMPLE_NEAREST / _LINEAR; SZ3HIP_FLOAT / SZ3HIP_DOUBLE: d_coords' type */
+    uint32_t flags, reserved;         /* SZ3HIP_SAMPLE_CLAMP; 0 */
+    double fill;                      /* what an unanswered query yields, as (T)fill */
+} sz3hip_sample_opts;
+typedef struct sz3hip_sample_plan {   /* 40 bytes */
+    uint32_t n;
+    int32_t finest_level, coarsest_level, n_levels;
+    uint64_t points, scratch_elems, queries;
+} sz3hip_sample_plan;
+int sz3hip_sample_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_sample_req *reqs, uint32_t n, const sz3hip_sample_opts *opts,
+                           sz3hip_sample_plan *out);
+int sz3hip_stream_sample(sz3hip_stream *h, const sz3hip_sample_req *reqs, uint32_t n, const sz3hip_sample_opts *opts, void *stream);
+int sz3hip_sample_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_sample_opts *opts,
+                         const sz3hip_sample_req *query, void *stream);
 /* development switch, process-wide: a request of a handle runs its coarsest c levels in ONE launch (one workgroup per box walks first point,
  * regrids and passes with a barrier between steps), c the largest count such that for every box every pass of those levels has at most
  * `points` points. 0: off — the request issues exactly the launches sz3hip_decompress_device_tiles issues. Environment twin, read once when

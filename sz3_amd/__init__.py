@@ -209,6 +209,23 @@ class _CMapPlan(C.Structure):
                 ("scratch_elems", C.c_uint64), ("out_elem_bytes", C.c_uint64)]
 
 
+class _CSampleReq(C.Structure):
+    # sz3hip_sample_req: 248 bytes
+    _fields_ = [("level", C.c_int32), ("reserved", C.c_uint32), ("box", _CBox), ("d_coords", C.c_void_p), ("d_out", C.c_void_p), ("n_points", C.c_uint64),
+                ("counts", C.c_uint64 * 3), ("origin", C.c_double * 4), ("steps", (C.c_double * 4) * 3)]
+
+
+class _CSampleOpts(C.Structure):
+    # sz3hip_sample_opts: 24 bytes
+    _fields_ = [("filter", C.c_uint32), ("coord_type", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("fill", C.c_double)]
+
+
+class _CSamplePlan(C.Structure):
+    # sz3hip_sample_plan
+    _fields_ = [("n", C.c_uint32), ("finest_level", C.c_int32), ("coarsest_level", C.c_int32), ("n_levels", C.c_int32), ("points", C.c_uint64),
+                ("scratch_elems", C.c_uint64), ("queries", C.c_uint64)]
+
+
 class _CStreamStats(C.Structure):
     """struct sz3hip_stream_stats (include/sz3hip.h)"""
     _fields_ = [("fast", C.c_uint32), ("huffman_stages", C.c_uint32), ("launches_last_request", C.c_uint32), ("chain_levels_last_request", C.c_uint32),
@@ -386,6 +403,12 @@ def lib():
     L.sz3hip_stream_map.argtypes = [C.c_void_p, P(_CTileReq), C.c_uint32, P(_CMapOpts), C.c_void_p]
     L.sz3hip_map_device.restype = C.c_int
     L.sz3hip_map_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CMapOpts), C.c_void_p, P(C.c_int64), C.c_void_p]
+    L.sz3hip_sample_plan_for.restype = C.c_int
+    L.sz3hip_sample_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CSampleReq), C.c_uint32, P(_CSampleOpts), P(_CSamplePlan)]
+    L.sz3hip_stream_sample.restype = C.c_int
+    L.sz3hip_stream_sample.argtypes = [C.c_void_p, P(_CSampleReq), C.c_uint32, P(_CSampleOpts), C.c_void_p]
+    L.sz3hip_sample_device.restype = C.c_int
+    L.sz3hip_sample_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CSampleOpts), P(_CSampleReq), C.c_void_p]
     L.sz3hip_request_plan_for.restype = C.c_int
     L.sz3hip_request_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CRequestPlan)]
     L.sz3hip_stream_close.restype = None
@@ -1252,6 +1275,139 @@ def map_points(tensor, out_type, lo=0.0, hi=0.0, nan_code=0, lut=None, out=None,
     return out
 
 
+SAMPLE_NEAREST, SAMPLE_LINEAR = 0, 1  # SZ3HIP_SAMPLE_*
+SAMPLE_CLAMP = 1                      # SZ3HIP_SAMPLE_CLAMP
+_SAMPLE_MODES = {"nearest": SAMPLE_NEAREST, "linear": SAMPLE_LINEAR}
+
+
+def _sample_mode(mode):
+    if isinstance(mode, str) and mode.lower() in _SAMPLE_MODES:
+        return _SAMPLE_MODES[mode.lower()]
+    if not isinstance(mode, str) and int(mode) in _SAMPLE_MODES.values():
+        return int(mode)
+    raise ValueError("mode is 'nearest' or 'linear' (got %r)" % (mode,))
+
+
+def _sample_query(q, N, i, req):
+    """fills box i's query words of `req` from q — a (n, N) float32 / float64 tensor, a lattice (origin, steps, counts), or (the plan only)
+    an int: that many points at a placeholder address. Returns (the coordinates' dtype name or None, the output's shape)."""
+    if isinstance(q, (int, np.integer)) and not isinstance(q, bool):
+        req.d_coords = 1 << 38
+        req.n_points = int(q)
+        return None, (int(q),)
+    if _is_tensor(q):
+        name = str(q.dtype).replace("torch.", "")
+        if name not in ("float32", "float64") or q.dim() != 2 or int(q.shape[1]) != N or not q.is_contiguous():
+            raise ValueError("query %d: coordinates are a contiguous (n, %d) float32 / float64 tensor" % (i, N))
+        req.d_coords = q.data_ptr()
+        req.n_points = int(q.shape[0])
+        return name, (int(q.shape[0]),)
+    if not isinstance(q, (tuple, list)) or len(q) != 3:
+        raise ValueError("query %d: a query is a coordinate tensor or a lattice (origin, steps, counts)" % i)
+    origin, steps, counts = q
+    origin = [float(v) for v in origin]
+    steps = [[float(v) for v in st] for st in steps]
+    counts = [int(c) for c in counts]
+    if len(origin) != N or any(len(st) != N for st in steps):
+        raise ValueError("query %d: the lattice's origin and every step need one entry per extent of the array (%d)" % (i, N))
+    if not 1 <= len(counts) <= 3 or len(steps) != len(counts) or any(c < 0 for c in counts):
+        raise ValueError("query %d: a lattice has 1 .. 3 axes, a step and a count each" % i)
+    pad = 3 - len(counts)  # (the axes given are the fastest ones)
+    req.d_coords = None
+    req.origin[:N] = origin
+    total = 1
+    for a in range(3):
+        req.counts[a] = counts[a - pad] if a >= pad else 1
+        total *= int(req.counts[a])
+        if a >= pad:
+            req.steps[a][:N] = steps[a - pad]
+    req.n_points = total
+    return None, tuple(counts)
+
+
+def _sample_reqs(N, items, queries):
+    items = [tuple(it) for it in items]
+    if any(len(it) != 3 for it in items):
+        raise ValueError("an item is (level, lo, shape)")
+    queries = list(queries)
+    if len(queries) != len(items):
+        raise ValueError("queries holds one entry per item (%d)" % len(items))
+    arr, _ = _boxes(N, [(it[1], it[2]) for it in items])
+    reqs = (_CSampleReq * max(len(items), 1))()
+    names, shapes = set(), []
+    for i, (it, q) in enumerate(zip(items, queries)):
+        reqs[i].level = int(it[0])
+        reqs[i].box = arr[i]
+        name, shape = _sample_query(q, N, i, reqs[i])
+        shapes.append(shape)
+        if name:
+            names.add(name)
+    if len(names) > 1:
+        raise ValueError("the coordinate tensors of one call are all float32 or all float64")
+    return reqs, len(items), (names.pop() if names else "float64"), shapes
+
+
+def _sample_opts(mode, clamp, fill, coord_name):
+    o = _CSampleOpts()
+    o.filter = _sample_mode(mode)
+    o.coord_type = _SZ_TYPES[coord_name]
+    o.flags = SAMPLE_CLAMP if clamp else 0
+    o.fill = float(fill)
+    return o
+
+
+def sample_plan(conf, dtype, items, queries, mode="linear", clamp=False, fill=float("nan")):
+    """what one Stream.sample for `items` and `queries` touches (sz3hip_sample_plan_for), without a device: the sample call's own checks run
+    (the outputs are laid out one behind the other). A query is Stream.sample's, or an int: that many float64 points at a placeholder
+    address. Returns a dict with request_plan's fields and queries, the sum of the queries' points."""
+    reqs, n, cname, _ = _sample_reqs(conf.N, items, queries)
+    dt = _np_dtype(dtype)
+    at = 1 << 40
+    for i in range(n):  # (stand-in addresses: the plan checks the outputs' rules, not whether they are device memory)
+        reqs[i].d_out = at
+        at += (int(reqs[i].n_points) * 8 + 255) & ~255
+    opts = _sample_opts(mode, clamp, fill, cname)
+    plan = _CSamplePlan()
+    _check(lib().sz3hip_sample_plan_for(C.byref(conf._c), _dtype_id(dt), reqs, n, C.byref(opts), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k, _ in _CSamplePlan._fields_}
+
+
+def sample_points(tensor, query, mode="linear", clamp=False, fill=float("nan"), stream=None):
+    """one float32 / float64 torch tensor on a HIP device sampled at fractional positions (sz3hip_sample_device): the sampling Stream.sample
+    runs per box, over a plain view — 1 .. 4 dimensions, any strides that are not negative. `query`: a contiguous (n, tensor.dim()) float32 /
+    float64 tensor of coordinates on the device — every dimension has its coordinate, those of size 1 too — or a lattice (origin, steps,
+    counts). mode "nearest": the nearest point's bytes; "linear": the multilinear interpolation in double, rounded once. A query outside
+    [0, size - 1] yields `fill`, or is clamped (clamp=True); a NaN coordinate always yields `fill`. Asynchronous on `stream`; returns a
+    tensor of the input's dtype: (n,) for coordinates, of shape `counts` for a lattice."""
+    if not _is_tensor(tensor):
+        raise TypeError("sample_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
+    if not _gpu_tensor(tensor):
+        raise ValueError("sample_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
+    name = str(tensor.dtype).replace("torch.", "")
+    if name not in _SZ_TYPES:
+        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
+    if tensor.numel() == 0:
+        raise ValueError("sample_points: the tensor is empty")
+    N = tensor.dim()
+    if not 1 <= N <= 4:
+        raise ValueError("sample_points: %d dimensions (1 .. 4 are supported)" % N)
+    import torch
+    req = _CSampleReq()
+    cname, shape = _sample_query(query, N, 0, req)
+    if _is_tensor(query) and (not _gpu_tensor(query) or query.device != tensor.device):
+        raise ValueError("sample_points: the coordinates must be on %s" % tensor.device)
+    if isinstance(query, (int, np.integer)):
+        raise ValueError("sample_points: a query is a coordinate tensor or a lattice (origin, steps, counts)")
+    out = torch.empty(shape, dtype=tensor.dtype, device=tensor.device)
+    req.d_out = out.data_ptr()
+    opts = _sample_opts(mode, clamp, fill, cname or "float64")
+    dims = [int(d) for d in tensor.shape]
+    strides = [int(v) for v in tensor.stride()]
+    _check(lib().sz3hip_sample_device(_SZ_TYPES[name], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*strides), C.byref(opts), C.byref(req),
+                                      _stream_handle(tensor.device, stream)))
+    return out
+
+
 def set_chain_points(points):
     """development switch (sz3hip_debug_chain_points): a Stream request runs its coarsest levels — those whose every pass has at most
     `points` points for every box — in one launch; 0 switches the chain off"""
@@ -1390,6 +1546,28 @@ class Stream:
         reqs, outs = _map_reqs(N, items, shapes, arr, name, self.device, True)
         opts = _map_opts(code, lo, hi, nan_code, lut)
         _check(lib().sz3hip_stream_map(self._h, reqs, len(items), C.byref(opts), _stream_handle(self.device, stream)))
+        return outs
+
+    def sample(self, items, queries, mode="linear", clamp=False, fill=float("nan"), stream=None):
+        """boxes sampled at fractional positions (sz3hip_stream_sample): `items` are (level, lo, shape); queries[i]
+        belongs to item i and is a contiguous (n_i, N) float32 / float64 tensor of box-local coordinates on the device (slowest dimension
+        first; all tensors of a call of one dtype), or a lattice (origin, steps, counts): 1 .. 3 axes, slowest first, a step of N entries
+        and a count each. mode "nearest": the nearest point's bytes; "linear": the multilinear interpolation in double, rounded once. A
+        query outside the box yields `fill`, or is clamped into it (clamp=True); a NaN coordinate always yields `fill`. The request's
+        launch sequence with one sampling launch in the gather's place. Asynchronous on `stream`, as tiles. Returns the list of tensors of
+        the stream's dtype: (n_i,) for coordinates, of shape `counts` for a lattice."""
+        import torch
+        reqs, n, cname, shapes = _sample_reqs(self.conf.N, items, queries)
+        for i, q in enumerate(queries):
+            if isinstance(q, (int, np.integer)):
+                raise ValueError("query %d: a query is a coordinate tensor or a lattice (origin, steps, counts)" % i)
+            if _is_tensor(q) and (not _gpu_tensor(q) or q.device != self.device):
+                raise ValueError("query %d: the coordinates must be on %s" % (i, self.device))
+        outs = [torch.empty(shape, dtype=getattr(torch, np.dtype(self.dtype).name), device=self.device) for shape in shapes]
+        for i, t in enumerate(outs):
+            reqs[i].d_out = t.data_ptr()
+        opts = _sample_opts(mode, clamp, fill, cname)
+        _check(lib().sz3hip_stream_sample(self._h, reqs, n, C.byref(opts), _stream_handle(self.device, stream)))
         return outs
 
     def tile(self, level, lo, shape, out=None, stream=None):

@@ -477,9 +477,15 @@ struct szk_reduce_hist {  // nbins 0: no histogram
 // kind SZK_SINK_MAP (kernels: sz3hip_map.hip): the boxes' values mapped to texels, ONE launch in the gather's place on
 // every route. Unlike the other two sinks it reads the records' real `dst` and `dstr` (in OUTPUT elements). map: the options with scale and M
 // worked out on the host; map_threads: the lanes the largest box needs in the form the launcher takes (szk_map_threads over the boxes' extents)
+// kind SZK_SINK_SAMPLE (kernels: sz3hip_sample.hip): the boxes sampled at fractional positions, ONE launch in the gather's
+// place on every route. A record's `dst` word is the box's index in the request, `dstr` is not read. smp_queries: HOST, one szk_sample_query
+// (SZK_SAMPLE_WORDS words) per box in the request's order — the launchers put them into the table behind the records of every launch, in the
+// records' order, where the workgroups of box blockIdx.y read theirs at words SZK_SAMPLE_WORDS * blockIdx.y behind the gridDim.y records;
+// smp_threads: the largest box's n_points
 #define SZK_SINK_REDUCE 0
 #define SZK_SINK_SELECT 1
 #define SZK_SINK_MAP 2
+#define SZK_SINK_SAMPLE 3
 #define SZK_SELECT_OUT_WORDS 3
 struct szk_select_opts {
     double lo, hi;
@@ -500,6 +506,19 @@ __host__ __device__ static inline uint64_t szk_map_row_units(uint64_t ext_x, uin
 __host__ __device__ static inline uint64_t szk_map_threads(uint64_t total, uint64_t ext_x, int64_t dstr_x, uint32_t out_bytes, bool packed) {
     return packed && out_bytes < 4 && (dstr_x == 1 || ext_x == 1) ? total / ext_x * szk_map_row_units(ext_x, out_bytes) : total;
 }
+struct szk_sample_opts {
+    uint32_t filter, coord_type;      // SZ3HIP_SAMPLE_*; 0: f32 coordinates, 1: f64
+    uint32_t flags, N;                // SZ3HIP_SAMPLE_CLAMP; the stream's dimension count: a query has N coordinates
+    double fill;
+};
+struct szk_sample_query {             // a box's queries; origin and steps hold their N entries in the LAST N of four places, as a record's ext
+    const void *coords;               // device, n_points * N coordinates; NULL: the lattice form
+    void *out;                        // device, n_points elements of T
+    uint64_t n_points;
+    uint64_t counts[3];
+    double origin[4], steps[3][4];
+};
+#define SZK_SAMPLE_WORDS 22
 struct szk_region_sink {
     szk_reduce_part *partials;
     void *d_stats;
@@ -513,7 +532,13 @@ struct szk_region_sink {
     szk_map_opts map;
     uint64_t map_threads;
     bool map_packed;
+    szk_sample_opts smp;
+    const szk_sample_query *smp_queries;
+    uint64_t smp_threads;
 };
+// the sampling's one launch over n records in device memory, the boxes' queries behind them (one box: record and query by value)
+int szk_launch_region_sample(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
+                             uint32_t n, const szk_region_sink *sink, hipStream_t s);
 // the mapping's one launch over n records in device memory (one box: by value)
 int szk_launch_region_map(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
                           uint32_t n, const szk_region_sink *sink, hipStream_t s);
@@ -532,7 +557,8 @@ uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n);
 // sink non-null: the request reduces (outs[i].dst: box i's SZK_REDUCE_DST word, cast; the strides are not read) — reduce and final stand
 // in the strided gather's place, *launches is the request's count plus one; a selecting sink (kind SZK_SINK_SELECT): count, scan and write,
 // the request's count plus two, table_words with room for n * SZK_SELECT_OUT_WORDS more; a mapping sink (kind SZK_SINK_MAP): outs are the
-// real views in output elements, one launch, the request's count
+// real views in output elements, one launch, the request's count; a sampling sink (kind SZK_SINK_SAMPLE): outs[i].dst is i, one launch, the
+// request's count, table_words with room for n * SZK_SAMPLE_WORDS more
 int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                                 const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                                 void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,

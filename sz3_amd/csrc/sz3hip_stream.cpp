@@ -17,6 +17,9 @@
 // that selection over one plain view.
 // sz3hip_stream_map takes the request's own boxes and views, the views in OUTPUT elements, and leaves texels: the same
 // geometry and sequence with one mapping launch (sz3hip_map.hip) in the gather's place; sz3hip_map_device is that mapping over one plain view.
+// sz3hip_stream_sample takes the boxes with queries at fractional positions each and leaves the nearest point's bytes
+// or the linear interpolation: the same geometry and sequence with one sampling launch (sz3hip_sample.hip) in the gather's place;
+// sz3hip_sample_device is that sampling over one plain view.
 // A handle serves one request at a time; it is not thread-safe.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1144,6 +1147,225 @@ extern "C" int sz3hip_map_device(int dataType, int N, const uint64_t *dims, cons
     DeviceScope scope;
     HIPCHK(hipSetDevice(dev));
     if (szk_launch_region_map(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the mapping could not be launched");
+    return 0;
+}
+
+// ---- boxes sampled at fractional positions: nearest and linear ---------------------------------------------------------------
+namespace {
+int sample_opts_check(const sz3hip_sample_opts *opts, szk_sample_opts *so) {
+    memset(so, 0, sizeof(*so));
+    if (!opts) return fail(SZ3HIP_EINVAL, "NULL argument (opts): a sampling needs its filter");
+    if (opts->filter > SZ3HIP_SAMPLE_LINEAR) return fail(SZ3HIP_EINVAL, "the options' filter (%u) is not SZ3HIP_SAMPLE_NEAREST or SZ3HIP_SAMPLE_LINEAR (0, 1)", opts->filter);
+    if (opts->coord_type > SZ3HIP_DOUBLE) return fail(SZ3HIP_EINVAL, "the options' coord_type (%u) is not SZ3HIP_FLOAT or SZ3HIP_DOUBLE (0, 1)", opts->coord_type);
+    if (opts->flags & ~SZ3HIP_SAMPLE_CLAMP) return fail(SZ3HIP_EINVAL, "the options' flags (0x%x) hold bits beyond SZ3HIP_SAMPLE_CLAMP", opts->flags);
+    if (opts->reserved) return fail(SZ3HIP_EINVAL, "the options' reserved word is %u, not 0", opts->reserved);
+    so->filter = opts->filter;
+    so->coord_type = opts->coord_type;
+    so->flags = opts->flags;
+    so->fill = opts->fill;
+    return 0;
+}
+// one box's queries by themselves, before any geometry (prefix: "box <i>: " or nothing); csz: a coordinate's bytes
+int sample_query_args(const char *prefix, const sz3hip_sample_req &q, size_t tsz, size_t csz) {
+    if (!q.d_out) return fail(SZ3HIP_EINVAL, "%sthe output array is NULL", prefix);
+    if ((uintptr_t)q.d_out % tsz) return fail(SZ3HIP_EINVAL, "%sthe output is not aligned to its element size (%zu bytes)", prefix, tsz);
+    if (q.n_points < 1 || q.n_points > (1ull << 31))
+        return fail(SZ3HIP_EINVAL, "%sn_points is %llu: 1 .. 2^31 queries are supported", prefix, (unsigned long long)q.n_points);
+    if (q.d_coords) {
+        if ((uintptr_t)q.d_coords % csz) return fail(SZ3HIP_EINVAL, "%sd_coords is not aligned to its coordinate size (%zu bytes)", prefix, csz);
+        bool zero = !(q.counts[0] | q.counts[1] | q.counts[2]);
+        for (int j = 0; j < 4; j++) zero = zero && q.origin[j] == 0.0 && q.steps[0][j] == 0.0 && q.steps[1][j] == 0.0 && q.steps[2][j] == 0.0;
+        if (!zero) return fail(SZ3HIP_EINVAL, "%sd_coords is given with a lattice: counts, origin and steps must be 0 in the points form", prefix);
+        return 0;
+    }
+    uint64_t product = 1;
+    for (int a = 0; a < 3; a++) {
+        if (q.counts[a] == 0) return fail(SZ3HIP_EINVAL, "%sthe lattice's count of axis %d is 0", prefix, a);
+        product = q.counts[a] > (1ull << 31) || product > (1ull << 31) ? ~0ull : product * q.counts[a];  // (~0: beyond any n_points; nothing wraps)
+    }
+    if (product != q.n_points)
+        return fail(SZ3HIP_EINVAL, "%sthe lattice's counts (%llu x %llu x %llu) do not multiply to n_points (%llu)", prefix, (unsigned long long)q.counts[0],
+                    (unsigned long long)q.counts[1], (unsigned long long)q.counts[2], (unsigned long long)q.n_points);
+    return 0;
+}
+// ... and what needs the dimension count: the lattice's N used entries are finite
+int sample_query_lattice(const char *prefix, const sz3hip_sample_req &q, int N) {
+    if (q.d_coords) return 0;
+    for (int j = 0; j < N; j++) {
+        if (!(fabs(q.origin[j]) < INFINITY)) return fail(SZ3HIP_EINVAL, "%sthe lattice's origin[%d] is not finite", prefix, j);
+        for (int a = 0; a < 3; a++)
+            if (!(fabs(q.steps[a][j]) < INFINITY)) return fail(SZ3HIP_EINVAL, "%sthe lattice's steps[%d][%d] is not finite", prefix, a, j);
+    }
+    return 0;
+}
+// the arguments before any geometry: the boxes as a request's (no view), every box's queries, no two outputs meeting
+int sample_args(const char *who, const sz3hip_sample_req *reqs, uint32_t n, size_t tsz, size_t csz, std::vector<sz3hip_tile_req> &tr) {
+    int rc = szi_boxes_args(who, reqs, n, reqs, "reqs");
+    if (rc) return rc;
+    tr.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        char prefix[32];
+        snprintf(prefix, sizeof(prefix), "box %u: ", i);
+        if (reqs[i].reserved) return fail(SZ3HIP_EINVAL, "box %u: the reserved word is %u, not 0", i, reqs[i].reserved);
+        if ((rc = sample_query_args(prefix, reqs[i], tsz, csz))) return rc;
+        memset(&tr[i], 0, sizeof(tr[i]));
+        tr[i].level = reqs[i].level;
+        tr[i].box = reqs[i].box;
+    }
+    for (uint32_t i = 1; i < n; i++)
+        for (uint32_t k = 0; k < i; k++) {
+            const uintptr_t a = (uintptr_t)reqs[i].d_out, b = (uintptr_t)reqs[k].d_out;
+            if (a - b < reqs[k].n_points * tsz || b - a < reqs[i].n_points * tsz) return fail(SZ3HIP_EINVAL, "box %u: the output overlaps box %u's", i, k);
+        }
+    return 0;
+}
+int sample_lattices(const sz3hip_sample_req *reqs, uint32_t n, int N) {
+    for (uint32_t i = 0; i < n; i++) {
+        char prefix[32];
+        snprintf(prefix, sizeof(prefix), "box %u: ", i);
+        const int rc = sample_query_lattice(prefix, reqs[i], N);
+        if (rc) return rc;
+    }
+    return 0;
+}
+// a box's queries as the kernel reads them: origin and steps in the last N of four places
+void sample_query_words(const sz3hip_sample_req &q, int N, szk_sample_query *w) {
+    memset(w, 0, sizeof(*w));
+    w->coords = q.d_coords;
+    w->out = q.d_out;
+    w->n_points = q.n_points;
+    for (int a = 0; a < 3; a++) w->counts[a] = q.d_coords ? 1 : q.counts[a];
+    for (int j = 0; j < N && !q.d_coords; j++) {
+        w->origin[4 - N + j] = q.origin[j];
+        for (int a = 0; a < 3; a++) w->steps[a][4 - N + j] = q.steps[a][j];
+    }
+}
+}  // namespace
+
+extern "C" int sz3hip_sample_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_sample_req *reqs, uint32_t n, const sz3hip_sample_opts *opts,
+                                      sz3hip_sample_plan *out) {
+    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_sample_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
+    int rc = dtype_check(dataType);
+    std::vector<sz3hip_tile_req> tr;
+    szk_sample_opts so;
+    if (rc || (rc = sample_opts_check(opts, &so)) || (rc = sample_args("sz3hip_sample_plan_for", reqs, n, tsize(dataType), tsize((int)so.coord_type), tr))) return rc;
+    std::vector<szk_region_geom> gs;
+    memset(out, 0, sizeof(*out));
+    if ((rc = szi_request_geometry_conf(conf, tr.data(), n, gs, &out->scratch_elems)) || (rc = sample_lattices(reqs, n, conf->N))) return rc;
+    out->n = n;
+    out->finest_level = out->coarsest_level = reqs[0].level;
+    for (uint32_t i = 0; i < n; i++) {
+        out->finest_level = std::min(out->finest_level, reqs[i].level);
+        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
+        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
+        out->points += gs[i].points;
+        out->queries += reqs[i].n_points;
+    }
+    return 0;
+}
+
+extern "C" int sz3hip_stream_sample(sz3hip_stream *h, const sz3hip_sample_req *reqs, uint32_t n, const sz3hip_sample_opts *opts, void *stream) {
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_sample: no handle");
+    std::vector<sz3hip_tile_req> tr;
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    sink.kind = SZK_SINK_SAMPLE;
+    int rc = sample_opts_check(opts, &sink.smp);
+    if (rc || (rc = sample_args("sz3hip_stream_sample", reqs, n, tsize(h->dtype), tsize((int)sink.smp.coord_type), tr))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    std::vector<szk_region_geom> gs;
+    uint64_t elems = 0, words = 0;
+    const int N = h->fast ? h->codes.ip.N : h->N;
+    // (behind the boxes' records: every box's queries, in the table's one copy)
+    const uint64_t tail = (uint64_t)n * SZK_SAMPLE_WORDS;
+    if (!h->fast) {
+        if ((rc = full_boxes_check(h, tr.data(), n))) return rc;
+        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
+    } else {
+        const szk_interp_params &ip = h->codes.ip;
+        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, tr.data(), n, gs, &elems))) return rc;
+        words = szk_region_request_table_words(gs.data(), n) + tail;
+    }
+    if ((rc = sample_lattices(reqs, n, N))) return rc;
+    std::vector<szk_sample_query> queries(n);
+    sink.smp.N = (uint32_t)N;
+    sink.smp_threads = 1;
+    for (uint32_t i = 0; i < n; i++) {
+        tr[i].d_out = (void *)(uintptr_t)i;  // (the `dst` word: the box's index in the request)
+        sample_query_words(reqs[i], N, &queries[i]);
+        sink.smp_threads = std::max(sink.smp_threads, reqs[i].n_points);
+    }
+    sink.smp_queries = queries.data();
+    HIPCHK(hipSetDevice(h->device));
+    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    const uint32_t chain_points = sz3hip_debug_get_chain_points();
+    uint32_t chain_levels = 0, launches = 0, levels = 0;
+    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
+    int lr;
+    if (!h->fast) {
+        std::vector<szk_region_gather_strided_box> full_recs(n);
+        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
+        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
+        launches = 1;
+    } else {
+        std::vector<szk_region_out> ro(n);
+        for (uint32_t i = 0; i < n; i++) {
+            memset(&ro[i], 0, sizeof(ro[i]));
+            ro[i].dst = tr[i].d_out;
+        }
+        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
+                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, ro.data(), h->h_table,
+                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
+    }
+    HIPCHK(hipEventRecord(h->ev_req, s));
+    h->req_pending = true;
+    h->last_stream = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's sampling could not be launched (%d)", lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+extern "C" int sz3hip_sample_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_sample_opts *opts,
+                                    const sz3hip_sample_req *query, void *stream) {
+    int rc = dtype_check(dataType);
+    if (rc) return rc;
+    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++)
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+    if (!query) return fail(SZ3HIP_EINVAL, "sz3hip_sample_device: NULL argument (query)");
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    sink.kind = SZK_SINK_SAMPLE;
+    if ((rc = sample_opts_check(opts, &sink.smp))) return rc;
+    bool zero = query->level == 0 && query->reserved == 0;
+    for (int j = 0; j < 4; j++) zero = zero && query->box.lo[j] == 0 && query->box.ext[j] == 0;
+    if (!zero) return fail(SZ3HIP_EINVAL, "the query's level, reserved word and box must be 0: the view is the box");
+    if ((rc = sample_query_args("", *query, tsize(dataType), tsize((int)sink.smp.coord_type))) || (rc = sample_query_lattice("", *query, N))) return rc;
+    uint64_t str[4] = {0, 0, 0, 0};
+    int dev = 0;
+    if ((rc = szi_dev_view_strides(N, dims, strides, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
+    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    szk_region_gather_strided_box rec;
+    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);
+    szk_sample_query q;
+    sample_query_words(*query, N, &q);
+    sink.smp.N = (uint32_t)N;
+    sink.smp_threads = query->n_points;
+    sink.smp_queries = &q;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    HIPCHK(hipSetDevice(dev));
+    if (szk_launch_region_sample(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the sampling could not be launched");
     return 0;
 }
 
