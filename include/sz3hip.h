@@ -723,6 +723,62 @@ int sz3hip_sample_plan_for(const sz3hip_config *conf, int dataType, const sz3hip
 int sz3hip_stream_sample(sz3hip_stream *h, const sz3hip_sample_req *reqs, uint32_t n, const sz3hip_sample_opts *opts, void *stream);
 int sz3hip_sample_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_sample_opts *opts,
                          const sz3hip_sample_req *query, void *stream);
+/* ---- boxes projected along an axis: min, max, sum, mean, arg, count ----
+ * A maximum-intensity projection of a brick with the depth of the maximum, a column integral or mean, a minimum along time: a box
+ * collapsed along ONE axis. sz3hip_stream_project takes sz3hip_stream_request's own sz3hip_tile_req, 1 .. SZ3HIP_MAX_BOXES boxes that each
+ * name their own level (geometry, codes and wording are that call's, "box <i>: " in front; repeated and overlapping boxes are allowed;
+ * everything is checked before anything is launched or written), and runs the same launch sequence with ONE projecting launch in the
+ * strided gather's place: stats.launches_last_request is the same boxes' sz3hip_stream_request's (a handle that keeps the full array: 1).
+ * It counts as a request in sz3hip_stream_stats. One op and one axis hold for the whole call.
+ * The output of a box is the box with extent 1 along `axis` (keepdim): d_out and strides[] describe a view in OUTPUT elements (4 or 8
+ *   bytes), all N strides given (or none: contiguous); the stride at `axis` is not read, as the stride of any extent-1 dimension is not.
+ *   The view rules, the alignment rule and the overlap rule are the request's, applied to that collapsed box with the output element's size.
+ * The rule: the column of an output point is the box's values v_0 .. v_{E-1} along `axis`, ascending — exactly the values
+ *   sz3hip_stream_request would deliver —, each taken as x_i = (double)v_i. A point is finite when fabs(x_i) < INFINITY; NaN and +-Inf
+ *   points are left out of everything, as in sz3hip_stream_reduce.
+ *   COUNT: the number of finite points (uint32_t).
+ *   ARGMIN: the smallest i at which no finite point is smaller (compared in double: -0.0 and +0.0 tie, the first wins); E if none is
+ *     finite. ARGMAX symmetric. E > 2^32 - 1 with an index op: SZ3HIP_EINVAL.
+ *   MIN / MAX: (Tout)x_i at that index — the element's sign of zero kept; with Tout the handle's type a finite value's bytes pass
+ *     unchanged; double -> float rounds to nearest even and may give Inf —, (Tout)fill if none is finite.
+ *   SUM: s = 0.0; for i ascending over the finite points: s = s + x_i; then (Tout)s — the plain sequential fold in double, rounded once
+ *     at the end, whichever axis is folded. A column without a finite point gives (Tout)0.0.
+ *   MEAN: (Tout)(s / (double)m) with SUM's s and m the finite count; m == 0 gives (Tout)fill.
+ * The output depends on the column, the op and the options alone — not on the route, the grid, the other boxes or the handle's kind:
+ * sz3hip_stream_project is byte-identical to sz3hip_project_device over the same values. No device-to-host copy, no host synchronisation
+ * beyond a request's own waits; no workspace. A 1-D box is one column and so one lane's work: sz3hip_stream_reduce is the call for one
+ * number about a long 1-D box.
+ * Errors (SZ3HIP_EINVAL): opts NULL; op above SZ3HIP_PROJECT_COUNT; axis >= N; out_type above SZ3HIP_DOUBLE, or not 0 with an index op;
+ * reserved not 0 (fill is not checked: any double); d_out NULL or not aligned to the output element; the request's view and overlap cases
+ * on the collapsed box; and sz3hip_stream_request's for the boxes. Integer types: SZ3HIP_EUNSUPPORTED. A refused call launches and writes
+ * nothing, and the handle serves the next request.
+ * sz3hip_project_device: the same projection of ONE plain view in device memory (what a handle that keeps the full array runs, in one
+ * launch): N, dims, strides_in and d_in's rules are sz3hip_map_device's (x stride 2, stride-0 broadcasts and transposed views included);
+ * d_out / strides_out: the view of the collapsed array in output elements (strides_out NULL: contiguous). Asynchronous on `stream`.
+ * sz3hip_project_plan_for: a pure function (no device) with sz3hip_stream_project's checks. */
+#define SZ3HIP_PROJECT_MIN    0u   /* value ops: the output element is out_type's */
+#define SZ3HIP_PROJECT_MAX    1u
+#define SZ3HIP_PROJECT_SUM    2u
+#define SZ3HIP_PROJECT_MEAN   3u
+#define SZ3HIP_PROJECT_ARGMIN 4u   /* index ops: the output element is uint32_t, out_type must be 0 */
+#define SZ3HIP_PROJECT_ARGMAX 5u
+#define SZ3HIP_PROJECT_COUNT  6u
+typedef struct sz3hip_project_opts {   /* 24 bytes */
+    uint32_t op, axis;                 /* SZ3HIP_PROJECT_*; 0 .. N-1, slowest first: the dimension that is folded away */
+    uint32_t out_type, reserved;       /* value ops: SZ3HIP_FLOAT / SZ3HIP_DOUBLE, whatever the handle's type; 0 */
+    double fill;                       /* a column without a finite point (MIN, MAX, MEAN): (Tout)fill; any double, not checked */
+} sz3hip_project_opts;
+typedef struct sz3hip_project_plan {   /* 48 bytes */
+    uint32_t n; int32_t finest_level, coarsest_level, n_levels;
+    uint64_t points, scratch_elems;    /* sz3hip_request_plan_for's */
+    uint64_t out_points;               /* the sum over the boxes of points / ext[axis] */
+    uint32_t out_elem_bytes, reserved; /* 4 or 8 */
+} sz3hip_project_plan;
+int sz3hip_project_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n,
+                            const sz3hip_project_opts *opts, sz3hip_project_plan *out);
+int sz3hip_stream_project(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_project_opts *opts, void *stream);
+int sz3hip_project_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in,
+                          const sz3hip_project_opts *opts, void *d_out, const int64_t *strides_out, void *stream);
 /* development switch, process-wide: a request of a handle runs its coarsest c levels in ONE launch (one workgroup per box walks first point,
  * regrids and passes with a barrier between steps), c the largest count such that for every box every pass of those levels has at most
  * `points` points. 0: off — the request issues exactly the launches sz3hip_decompress_device_tiles issues. Environment twin, read once when

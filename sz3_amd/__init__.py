@@ -226,6 +226,17 @@ class _CSamplePlan(C.Structure):
                 ("scratch_elems", C.c_uint64), ("queries", C.c_uint64)]
 
 
+class _CProjectOpts(C.Structure):
+    # sz3hip_project_opts: 24 bytes
+    _fields_ = [("op", C.c_uint32), ("axis", C.c_uint32), ("out_type", C.c_uint32), ("reserved", C.c_uint32), ("fill", C.c_double)]
+
+
+class _CProjectPlan(C.Structure):
+    # sz3hip_project_plan: 48 bytes
+    _fields_ = [("n", C.c_uint32), ("finest_level", C.c_int32), ("coarsest_level", C.c_int32), ("n_levels", C.c_int32), ("points", C.c_uint64),
+                ("scratch_elems", C.c_uint64), ("out_points", C.c_uint64), ("out_elem_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _CStreamStats(C.Structure):
     """struct sz3hip_stream_stats (include/sz3hip.h)"""
     _fields_ = [("fast", C.c_uint32), ("huffman_stages", C.c_uint32), ("launches_last_request", C.c_uint32), ("chain_levels_last_request", C.c_uint32),
@@ -409,6 +420,12 @@ def lib():
     L.sz3hip_stream_sample.argtypes = [C.c_void_p, P(_CSampleReq), C.c_uint32, P(_CSampleOpts), C.c_void_p]
     L.sz3hip_sample_device.restype = C.c_int
     L.sz3hip_sample_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CSampleOpts), P(_CSampleReq), C.c_void_p]
+    L.sz3hip_project_plan_for.restype = C.c_int
+    L.sz3hip_project_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CProjectOpts), P(_CProjectPlan)]
+    L.sz3hip_stream_project.restype = C.c_int
+    L.sz3hip_stream_project.argtypes = [C.c_void_p, P(_CTileReq), C.c_uint32, P(_CProjectOpts), C.c_void_p]
+    L.sz3hip_project_device.restype = C.c_int
+    L.sz3hip_project_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CProjectOpts), C.c_void_p, P(C.c_int64), C.c_void_p]
     L.sz3hip_request_plan_for.restype = C.c_int
     L.sz3hip_request_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CRequestPlan)]
     L.sz3hip_stream_close.restype = None
@@ -1408,6 +1425,100 @@ def sample_points(tensor, query, mode="linear", clamp=False, fill=float("nan"), 
     return out
 
 
+PROJECT_MIN, PROJECT_MAX, PROJECT_SUM, PROJECT_MEAN, PROJECT_ARGMIN, PROJECT_ARGMAX, PROJECT_COUNT = range(7)  # SZ3HIP_PROJECT_*
+_PROJECT_OPS = {"min": PROJECT_MIN, "max": PROJECT_MAX, "sum": PROJECT_SUM, "mean": PROJECT_MEAN, "argmin": PROJECT_ARGMIN, "argmax": PROJECT_ARGMAX,
+                "count": PROJECT_COUNT}
+
+
+def _project_opts(op, axis, N, dtype_name, out_dtype, fill):
+    """the options struct and the outputs' dtype name: the handle's, or out_dtype (float32 / float64); an index op ("argmin", "argmax",
+    "count") writes uint32 and takes no out_dtype — its values live in int32 tensors, the same four bytes"""
+    if not isinstance(op, str) or op.lower() not in _PROJECT_OPS:
+        raise ValueError("op is one of 'min', 'max', 'sum', 'mean', 'argmin', 'argmax', 'count' (got %r)" % (op,))
+    code = _PROJECT_OPS[op.lower()]
+    axis = int(axis)
+    if not -N <= axis < N:
+        raise ValueError("axis %d is not one of the %d dimensions" % (axis, N))
+    o = _CProjectOpts()
+    o.op = code
+    o.axis = axis % N
+    o.fill = float(fill)
+    if code >= PROJECT_ARGMIN:
+        if out_dtype is not None:
+            raise ValueError("op %r writes indices: it takes no out_dtype" % op)
+        return o, "int32"
+    name = dtype_name if out_dtype is None else str(out_dtype).replace("torch.", "")
+    if name not in ("float32", "float64") and out_dtype is not None:  # (a numpy dtype or type)
+        try:
+            name = np.dtype(out_dtype).name
+        except TypeError:
+            pass
+    if name not in ("float32", "float64"):
+        raise ValueError("out_dtype is float32 or float64 (got %r)" % (out_dtype,))
+    o.out_type = _SZ_TYPES[name]
+    return o, name
+
+
+def _project_items(items):
+    items = [tuple(it) for it in items]
+    if any(len(it) not in (3, 4) for it in items):
+        raise ValueError("an item is (level, lo, shape) or (level, lo, shape, out)")
+    return [it if len(it) == 3 or it[3] is not None else it[:3] for it in items]
+
+
+def project_plan(conf, dtype, items, op, axis, out_dtype=None):
+    """what one Stream.project for `items` touches (sz3hip_project_plan_for), without a device: `items` are Stream.project's — (level, lo,
+    shape) or (level, lo, shape, out) — and the call's own checks run, the views and overlaps of the collapsed boxes in OUTPUT elements
+    included. Returns a dict with request_plan's fields, out_points and out_elem_bytes."""
+    items = _project_items(items)
+    dt = _np_dtype(dtype)
+    opts, name = _project_opts(op, axis, conf.N, dt.name, out_dtype, float("nan"))
+    arr, shapes = _boxes(conf.N, [(it[1], it[2]) for it in items])
+    flat = [tuple(1 if j == opts.axis else v for j, v in enumerate(shape)) for shape in shapes]
+    reqs, _ = _map_reqs(conf.N, items, flat, arr, name, None, False)
+    plan = _CProjectPlan()
+    _check(lib().sz3hip_project_plan_for(C.byref(conf._c), _dtype_id(dt), reqs, len(items), C.byref(opts), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k, _ in _CProjectPlan._fields_ if k != "reserved"}
+
+
+def project_points(tensor, op, axis, out_dtype=None, fill=float("nan"), out=None, stream=None):
+    """one float32 / float64 torch tensor on a HIP device collapsed along `axis` (sz3hip_project_device): the projection Stream.project runs
+    per box, over a plain view — any strides that are not negative, at most 4 dimensions above size 1 (the axis counts as one). op: "min",
+    "max", "sum", "mean" (values, of the tensor's dtype or `out_dtype`), "argmin", "argmax", "count" (uint32 in an int32 tensor). NaN and
+    +-Inf points are left out; a column without a finite point gives `fill` (min, max, mean), 0 (sum, count) or the axis' size (argmin,
+    argmax). The sum is the sequential fold in double along the axis, rounded once. `out`: a tensor of the input's shape with 1 at `axis`,
+    any view whose strides nest in row-major order (default: allocated, contiguous). Asynchronous on `stream`; returns `out`. One number
+    about a long 1-D tensor is reduce_stats' work: a 1-D projection is one lane's."""
+    if not _is_tensor(tensor):
+        raise TypeError("project_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
+    if not _gpu_tensor(tensor):
+        raise ValueError("project_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
+    tname = str(tensor.dtype).replace("torch.", "")
+    if tname not in _SZ_TYPES:
+        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
+    if tensor.numel() == 0 or tensor.dim() == 0:
+        raise ValueError("project_points: the tensor is empty or has no dimension")
+    import torch
+    opts, name = _project_opts(op, axis, tensor.dim(), tname, out_dtype, fill)
+    axis = int(opts.axis)
+    shape = tuple(1 if i == axis else int(d) for i, d in enumerate(tensor.shape))
+    if out is None:
+        out = torch.empty(shape, dtype=getattr(torch, name), device=tensor.device)
+    if not _gpu_tensor(out) or str(out.dtype) != "torch." + name or tuple(out.shape) != shape or out.device != tensor.device:
+        raise ValueError("project_points: out must be a %s tensor of shape %s on %s" % (name, shape, tensor.device))
+    keep = [i for i, d in enumerate(tensor.shape) if int(d) != 1 or i == axis]
+    if len(keep) > 4:
+        raise ValueError("project_points: %d dimensions above size 1, the axis included (at most 4 are supported)" % len(keep))
+    dims = [int(tensor.shape[i]) for i in keep]
+    sin = [int(tensor.stride(i)) for i in keep]
+    sout = [int(out.stride(i)) for i in keep]
+    N = len(dims)
+    opts.axis = keep.index(axis)
+    _check(lib().sz3hip_project_device(_SZ_TYPES[tname], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*sin), C.byref(opts), out.data_ptr(),
+                                       (C.c_int64 * N)(*sout), _stream_handle(tensor.device, stream)))
+    return out
+
+
 def set_chain_points(points):
     """development switch (sz3hip_debug_chain_points): a Stream request runs its coarsest levels — those whose every pass has at most
     `points` points for every box — in one launch; 0 switches the chain off"""
@@ -1568,6 +1679,22 @@ class Stream:
             reqs[i].d_out = t.data_ptr()
         opts = _sample_opts(mode, clamp, fill, cname)
         _check(lib().sz3hip_stream_sample(self._h, reqs, n, C.byref(opts), _stream_handle(self.device, stream)))
+        return outs
+
+    def project(self, items, op, axis, out_dtype=None, fill=float("nan"), stream=None):
+        """boxes collapsed along one axis (sz3hip_stream_project): `items` are request's — (level, lo, shape) or (level,
+        lo, shape, out) — with `out` a view of OUTPUT elements of the box's shape with 1 at `axis`. op: "min", "max", "sum", "mean" (values:
+        the stream's dtype, or `out_dtype` float32 / float64), "argmin", "argmax", "count" (uint32 in int32 tensors). NaN and +-Inf points are
+        left out; a column without a finite point gives `fill` (min, max, mean), 0 (sum, count) or the axis' extent (argmin, argmax). The
+        sum is the sequential fold in double along the axis, rounded once: bit-defined. The request's launch sequence with one projecting
+        launch in the gather's place. Missing outputs are allocated. Asynchronous on `stream`, as tiles. Returns the list of tensors."""
+        items = _project_items(items)
+        N = self.conf.N
+        opts, name = _project_opts(op, axis, N, np.dtype(self.dtype).name, out_dtype, fill)
+        arr, shapes = _boxes(N, [(it[1], it[2]) for it in items])
+        flat = [tuple(1 if j == opts.axis else v for j, v in enumerate(shape)) for shape in shapes]
+        reqs, outs = _map_reqs(N, items, flat, arr, name, self.device, True)
+        _check(lib().sz3hip_stream_project(self._h, reqs, len(items), C.byref(opts), _stream_handle(self.device, stream)))
         return outs
 
     def tile(self, level, lo, shape, out=None, stream=None):

@@ -482,10 +482,16 @@ struct szk_reduce_hist {  // nbins 0: no histogram
 // (SZK_SAMPLE_WORDS words) per box in the request's order — the launchers put them into the table behind the records of every launch, in the
 // records' order, where the workgroups of box blockIdx.y read theirs at words SZK_SAMPLE_WORDS * blockIdx.y behind the gridDim.y records;
 // smp_threads: the largest box's n_points
+// kind SZK_SINK_PROJECT (kernels: sz3hip_project.hip): the boxes collapsed along one axis, ONE launch in the gather's
+// place on every route, no final and nothing behind the records in the table. As the mapping it reads the records' real `dst` and `dstr`
+// (in OUTPUT elements; the entry at the axis is not read). prj: the options, the axis counted in the record's four places; prj_threads: the
+// largest box's output points (a thread per output point in both bodies); prj_rows: every box's dimensions behind the axis have extent 1 —
+// the axis is the fastest one that counts and the launch takes the body that stages through LDS
 #define SZK_SINK_REDUCE 0
 #define SZK_SINK_SELECT 1
 #define SZK_SINK_MAP 2
 #define SZK_SINK_SAMPLE 3
+#define SZK_SINK_PROJECT 4
 #define SZK_SELECT_OUT_WORDS 3
 struct szk_select_opts {
     double lo, hi;
@@ -519,6 +525,11 @@ struct szk_sample_query {             // a box's queries; origin and steps hold 
     double origin[4], steps[3][4];
 };
 #define SZK_SAMPLE_WORDS 22
+struct szk_project_opts {
+    uint32_t op, axis;                // SZ3HIP_PROJECT_*; the folded dimension's place among a record's four (4 - N + the caller's axis)
+    uint32_t out_type, N;             // 0: f32 outputs, 1: f64 (index ops: 0, the element is uint32_t); the stream's dimension count
+    double fill;
+};
 struct szk_region_sink {
     szk_reduce_part *partials;
     void *d_stats;
@@ -535,7 +546,13 @@ struct szk_region_sink {
     szk_sample_opts smp;
     const szk_sample_query *smp_queries;
     uint64_t smp_threads;
+    szk_project_opts prj;
+    uint64_t prj_threads;
+    bool prj_rows;
 };
+// the projection's one launch over n records in device memory (one box: by value)
+int szk_launch_region_project(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
+                              uint32_t n, const szk_region_sink *sink, hipStream_t s);
 // the sampling's one launch over n records in device memory, the boxes' queries behind them (one box: record and query by value)
 int szk_launch_region_sample(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
                              uint32_t n, const szk_region_sink *sink, hipStream_t s);
@@ -558,7 +575,8 @@ uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n);
 // in the strided gather's place, *launches is the request's count plus one; a selecting sink (kind SZK_SINK_SELECT): count, scan and write,
 // the request's count plus two, table_words with room for n * SZK_SELECT_OUT_WORDS more; a mapping sink (kind SZK_SINK_MAP): outs are the
 // real views in output elements, one launch, the request's count; a sampling sink (kind SZK_SINK_SAMPLE): outs[i].dst is i, one launch, the
-// request's count, table_words with room for n * SZK_SAMPLE_WORDS more
+// request's count, table_words with room for n * SZK_SAMPLE_WORDS more; a projecting sink (kind SZK_SINK_PROJECT): outs are the real views of
+// the collapsed boxes in output elements, one launch, the request's count
 int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                                 const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                                 void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,

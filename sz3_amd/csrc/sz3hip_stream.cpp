@@ -20,6 +20,9 @@
 // sz3hip_stream_sample takes the boxes with queries at fractional positions each and leaves the nearest point's bytes
 // or the linear interpolation: the same geometry and sequence with one sampling launch (sz3hip_sample.hip) in the gather's place;
 // sz3hip_sample_device is that sampling over one plain view.
+// sz3hip_stream_project takes the request's own boxes and collapses each along one axis into a view of OUTPUT elements:
+// the same geometry and sequence with one projecting launch (sz3hip_project.hip) in the gather's place; sz3hip_project_device is that
+// projection over one plain view.
 // A handle serves one request at a time; it is not thread-safe.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1366,6 +1369,178 @@ extern "C" int sz3hip_sample_device(int dataType, int N, const uint64_t *dims, c
     DeviceScope scope;
     HIPCHK(hipSetDevice(dev));
     if (szk_launch_region_sample(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the sampling could not be launched");
+    return 0;
+}
+
+// ---- boxes projected along an axis: min, max, sum, mean, arg, count -----------------------------------------------------------
+namespace {
+bool project_index_op(uint32_t op) { return op == SZ3HIP_PROJECT_ARGMIN || op == SZ3HIP_PROJECT_ARGMAX || op == SZ3HIP_PROJECT_COUNT; }
+size_t project_out_bytes(const szk_project_opts &po) { return project_index_op(po.op) || po.out_type == 0 ? 4 : 8; }
+int project_opts_check(const sz3hip_project_opts *opts, szk_project_opts *po) {
+    memset(po, 0, sizeof(*po));
+    if (!opts) return fail(SZ3HIP_EINVAL, "NULL argument (opts): a projection needs its op and axis");
+    if (opts->op > SZ3HIP_PROJECT_COUNT) return fail(SZ3HIP_EINVAL, "the options' op (%u) is not one of SZ3HIP_PROJECT_MIN .. SZ3HIP_PROJECT_COUNT (0 .. 6)", opts->op);
+    if (opts->out_type > SZ3HIP_DOUBLE) return fail(SZ3HIP_EINVAL, "the options' out_type (%u) is not SZ3HIP_FLOAT or SZ3HIP_DOUBLE (0, 1)", opts->out_type);
+    if (project_index_op(opts->op) && opts->out_type)
+        return fail(SZ3HIP_EINVAL, "the options' out_type is %u: an index op (ARGMIN, ARGMAX, COUNT) writes uint32_t and takes out_type 0", opts->out_type);
+    if (opts->reserved) return fail(SZ3HIP_EINVAL, "the options' reserved word is %u, not 0", opts->reserved);
+    po->op = opts->op;
+    po->out_type = opts->out_type;
+    po->fill = opts->fill;
+    return 0;
+}
+// ... and what needs the dimension count: the axis, counted in a record's four places from here on
+int project_axis(const sz3hip_project_opts *opts, int N, szk_project_opts *po) {
+    if (opts->axis >= (uint32_t)N) return fail(SZ3HIP_EINVAL, "the options' axis (%u) is not one of the %d dimensions (0 .. %d)", opts->axis, N, N - 1);
+    po->axis = opts->axis + (uint32_t)(4 - N);
+    po->N = (uint32_t)N;
+    return 0;
+}
+// the views of the collapsed boxes — the requests with extent 1 at the axis, by the mapping's rules with the output element's size — and the
+// sink: a thread per output point of the largest box; the body through LDS where the axis is every box's fastest dimension that counts
+int project_views(int N, uint32_t axis, const sz3hip_tile_req *reqs, uint32_t n, szk_region_sink *sink, std::vector<ReqView> &vs) {
+    const bool index_op = project_index_op(sink->prj.op);
+    std::vector<sz3hip_tile_req> flat(reqs, reqs + n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (index_op && reqs[i].box.ext[axis] > 0xFFFFFFFFull)
+            return fail(SZ3HIP_EINVAL, "box %u: the extent along the axis (%llu) is beyond an index op's uint32_t (2^32 - 1 at most)", i, (unsigned long long)reqs[i].box.ext[axis]);
+        flat[i].box.ext[axis] = 1;
+    }
+    const int rc = map_views(N, flat.data(), n, project_out_bytes(sink->prj), vs);
+    if (rc) return rc;
+    sink->kind = SZK_SINK_PROJECT;
+    sink->prj_threads = 1;
+    sink->prj_rows = true;
+    for (uint32_t i = 0; i < n; i++) {
+        uint64_t outs = 1;
+        for (int j = 0; j < N; j++) outs *= flat[i].box.ext[j];
+        sink->prj_threads = std::max(sink->prj_threads, outs);
+        for (int j = (int)axis + 1; j < N; j++) sink->prj_rows = sink->prj_rows && reqs[i].box.ext[j] == 1;
+        vs[i].str[axis] = 0;  // (not read)
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int sz3hip_project_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_project_opts *opts,
+                                       sz3hip_project_plan *out) {
+    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_project_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
+    int rc = dtype_check(dataType);
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    if (rc || (rc = request_args("sz3hip_project_plan_for", reqs, n)) || (rc = project_opts_check(opts, &sink.prj))) return rc;
+    std::vector<szk_region_geom> gs;
+    std::vector<ReqView> vs;
+    memset(out, 0, sizeof(*out));
+    if ((rc = szi_request_geometry_conf(conf, reqs, n, gs, &out->scratch_elems)) || (rc = project_axis(opts, conf->N, &sink.prj)) ||
+        (rc = project_views(conf->N, opts->axis, reqs, n, &sink, vs))) {
+        memset(out, 0, sizeof(*out));
+        return rc;
+    }
+    out->n = n;
+    out->finest_level = out->coarsest_level = reqs[0].level;
+    for (uint32_t i = 0; i < n; i++) {
+        out->finest_level = std::min(out->finest_level, reqs[i].level);
+        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
+        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
+        out->points += gs[i].points;
+        uint64_t outs = 1;
+        for (int j = 0; j < conf->N; j++) outs *= j == (int)opts->axis ? 1 : reqs[i].box.ext[j];
+        out->out_points += outs;
+    }
+    out->out_elem_bytes = (uint32_t)project_out_bytes(sink.prj);
+    return 0;
+}
+
+extern "C" int sz3hip_stream_project(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_project_opts *opts, void *stream) {
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_project: no handle");
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    int rc = request_args("sz3hip_stream_project", reqs, n);
+    if (rc || (rc = project_opts_check(opts, &sink.prj))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    std::vector<ReqView> vs;
+    std::vector<szk_region_geom> gs;
+    uint64_t elems = 0, words = 0;
+    const int N = h->fast ? h->codes.ip.N : h->N;
+    if (!h->fast) {
+        if ((rc = full_boxes_check(h, reqs, n))) return rc;
+        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
+    } else {
+        const szk_interp_params &ip = h->codes.ip;
+        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
+        words = szk_region_request_table_words(gs.data(), n);
+    }
+    if ((rc = project_axis(opts, N, &sink.prj)) || (rc = project_views(N, opts->axis, reqs, n, &sink, vs))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    const uint32_t chain_points = sz3hip_debug_get_chain_points();
+    uint32_t chain_levels = 0, launches = 0, levels = 0;
+    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
+    int lr;
+    if (!h->fast) {
+        std::vector<szk_region_gather_strided_box> full_recs(n);
+        for (uint32_t b = 0; b < n; b++) full_record(h, reqs[b], vs[b].str, &full_recs[b]);
+        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
+        launches = 1;
+    } else {
+        std::vector<szk_region_out> outs(n);
+        for (uint32_t i = 0; i < n; i++) {
+            outs[i].dst = reqs[i].d_out;
+            for (int j = 0; j < 4; j++) outs[i].str[j] = j < N ? vs[i].str[j] : 0;
+        }
+        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
+                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, outs.data(), h->h_table,
+                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
+    }
+    HIPCHK(hipEventRecord(h->ev_req, s));
+    h->req_pending = true;
+    h->last_stream = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's projection could not be launched (%d)", lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+extern "C" int sz3hip_project_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_project_opts *opts,
+                                     void *d_out, const int64_t *strides_out, void *stream) {
+    int rc = dtype_check(dataType);
+    if (rc) return rc;
+    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++)
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+    if (!d_out) return fail(SZ3HIP_EINVAL, "sz3hip_project_device: NULL argument (d_out)");
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    if ((rc = project_opts_check(opts, &sink.prj)) || (rc = project_axis(opts, N, &sink.prj))) return rc;
+    uint64_t str[4] = {0, 0, 0, 0};
+    int dev = 0;
+    if ((rc = szi_dev_view_strides(N, dims, strides_in, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
+    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    sz3hip_tile_req q;  // the output as a request's view of the whole array
+    memset(&q, 0, sizeof(q));
+    for (int i = 0; i < N; i++) {
+        q.box.ext[i] = dims[i];
+        q.strides[i] = strides_out ? strides_out[i] : 0;
+    }
+    q.d_out = d_out;
+    std::vector<ReqView> vs;
+    if ((rc = project_views(N, opts->axis, &q, 1, &sink, vs))) return rc;
+    szk_region_gather_strided_box rec;
+    szi_view_record(N, dims, str, 0, d_out, vs[0].str, &rec);
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    HIPCHK(hipSetDevice(dev));
+    if (szk_launch_region_project(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the projection could not be launched");
     return 0;
 }
 
