@@ -13,109 +13,14 @@ import pytest
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
 from partial_cases import CODES, DEV, FALLBACKS, INTERP_IDS, box_slices, conf_for, container, device_payload, smooth  # noqa: E402
+from sink_models import (FILL, LAST, NAN_TEXEL, NP_OUT, TORCH_OUT, make_lut, map_expected as expected, map_filled as filled, map_host as host,  # noqa: E402,F401
+                         map_untouched as untouched, np_codes, opts_for, same_texels, texel_atlas)
 from test_gpu_request import FB_ITEMS, ask, chain, mixed, same  # noqa: E402,F401
 from test_gpu_stream import SHAPES, IDS, case, coarse_shape, coarse_view, opens, tile_boxes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
-FILL = 0x4D
 TYPES = ["u8", "u16", "f16", "f32", "lut32"]
-NP_OUT = {"u8": np.uint8, "u16": np.uint16, "f16": np.float16, "f32": np.float32, "lut32": np.uint32}
-TORCH_OUT = {"u8": torch.uint8, "u16": torch.int16, "f16": torch.float16, "f32": torch.float32, "lut32": torch.int32}
-LAST = {"u8": 255, "u16": 65535}
-NAN_TEXEL = 0xDEADBEEF
-
-
-def np_codes(x, lo, hi, M, nan_code):
-    """the header's rule over float64 values: scale once, NaN -> nan_code, x < lo -> 0, x >= hi -> M, else min(uint64((x - lo) * scale), M)"""
-    x = np.asarray(x, dtype=np.float64)
-    lo, hi = np.float64(lo), np.float64(hi)
-    scale = np.float64(M + 1) / (hi - lo)
-    with np.errstate(invalid="ignore", over="ignore"):
-        inside = (x >= lo) & (x < hi)
-        k = np.minimum(np.where(inside, (x - lo) * scale, 0.0).astype(np.uint64), np.uint64(M))
-        c = np.where(x < lo, np.uint64(0), np.where(x >= hi, np.uint64(M), k))
-    return np.where(np.isnan(x), np.uint64(nan_code), c)
-
-
-def make_lut(n, seed=5):
-    """a seeded random table of n 32-bit texels that does not hold NAN_TEXEL: (host uint32 array, device int32 tensor)"""
-    t = np.random.default_rng(seed + n).integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
-    t[t == NAN_TEXEL] = 1
-    return t, torch.from_numpy(t.view(np.int32).copy()).to(DEV)
-
-
-def opts_for(out_type, lo=0.0, hi=0.0, nan_code=0, lut=None):
-    """keyword arguments of Stream.map / map_points for one output type (a float output takes no window)"""
-    if out_type in ("f16", "f32"):
-        return {}
-    if out_type == "lut32":
-        return dict(lo=lo, hi=hi, nan_code=NAN_TEXEL, lut=lut[1])
-    return dict(lo=lo, hi=hi, nan_code=nan_code)
-
-
-def expected(s, out_type, lo=0.0, hi=0.0, nan_code=0, lut=None):
-    s = np.asarray(s)
-    if out_type == "f32":
-        with np.errstate(over="ignore"):
-            return s.astype(np.float32)
-    if out_type == "f16":
-        with np.errstate(over="ignore"):
-            return s.astype(np.float32).astype(np.float16)
-    x = s.astype(np.float64)
-    if out_type == "lut32":
-        codes = np_codes(x, lo, hi, lut[0].size - 1, 0)
-        return np.where(np.isnan(x), np.uint32(NAN_TEXEL), lut[0][codes.astype(np.int64)])
-    return np_codes(x, lo, hi, LAST[out_type], nan_code).astype(NP_OUT[out_type])
-
-
-def filled(shape, out_type):
-    """a contiguous tensor of the output type, every byte 0x4D"""
-    td = TORCH_OUT[out_type]
-    n = int(np.prod(shape))
-    return torch.full((n * torch.empty((), dtype=td).element_size(),), FILL, dtype=torch.uint8, device=DEV).view(td).reshape(tuple(shape))
-
-
-def host(t, out_type):
-    """a tensor's elements on the host, in the numpy type of the output"""
-    return t.contiguous().cpu().numpy().view(NP_OUT[out_type])
-
-
-def same_texels(got, want, out_type, what=""):
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    if out_type in ("f16", "f32"):
-        nan = np.isnan(want)
-        assert np.isnan(got[nan]).all(), what + " a NaN point is no NaN"
-        u = np.uint16 if out_type == "f16" else np.uint32
-        assert np.array_equal(got.view(u)[~nan], want.view(u)[~nan]), what + " the texels' bytes differ"
-    else:
-        assert np.array_equal(got, want), what + " the texels differ"
-
-
-def untouched(buf, out_type, slices):
-    """every byte of buf outside the slices still holds 0x4D"""
-    a = buf.cpu().numpy()
-    mask = np.zeros(a.shape, dtype=bool)
-    for sl in slices:
-        mask[sl] = True
-    by = a.view(np.uint8).reshape(a.shape + (a.dtype.itemsize,))
-    return bool((by[~mask] == FILL).all())
-
-
-def texel_atlas(items, out_type):
-    """one atlas of the output type and the items' rectangles in it, side by side along x with a gap of one texel; the row pitch is odd (in
-    texels), so that the rows of a one-byte atlas start on all four byte alignments: (atlas, views, slices)"""
-    N = len(items[0][2])
-    dims = [max(it[2][j] for it in items) + 1 for j in range(N - 1)] + [sum(it[2][-1] + 1 for it in items)]
-    dims[-1] += 1 - dims[-1] % 2
-    atlas = filled(dims, out_type)
-    views, slices, x = [], [], 0
-    for _, _, ext in items:
-        sl = tuple(slice(0, e) for e in ext[:-1]) + (slice(x, x + ext[-1]),)
-        slices.append(sl)
-        views.append(atlas[sl])
-        x += ext[-1] + 1
-    return atlas, views, slices
 
 
 def slices_of(full, items):

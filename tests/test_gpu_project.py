@@ -17,114 +17,13 @@ import pytest
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
 from partial_cases import CODES, DEV, FALLBACKS, INTERP_IDS, box_slices, conf_for, container, device_payload, smooth  # noqa: E402
+from sink_models import (FILL, INDEX_OPS, NAN, OPS, OUTS, atlas_of, combos, flat, np_fold, out_name, project_expected as expected,  # noqa: E402,F401
+                         project_filled as filled, project_host as host, project_untouched as untouched, same_bytes)
 from test_gpu_request import FB_ITEMS, ask, chain, mixed, same  # noqa: E402,F401
 from test_gpu_stream import SHAPES, IDS, case, coarse_shape, coarse_view, opens, tile_boxes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
-FILL = 0x4D
-NAN = float("nan")
-OPS = ["min", "max", "sum", "mean", "argmin", "argmax", "count"]
-INDEX_OPS = ("argmin", "argmax", "count")
-OUTS = ["float32", "float64"]
-
-
-def combos():
-    """(op, out_dtype name or None): every op, the value ops into both output types"""
-    return [(op, None) for op in INDEX_OPS] + [(op, o) for op in OPS[:4] for o in OUTS]
-
-
-def np_fold(s, axis):
-    """the header's rule over a slice: one pass over the axis index, ascending, every column at once"""
-    x = np.moveaxis(np.asarray(s).astype(np.float64), axis, 0)
-    E, shape = x.shape[0], x.shape[1:]
-    ssum, cnt = np.zeros(shape), np.zeros(shape, dtype=np.int64)
-    amin, amax = np.full(shape, E, dtype=np.int64), np.full(shape, E, dtype=np.int64)
-    vmin, vmax = np.zeros(shape), np.zeros(shape)
-    with np.errstate(all="ignore"):
-        for i in range(E):
-            xi = x[i]
-            fin = np.abs(xi) < np.inf
-            ssum = np.where(fin, ssum + xi, ssum)
-            cnt = cnt + fin
-            lower = fin & ((amin == E) | (xi < vmin))  # (strictly smaller: of equal values, -0.0 and +0.0 among them, the first stays)
-            vmin, amin = np.where(lower, xi, vmin), np.where(lower, i, amin)
-            upper = fin & ((amax == E) | (xi > vmax))
-            vmax, amax = np.where(upper, xi, vmax), np.where(upper, i, amax)
-    return dict(E=E, sum=ssum, count=cnt, argmin=amin, argmax=amax, min=vmin, max=vmax)
-
-
-def expected(f, op, axis, out_name, fill=NAN):
-    """the output of a fold: fill and the one rounding, the axis kept with extent 1"""
-    with np.errstate(all="ignore"):
-        if op in INDEX_OPS:
-            r = f[op].astype(np.uint32)
-        else:
-            t = np.dtype(out_name).type
-            if op == "sum":
-                r = f["sum"].astype(t)
-            elif op == "mean":
-                r = np.where(f["count"] > 0, f["sum"] / f["count"].astype(np.float64), np.float64(fill)).astype(t)
-            else:
-                r = np.where(f["arg" + op] < f["E"], f[op], np.float64(fill)).astype(t)
-    return np.expand_dims(r, axis)
-
-
-def out_name(op, out, dtype):
-    return "int32" if op in INDEX_OPS else (out or np.dtype(dtype).name)
-
-
-def filled(shape, name):
-    """a contiguous tensor of the output's torch type (int32 for the index ops), every byte 0x4D"""
-    td = getattr(torch, name)
-    n = int(np.prod(shape))
-    return torch.full((n * torch.empty((), dtype=td).element_size(),), FILL, dtype=torch.uint8, device=DEV).view(td).reshape(tuple(shape))
-
-
-def host(t):
-    a = t.contiguous().cpu().numpy()
-    return a.view(np.uint32) if a.dtype == np.int32 else a
-
-
-def same_bytes(got, want, what=""):
-    assert got.shape == want.shape and got.dtype == want.dtype, "%s %s %s / %s %s" % (what, got.shape, got.dtype, want.shape, want.dtype)
-    if want.dtype.kind == "f":
-        nan = np.isnan(want)
-        assert np.isnan(got[nan]).all(), what + " a NaN output is no NaN"
-        u = np.uint32 if want.dtype.itemsize == 4 else np.uint64
-        bad = got.view(u)[~nan] != want.view(u)[~nan]
-        assert not bad.any(), "%s %d outputs' bytes differ, first: got %r want %r" % (what, int(bad.sum()), got[~nan][bad][:3], want[~nan][bad][:3])
-    else:
-        assert np.array_equal(got, want), what + " the indices differ"
-
-
-def untouched(buf, slices):
-    """every byte of buf outside the slices still holds 0x4D"""
-    a = buf.cpu().numpy()
-    mask = np.zeros(a.shape, dtype=bool)
-    for sl in slices:
-        mask[sl] = True
-    by = a.view(np.uint8).reshape(a.shape + (a.dtype.itemsize,))
-    return bool((by[~mask] == FILL).all())
-
-
-def flat(ext, axis):
-    return tuple(1 if j == axis else e for j, e in enumerate(ext))
-
-
-def atlas_of(shapes, name):
-    """one atlas of the output type and the shapes' rectangles in it, side by side along x with a gap of one element; the row pitch is odd"""
-    N = len(shapes[0])
-    dims = [max(s[j] for s in shapes) + 1 for j in range(N - 1)] + [sum(s[-1] + 1 for s in shapes)]
-    dims[-1] += 1 - dims[-1] % 2
-    atlas = filled(dims, name)
-    views, slices, x = [], [], 0
-    for s in shapes:
-        sl = tuple(slice(0, e) for e in s[:-1]) + (slice(x, x + s[-1]),)
-        slices.append(sl)
-        views.append(atlas[sl])
-        x += s[-1] + 1
-    return atlas, views, slices
 
 
 def slices_of(full, items):

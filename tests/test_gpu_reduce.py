@@ -19,79 +19,19 @@ import pytest
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
 from partial_cases import CODES, DEV, FALLBACKS, INTERP_IDS, box_slices, conf_for, container, device_payload, smooth  # noqa: E402
+from sink_models import EXACT_POINTS, bits, gamma, hist_of, reduce_check_box as check_box  # noqa: E402,F401
 from test_gpu_request import FB_ITEMS, alloc, ask, atlas_for, chain, chain_off, mixed, same  # noqa: E402,F401
 from test_gpu_stream import SHAPES, IDS, case, coarse_shape, coarse_view, opens, spiky_blob, tile_boxes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
-EXACT_POINTS = 20000
-U = Fraction(1, 2 ** 53)
 FIELDS = list(sz3_amd.BOX_STATS_DTYPE.names)
-
-
-def gamma(k):
-    return k * U / (1 - k * U)
 
 
 def rows(res):
     """(stats as raw int64 rows, histogram rows or None): synchronises"""
     torch.cuda.synchronize()
     return res.stats.cpu().numpy().copy(), None if res.hist is None else res.hist.cpu().numpy().copy()
-
-
-def bits(x):
-    return np.float64(x).tobytes()
-
-
-def hist_of(x, bins, lo, hi):
-    """the header's rule in numpy float64: slot 0 under, slot bins + 1 over, else 1 + min((uint64)((x - lo) * scale), bins - 1)"""
-    lo, hi = np.float64(lo), np.float64(hi)
-    scale = np.float64(bins) / (hi - lo)
-    x = x[np.isfinite(x)]
-    want = np.zeros(bins + 2, dtype=np.uint64)
-    want[0] = (x < lo).sum()
-    want[bins + 1] = (x >= hi).sum()
-    mid = x[(x >= lo) & (x < hi)]
-    k = np.minimum(((mid - lo) * scale).astype(np.uint64), np.uint64(bins - 1))
-    want[1:bins + 1] = np.bincount(k.astype(np.int64), minlength=bins)
-    return want
-
-
-def check_box(s, h, v, bins=0, lo=0.0, hi=0.0, what=""):
-    """one sz3hip_box_stats record (a row of the structured array) and its histogram row against the numpy array v (the box's values)"""
-    x = np.asarray(v).astype(np.float64).reshape(-1)  # ((double)v: exact)
-    fin = np.isfinite(x)
-    n, nf = x.size, int(fin.sum())
-    assert int(s["n"]) == n and int(s["n_nonfinite"]) == n - nf, what
-    if nf:
-        amin, amax = int(np.where(fin, x, np.inf).argmin()), int(np.where(fin, x, -np.inf).argmax())
-        assert (int(s["argmin"]), int(s["argmax"])) == (amin, amax), what
-        assert bits(s["min"]) == bits(x[amin]) and bits(s["max"]) == bits(x[amax]), what
-    else:
-        assert int(s["argmin"]) == n and int(s["argmax"]) == n and np.isnan(s["min"]) and np.isnan(s["max"]), what
-    K = x[0] if fin[0] else np.float64(0.0)
-    assert bits(s["shift"]) == bits(K), what
-    with np.errstate(all="ignore"):
-        m = np.float64(int(s["n"]) - int(s["n_nonfinite"]))
-        mean = s["shift"] + s["sum"] / m
-        var = (s["sum_sq"] - s["sum"] * s["sum"] / m) / m
-    if nf:
-        assert bits(s["mean"]) == bits(mean) and bits(s["variance"]) == bits(var), what
-    else:
-        assert np.isnan(s["mean"]) and np.isnan(s["variance"]) and s["sum"] == 0.0 and s["sum_sq"] == 0.0, what
-    if n <= EXACT_POINTS:
-        d = [Fraction(float(t)) - Fraction(float(K)) for t in x[fin]]
-        s1, a1, s2 = sum(d, Fraction(0)), sum((abs(t) for t in d), Fraction(0)), sum((t * t for t in d), Fraction(0))
-        e1, e2 = abs(Fraction(float(s["sum"])) - s1), abs(Fraction(float(s["sum_sq"])) - s2)
-        print("%s n %d: |sum - exact| %.3e (bound %.3e), |sum_sq - exact| %.3e (bound %.3e)" % (what, n, e1, gamma(n) * a1, e2, gamma(n + 2) * s2))
-        assert e1 <= gamma(n) * a1, what
-        assert e2 <= gamma(n + 2) * s2, what
-    if bins:
-        want = hist_of(x, bins, lo, hi)
-        assert np.array_equal(h.view(np.uint64), want), what
-        assert int(h.sum()) == nf, what
-    else:
-        assert h is None
 
 
 def check_items(res, full, items, bins=0, lo=0.0, hi=0.0, what=""):

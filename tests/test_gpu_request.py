@@ -10,11 +10,11 @@ import pytest
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
 from partial_cases import CODES, DEV, FALLBACKS, INTERP_IDS, box_slices, conf_for, container, device_payload, raw, smooth  # noqa: E402
+from sink_models import SENTINEL, atlas_for, tdt, untouched  # noqa: E402
 from test_gpu_stream import SHAPES, IDS, case, coarse_shape, coarse_view, opens, spiky_blob, tile_boxes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
-SENTINEL = 77.0
 LEVELS = (2, 0, 3, 1)  # interleaved: no two neighbours of a request share a level
 
 
@@ -33,10 +33,6 @@ def mixed(shape, levels=LEVELS):
     k0 = min(levels)
     lo, ext = per[k0][2]
     return items + [(levels[0],) + per[levels[0]][1], (k0, lo, ext), (k0, tuple(a + (e > 1) for a, e in zip(lo, ext)), tuple(max(1, e - 1) for e in ext))]
-
-
-def tdt(st):
-    return getattr(torch, st.dtype.name)
 
 
 def same(outs, full, items, what=""):
@@ -70,28 +66,6 @@ def by_tiles(st, items):
             outs[i] = o
     torch.cuda.synchronize()
     return outs
-
-
-def atlas_for(st, items, pad=0):
-    """one atlas tensor and the items' rectangles in it, side by side along x (their byte hulls interleave): (atlas, views)"""
-    N = len(items[0][2])
-    dims = [max(it[2][j] for it in items) + pad for j in range(N - 1)] + [sum(it[2][-1] + pad for it in items)]
-    atlas = torch.full(dims, SENTINEL, dtype=tdt(st), device=DEV)
-    views, x = [], 0
-    for _, _, ext in items:
-        views.append(atlas[tuple(slice(0, e) for e in ext[:-1]) + (slice(x, x + ext[-1]),)])
-        x += ext[-1] + pad
-    return atlas, views
-
-
-def untouched(buf, views):
-    """everything of buf outside the views still holds the sentinel"""
-    mask = torch.zeros(buf.shape, dtype=torch.bool, device=buf.device)
-    base = buf.data_ptr()
-    for v in views:
-        off = (v.data_ptr() - base) // buf.element_size()
-        mask.view(-1).as_strided(tuple(v.shape), tuple(v.stride()), off).fill_(True)
-    return bool((buf[~mask] == SENTINEL).all())
 
 
 @contextlib.contextmanager

@@ -11,6 +11,7 @@ import pytest
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
 from partial_cases import CODES, DEV, FALLBACKS, INTERP_IDS, box_slices, conf_for, container, smooth  # noqa: E402
+from sink_models import NAN, RAW, np_lattice, np_sample, same_values  # noqa: E402,F401
 from test_gpu_request import FB_ITEMS, ask, chain, mixed, same  # noqa: E402,F401
 from test_gpu_stream import SHAPES, IDS, case, coarse_shape, coarse_view, opens, tile_boxes  # noqa: E402
 
@@ -18,69 +19,11 @@ pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
 FILL = 0x4D
 PAD = 5  # elements behind every output that must stay 0x4D
-NAN = float("nan")
 MODES = ["nearest", "linear"]
 SIZES = (1, 255, 256, 257, 3 * 256 + 1)
-RAW = {np.dtype("float32"): np.uint32, np.dtype("float64"): np.uint64}
 
 
 # ---- the rule, in numpy ----------------------------------------------------------------------------------------------------------------------
-def np_sample(s, coords, mode, clamp=False, fill=NAN):
-    """s: the box's values (a numpy array of the stream's type); coords: (n, N) float32 / float64. The header's rule, in float64."""
-    s = np.asarray(s)
-    N = s.ndim
-    c = np.asarray(coords).astype(np.float64)  # (exact)
-    assert c.ndim == 2 and c.shape[1] == N
-    last = np.array(s.shape, dtype=np.int64) - 1
-    hi = last.astype(np.float64)
-    nan = np.isnan(c).any(axis=1)
-    with np.errstate(invalid="ignore", over="ignore"):
-        if clamp:
-            c = np.where(np.isnan(c), c, np.where(c < 0.0, 0.0, np.where(c > hi, hi, c)))
-            inside = ~nan
-        else:
-            inside = ((0.0 <= c) & (c <= hi)).all(axis=1)
-        out = np.full(c.shape[0], fill, dtype=np.float64).astype(s.dtype)
-        ci = c[inside]
-        if mode == "nearest":
-            i = np.minimum(np.floor(ci + 0.5).astype(np.int64), last)
-            u = RAW[s.dtype]
-            out.view(u)[inside] = s.view(u)[tuple(i.T)]  # raw bytes
-            return out
-        fl = np.floor(ci)
-        i = fl.astype(np.int64)
-        f = ci - fl
-        i1 = np.minimum(i + 1, last)
-        # corner k: bit d of k picks i + 1 along dimension N - 1 - d
-        w = [s[tuple((i1 if (k >> (N - 1 - j)) & 1 else i)[:, j] for j in range(N))].astype(np.float64) for k in range(1 << N)]
-        for d in range(N):  # the fastest dimension first
-            fd = f[:, N - 1 - d]
-            gd = 1.0 - fd
-            w = [np.where(fd == 0.0, w[2 * m], gd * w[2 * m] + fd * w[2 * m + 1]) for m in range(len(w) // 2)]
-        out[inside] = w[0].astype(s.dtype)  # one rounding
-    return out
-
-
-def np_lattice(origin, steps, counts):
-    """the lattice's coordinates by the header's formula: ((origin + i0 * s0) + i1 * s1) + i2 * s2 in float64, query-major"""
-    counts = (1,) * (3 - len(counts)) + tuple(counts)
-    steps = [(0.0,) * len(origin)] * (3 - len(steps)) + [tuple(st) for st in steps]
-    i0, i1, i2 = [g.reshape(-1).astype(np.float64) for g in np.meshgrid(*[np.arange(c) for c in counts], indexing="ij")]
-    cols = []
-    for j, o in enumerate(origin):
-        cols.append(((np.float64(o) + i0 * np.float64(steps[0][j])) + i1 * np.float64(steps[1][j])) + i2 * np.float64(steps[2][j]))
-    return np.stack(cols, axis=1)
-
-
-def same_values(got, want, what=""):
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    nan = np.isnan(want)
-    assert np.isnan(got[nan]).all(), what + " a NaN result is no NaN"
-    u = RAW[want.dtype]
-    bad = np.flatnonzero(got.view(u)[~nan] != want.view(u)[~nan])
-    assert bad.size == 0, "%s %d results differ in their bytes, the first at %d: %r, not %r" % (what, bad.size, bad[0], got[~nan][bad[0]], want[~nan][bad[0]])
-
-
 # ---- buffers and calls -----------------------------------------------------------------------------------------------------------------------
 def filled(n, tdtype):
     """n elements of the torch type, every byte 0x4D"""

@@ -13,47 +13,14 @@ import pytest
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
 from partial_cases import CODES, DEV, FALLBACKS, INTERP_IDS, box_slices, conf_for, container, device_payload, smooth  # noqa: E402
+from sink_models import SENT, pred, raw_select, select_check_box as check_box, sentinels, t_size, utype  # noqa: E402,F401
 from test_gpu_request import FB_ITEMS, alloc, ask, atlas_for, chain, chain_off, mixed, same  # noqa: E402,F401
 from test_gpu_stream import SHAPES, IDS, case, coarse_shape, coarse_view, opens, spiky_blob, tile_boxes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
-SENT = 0x4D4D4D4D4D4D4D4D
 CHUNK = 4096
 FLAGS = [(False, False), (True, False), (False, True), (True, True)]
-
-
-def pred(x, lo, hi, invert=False, nan=False):
-    """the header's rule over float64 values"""
-    with np.errstate(invalid="ignore"):
-        inside = (lo <= x) & (x <= hi)
-    return np.where(np.isnan(x), bool(nan), inside != bool(invert))
-
-
-def utype(dt):
-    return np.uint32 if np.dtype(dt).itemsize == 4 else np.uint64
-
-
-def sentinels(caps, tdtype, values=True):
-    """index and value arrays of the capacities (at least one element each, so that a capacity of 0 has something to leave alone), every byte 0x4D"""
-    index = [torch.full((max(c, 1),), SENT, dtype=torch.int64, device=DEV) for c in caps]
-    value = [torch.full((max(c, 1) * t_size(tdtype),), 0x4D, dtype=torch.uint8, device=DEV).view(tdtype) for c in caps] if values else None
-    return index, value
-
-
-def t_size(tdtype):
-    return 4 if tdtype == torch.float32 else 8
-
-
-def raw_select(st, items, caps, lo, hi, invert=False, nan=False, values=True, stream=None, n=None):
-    """sz3hip_stream_select into sentinel-filled arrays: (rc, heads, index, value) — nothing waits"""
-    tdtype = getattr(torch, st.dtype.name)
-    heads = torch.full((max(len(items), 1), 4), SENT, dtype=torch.int64, device=DEV)
-    index, value = sentinels(caps, tdtype, values)
-    reqs, cnt = sz3_amd._select_reqs(st.conf.N, items, caps, index, value)
-    opts = sz3_amd._select_opts(lo, hi, invert, nan)
-    rc = L.sz3hip_stream_select(st._h, reqs, cnt if n is None else n, C.byref(opts), heads.data_ptr(), sz3_amd._stream_handle(DEV, stream))
-    return rc, heads, index, value
 
 
 def raw_points(t, cap, lo, hi, invert=False, nan=False, values=True, stream=None):
@@ -76,22 +43,6 @@ def to_bytes(heads, index, value):
     """(heads, per-box index bytes, per-box value bytes) on the host: synchronises"""
     torch.cuda.synchronize()
     return (heads.cpu().numpy().tobytes(), [t.cpu().numpy().tobytes() for t in index], None if value is None else [t.cpu().numpy().tobytes() for t in value])
-
-
-def check_box(head, index, value, s, cap, lo, hi, invert=False, nan=False, what=""):
-    """one head row, one sentinel-filled index array and value array (host copies) against the numpy array s (the box's values)"""
-    s = np.asarray(s)
-    x = s.astype(np.float64).reshape(-1)
-    idx = np.flatnonzero(pred(x, lo, hi, invert, nan))
-    written = min(idx.size, cap)
-    assert [int(v) for v in head] == [x.size, idx.size, written, cap], "%s head %s, expected n %d count %d written %d capacity %d" % (what, head, x.size, idx.size, written, cap)
-    assert np.array_equal(index[:written], idx[:written]), what + " the indices differ"
-    assert (index[written:].view(np.uint64) == SENT).all(), what + " an index behind `written` was touched"
-    if value is not None:
-        u = utype(s.dtype)
-        assert np.array_equal(value.view(u)[:written], s.reshape(-1)[idx[:written]].view(u)), what + " the values' bytes differ"
-        assert (value.view(np.uint8)[written * s.dtype.itemsize:] == 0x4D).all(), what + " a value behind `written` was touched"
-    return idx.size
 
 
 def slices_of(full, items):

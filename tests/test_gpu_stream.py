@@ -12,6 +12,7 @@ import pytest
 torch = pytest.importorskip("torch")
 import sz3_amd  # noqa: E402
 from partial_cases import CODES, DEV, FALLBACKS, INTERP_IDS, box_slices, boxes_of, conf_for, container, device_payload, raw, smooth, spiky  # noqa: E402
+from sink_models import coarse_shape, coarse_view  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 L = sz3_amd.lib()
@@ -19,14 +20,6 @@ SENTINEL = 77.0
 CHAIN_DEFAULT = sz3_amd.get_chain_points()
 SHAPES = [(65, 47, 130), (33, 70), (1000,), (9, 12, 17, 20), (5, 9, 1100)]
 IDS = ["x".join(map(str, s)) for s in SHAPES]
-
-
-def coarse_shape(shape, k):
-    return tuple(((d - 1) >> k) + 1 for d in shape)
-
-
-def coarse_view(full, k):
-    return full[tuple(slice(None, None, 1 << k) for _ in full.shape)]
 
 
 def tile_boxes(shape):

@@ -11,6 +11,7 @@ import sys
 import pytest
 
 import sz3_amd
+from sweep_seeds import PARTIAL_SWEEP_N, PARTIAL_SWEEP_SEEDS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -160,3 +161,15 @@ def test_context_history_sweep_with_wild_arrays(monkeypatch):
     monkeypatch.setenv("WILD", "1")
     out = _run("history_sweep.py", 43, 120)
     assert "mismatches 0" in out
+
+
+@pytest.mark.parametrize("seed", PARTIAL_SWEEP_SEEDS)
+def test_partial_decode_sweep(seed):
+    """tests/checks/partial_sweep.py: 15 random cases of the partial decodes per seed — ranks 1 .. 4 at edge extents, every
+    interpolation order, anchor strides 0 .. 64 and the default, raw records and non-finite values in the field, boxes of mixed levels on every
+    route (chain, merged sequence, level group by level group) — through the region / tile / tiles / coarse calls, Stream.request into arrays,
+    atlas rectangles and stepped views, and two of the five sinks, byte for byte against this library's full decode, a device context's, or the
+    ORACLE's decode of a container the oracle wrote. The same seeds pass the plan functions and the coverage floors in
+    test_partial_sweep_cpu.py; at most one in ten interpolation cases may open as a fallback handle."""
+    out = _run("partial_sweep.py", seed, PARTIAL_SWEEP_N)
+    assert "failures 0" in out, out[-3000:]
