@@ -779,6 +779,63 @@ int sz3hip_project_plan_for(const sz3hip_config *conf, int dataType, const sz3hi
 int sz3hip_stream_project(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_project_opts *opts, void *stream);
 int sz3hip_project_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in,
                           const sz3hip_project_opts *opts, void *d_out, const int64_t *strides_out, void *stream);
+/* ---- gradients of boxes: central differences, magnitude, vector ----
+ * A gradient-magnitude transfer function, a shading normal, an edge or front detector: the derivative of a box along its axes.
+ * sz3hip_stream_gradient takes sz3hip_stream_request's own sz3hip_tile_req, 1 .. SZ3HIP_MAX_BOXES boxes that each name their own level
+ * (geometry, codes and wording are that call's, "box <i>: " in front; repeated and overlapping boxes are allowed; everything is checked
+ * before anything is launched or written), and runs the same launch sequence with ONE differentiating launch in the strided gather's
+ * place: stats.launches_last_request is the same boxes' sz3hip_stream_request's (a handle that keeps the full array: 1). It counts as a
+ * request in sz3hip_stream_stats. One op and one set of options hold for the whole call.
+ * The output of a box has the box's shape; under SZ3HIP_GRADIENT_INTERIOR the box loses its first and its last point along every
+ *   differentiated axis (DERIV: `axis`; the other ops: all N), and such an extent must be at least 3. A caller who asks for a tile with a
+ *   halo of one point gets the tile's own points, every one a central difference. The output element is Tout (out_type), for VECTOR N
+ *   consecutive Tout, component j the derivative along axis j, slowest first. d_out and strides[] describe a view in OUTPUT ELEMENTS
+ *   (sizeof(Tout), or N * sizeof(Tout) bytes), all N strides given (or none: contiguous); d_out is aligned to sizeof(Tout). The view rules
+ *   and the overlap rule are the request's, applied to the output box with the output element's size.
+ * The rule: v the values sz3hip_stream_request would deliver for the box, x = (double)v. Along axis a the box has extent E and the point
+ *   sits at index i:
+ *     ip = min(i + 1, E - 1), im = max(i, 1) - 1, s_a = ldexp(spacing[a], level)
+ *     d_a = E == 1 ? +0.0 : (x[ip] - x[im]) / ((double)(ip - im) * s_a)
+ *   — the two values differ in the index along a only; one subtraction, one multiplication and one division in IEEE double, nothing
+ *   contracted; central inside the box, one-sided at its first and last point; only points of the box are read: numpy.gradient's
+ *   edge_order=1 with a spacing that knows the level.
+ *   DERIV: (Tout)d_axis. VECTOR: every (Tout)d_j. MAG2: m = 0.0; for a ascending: m = m + d_a * d_a; (Tout)m. MAG: (Tout)sqrt(m), the
+ *   square root in double. Non-finite values get no special case (a NaN neighbour gives NaN, Inf - Inf gives NaN; a NaN output's sign and
+ *   payload are not part of the contract); double -> float rounds to nearest even and may give Inf.
+ * The output depends on the box's values, the box's level and the options alone — not on the route, the grid, the other boxes or the
+ * handle's kind: sz3hip_stream_gradient is byte-identical to sz3hip_gradient_device over the same values with spacing pre-multiplied by
+ * 2^level. No device-to-host copy, no host synchronisation beyond a request's own waits; no workspace.
+ * Errors (SZ3HIP_EINVAL): opts NULL; op above SZ3HIP_GRADIENT_VECTOR; axis >= N, or not 0 with another op than DERIV; out_type above
+ * SZ3HIP_DOUBLE; flag bits beyond SZ3HIP_GRADIENT_INTERIOR; a spacing[a], a < N, that is not finite and above 0, or whose s_a at some
+ * box's level is not finite (entries at and beyond N are not read); INTERIOR with a differentiated extent below 3; d_out NULL or not
+ * aligned to sizeof(Tout); the request's view and overlap cases on the output box; and sz3hip_stream_request's for the boxes. Integer
+ * types: SZ3HIP_EUNSUPPORTED. A refused call launches and writes nothing, and the handle serves the next request.
+ * sz3hip_gradient_device: the same gradient of ONE plain view in device memory at level 0 (what a handle that keeps the full array runs,
+ * in one launch): N, dims, strides_in and d_in's rules are sz3hip_map_device's (x stride 2, stride-0 broadcasts and transposed views
+ * included), the options checked before any pointer; d_out / strides_out: the view of the output box in output elements (strides_out
+ * NULL: contiguous). Asynchronous on `stream`.
+ * sz3hip_gradient_plan_for: a pure function (no device) with sz3hip_stream_gradient's checks. */
+#define SZ3HIP_GRADIENT_DERIV  0u   /* the derivative along `axis` */
+#define SZ3HIP_GRADIENT_MAG2   1u   /* the sum of the squared derivatives */
+#define SZ3HIP_GRADIENT_MAG    2u   /* its square root */
+#define SZ3HIP_GRADIENT_VECTOR 3u   /* all N derivatives, N consecutive Tout */
+#define SZ3HIP_GRADIENT_INTERIOR 1u /* flags: drop the first and last point along every differentiated axis */
+typedef struct sz3hip_gradient_opts {  /* 48 bytes */
+    uint32_t op, axis;                 /* SZ3HIP_GRADIENT_*; 0 .. N-1, slowest first: read by DERIV only, 0 otherwise */
+    uint32_t out_type, flags;          /* SZ3HIP_FLOAT / SZ3HIP_DOUBLE, whatever the handle's type; SZ3HIP_GRADIENT_INTERIOR or 0 */
+    double spacing[4];                 /* the level-0 grid step per axis, N entries used: finite and above 0 */
+} sz3hip_gradient_opts;
+typedef struct sz3hip_gradient_plan {  /* 48 bytes */
+    uint32_t n; int32_t finest_level, coarsest_level, n_levels;
+    uint64_t points, scratch_elems;    /* sz3hip_request_plan_for's */
+    uint64_t out_points;               /* output elements over the boxes, after INTERIOR */
+    uint32_t out_elem_bytes, reserved; /* sizeof(Tout), times N for VECTOR */
+} sz3hip_gradient_plan;
+int sz3hip_gradient_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n,
+                             const sz3hip_gradient_opts *opts, sz3hip_gradient_plan *out);
+int sz3hip_stream_gradient(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_gradient_opts *opts, void *stream);
+int sz3hip_gradient_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in,
+                           const sz3hip_gradient_opts *opts, void *d_out, const int64_t *strides_out, void *stream);
 /* development switch, process-wide: a request of a handle runs its coarsest c levels in ONE launch (one workgroup per box walks first point,
  * regrids and passes with a barrier between steps), c the largest count such that for every box every pass of those levels has at most
  * `points` points. 0: off — the request issues exactly the launches sz3hip_decompress_device_tiles issues. Environment twin, read once when

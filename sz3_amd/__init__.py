@@ -237,6 +237,17 @@ class _CProjectPlan(C.Structure):
                 ("scratch_elems", C.c_uint64), ("out_points", C.c_uint64), ("out_elem_bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _CGradientOpts(C.Structure):
+    # sz3hip_gradient_opts: 48 bytes
+    _fields_ = [("op", C.c_uint32), ("axis", C.c_uint32), ("out_type", C.c_uint32), ("flags", C.c_uint32), ("spacing", C.c_double * 4)]
+
+
+class _CGradientPlan(C.Structure):
+    # sz3hip_gradient_plan: 48 bytes
+    _fields_ = [("n", C.c_uint32), ("finest_level", C.c_int32), ("coarsest_level", C.c_int32), ("n_levels", C.c_int32), ("points", C.c_uint64),
+                ("scratch_elems", C.c_uint64), ("out_points", C.c_uint64), ("out_elem_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _CStreamStats(C.Structure):
     """struct sz3hip_stream_stats (include/sz3hip.h)"""
     _fields_ = [("fast", C.c_uint32), ("huffman_stages", C.c_uint32), ("launches_last_request", C.c_uint32), ("chain_levels_last_request", C.c_uint32),
@@ -426,6 +437,12 @@ def lib():
     L.sz3hip_stream_project.argtypes = [C.c_void_p, P(_CTileReq), C.c_uint32, P(_CProjectOpts), C.c_void_p]
     L.sz3hip_project_device.restype = C.c_int
     L.sz3hip_project_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CProjectOpts), C.c_void_p, P(C.c_int64), C.c_void_p]
+    L.sz3hip_gradient_plan_for.restype = C.c_int
+    L.sz3hip_gradient_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CGradientOpts), P(_CGradientPlan)]
+    L.sz3hip_stream_gradient.restype = C.c_int
+    L.sz3hip_stream_gradient.argtypes = [C.c_void_p, P(_CTileReq), C.c_uint32, P(_CGradientOpts), C.c_void_p]
+    L.sz3hip_gradient_device.restype = C.c_int
+    L.sz3hip_gradient_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CGradientOpts), C.c_void_p, P(C.c_int64), C.c_void_p]
     L.sz3hip_request_plan_for.restype = C.c_int
     L.sz3hip_request_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CRequestPlan)]
     L.sz3hip_stream_close.restype = None
@@ -1519,6 +1536,151 @@ def project_points(tensor, op, axis, out_dtype=None, fill=float("nan"), out=None
     return out
 
 
+GRADIENT_DERIV, GRADIENT_MAG2, GRADIENT_MAG, GRADIENT_VECTOR = range(4)  # SZ3HIP_GRADIENT_*
+GRADIENT_INTERIOR = 1                                                    # SZ3HIP_GRADIENT_INTERIOR
+_GRADIENT_OPS = {"deriv": GRADIENT_DERIV, "mag2": GRADIENT_MAG2, "mag": GRADIENT_MAG, "vector": GRADIENT_VECTOR}
+
+
+def _gradient_opts(op, axis, N, dtype_name, spacing, out_dtype, interior):
+    """the options struct and the outputs' dtype name: the input's, or out_dtype (float32 / float64). spacing: None (1.0 per axis), a
+    scalar for every axis, or one value per axis"""
+    if not isinstance(op, str) or op.lower() not in _GRADIENT_OPS:
+        raise ValueError("op is one of 'deriv', 'mag2', 'mag', 'vector' (got %r)" % (op,))
+    code = _GRADIENT_OPS[op.lower()]
+    axis = int(axis)
+    if not -N <= axis < N:
+        raise ValueError("axis %d is not one of the %d dimensions" % (axis, N))
+    if code != GRADIENT_DERIV and axis != 0:
+        raise ValueError("op %r differentiates along every axis: it takes no axis" % op)
+    o = _CGradientOpts()
+    o.op = code
+    o.axis = axis % N
+    o.flags = GRADIENT_INTERIOR if interior else 0
+    if spacing is None:
+        steps = [1.0] * N
+    elif np.ndim(spacing) == 0:
+        steps = [float(spacing)] * N
+    else:
+        steps = [float(v) for v in spacing]
+        if len(steps) != N:
+            raise ValueError("spacing needs one value per extent of the array (%d), or one scalar" % N)
+    o.spacing[:N] = steps
+    name = dtype_name if out_dtype is None else str(out_dtype).replace("torch.", "")
+    if name not in ("float32", "float64") and out_dtype is not None:  # (a numpy dtype or type)
+        try:
+            name = np.dtype(out_dtype).name
+        except TypeError:
+            pass
+    if name not in ("float32", "float64"):
+        raise ValueError("out_dtype is float32 or float64 (got %r)" % (out_dtype,))
+    o.out_type = _SZ_TYPES[name]
+    return o, name
+
+
+def _gradient_shape(shape, opts):
+    """a box's output shape: the box's, without the first and last point of every differentiated axis under INTERIOR (never below 0)"""
+    if not opts.flags & GRADIENT_INTERIOR:
+        return tuple(shape)
+    return tuple(max(v - 2, 0) if opts.op != GRADIENT_DERIV or j == opts.axis else v for j, v in enumerate(shape))
+
+
+def _vector_strides(t, N, what):
+    """the strides of a VECTOR output in output ELEMENTS (N values each): the tensor's without the last dimension, divided by N"""
+    if t.shape[-1] > 1 and int(t.stride(-1)) != 1:
+        raise ValueError("%s: a vector output's last dimension (the %d components) must be contiguous (its stride is %d)" % (what, N, int(t.stride(-1))))
+    strides = [int(v) for v in t.stride()[:-1]]
+    if any(v % N for v, e in zip(strides, t.shape[:-1]) if int(e) != 1):
+        raise ValueError("%s: a vector output's strides %s must be divisible by the component count %d: a view is counted in elements of %d values"
+                         % (what, tuple(strides), N, N))
+    return [v // N for v in strides]
+
+
+def _gradient_reqs(N, items, shapes, arr, name, opts, device, alloc):
+    """the request structs over out tensors of dtype `name` and the output boxes' shapes (VECTOR: plus a last dimension N); alloc: missing
+    outputs are allocated (else given placeholders that overlap no other, for the plan)"""
+    import sys
+    torch = sys.modules.get("torch")
+    vec = opts.op == GRADIENT_VECTOR
+    elem = np.dtype(name).itemsize * (N if vec else 1)
+    reqs = (_CTileReq * max(len(items), 1))()
+    outs = []
+    at = 1 << 40
+    for i, (it, shape) in enumerate(zip(items, shapes)):
+        oshape = _gradient_shape(shape, opts)
+        full = oshape + (N,) if vec else oshape
+        t = it[3] if len(it) == 4 else None
+        if alloc and not all(oshape):
+            raise ValueError("item %d: interior needs at least 3 points along every differentiated axis (the box's shape is %s)" % (i, tuple(shape)))
+        if t is None and alloc:
+            t = torch.empty(full, dtype=getattr(torch, name), device=device)
+        reqs[i].level = int(it[0])
+        reqs[i].box = arr[i]
+        if t is not None:
+            if str(t.dtype) != "torch." + name or tuple(t.shape) != full or (alloc and (not _gpu_tensor(t) or t.device != device)):
+                raise ValueError("item %d: out must be a %s tensor of shape %s%s" % (i, name, full, " on %s" % device if alloc else ""))
+            reqs[i].d_out = t.data_ptr()
+            reqs[i].strides[:N] = _vector_strides(t, N, "item %d" % i) if vec else [int(v) for v in t.stride()]
+        else:
+            reqs[i].d_out = at
+            at += (int(np.prod(oshape, dtype=np.uint64)) * elem + 255) & ~255
+        outs.append(t)
+    return reqs, outs
+
+
+def gradient_plan(conf, dtype, items, op, axis=0, spacing=None, out_dtype=None, interior=False):
+    """what one Stream.gradient for `items` touches (sz3hip_gradient_plan_for), without a device: `items` are Stream.gradient's — (level,
+    lo, shape) or (level, lo, shape, out) — and the call's own checks run, the views and overlaps of the output boxes in OUTPUT elements
+    included. Returns a dict with request_plan's fields, out_points (after `interior`) and out_elem_bytes."""
+    items = _project_items(items)
+    dt = _np_dtype(dtype)
+    opts, name = _gradient_opts(op, axis, conf.N, dt.name, spacing, out_dtype, interior)
+    arr, shapes = _boxes(conf.N, [(it[1], it[2]) for it in items])
+    reqs, _ = _gradient_reqs(conf.N, items, shapes, arr, name, opts, None, False)
+    plan = _CGradientPlan()
+    _check(lib().sz3hip_gradient_plan_for(C.byref(conf._c), _dtype_id(dt), reqs, len(items), C.byref(opts), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k, _ in _CGradientPlan._fields_ if k != "reserved"}
+
+
+def gradient_points(tensor, op, axis=0, spacing=None, out_dtype=None, interior=False, out=None, stream=None):
+    """the gradient of one float32 / float64 torch tensor of 1 .. 4 dimensions on a HIP device (sz3hip_gradient_device): what
+    Stream.gradient runs per box, over a plain view — any strides that are not negative. op: "deriv" (along `axis`), "mag2" (the sum of
+    the squared derivatives), "mag" (its square root) or "vector" (all derivatives: the output has a last dimension of tensor.dim()
+    components, slowest axis first). Central differences inside, one-sided at the first and last point (numpy.gradient's edge_order=1),
+    in IEEE double, rounded once into the tensor's dtype or `out_dtype`. spacing: the grid step, one scalar or one value per axis
+    (default 1.0). interior: the output loses the first and last point of every differentiated axis, so every point is a central
+    difference. `out`: a tensor of the output's shape, any view whose strides nest in row-major order (default: allocated, contiguous);
+    a vector output must have its last dimension contiguous and its other strides divisible by the component count. Asynchronous on
+    `stream`; returns `out`."""
+    if not _is_tensor(tensor):
+        raise TypeError("gradient_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
+    if not _gpu_tensor(tensor):
+        raise ValueError("gradient_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
+    tname = str(tensor.dtype).replace("torch.", "")
+    if tname not in _SZ_TYPES:
+        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
+    if tensor.numel() == 0 or not 1 <= tensor.dim() <= 4:
+        raise ValueError("gradient_points: the tensor is empty or does not have 1 .. 4 dimensions")
+    import torch
+    N = tensor.dim()
+    opts, name = _gradient_opts(op, axis, N, tname, spacing, out_dtype, interior)
+    vec = opts.op == GRADIENT_VECTOR
+    shape = _gradient_shape(tuple(int(d) for d in tensor.shape), opts)
+    full = shape + (N,) if vec else shape
+    for j, e in enumerate(shape):
+        if e == 0:
+            raise ValueError("gradient_points: interior needs at least 3 points along every differentiated axis (dimension %d is %d)" % (j, int(tensor.shape[j])))
+    if out is None:
+        out = torch.empty(full, dtype=getattr(torch, name), device=tensor.device)
+    if (not _gpu_tensor(out) or str(out.dtype) != "torch." + name or tuple(out.shape) != full or out.device != tensor.device):
+        raise ValueError("gradient_points: out must be a %s tensor of shape %s on %s" % (name, full, tensor.device))
+    dims = [int(d) for d in tensor.shape]
+    sin = [int(v) for v in tensor.stride()]
+    sout = _vector_strides(out, N, "gradient_points") if vec else [int(v) for v in out.stride()]
+    _check(lib().sz3hip_gradient_device(_SZ_TYPES[tname], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*sin), C.byref(opts),
+                                        out.data_ptr(), (C.c_int64 * N)(*sout), _stream_handle(tensor.device, stream)))
+    return out
+
+
 def set_chain_points(points):
     """development switch (sz3hip_debug_chain_points): a Stream request runs its coarsest levels — those whose every pass has at most
     `points` points for every box — in one launch; 0 switches the chain off"""
@@ -1695,6 +1857,23 @@ class Stream:
         flat = [tuple(1 if j == opts.axis else v for j, v in enumerate(shape)) for shape in shapes]
         reqs, outs = _map_reqs(N, items, flat, arr, name, self.device, True)
         _check(lib().sz3hip_stream_project(self._h, reqs, len(items), C.byref(opts), _stream_handle(self.device, stream)))
+        return outs
+
+    def gradient(self, items, op, axis=0, spacing=None, out_dtype=None, interior=False, stream=None):
+        """the derivatives of boxes by central differences (sz3hip_stream_gradient): `items` are request's — (level,
+        lo, shape) or (level, lo, shape, out) — with `out` a view of OUTPUT elements of the box's shape. op: "deriv" (along `axis`),
+        "mag2", "mag" or "vector" (a last dimension of N components, slowest axis first; a given `out` must have it contiguous and its
+        other strides divisible by N). spacing: the level-0 grid step, one scalar or one value per axis (default 1.0); a box of level k
+        is differentiated with 2**k times it. interior: every box loses its first and last point along every differentiated axis — ask
+        for a tile with a halo of one point and get the tile, every point a central difference. In IEEE double, rounded once into the
+        stream's dtype or `out_dtype`: bit-defined. The request's launch sequence with one differentiating launch in the gather's place.
+        Missing outputs are allocated. Asynchronous on `stream`, as tiles. Returns the list of tensors."""
+        items = _project_items(items)
+        N = self.conf.N
+        opts, name = _gradient_opts(op, axis, N, np.dtype(self.dtype).name, spacing, out_dtype, interior)
+        arr, shapes = _boxes(N, [(it[1], it[2]) for it in items])
+        reqs, outs = _gradient_reqs(N, items, shapes, arr, name, opts, self.device, True)
+        _check(lib().sz3hip_stream_gradient(self._h, reqs, len(items), C.byref(opts), _stream_handle(self.device, stream)))
         return outs
 
     def tile(self, level, lo, shape, out=None, stream=None):

@@ -487,11 +487,17 @@ struct szk_reduce_hist {  // nbins 0: no histogram
 // (in OUTPUT elements; the entry at the axis is not read). prj: the options, the axis counted in the record's four places; prj_threads: the
 // largest box's output points (a thread per output point in both bodies); prj_rows: every box's dimensions behind the axis have extent 1 —
 // the axis is the fastest one that counts and the launch takes the body that stages through LDS
+// kind SZK_SINK_GRADIENT (kernels: sz3hip_gradient.hip): the boxes' derivatives by central differences, ONE launch in the
+// gather's place on every route, no final. As the sampling's, a record's `dst` word is the box's index in the request and `dstr` is not read.
+// grd: the options, the axis counted in the record's four places; grd_boxes: HOST, one szk_gradient_box (SZK_GRADIENT_WORDS words) per box in
+// the request's order — the launchers put them into the table behind the records of every launch, in the records' order; grd_threads: the
+// largest box's output points
 #define SZK_SINK_REDUCE 0
 #define SZK_SINK_SELECT 1
 #define SZK_SINK_MAP 2
 #define SZK_SINK_SAMPLE 3
 #define SZK_SINK_PROJECT 4
+#define SZK_SINK_GRADIENT 5
 #define SZK_SELECT_OUT_WORDS 3
 struct szk_select_opts {
     double lo, hi;
@@ -530,6 +536,17 @@ struct szk_project_opts {
     uint32_t out_type, N;             // 0: f32 outputs, 1: f64 (index ops: 0, the element is uint32_t); the stream's dimension count
     double fill;
 };
+struct szk_gradient_opts {
+    uint32_t op, axis;                // SZ3HIP_GRADIENT_*; DERIV's dimension, its place among a record's four (4 - N + the caller's axis)
+    uint32_t out_type, flags;         // 0: f32 outputs, 1: f64; SZ3HIP_GRADIENT_INTERIOR
+    uint32_t N, pad;                  // the stream's dimension count
+};
+struct szk_gradient_box {             // a box's output and grid steps; dstr and scale hold their N entries in the LAST N of four places
+    void *dst;                        // device, the view's element [0, .., 0]
+    int64_t dstr[4];                  // in OUTPUT elements (Tout, or N Tout for VECTOR); 0 where the output's extent is 1
+    double scale[4];                  // spacing[a] * 2^level
+};
+#define SZK_GRADIENT_WORDS 9
 struct szk_region_sink {
     szk_reduce_part *partials;
     void *d_stats;
@@ -549,7 +566,13 @@ struct szk_region_sink {
     szk_project_opts prj;
     uint64_t prj_threads;
     bool prj_rows;
+    szk_gradient_opts grd;
+    const szk_gradient_box *grd_boxes;
+    uint64_t grd_threads;
 };
+// the gradient's one launch over n records in device memory, the boxes' entries behind them (one box: record and entry by value)
+int szk_launch_region_gradient(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
+                               uint32_t n, const szk_region_sink *sink, hipStream_t s);
 // the projection's one launch over n records in device memory (one box: by value)
 int szk_launch_region_project(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
                               uint32_t n, const szk_region_sink *sink, hipStream_t s);
@@ -576,7 +599,8 @@ uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n);
 // the request's count plus two, table_words with room for n * SZK_SELECT_OUT_WORDS more; a mapping sink (kind SZK_SINK_MAP): outs are the
 // real views in output elements, one launch, the request's count; a sampling sink (kind SZK_SINK_SAMPLE): outs[i].dst is i, one launch, the
 // request's count, table_words with room for n * SZK_SAMPLE_WORDS more; a projecting sink (kind SZK_SINK_PROJECT): outs are the real views of
-// the collapsed boxes in output elements, one launch, the request's count
+// the collapsed boxes in output elements, one launch, the request's count; a gradient sink (kind SZK_SINK_GRADIENT): outs[i].dst is i, one
+// launch, the request's count, table_words with room for n * SZK_GRADIENT_WORDS more
 int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                                 const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                                 void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,

@@ -23,6 +23,9 @@
 // sz3hip_stream_project takes the request's own boxes and collapses each along one axis into a view of OUTPUT elements:
 // the same geometry and sequence with one projecting launch (sz3hip_project.hip) in the gather's place; sz3hip_project_device is that
 // projection over one plain view.
+// sz3hip_stream_gradient takes the request's own boxes and leaves their derivatives by central differences — one axis,
+// the squared magnitude, the magnitude or the vector — in views of OUTPUT elements: the same geometry and sequence with one differentiating
+// launch (sz3hip_gradient.hip) in the gather's place; sz3hip_gradient_device is that gradient over one plain view.
 // A handle serves one request at a time; it is not thread-safe.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1541,6 +1544,204 @@ extern "C" int sz3hip_project_device(int dataType, int N, const uint64_t *dims, 
     DeviceScope scope;
     HIPCHK(hipSetDevice(dev));
     if (szk_launch_region_project(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the projection could not be launched");
+    return 0;
+}
+
+// ---- gradients of boxes: central differences, magnitude, vector --------------------------------------------------------------
+namespace {
+int gradient_opts_check(const sz3hip_gradient_opts *opts, szk_gradient_opts *go) {
+    memset(go, 0, sizeof(*go));
+    if (!opts) return fail(SZ3HIP_EINVAL, "NULL argument (opts): a gradient needs its op and spacing");
+    if (opts->op > SZ3HIP_GRADIENT_VECTOR) return fail(SZ3HIP_EINVAL, "the options' op (%u) is not one of SZ3HIP_GRADIENT_DERIV .. SZ3HIP_GRADIENT_VECTOR (0 .. 3)", opts->op);
+    if (opts->op != SZ3HIP_GRADIENT_DERIV && opts->axis)
+        return fail(SZ3HIP_EINVAL, "the options' axis is %u: only SZ3HIP_GRADIENT_DERIV reads it, every other op takes axis 0", opts->axis);
+    if (opts->out_type > SZ3HIP_DOUBLE) return fail(SZ3HIP_EINVAL, "the options' out_type (%u) is not SZ3HIP_FLOAT or SZ3HIP_DOUBLE (0, 1)", opts->out_type);
+    if (opts->flags & ~SZ3HIP_GRADIENT_INTERIOR) return fail(SZ3HIP_EINVAL, "the options' flags (0x%x) hold bits beyond SZ3HIP_GRADIENT_INTERIOR", opts->flags);
+    go->op = opts->op;
+    go->out_type = opts->out_type;
+    go->flags = opts->flags;
+    return 0;
+}
+// ... and what needs the dimension count: the axis, counted in a record's four places from here on, and the N spacings
+int gradient_axis(const sz3hip_gradient_opts *opts, int N, szk_gradient_opts *go) {
+    if (opts->axis >= (uint32_t)N) return fail(SZ3HIP_EINVAL, "the options' axis (%u) is not one of the %d dimensions (0 .. %d)", opts->axis, N, N - 1);
+    for (int a = 0; a < N; a++)
+        if (!(opts->spacing[a] > 0.0 && opts->spacing[a] < INFINITY))
+            return fail(SZ3HIP_EINVAL, "the options' spacing[%d] (%g) is not finite and above 0", a, opts->spacing[a]);
+    go->axis = opts->axis + (uint32_t)(4 - N);
+    go->N = (uint32_t)N;
+    return 0;
+}
+size_t gradient_out_bytes(const szk_gradient_opts &go) { return (go.out_type == 0 ? 4 : 8) * (go.op == SZ3HIP_GRADIENT_VECTOR ? go.N : 1); }
+bool gradient_differentiated(const szk_gradient_opts &go, int N, int j) { return go.op != SZ3HIP_GRADIENT_DERIV || (uint32_t)(4 - N + j) == go.axis; }
+// the boxes' grid steps, the output boxes — the requests trimmed under INTERIOR — and their views by the request's rules with the output
+// element's size; the sink with every box's table entry (boxes: n entries, in the request's order) and the largest box's output points
+int gradient_views(int N, const sz3hip_gradient_opts *opts, const sz3hip_tile_req *reqs, uint32_t n, szk_region_sink *sink, std::vector<szk_gradient_box> &boxes,
+                   uint64_t *out_points) {
+    const szk_gradient_opts &go = sink->grd;
+    const bool interior = (go.flags & SZ3HIP_GRADIENT_INTERIOR) != 0;
+    const size_t tout = go.out_type == 0 ? 4 : 8;
+    boxes.assign(n, szk_gradient_box());
+    std::vector<sz3hip_tile_req> trimmed(reqs, reqs + n);
+    for (uint32_t i = 0; i < n; i++) {
+        memset(&boxes[i], 0, sizeof(boxes[i]));
+        for (int j = 0; j < N; j++) {
+            const double s = ldexp(opts->spacing[j], reqs[i].level);
+            if (!(s < INFINITY))
+                return fail(SZ3HIP_EINVAL, "box %u: the grid step of dimension %d, spacing (%g) * 2^%d, is not finite", i, j, opts->spacing[j], reqs[i].level);
+            boxes[i].scale[4 - N + j] = s;
+            if (!interior || !gradient_differentiated(go, N, j)) continue;
+            if (reqs[i].box.ext[j] < 3)
+                return fail(SZ3HIP_EINVAL, "box %u: the extent of dimension %d is %llu: SZ3HIP_GRADIENT_INTERIOR drops the first and the last point of a differentiated axis and needs at least 3",
+                            i, j, (unsigned long long)reqs[i].box.ext[j]);
+            trimmed[i].box.ext[j] -= 2;
+        }
+    }
+    for (uint32_t i = 0; i < n; i++)
+        if ((uintptr_t)reqs[i].d_out % tout) return fail(SZ3HIP_EINVAL, "box %u: the output is not aligned to its element size (%zu bytes)", i, tout);
+    std::vector<ReqView> vs;
+    const int rc = request_views(N, trimmed.data(), n, gradient_out_bytes(go), vs);
+    if (rc) return rc;
+    sink->kind = SZK_SINK_GRADIENT;
+    sink->grd_threads = 1;
+    if (out_points) *out_points = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        uint64_t outs = 1;
+        boxes[i].dst = reqs[i].d_out;
+        for (int j = 0; j < N; j++) {
+            outs *= trimmed[i].box.ext[j];
+            boxes[i].dstr[4 - N + j] = trimmed[i].box.ext[j] > 1 ? vs[i].str[j] : 0;
+        }
+        sink->grd_threads = std::max(sink->grd_threads, outs);
+        if (out_points) *out_points += outs;
+    }
+    sink->grd_boxes = boxes.data();
+    return 0;
+}
+}  // namespace
+
+extern "C" int sz3hip_gradient_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_gradient_opts *opts,
+                                        sz3hip_gradient_plan *out) {
+    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_gradient_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
+    int rc = dtype_check(dataType);
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    if (rc || (rc = request_args("sz3hip_gradient_plan_for", reqs, n)) || (rc = gradient_opts_check(opts, &sink.grd))) return rc;
+    std::vector<szk_region_geom> gs;
+    std::vector<szk_gradient_box> boxes;
+    uint64_t out_points = 0;
+    memset(out, 0, sizeof(*out));
+    if ((rc = szi_request_geometry_conf(conf, reqs, n, gs, &out->scratch_elems)) || (rc = gradient_axis(opts, conf->N, &sink.grd)) ||
+        (rc = gradient_views(conf->N, opts, reqs, n, &sink, boxes, &out_points))) {
+        memset(out, 0, sizeof(*out));
+        return rc;
+    }
+    out->n = n;
+    out->finest_level = out->coarsest_level = reqs[0].level;
+    for (uint32_t i = 0; i < n; i++) {
+        out->finest_level = std::min(out->finest_level, reqs[i].level);
+        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
+        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
+        out->points += gs[i].points;
+    }
+    out->out_points = out_points;
+    out->out_elem_bytes = (uint32_t)gradient_out_bytes(sink.grd);
+    return 0;
+}
+
+extern "C" int sz3hip_stream_gradient(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_gradient_opts *opts, void *stream) {
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_gradient: no handle");
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    int rc = request_args("sz3hip_stream_gradient", reqs, n);
+    if (rc || (rc = gradient_opts_check(opts, &sink.grd))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    std::vector<szk_region_geom> gs;
+    std::vector<szk_gradient_box> boxes;
+    uint64_t elems = 0, words = 0;
+    const int N = h->fast ? h->codes.ip.N : h->N;
+    // (behind the boxes' records: every box's entry, in the table's one copy)
+    const uint64_t tail = (uint64_t)n * SZK_GRADIENT_WORDS;
+    if (!h->fast) {
+        if ((rc = full_boxes_check(h, reqs, n))) return rc;
+        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
+    } else {
+        const szk_interp_params &ip = h->codes.ip;
+        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
+        words = szk_region_request_table_words(gs.data(), n) + tail;
+    }
+    if ((rc = gradient_axis(opts, N, &sink.grd)) || (rc = gradient_views(N, opts, reqs, n, &sink, boxes, nullptr))) return rc;
+    std::vector<sz3hip_tile_req> tr(reqs, reqs + n);
+    for (uint32_t i = 0; i < n; i++) tr[i].d_out = (void *)(uintptr_t)i;  // (the `dst` word: the box's index in the request)
+    HIPCHK(hipSetDevice(h->device));
+    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    const uint32_t chain_points = sz3hip_debug_get_chain_points();
+    uint32_t chain_levels = 0, launches = 0, levels = 0;
+    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
+    int lr;
+    if (!h->fast) {
+        std::vector<szk_region_gather_strided_box> full_recs(n);
+        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
+        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
+        launches = 1;
+    } else {
+        std::vector<szk_region_out> ro(n);
+        for (uint32_t i = 0; i < n; i++) {
+            memset(&ro[i], 0, sizeof(ro[i]));
+            ro[i].dst = tr[i].d_out;
+        }
+        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
+                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, ro.data(), h->h_table,
+                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
+    }
+    HIPCHK(hipEventRecord(h->ev_req, s));
+    h->req_pending = true;
+    h->last_stream = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's gradient could not be launched (%d)", lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+extern "C" int sz3hip_gradient_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_gradient_opts *opts,
+                                      void *d_out, const int64_t *strides_out, void *stream) {
+    int rc = dtype_check(dataType);
+    if (rc) return rc;
+    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++)
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    if ((rc = gradient_opts_check(opts, &sink.grd)) || (rc = gradient_axis(opts, N, &sink.grd))) return rc;  // (the options before any pointer)
+    if (!d_out) return fail(SZ3HIP_EINVAL, "sz3hip_gradient_device: NULL argument (d_out)");
+    uint64_t str[4] = {0, 0, 0, 0};
+    int dev = 0;
+    if ((rc = szi_dev_view_strides(N, dims, strides_in, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
+    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    sz3hip_tile_req q;  // the output as a request's view of the whole array, at level 0
+    memset(&q, 0, sizeof(q));
+    for (int i = 0; i < N; i++) {
+        q.box.ext[i] = dims[i];
+        q.strides[i] = strides_out ? strides_out[i] : 0;
+    }
+    q.d_out = d_out;
+    std::vector<szk_gradient_box> boxes;
+    if ((rc = gradient_views(N, opts, &q, 1, &sink, boxes, nullptr))) return rc;
+    szk_region_gather_strided_box rec;
+    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    HIPCHK(hipSetDevice(dev));
+    if (szk_launch_region_gradient(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the gradient could not be launched");
     return 0;
 }
 
