@@ -46,18 +46,15 @@ def dualquant(a, eb, radius=32768, narrow=False):
         diff = np.abs(dec - a)
         bad = ~(diff <= eb_lo)
     # N-d Lorenzo = successive first differences with zero halo, wrap-around integer arithmetic
-    d = q.copy()
+    d = q
     for ax in range(a.ndim):
-        if a.shape[ax] > 1 or True:
-            pad = [(0, 0)] * a.ndim
-            pad[ax] = (1, 0)
-            p = np.pad(d, pad)
-            sl_hi = [slice(None)] * a.ndim
-            sl_lo = [slice(None)] * a.ndim
-            sl_hi[ax] = slice(1, None)
-            sl_lo[ax] = slice(0, -1)
-            with np.errstate(over="ignore"):
-                d = (p[tuple(sl_hi)] - p[tuple(sl_lo)]).astype(qt)
+        sl_hi = [slice(None)] * a.ndim
+        sl_lo = [slice(None)] * a.ndim
+        sl_hi[ax] = slice(1, None)
+        sl_lo[ax] = slice(0, -1)
+        nd = d.copy()  # (the first element along the axis keeps its value: the halo is zero)
+        nd[tuple(sl_hi)] -= d[tuple(sl_lo)]
+        d = nd
     inr = ((d >= -127) & (d <= 127)) if narrow else ((d > -radius) & (d < radius))
     codes = np.where(inr, d + radius, 0).astype(np.uint16)
     return q, d, codes, bad, ~inr
@@ -305,8 +302,9 @@ def reconstruct(h, sec, codes):
     d[sec["dout_idx"].astype(np.int64)] = sec["dout_val"]
     q = d.reshape(h["dims"])
     for ax in range(4):
-        with np.errstate(over="ignore"):
-            q = np.cumsum(q, axis=ax, dtype=Q)
+        if q.shape[ax] > 1:  # (a sum along an extent of one is the array itself)
+            with np.errstate(over="ignore"):
+                q = np.cumsum(q, axis=ax, dtype=Q)
     x = (q.astype(T) * T(2.0 * h["eb"])).reshape(-1)
     x[sec["vout_idx"].astype(np.int64)] = sec["vout_val"]
     return x

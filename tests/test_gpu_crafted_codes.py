@@ -18,6 +18,8 @@ import pytest
 
 import sz3_amd
 import crafted_codes as cc
+import payload_checks
+import sampled_model
 import szh_ref
 from test_gpu_stages import _conf
 
@@ -80,72 +82,16 @@ def _expected(prescribed, narrow):
 
 
 def _check_payload(case, form, x, prescribed, blob, codes, st, dec):
-    """everything the issue asks of one payload; -> its header"""
-    n = x.size
+    """everything the issue asks of one payload (tests/payload_checks.py); -> its header"""
     # stage 1: the prescribed codes; no value is listed, and a delta only where one-byte codes cannot hold it
     exp, listed = _expected(prescribed, st["narrow_codes"])
-    assert np.array_equal(codes, exp), "quantisation codes differ from the prescribed stream"
-    h, o, sec = szh_ref.parse(blob)
-    assert h["magic"] == szh_ref.MAGIC and h["n"] == n and h["payload_bytes"] == len(blob) == st["payload_bytes"]
-    assert h["n_vout"] == 0 and h["n_dout"] == len(listed) and st["n_value_outliers"] == 0 and st["n_delta_outliers"] == len(listed)
-    assert np.array_equal(sec["dout_idx"].astype(np.int64), listed)
-    assert np.array_equal(sec["dout_val"].astype(np.int64), prescribed[listed].astype(np.int64) - cc.RADIUS)
-    lens = sec["lens"].astype(np.int64)
-    present = np.unique(exp)
-    have = set((h["sym_min"] + np.nonzero(lens)[0]).tolist())
-    freq = np.bincount(exp, minlength=65536)[h["sym_min"]:h["sym_min"] + h["sym_count"]].astype(np.int64)
-    kraft_units = sum(1 << (szh_ref.MAX_LEN - int(l)) for l in lens[lens > 0])
-    assert h["max_len"] == lens.max() == st["max_code_len"]
-    if h["esc_sym"]:
-        # the sampled book (test_gpu_sampled.py's header rules): a code word for every byte value, whatever the sample met — the clustered
-        # order hides the rare run from it on purpose; a valid prefix code, no claim about its cost
-        assert st["narrow_codes"] == 1 and n >= 1 << 22
-        assert h["esc_sym"] == h["radius"] + 128 and h["sym_min"] == h["radius"] - 127 and h["sym_count"] == 256 and h["version"] == 5
-        assert set(present.tolist()) <= have and h["esc_sym"] in have and freq.sum() == n
-        assert kraft_units <= 1 << szh_ref.MAX_LEN and lens.max() <= szh_ref.MAX_LEN
-        limit = szh_ref.MAX_LEN
-        bfreq = freq
-    else:
-        assert h["version"] == 4
-        book, filled = szh_ref.book_symbols(present)
-        assert have == book, "the book's symbols are not the stream's (+ margins)"
-        limit = szh_ref.SHORT_LEN if len(book) <= szh_ref.SHORT_SYMS else szh_ref.MAX_LEN
-        assert kraft_units == 1 << szh_ref.MAX_LEN, "Kraft sum %d / 2^24" % kraft_units
-        assert lens.max() <= limit
-        bfreq, bmin, blimit = szh_ref.book_histogram(np.bincount(exp, minlength=65536)[present.min():present.max() + 1], int(present.min()))
-        assert blimit == limit and freq.sum() == n
-        if filled:
-            assert h["sym_min"] == bmin == min(book) and h["sym_count"] == len(book) == len(bfreq)
-            assert np.array_equal(np.maximum(freq, 1), bfreq)
-        else:
-            assert h["sym_min"] == bmin and h["sym_count"] == len(bfreq) and np.array_equal(freq, bfreq)
-    # the book's cost: never below the length-limited optimum; the project's rule against the unlimited code; the kernel's documented loss
-    pm = szh_ref.package_merge_lengths(bfreq, limit)
-    pm_cost, gpu_cost = int((bfreq * pm).sum()), int((bfreq * lens).sum())
-    unlimited, height = szh_ref.huffman_cost(bfreq)
-    bits, chunkwords, subbits = szh_ref.chunk_table(exp, lens, h["sym_min"], h["esc_sym"])
-    FIGURES.append((case, form, int(st["narrow_codes"]), len(bfreq), limit, int(lens.max()), height, (gpu_cost - pm_cost) / n, (gpu_cost - unlimited) / n, float(bits.max()) / (szh_ref.CHUNK * limit)))
-    if not h["esc_sym"]:
-        assert pm_cost <= gpu_cost, "the book costs less than the length-limited optimum: not a code of that limit"
-        szh_ref.assert_book_optimal(bfreq, lens, limit)
-        if len(bfreq) <= szh_ref.SHORT_SYMS:
-            assert (gpu_cost - unlimited) / n < 0.01, "16-bit limit: %.5f bit/symbol over the unlimited code" % ((gpu_cost - unlimited) / n)
-    # the packed stream: the chunk table of the whole payload from the payload's own lengths, the slow decoder on the densest, first and last chunk
-    assert h["n_chunks"] == len(bits) and h["bitstream_words"] == int(chunkwords.sum())
-    assert np.array_equal(sec["chunkwords"], chunkwords), "chunkwords differ from the lengths' sums"
-    assert np.array_equal(sec["subbits"], subbits), "restart offsets differ from the lengths' sums"
-    if n <= 120000:
-        assert np.array_equal(szh_ref.huffman_decode(h, sec), exp), "the bit stream does not decode to the prescribed codes"
-    else:
-        pick = sorted({int(np.argmax(bits)), 0, h["n_chunks"] - 1})
-        got = szh_ref.huffman_decode(h, sec, chunks=pick)
-        for c in pick:
-            sl = slice(c * szh_ref.CHUNK, (c + 1) * szh_ref.CHUNK)
-            assert np.array_equal(got[sl], exp[sl]), "chunk %d does not decode to the prescribed codes" % c
-    # the decode: the model's array bit for bit, within the bound
-    model = szh_ref.reconstruct(h, sec, exp).reshape(x.shape)
-    assert np.array_equal(dec, model), "the decoder's array differs from the model's"
-    assert np.max(np.abs(dec.astype(np.float64) - x.astype(np.float64))) <= EB
+    # (the array of the sampled book in the default form: its book is held to the sample's counts, which numpy computes from the prescribed
+    # deltas; the other forms of the encoder keep the rules they had: header, a valid prefix code)
+    sample = None
+    if form == "default" and st["narrow_codes"] and sampled_model.takes_sampled_book(x.shape, x.dtype, cc.RADIUS):
+        sample = sampled_model.sample_counts(prescribed.astype(np.int64) - cc.RADIUS, x.shape)
+    h, fig = payload_checks.check_payload(x, EB, exp, listed, prescribed[listed].astype(np.int64) - cc.RADIUS, np.zeros(0, dtype=np.int64), blob, codes, st, dec, sample=sample)
+    FIGURES.append((case, form, fig["narrow"], fig["symbols"], fig["limit"], fig["max_len"], fig["height"], fig["over_pm"], fig["over_unlimited"], fig["densest"]))
     return h
 
 

@@ -11,7 +11,7 @@ import sys
 import pytest
 
 import sz3_amd
-from sweep_seeds import PARTIAL_SWEEP_N, PARTIAL_SWEEP_SEEDS
+from sweep_seeds import PARTIAL_SWEEP_N, PARTIAL_SWEEP_SEEDS, SAMPLED_SWEEP_N, SAMPLED_SWEEP_SEEDS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,4 +172,16 @@ def test_partial_decode_sweep(seed):
     ORACLE's decode of a container the oracle wrote. The same seeds pass the plan functions and the coverage floors in
     test_partial_sweep_cpu.py; at most one in ten interpolation cases may open as a fallback handle."""
     out = _run("partial_sweep.py", seed, PARTIAL_SWEEP_N)
+    assert "failures 0" in out, out[-3000:]
+
+
+@pytest.mark.parametrize("seed", SAMPLED_SWEEP_SEEDS)
+def test_sampled_path_sweep(seed):
+    """tests/checks/sampled_sweep.py: per seed four drawn arrays and two fixed ones of 2^22 .. 6.5e6 elements on the
+    sampled-book Lorenzo path — ranks 1 .. 3 at the extents where stage 1's tasks end ragged, f32 and f64, eight kinds of data, neighbours that
+    must not take the path — the first payload held to the numpy model in full (codes, lists, header, the book against the sample's counts, the
+    chunk table, the slow decoder on up to nine chunks, the decode bit for bit), then the context's later calls, three encoder settings, the
+    context after another array and a decoder form byte for byte. The same seeds pass the model's premises and the coverage floors in
+    test_sampled_sweep_cpu.py."""
+    out = _run("sampled_sweep.py", seed, SAMPLED_SWEEP_N)
     assert "failures 0" in out, out[-3000:]
