@@ -2131,9 +2131,13 @@ __global__ __launch_bounds__(256) void k_hist_reduce(const uint32_t *__restrict_
 // leaves to the limit: next to free when the clamp meets a few rare leaves (a field's tail, the margins' bins), far from the
 // length-limited optimum on deep trees (Fibonacci-like counts: 0.27 % of the stream with five levels clamped, 3.6 % with eleven). The
 // small path therefore measures what the repair cost and, beyond 1 / 2048 of the stream, takes the optimum by package-merge
-// (cb_package_merge: alphabets up to 512 symbols, arrays below 2^28 elements; the loss is then < 0.01 bit/symbol and < 0.2 %). The wide
-// path's 24-bit limit keeps the closed form: 0.12 % on Fibonacci counts three levels too deep. profiles/r16_crafted_codes.txt,
-// tests/test_gpu_crafted_codes.py.
+// (cb_package_merge: alphabets up to 512 symbols, arrays below 2^28 elements; the loss is then < 0.01 bit/symbol and < 0.2 %). (deep24's
+// 0.12 % — Fibonacci counts three levels beyond 24 bits — is this path's figure too: its 518 dense symbols never reach the wide path.)
+// The wide path (codebook_wide) follows the same rule for constructions of up to CB_WIDE_PM_SYMS keys at either limit — 257 .. 512
+// symbols spread over more than SZK_CB_PART0_RANGE bins have the 16-bit limit there: with the closed form alone the wide path cost
+// 6.7 % on Fibonacci counts five levels beyond 16 bits and 0.43 % three levels beyond 24, with package-merge 0.14 % and 0.015 %
+// (profiles/r28_wide_books.txt). Beyond CB_WIDE_PM_SYMS keys the wide path keeps the closed form.
+// profiles/r16_crafted_codes.txt, tests/test_gpu_crafted_codes.py, tests/test_gpu_wide_books.py.
 // ------------------------------------------------------------------------------------------------------------
 #define CB_THREADS 256       // threads of the small-alphabet path
 #define CB_LAUNCH 1024       // threads per workgroup of the launch
@@ -2627,8 +2631,14 @@ __device__ void cb_kraft_repair(uint16_t *pleaf, uint32_t m, uint32_t *s_cnt, ui
 // per place says "leaf". The cheapest 2m - 2 items of the top level are the solution; walking down, every package taken stands for
 // two items of the level below, and a leaf's length is the number of levels that took it — the q cheapest leaves of a level are the
 // ones taken. NT live threads. M: [2m] u32, P: [m] u32, F: [L * ceil(2m / 32)] u32, all LDS. pleaf and s_cnt are rebuilt.
-__device__ void cb_package_merge(const uint64_t *keys, uint32_t m, uint32_t L, uint16_t *pleaf, uint32_t *s_cnt, uint32_t *M, uint32_t *P,
+// W32 (the wide path, whose keys lie in global memory): keys is a u32 array of the weights alone, ascending, in LDS; the weights' sum
+// times L stays below 2^32.
+template <bool W32 = false>
+__device__ void cb_package_merge(const uint64_t *keys64, uint32_t m, uint32_t L, uint16_t *pleaf, uint32_t *s_cnt, uint32_t *M, uint32_t *P,
                                  uint32_t *F, uint32_t NT) {
+    const auto weight = [keys64](uint32_t i) -> uint32_t {
+        return W32 ? reinterpret_cast<const uint32_t *>(keys64)[i] : (uint32_t)(keys64[i] >> 16);
+    };
     const uint32_t t = threadIdx.x;
     const uint32_t SW = (2 * m + 31) / 32;
     for (uint32_t i = t; i < L * SW; i += NT) F[i] = 0;
@@ -2637,7 +2647,7 @@ __device__ void cb_package_merge(const uint64_t *keys, uint32_t m, uint32_t L, u
     for (uint32_t lev = 0; lev < L; lev++) {
         uint32_t *f = F + lev * SW;
         for (uint32_t i = t; i < m; i += NT) {
-            const uint32_t w = (uint32_t)(keys[i] >> 16);
+            const uint32_t w = weight(i);
             uint32_t a = 0, b = np;  // packages lighter than the leaf
             while (a < b) {
                 const uint32_t mid = (a + b) >> 1;
@@ -2653,7 +2663,7 @@ __device__ void cb_package_merge(const uint64_t *keys, uint32_t m, uint32_t L, u
             uint32_t a = 0, b = m;  // leaves not heavier than the package
             while (a < b) {
                 const uint32_t mid = (a + b) >> 1;
-                if ((uint32_t)(keys[mid] >> 16) <= w) a = mid + 1;
+                if (weight(mid) <= w) a = mid + 1;
                 else b = mid;
             }
             M[j + a] = w;
@@ -2764,6 +2774,7 @@ __device__ void cb_assign_codes(const uint16_t *len_of, const uint16_t *syms, ui
 #define CB_CLASS_MIN 4096u
 #define CB_CLASS_KEEP 3072u    // first choice: everything after it runs on one 4096-key LDS tile
 #define CB_CLASS_KEEP2 12288u  // second choice when the first would put too many occurrences into the rare class
+#define CB_WIDE_PM_SYMS 4096u   // keys up to which a binding length limit may take the optimum by package-merge (its tables in the LDS pool)
 // pre (round 5): the compaction was made by k_cb_compact over the whole chip in front of this launch — keys[] / syms[] hold the
 // non-empty bins in symbol order, ifreq[0 .. CBC_BLOCKS) the workgroups' sums of counts (one workgroup reading the 48 183-bin range of
 // C3 twice was 46 of the wide book's 164 us: the rate ONE compute unit reads memory at)
@@ -2965,10 +2976,12 @@ __device__ void codebook_wide(const uint64_t *__restrict__ hist, const szk_cb_pa
     if (t == 0) p.info->ts[4] = wall_clock64();
     // 4. depth of every internal node by pointer doubling (min(depth, 2^rounds) is all the clamp needs); the four
     //    u16 arrays ping-pong in the LDS pool when they fit (m <= 16384), else in global memory
+    __shared__ unsigned long long s_pm[3];  // bits of: [0] what the clamp cut off, [1] the clamped lengths, [2] the repaired code
     {
         const bool in_lds = mk <= CB_POOL_BYTES / 8;
         uint16_t *dA = in_lds ? reinterpret_cast<uint16_t *>(pool) : aux, *pA = in_lds ? dA + CB_POOL_BYTES / 8 : pint;
         uint16_t *dB = in_lds ? pA + CB_POOL_BYTES / 8 : aux2, *pB = in_lds ? dB + CB_POOL_BYTES / 8 : pint2;
+        if (t < 3) s_pm[t] = 0;
         __syncthreads();  // (the merge's LDS queues are dead from here on)
         for (uint32_t q = t; q + 1 < mk; q += NT) {
             pA[q] = q == mk - 2 ? (uint16_t)q : pint[q];
@@ -2993,7 +3006,8 @@ __device__ void codebook_wide(const uint64_t *__restrict__ hist, const szk_cb_pa
         // leaf lengths in sorted order, clamped
         for (uint32_t q = t; q < mk; q += NT) {
             uint32_t l = (uint32_t)dA[pleaf[q]] + 1;
-            if (l > L) {
+            if (l > L) {  // (rare: the only leaves whose weights this loop reads; depths beyond 2^rounds count 2^rounds)
+                atomicAdd(&s_pm[0], (unsigned long long)(p.keys[q] >> 16) * (l - L));
                 l = L;
                 s_misc[4] = 1;
             }
@@ -3003,8 +3017,31 @@ __device__ void codebook_wide(const uint64_t *__restrict__ hist, const szk_cb_pa
         __syncthreads();
     }
     if (t == 0) p.info->ts[5] = wall_clock64();
-    // 5. Kraft repair when a natural depth exceeded the limit
-    if (s_misc[4]) cb_kraft_repair(pleaf, mk, s_cnt, L, NT, reinterpret_cast<uint64_t *>(pool));
+    // 5. Kraft repair when a natural depth exceeded the limit. As on the small path, the closed form is kept where it costs less than
+    //    1 / 2048 of the stream; beyond that (deep trees: Fibonacci-like counts — 6.7 % at 16 bits, 0.43 % at 24 bits three levels
+    //    deep, profiles/r28_wide_books.txt) a construction of up to CB_WIDE_PM_SYMS keys, whose package-merge tables fit the LDS pool,
+    //    takes the length-limited optimum.
+    if (s_misc[4]) {
+        const bool pm_fits = mk <= CB_WIDE_PM_SYMS && total * L < (1ull << 32);
+        unsigned long long bits = 0;
+        for (uint32_t q = t; q < mk && pm_fits; q += NT) bits += (unsigned long long)(p.keys[q] >> 16) * pleaf[q];
+        if (bits) atomicAdd(&s_pm[1], bits);
+        cb_kraft_repair(pleaf, mk, s_cnt, L, NT, reinterpret_cast<uint64_t *>(pool));
+        if (pm_fits) {
+            bits = 0;
+            for (uint32_t q = t; q < mk; q += NT) bits += (unsigned long long)(p.keys[q] >> 16) * pleaf[q];
+            if (bits) atomicAdd(&s_pm[2], bits);
+            __syncthreads();
+            const unsigned long long unclamped = s_pm[0] + s_pm[1];
+            if ((s_pm[2] - unclamped) * 2048ull > unclamped) {
+                uint32_t *M = reinterpret_cast<uint32_t *>(pool), *P = M + 2 * CB_WIDE_PM_SYMS, *F = P + CB_WIDE_PM_SYMS;
+                uint32_t *W = F + SZH_MAX_LEN * (2 * CB_WIDE_PM_SYMS / 32);  // 32 + 16 + 24 + 16 KiB of the pool's 128
+                for (uint32_t q = t; q < mk; q += NT) W[q] = (uint32_t)(p.keys[q] >> 16);
+                __syncthreads();
+                cb_package_merge<true>(reinterpret_cast<const uint64_t *>(W), mk, L, pleaf, s_cnt, M, P, F, NT);
+            }
+        }
+    }
     // 6. lengths to symbol order (through the serialised lens[] table), then canonical codes
     __syncthreads();
     for (uint32_t qb = t; qb < mk; qb += 4 * NT) {  // (four loads in flight per step, as in the compaction)
@@ -3746,6 +3783,7 @@ __global__ __launch_bounds__(CB_LAUNCH) void k_codebook(const uint64_t *__restri
             p.info->sym_count = 0;
             p.info->win_lo = 0;
             p.info->reserved = 0;
+            p.info->esc_sym = 0;  // (a sampled book's escape is the previous call's, not this empty book's)
         }
         return;
     }
@@ -4435,6 +4473,7 @@ __device__ void role_book(const szk_role_params &rp, szk_state *state, uint8_t *
             p.info->sym_count = 0;
             p.info->win_lo = 0;
             p.info->reserved = 0;
+            p.info->esc_sym = 0;  // (a sampled book's escape is the previous call's, not this empty book's)
         }
         built = true;
     } else {

@@ -5,13 +5,15 @@ exactly d + radius, in exactly the order chosen: the test prescribes the histogr
 field does. The families below are the inputs on which Huffman constructions classically break: trees deeper than the length limit
 (Fibonacci counts), massive ties (equal counts, powers of two), alphabets at the code-book paths' boundaries, and runs of a
 thousand longest code words (a chunk near SZH_CHUNK_SYMS * limit bits). tests/test_crafted_codes_cpu.py holds every family to its
-stated regime with the numpy model alone; tests/test_gpu_crafted_codes.py shows the streams to the kernels."""
+stated regime with the numpy model alone; tests/test_gpu_crafted_codes.py shows the streams to the kernels. The wide code books'
+families (300 .. 65 535 symbols, the "balanced" order, sparse alphabets) are WIDE_FAMILIES below: tests/test_widebook_model_cpu.py,
+tests/test_gpu_wide_books.py."""
 import functools
 import numpy as np
 
 RADIUS = 32768
 EB = 2.0 ** -10          # a power of two: q * 2 eb is exact in f32 and f64, and x / (2 eb) gives q back exactly
-ORDERS = ("clustered", "shuffled", "periodic")
+ORDERS = ("clustered", "shuffled", "periodic")   # (the orders of the families up to 2049 symbols; the wide families below: "balanced")
 PERIOD = 512             # = szh_ref.UNIT: the periodic order's rare symbols sit on the unit and chunk borders
 
 
@@ -50,6 +52,74 @@ FAMILIES[SAMPLED_FAMILY] = ([56 * c for c in FAMILIES["fib17"][0]], "fib17 at th
 # (a shape with more elements than the family: the most frequent symbol that many more times)
 SHAPES_3D = {"fib17": (19, 30, 132), "deep16": (29, 60, 260)}
 
+# ---- the wide code books (tests/widebook_model.py, tests/test_gpu_wide_books.py): alphabets of 300 .. 65 535 symbols in the "balanced" order.
+# family -> (counts, the regime it binds); WIDE_REGIME: what tests/test_widebook_model_cpu.py holds each to without a GPU:
+#   path        widebook_model.path
+#   limit       the length limit of the book
+#   tier        None: one class; else (keep, k) of the tier taken
+#   and n_rare, rare_bits, floor (the class's weight is the floor's), binds (the unlimited tree is deeper than the limit), in_lds (the keys
+#   of the construction fit the LDS queues and depth arrays: mk <= 16384)
+SPACING = {}   # family -> the spacing of its symbols (default 1: dense)
+WIDE_FAMILIES = {}
+WIDE_REGIME = {}
+
+
+def _wide(name, counts, text, spacing=1, **regime):
+    WIDE_FAMILIES[name] = FAMILIES[name] = (list(counts), text)
+    WIDE_REGIME[name] = regime
+    if spacing != 1:
+        SPACING[name] = spacing
+
+
+def _geometric(m, hi, lo):
+    """m counts falling from hi to lo in equal ratios"""
+    return [int(round(hi * (float(lo) / hi) ** (i / float(m - 1)))) for i in range(m)]
+
+
+_TAIL = [1] * 2500 + [2] * 1597          # 4097 rare symbols of 5694 occurrences; the tier rule's estimate of them: 2500 * 3 // 2 + 1597 * 3 = 8541
+_TAIL_MASS = 2500 * 3 // 2 + 1597 * 3
+_HEAD = _geometric(3000, 2040, 45)
+for _m, _t in ((640, "the last alphabet of the small book by count"), (641, "the first of the wide book by count"),
+               (4096, "CB_CLASS_MIN: the two-class form not considered"), (4097, "considered, both tiers rejected: the one-class form entered from the two-class one"),
+               (15360, "tier 2 skipped: nothing to gain"), (15361, "tier 2 weighed and rejected"),
+               (16384, "the last alphabet whose queues and depth arrays fit LDS"), (16385, "queues and depth arrays in global memory"),
+               (65535, "the whole alphabet")):
+    _wide("flat%d" % _m, [3] * _m, _t, path="small" if _m <= 640 else "wide1" if _m <= 4096 else "wide2", limit=24, tier=None, binds=False, in_lds=_m <= 16384)
+FLAT_WIDE_CLUSTERED = ("flat640", "flat641", "flat4096", "flat4097", "flat15360", "flat15361", "flat16384", "flat16385")
+_wide("sparse300", [3] * 300, "the wide book by span, 16-bit limit", spacing=16, path="wide1", limit=16, tier=None, binds=False, in_lds=True)
+_wide("sparse600", [3] * 600, "the wide book by span", spacing=16, path="wide1", limit=24, tier=None, binds=False, in_lds=True)
+_wide("sparse-fib16", [3] * 290 + [1200 * f for f in _fib(12)], "the wide book by span, the 16-bit limit binds", spacing=16,
+      path="wide1", limit=16, tier=None, binds=True, in_lds=True)
+_wide("tier1", _HEAD + _TAIL, "tier 1, 4097 rare symbols: 13 index bits, the class's weight is the floor's",
+      path="wide2", limit=24, tier=(3072, 1), n_rare=4097, rare_bits=13, floor=True, binds=False, in_lds=True)
+_wide("tier1-pow2", _HEAD + _TAIL[1:], "tier 1, 4096 rare symbols: 12 index bits, Kraft sum exactly 1, the class's weight its own",
+      path="wide2", limit=24, tier=(3072, 1), n_rare=4096, rare_bits=12, floor=False, binds=False, in_lds=True)
+_wide("tier1-keep", _geometric(3072, 2040, 45) + _TAIL, "3072 frequent symbols: above + oct[k] == keep",
+      path="wide2", limit=24, tier=(3072, 1), n_rare=4097, rare_bits=13, floor=True, binds=False, in_lds=True)
+_wide("tier1-keep+1", _geometric(3073, 2040, 45) + _TAIL, "3073 symbols above the tail: the walk stops four octaves higher, in the head",
+      path="wide2", limit=24, tier=(3072, 5), n_rare=4375, rare_bits=13, floor=False, binds=False, in_lds=True)
+_wide("tier1-heavy", _HEAD + [3] * 4097, "the rare class holds between 1/256 and 1/64 of the stream: its weight is its own",
+      path="wide2", limit=24, tier=(3072, 1), n_rare=4097, rare_bits=13, floor=False, binds=False, in_lds=True)
+# the licence at equality: the estimate 8541 * 64 == total, the head's first count taking up the difference; and one occurrence short of it
+_EDGE = _geometric(3000, 300, 45)
+_EDGE[0] += 64 * _TAIL_MASS - sum(_EDGE) - sum(_TAIL)
+_wide("tier1-edge", _EDGE + _TAIL, "mass * 64 == total: tier 1 taken", path="wide2", limit=24, tier=(3072, 1), n_rare=4097, rare_bits=13, floor=False,
+      binds=False, in_lds=True)
+_wide("tier1-edge-1", [_EDGE[0] - 1] + _EDGE[1:] + _TAIL, "mass * 64 == total + 1: tier 1 rejected, tier 2 skipped", path="wide2", limit=24, tier=None,
+      binds=False, in_lds=True)
+_wide("tier2", [100000] + [64] * 12000 + [1] * 8000, "tier 1 rejected, tier 2 taken: 12 002 keys", path="wide2", limit=24, tier=(12288, 0), n_rare=8000,
+      rare_bits=13, floor=False, binds=False, in_lds=True)
+_wide("deep24w", [1] * 1100 + _fib(31)[15:], "1116 dense symbols, unlimited height 27 > 24: the wide path's clamp and repair three levels deep",
+      path="wide1", limit=24, tier=None, binds=True, in_lds=True)
+# tier 1's 4097 rare symbols under a Fibonacci head: the class — its weight is the floor's, 1/256 of the stream + 1 — takes the place of the
+# term 17711, so the tree over the frequent symbols and the class is the chain itself: height 27
+_wide("deep24w2", [f for f in _fib(31)[2:] if f != 17711] + [1] * 4097, "tier 1 AND the limit binds in the frequent class (height 27)", path="wide2",
+      limit=24, tier=(3072, 0), n_rare=4097, rare_bits=13, floor=True, binds=True, in_lds=True)
+# (deep30w — deep24w with a natural height of 30 — would have 15 M elements, beyond the 8 M a test's array may have: left out)
+WIDE_1D = sorted(WIDE_FAMILIES)
+# the 3-D form (f64, balanced): the N-d prefix sum of deltas within +-3549 stays below the lattice's 2^22
+WIDE_SHAPE_ND = {"tier1": (33, 128, 384)}
+
 
 def deltas_by_count(counts):
     """-> (delta per entry of `counts`): 0, +1, -1, +2, ... by falling count (ties: by position), so the running sum stays small"""
@@ -59,13 +129,39 @@ def deltas_by_count(counts):
     return np.where(rank % 2 == 1, (rank + 1) // 2, -(rank // 2))
 
 
-def delta_stream(counts, order, seed=1):
+def balanced(deltas, rng):
+    """-> the deltas in an order whose running sum stays within max(|sum of all deltas|, the largest |delta|): the next one comes from
+    the shuffled negative pool while the running sum is positive, else from the positive pool (when one pool is empty the sum walks
+    straight to its end value); the zeros, which move nothing, are dealt among the others at random"""
+    deltas = np.asarray(deltas, dtype=np.int64)
+    neg = rng.permutation(deltas[deltas < 0]).tolist()
+    pos = rng.permutation(deltas[deltas > 0]).tolist()
+    walk, run, i, j = [0] * (len(neg) + len(pos)), 0, 0, 0
+    for t in range(len(walk)):
+        if (run > 0 and i < len(neg)) or j == len(pos):
+            v = neg[i]
+            i += 1
+        else:
+            v = pos[j]
+            j += 1
+        run += v
+        walk[t] = v
+    out = np.zeros(deltas.size, dtype=np.int64)
+    moved = np.ones(deltas.size, dtype=bool)
+    moved[rng.choice(deltas.size, size=deltas.size - len(walk), replace=False)] = False
+    out[moved] = walk
+    return out
+
+
+def delta_stream(counts, order, seed=1, spacing=1):
     """-> int64 deltas, sum(counts) of them, every entry i of `counts` counts[i] times, placed by `order`:
     clustered  rarest symbols first, every symbol's occurrences together: one run of the longest code words from element 0 on
     shuffled   a seeded shuffle
-    periodic   the rarest occurrences at every 512-th position and its two neighbours, the others shuffled around them"""
+    periodic   the rarest occurrences at every 512-th position and its two neighbours, the others shuffled around them
+    balanced   a seeded order whose running sum stays small (balanced()): alphabets of up to 65 535 symbols
+    spacing: the deltas are multiples of it — a sparse alphabet, one symbol every `spacing` bins"""
     counts = np.asarray(counts, dtype=np.int64)
-    delta = deltas_by_count(counts)
+    delta = deltas_by_count(counts) * int(spacing)
     by_rarity = np.argsort(counts, kind="stable")
     stream = np.repeat(delta[by_rarity], counts[by_rarity])  # clustered
     n = stream.size
@@ -74,6 +170,8 @@ def delta_stream(counts, order, seed=1):
         return stream
     if order == "shuffled":
         return rng.permutation(stream)
+    if order == "balanced":
+        return balanced(stream, rng)
     if order == "periodic":
         k = np.arange(PERIOD, n - 1, PERIOD)
         places = np.stack([k - 1, k, k + 1], axis=1).reshape(-1)
@@ -110,12 +208,18 @@ def assert_prescribed(x, codes):
         assert not bad.any() and not far.any()
 
 
+@functools.lru_cache(maxsize=2)
+def _deltas(family, order, counts):
+    """(f32 and f64 of one family share the stream)"""
+    return delta_stream(counts, order, spacing=SPACING.get(family, 1))
+
+
 @functools.lru_cache(maxsize=4)
 def _crafted(family, order, dtype_name, shape):
     counts = list(FAMILIES[family][0])
     if shape is not None:
         counts[int(np.argmax(counts))] += int(np.prod(shape)) - sum(counts)
-    x, codes = array_from_deltas(delta_stream(counts, order), np.dtype(dtype_name), shape)
+    x, codes = array_from_deltas(_deltas(family, order, tuple(counts)), np.dtype(dtype_name), shape)
     x.setflags(write=False)
     codes.setflags(write=False)
     return x, codes
@@ -129,7 +233,7 @@ def crafted(family, order, dtype, shape=None):
 def histogram(family):
     """-> (counts by symbol over [sym_min, sym_max], sym_min) of a family's stream"""
     counts = np.asarray(FAMILIES[family][0], dtype=np.int64)
-    sym = deltas_by_count(counts) + RADIUS
+    sym = deltas_by_count(counts) * SPACING.get(family, 1) + RADIUS
     freq = np.zeros(int(sym.max() - sym.min()) + 1, dtype=np.int64)
     freq[sym - sym.min()] = counts
     return freq, int(sym.min())

@@ -11,7 +11,7 @@ import sys
 import pytest
 
 import sz3_amd
-from sweep_seeds import PARTIAL_SWEEP_N, PARTIAL_SWEEP_SEEDS, SAMPLED_SWEEP_N, SAMPLED_SWEEP_SEEDS
+from sweep_seeds import PARTIAL_SWEEP_N, PARTIAL_SWEEP_SEEDS, SAMPLED_SWEEP_N, SAMPLED_SWEEP_SEEDS, WIDEBOOK_SWEEP_N, WIDEBOOK_SWEEP_SEEDS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -184,4 +184,16 @@ def test_sampled_path_sweep(seed):
     context after another array and a decoder form byte for byte. The same seeds pass the model's premises and the coverage floors in
     test_sampled_sweep_cpu.py."""
     out = _run("sampled_sweep.py", seed, SAMPLED_SWEEP_N)
+    assert "failures 0" in out, out[-3000:]
+
+
+@pytest.mark.parametrize("seed", WIDEBOOK_SWEEP_SEEDS)
+def test_wide_book_sweep(seed):
+    """tests/checks/widebook_sweep.py: per seed six drawn histograms of 300 .. 65 535 symbols — flat, geometric, Zipf, a head
+    over a rare tail for either tier, Fibonacci tails deeper than the 24- and the 16-bit limit, half of them at a boundary of the three code-book
+    constructions — as arrays of 50 K .. 1.5 M elements whose code stream has exactly those counts: the first payload held to the numpy model in
+    full (codes, header, the book against widebook_model's tier rule, class weight, Kraft sum and exact optimum, the chunk table, the slow decoder
+    on the picked chunks, the decode bit for bit), then the context's second call, one encoder form and one decoder form byte for byte. The same
+    seeds pass the model's premises and the coverage floors in test_widebook_sweep_cpu.py."""
+    out = _run("widebook_sweep.py", seed, WIDEBOOK_SWEEP_N)
     assert "failures 0" in out, out[-3000:]
