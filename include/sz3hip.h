@@ -836,6 +836,75 @@ int sz3hip_gradient_plan_for(const sz3hip_config *conf, int dataType, const sz3h
 int sz3hip_stream_gradient(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_gradient_opts *opts, void *stream);
 int sz3hip_gradient_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in,
                            const sz3hip_gradient_opts *opts, void *d_out, const int64_t *strides_out, void *stream);
+/* ---- boxes composited along an axis: front to back through an RGBA table ----
+ * The emission-absorption image of a brick: every column of a box folded front to back through a colour / opacity transfer function.
+ * sz3hip_stream_composite takes sz3hip_stream_request's own sz3hip_tile_req, 1 .. SZ3HIP_MAX_BOXES boxes that each name their own level
+ * (geometry, codes and wording are that call's, "box <i>: " in front; repeated and overlapping boxes are allowed; everything is checked
+ * before anything is launched or written), and runs the same launch sequence with ONE compositing launch in the strided gather's place:
+ * stats.launches_last_request is the same boxes' sz3hip_stream_request's (a handle that keeps the full array: 1). It counts as a request
+ * in sz3hip_stream_stats. One set of options holds for the whole call.
+ * The output of a box is the box with extent 1 along `axis` (keepdim): d_out and strides[] describe a view in OUTPUT elements, all N
+ *   strides given (or none: contiguous); the stride at `axis` is not read, as the stride of any extent-1 dimension is not. The view
+ *   rules, the alignment rule and the overlap rule are the request's, applied to that collapsed box with the output element's size.
+ *   SZ3HIP_COMPOSITE_RGBA32F: an element is four floats r, g, b, a (16 bytes), d_out aligned to 16. The colours are PREMULTIPLIED by
+ *   the opacity (the fold's sums as they are). SZ3HIP_COMPOSITE_RGBA8: 4 bytes, byte 0 = r .. byte 3 = a, d_out aligned to 4.
+ * The table: d_lut, lut_n entries (2 .. SZ3HIP_MAX_LUT) of four floats r, g, b, a in device memory, 16-byte aligned. Its contents are not
+ *   checked (as the map's are not): the rule is plain arithmetic on whatever is there.
+ * The rule, bit-defined; all arithmetic is IEEE double, each operation rounded on its own, nothing contracted:
+ *   1. The column of an output point is the box's values v_0 .. v_{E-1} along `axis` — exactly the values sz3hip_stream_request would
+ *      deliver —, visited ascending, or descending under SZ3HIP_COMPOSITE_REVERSE, each taken as x = (double)v.
+ *   2. A NaN point is skipped: it adds nothing and stops nothing. Any other point (+-Inf are ordinary values) has
+ *        code = x < lo ? 0 : x >= hi ? M : min((uint64_t)((x - lo) * scale), M),   M = lut_n - 1, scale = (double)(M + 1) / (hi - lo)
+ *      — the mapping's code (sz3hip_stream_map) to the letter.
+ *   3. The entry at `code`: r, g, b, a widened to double (exact). The opacity after s squarings: a itself when s == 0, otherwise
+ *        t = 1.0 - a; s times: t = t * t; a = 1.0 - t
+ *      with s = level_bias + (SZ3HIP_COMPOSITE_LEVEL_OPACITY ? the box's level : 0): a level-k box steps 2^k times as far per sample.
+ *      sz3hip_composite_device has no level: s = level_bias.
+ *   4. The fold: the state (R, G, B, A) starts at +0.0 — under SZ3HIP_COMPOSITE_ACCUMULATE at the four floats already at the output
+ *      element, widened. Per visited point, in this order:
+ *        w = (1.0 - A) * a;  R = R + w * r;  G = G + w * g;  B = B + w * b;  A = A + w
+ *      and after a point is folded the column stops if A >= cutoff (cutoff +Inf never stops).
+ *   5. The store. RGBA32F: (float) of each, rounded to nearest even. RGBA8: per channel q = c * 255.0 + 0.5 and the byte is
+ *        q > 0 ? (q >= 255 ? 255 : (uint8_t)q) : 0      (a NaN gives 0).
+ * The output depends on the column, the box's level and the options alone — not on the route, the grid, the other boxes or the handle's
+ * kind: sz3hip_stream_composite is byte-identical to sz3hip_composite_device over the same values with level_bias raised by the box's
+ * level when LEVEL_OPACITY is set. A column composited in two consecutive boxes, the second under ACCUMULATE into the first's RGBA32F
+ * output, is defined by the rule too; it is NOT byte-equal to the one-box result, because the carry passes through float. No
+ * device-to-host copy, no host synchronisation beyond a request's own waits; no workspace.
+ * Errors (SZ3HIP_EINVAL): opts NULL; out_type not one of the two; unknown flag bits; reserved not 0; axis >= N; lo or hi not finite,
+ * hi <= lo, or hi - lo not finite; cutoff NaN or <= 0; lut_n outside 2 .. SZ3HIP_MAX_LUT; d_lut NULL or not 16-byte aligned; s > 30 at
+ * some box's level; ACCUMULATE with RGBA8; d_out NULL or not aligned to the output element; the request's view and overlap cases on the
+ * collapsed box; and sz3hip_stream_request's for the boxes. Integer types: SZ3HIP_EUNSUPPORTED. A refused call launches and writes
+ * nothing, and the handle serves the next request.
+ * sz3hip_composite_device: the same fold of ONE plain view in device memory (what a handle that keeps the full array runs, in one
+ * launch): N, dims, strides_in and d_in's rules are sz3hip_map_device's (x stride 2, stride-0 broadcasts and transposed views included),
+ * the options checked before any pointer; d_out / strides_out: the view of the collapsed array in output elements (strides_out NULL:
+ * contiguous). Asynchronous on `stream`.
+ * sz3hip_composite_plan_for: a pure function (no device) with sz3hip_stream_composite's checks. */
+#define SZ3HIP_COMPOSITE_RGBA32F 0u
+#define SZ3HIP_COMPOSITE_RGBA8   1u
+#define SZ3HIP_COMPOSITE_REVERSE       1u /* flags: visit the column descending */
+#define SZ3HIP_COMPOSITE_LEVEL_OPACITY 2u /*        a box of level k has its opacities squared k more times */
+#define SZ3HIP_COMPOSITE_ACCUMULATE    4u /*        the fold starts at the output element's four floats (RGBA32F only) */
+typedef struct sz3hip_composite_opts {  /* 56 bytes */
+    double lo, hi;                      /* the window: finite, hi > lo */
+    double cutoff;                      /* a column stops once A >= cutoff: above 0, +Inf never stops */
+    uint32_t axis, out_type;            /* 0 .. N-1, slowest first: the dimension that is folded away; SZ3HIP_COMPOSITE_RGBA* */
+    uint32_t flags, lut_n;              /* SZ3HIP_COMPOSITE_REVERSE | _LEVEL_OPACITY | _ACCUMULATE; 2 .. SZ3HIP_MAX_LUT */
+    uint32_t level_bias, reserved;      /* squarings of every entry's 1 - a, 0 .. 30 together with the box's level; 0 */
+    const void *d_lut;                  /* device, lut_n entries of four floats r, g, b, a; 16-byte aligned */
+} sz3hip_composite_opts;
+typedef struct sz3hip_composite_plan {  /* 48 bytes */
+    uint32_t n; int32_t finest_level, coarsest_level, n_levels;
+    uint64_t points, scratch_elems;     /* sz3hip_request_plan_for's */
+    uint64_t out_points;                /* the sum over the boxes of points / ext[axis] */
+    uint32_t out_elem_bytes, reserved;  /* 16 or 4 */
+} sz3hip_composite_plan;
+int sz3hip_composite_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n,
+                              const sz3hip_composite_opts *opts, sz3hip_composite_plan *out);
+int sz3hip_stream_composite(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_composite_opts *opts, void *stream);
+int sz3hip_composite_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in,
+                            const sz3hip_composite_opts *opts, void *d_out, const int64_t *strides_out, void *stream);
 /* development switch, process-wide: a request of a handle runs its coarsest c levels in ONE launch (one workgroup per box walks first point,
  * regrids and passes with a barrier between steps), c the largest count such that for every box every pass of those levels has at most
  * `points` points. 0: off — the request issues exactly the launches sz3hip_decompress_device_tiles issues. Environment twin, read once when

@@ -248,6 +248,18 @@ class _CGradientPlan(C.Structure):
                 ("scratch_elems", C.c_uint64), ("out_points", C.c_uint64), ("out_elem_bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class _CCompositeOpts(C.Structure):
+    # sz3hip_composite_opts: 56 bytes
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("cutoff", C.c_double), ("axis", C.c_uint32), ("out_type", C.c_uint32), ("flags", C.c_uint32),
+                ("lut_n", C.c_uint32), ("level_bias", C.c_uint32), ("reserved", C.c_uint32), ("d_lut", C.c_void_p)]
+
+
+class _CCompositePlan(C.Structure):
+    # sz3hip_composite_plan: 48 bytes
+    _fields_ = [("n", C.c_uint32), ("finest_level", C.c_int32), ("coarsest_level", C.c_int32), ("n_levels", C.c_int32), ("points", C.c_uint64),
+                ("scratch_elems", C.c_uint64), ("out_points", C.c_uint64), ("out_elem_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _CStreamStats(C.Structure):
     """struct sz3hip_stream_stats (include/sz3hip.h)"""
     _fields_ = [("fast", C.c_uint32), ("huffman_stages", C.c_uint32), ("launches_last_request", C.c_uint32), ("chain_levels_last_request", C.c_uint32),
@@ -443,6 +455,12 @@ def lib():
     L.sz3hip_stream_gradient.argtypes = [C.c_void_p, P(_CTileReq), C.c_uint32, P(_CGradientOpts), C.c_void_p]
     L.sz3hip_gradient_device.restype = C.c_int
     L.sz3hip_gradient_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CGradientOpts), C.c_void_p, P(C.c_int64), C.c_void_p]
+    L.sz3hip_composite_plan_for.restype = C.c_int
+    L.sz3hip_composite_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CCompositeOpts), P(_CCompositePlan)]
+    L.sz3hip_stream_composite.restype = C.c_int
+    L.sz3hip_stream_composite.argtypes = [C.c_void_p, P(_CTileReq), C.c_uint32, P(_CCompositeOpts), C.c_void_p]
+    L.sz3hip_composite_device.restype = C.c_int
+    L.sz3hip_composite_device.argtypes = [C.c_int, C.c_int, P(C.c_uint64), C.c_void_p, P(C.c_int64), P(_CCompositeOpts), C.c_void_p, P(C.c_int64), C.c_void_p]
     L.sz3hip_request_plan_for.restype = C.c_int
     L.sz3hip_request_plan_for.argtypes = [P(_CConfig), C.c_int, P(_CTileReq), C.c_uint32, P(_CRequestPlan)]
     L.sz3hip_stream_close.restype = None
@@ -1681,6 +1699,125 @@ def gradient_points(tensor, op, axis=0, spacing=None, out_dtype=None, interior=F
     return out
 
 
+COMPOSITE_RGBA32F, COMPOSITE_RGBA8 = 0, 1                                    # SZ3HIP_COMPOSITE_RGBA*
+COMPOSITE_REVERSE, COMPOSITE_LEVEL_OPACITY, COMPOSITE_ACCUMULATE = 1, 2, 4   # SZ3HIP_COMPOSITE_* flags
+_COMPOSITE_TYPES = {"rgba32f": (COMPOSITE_RGBA32F, "float32"), "rgba8": (COMPOSITE_RGBA8, "int32")}
+
+
+def _composite_opts(axis, N, lut, lo, hi, out_type, reverse, level_opacity, accumulate, cutoff, level_bias):
+    """the options struct and the outputs' dtype name ("float32": a last dimension of 4; "int32": the four bytes of an RGBA8 element).
+    lut: a contiguous float32 tensor of shape (2 .. 1024, 4) on the device — or, for a plan, an int: the entry count (the table's address
+    is then a placeholder)"""
+    if not isinstance(out_type, str) or out_type.lower() not in _COMPOSITE_TYPES:
+        raise ValueError("out_type is 'rgba32f' or 'rgba8' (got %r)" % (out_type,))
+    code, name = _COMPOSITE_TYPES[out_type.lower()]
+    axis = int(axis)
+    if not -N <= axis < N:
+        raise ValueError("axis %d is not one of the %d dimensions" % (axis, N))
+    o = _CCompositeOpts()
+    o.lo, o.hi, o.cutoff = float(lo), float(hi), float(cutoff)
+    o.axis = axis % N
+    o.out_type = code
+    o.flags = (COMPOSITE_REVERSE if reverse else 0) | (COMPOSITE_LEVEL_OPACITY if level_opacity else 0) | (COMPOSITE_ACCUMULATE if accumulate else 0)
+    o.level_bias = int(level_bias)
+    if isinstance(lut, (int, np.integer)):
+        o.lut_n = int(lut)
+        o.d_lut = 1 << 39
+    else:
+        if not _is_tensor(lut) or str(lut.dtype) != "torch.float32" or lut.dim() != 2 or int(lut.shape[1]) != 4 or not lut.is_contiguous():
+            raise ValueError("lut is a contiguous float32 tensor of shape (entries, 4): r, g, b, a per entry")
+        if not _gpu_tensor(lut):
+            raise ValueError("lut must be on a HIP device (it is on %s)" % lut.device)
+        o.lut_n = int(lut.shape[0])
+        o.d_lut = lut.data_ptr()
+    return o, name
+
+
+def _composite_reqs(N, items, shapes, arr, name, axis, device, alloc):
+    """the request structs over out tensors of the collapsed boxes' shapes — float32 with a last dimension 4, or int32 —; alloc: missing
+    outputs are allocated (else given placeholders that overlap no other, for the plan)"""
+    import sys
+    torch = sys.modules.get("torch")
+    vec = name == "float32"
+    elem = 16 if vec else 4
+    reqs = (_CTileReq * max(len(items), 1))()
+    outs = []
+    at = 1 << 40
+    for i, (it, shape) in enumerate(zip(items, shapes)):
+        flat = tuple(1 if j == axis else int(v) for j, v in enumerate(shape))
+        full = flat + (4,) if vec else flat
+        t = it[3] if len(it) == 4 else None
+        if t is None and alloc:
+            t = torch.empty(full, dtype=getattr(torch, name), device=device)
+        reqs[i].level = int(it[0])
+        reqs[i].box = arr[i]
+        if t is not None:
+            if str(t.dtype) != "torch." + name or tuple(t.shape) != full or (alloc and (not _gpu_tensor(t) or t.device != device)):
+                raise ValueError("item %d: out must be a %s tensor of shape %s%s" % (i, name, full, " on %s" % device if alloc else ""))
+            reqs[i].d_out = t.data_ptr()
+            reqs[i].strides[:N] = _vector_strides(t, 4, "item %d" % i) if vec else [int(v) for v in t.stride()]
+        else:
+            reqs[i].d_out = at
+            at += (int(np.prod(flat, dtype=np.uint64)) * elem + 255) & ~255
+        outs.append(t)
+    return reqs, outs
+
+
+def composite_plan(conf, dtype, items, axis, lut, lo, hi, out_type="rgba32f", reverse=False, level_opacity=False, accumulate=False, cutoff=float("inf"),
+                   level_bias=0):
+    """what one Stream.composite for `items` touches (sz3hip_composite_plan_for), without a device: `items` are Stream.composite's — (level,
+    lo, shape) or (level, lo, shape, out) — and the call's own checks run, the views and overlaps of the collapsed boxes in OUTPUT elements
+    included. `lut`: the table, or an int (the entry count). Returns a dict with request_plan's fields, out_points and out_elem_bytes."""
+    items = _project_items(items)
+    dt = _np_dtype(dtype)
+    opts, name = _composite_opts(axis, conf.N, lut, lo, hi, out_type, reverse, level_opacity, accumulate, cutoff, level_bias)
+    arr, shapes = _boxes(conf.N, [(it[1], it[2]) for it in items])
+    reqs, _ = _composite_reqs(conf.N, items, shapes, arr, name, int(opts.axis), None, False)
+    plan = _CCompositePlan()
+    _check(lib().sz3hip_composite_plan_for(C.byref(conf._c), _dtype_id(dt), reqs, len(items), C.byref(opts), C.byref(plan)))
+    return {k: int(getattr(plan, k)) for k, _ in _CCompositePlan._fields_ if k != "reserved"}
+
+
+def composite_points(tensor, axis, lut, lo, hi, out_type="rgba32f", reverse=False, accumulate=False, cutoff=float("inf"), level_bias=0, out=None, stream=None):
+    """one float32 / float64 torch tensor of 1 .. 4 dimensions on a HIP device composited front to back along `axis` through the RGBA table
+    `lut` (sz3hip_composite_device): what Stream.composite runs per box, over a plain view — any strides that are not negative. A point's
+    value picks an entry by the window [lo, hi) as map's codes do; per visited point w = (1 - A) * a, the colours gain w * r, g, b and A
+    gains w, in IEEE double — bit-defined; NaN points are skipped; a column stops once A >= cutoff. reverse: back to front in index terms.
+    level_bias: every entry's 1 - a is squared that many times first. "rgba32f": a float32 tensor of the input's shape with 1 at `axis`
+    plus a last dimension 4 (premultiplied colours, opacity) — a given `out` must have that dimension contiguous and its other strides
+    divisible by 4; accumulate: the fold starts from what `out` holds. "rgba8": an int32 tensor, byte 0 = r .. byte 3 = a. Asynchronous
+    on `stream`; returns `out`."""
+    if not _is_tensor(tensor):
+        raise TypeError("composite_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
+    if not _gpu_tensor(tensor):
+        raise ValueError("composite_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
+    tname = str(tensor.dtype).replace("torch.", "")
+    if tname not in _SZ_TYPES:
+        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
+    if tensor.numel() == 0 or not 1 <= tensor.dim() <= 4:
+        raise ValueError("composite_points: the tensor is empty or does not have 1 .. 4 dimensions")
+    import torch
+    N = tensor.dim()
+    opts, name = _composite_opts(axis, N, lut, lo, hi, out_type, reverse, False, accumulate, cutoff, level_bias)
+    if isinstance(lut, (int, np.integer)) or lut.device != tensor.device:
+        raise ValueError("composite_points: lut must be a tensor on %s" % tensor.device)
+    vec = name == "float32"
+    flat = tuple(1 if j == int(opts.axis) else int(d) for j, d in enumerate(tensor.shape))
+    full = flat + (4,) if vec else flat
+    if out is None:
+        if accumulate:
+            raise ValueError("composite_points: accumulate needs `out`, the image to go on from")
+        out = torch.empty(full, dtype=getattr(torch, name), device=tensor.device)
+    if not _gpu_tensor(out) or str(out.dtype) != "torch." + name or tuple(out.shape) != full or out.device != tensor.device:
+        raise ValueError("composite_points: out must be a %s tensor of shape %s on %s" % (name, full, tensor.device))
+    dims = [int(d) for d in tensor.shape]
+    sin = [int(v) for v in tensor.stride()]
+    sout = _vector_strides(out, 4, "composite_points") if vec else [int(v) for v in out.stride()]
+    _check(lib().sz3hip_composite_device(_SZ_TYPES[tname], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*sin), C.byref(opts),
+                                         out.data_ptr(), (C.c_int64 * N)(*sout), _stream_handle(tensor.device, stream)))
+    return out
+
+
 def set_chain_points(points):
     """development switch (sz3hip_debug_chain_points): a Stream request runs its coarsest levels — those whose every pass has at most
     `points` points for every box — in one launch; 0 switches the chain off"""
@@ -1874,6 +2011,30 @@ class Stream:
         arr, shapes = _boxes(N, [(it[1], it[2]) for it in items])
         reqs, outs = _gradient_reqs(N, items, shapes, arr, name, opts, self.device, True)
         _check(lib().sz3hip_stream_gradient(self._h, reqs, len(items), C.byref(opts), _stream_handle(self.device, stream)))
+        return outs
+
+    def composite(self, items, axis, lut, lo, hi, out_type="rgba32f", reverse=False, level_opacity=False, accumulate=False, cutoff=float("inf"),
+                  level_bias=0, stream=None):
+        """boxes composited front to back along one axis through an RGBA transfer function (sz3hip_stream_composite):
+        `items` are request's — (level, lo, shape) or (level, lo, shape, out) — with `out` a view of OUTPUT elements of the box's shape with
+        1 at `axis`. `lut`: a contiguous float32 tensor of shape (2 .. 1024, 4) on the device, r, g, b, a per entry; the window [lo, hi)
+        picks a point's entry as map's codes do. Per visited point w = (1 - A) * a, the colours gain w * r, g, b and A gains w, in IEEE
+        double: bit-defined. NaN points are skipped; a column stops once A >= cutoff. reverse: the column is visited descending.
+        level_opacity: a box of level k has every entry's 1 - a squared k more times (it steps 2**k times as far per sample); level_bias:
+        squarings for every box. "rgba32f": float32 tensors with a last dimension 4 (premultiplied colours, opacity) — a given `out` must
+        have it contiguous and its other strides divisible by 4; accumulate: the fold goes on from what `out` holds. "rgba8": int32
+        tensors, byte 0 = r .. byte 3 = a. The request's launch sequence with one compositing launch in the gather's place. Missing
+        outputs are allocated. Asynchronous on `stream`, as tiles. Returns the list of tensors."""
+        items = _project_items(items)
+        N = self.conf.N
+        opts, name = _composite_opts(axis, N, lut, lo, hi, out_type, reverse, level_opacity, accumulate, cutoff, level_bias)
+        if isinstance(lut, (int, np.integer)) or lut.device != self.device:
+            raise ValueError("lut must be a tensor on %s" % self.device)
+        if accumulate and any(len(it) != 4 for it in items):
+            raise ValueError("accumulate needs every item's `out`, the image to go on from")
+        arr, shapes = _boxes(N, [(it[1], it[2]) for it in items])
+        reqs, outs = _composite_reqs(N, items, shapes, arr, name, int(opts.axis), self.device, True)
+        _check(lib().sz3hip_stream_composite(self._h, reqs, len(items), C.byref(opts), _stream_handle(self.device, stream)))
         return outs
 
     def tile(self, level, lo, shape, out=None, stream=None):

@@ -492,12 +492,18 @@ struct szk_reduce_hist {  // nbins 0: no histogram
 // grd: the options, the axis counted in the record's four places; grd_boxes: HOST, one szk_gradient_box (SZK_GRADIENT_WORDS words) per box in
 // the request's order — the launchers put them into the table behind the records of every launch, in the records' order; grd_threads: the
 // largest box's output points
+// kind SZK_SINK_COMPOSITE (kernels: sz3hip_composite.hip): the boxes folded front to back along one axis through an
+// RGBA table, ONE launch in the gather's place on every route, no final. As the gradient's, a record's `dst` word is the box's index in the
+// request and `dstr` is not read. cmp: the options, the axis counted in the record's four places; cmp_boxes: HOST, one szk_composite_box
+// (SZK_COMPOSITE_WORDS words) per box in the request's order — the launchers put them into the table behind the records of every launch,
+// in the records' order; cmp_threads: the largest box's output points; cmp_rows: every box's dimensions behind the axis have extent 1
 #define SZK_SINK_REDUCE 0
 #define SZK_SINK_SELECT 1
 #define SZK_SINK_MAP 2
 #define SZK_SINK_SAMPLE 3
 #define SZK_SINK_PROJECT 4
 #define SZK_SINK_GRADIENT 5
+#define SZK_SINK_COMPOSITE 6
 #define SZK_SELECT_OUT_WORDS 3
 struct szk_select_opts {
     double lo, hi;
@@ -509,6 +515,15 @@ struct szk_map_opts {
     uint32_t nan_code, lut_n;
     const uint32_t *d_lut;            // device, lut_n entries (LUT32)
 };
+// the code of a value in the window: sz3hip_reduce.hip's r_slot with nbins = M + 1, the outer slots folded into the end codes — the
+// mapping's and the compositing's one rule (the compositing skips a NaN before it asks)
+__host__ __device__ __forceinline__ uint32_t szk_map_code(double x, const szk_map_opts &o) {
+    if (x != x) return o.nan_code;
+    if (x < o.lo) return 0;
+    if (x >= o.hi) return o.M;
+    const uint64_t k = (uint64_t)((x - o.lo) * o.scale);
+    return (uint32_t)(k < (uint64_t)o.M ? k : (uint64_t)o.M);
+}
 // a texel's bytes (SZ3HIP_MAP_U8: 1; _U16, _F16: 2; _F32, _LUT32: 4)
 __host__ __device__ static inline uint32_t szk_map_out_bytes(uint32_t out_type) { return out_type == 1 ? 1u : out_type == 2 || out_type == 3 ? 2u : 4u; }
 // the packed form (one- and two-byte texels): a row of ext_x texels is cut at the destination's 4-byte boundaries; a row has at most this
@@ -547,6 +562,19 @@ struct szk_gradient_box {             // a box's output and grid steps; dstr and
     double scale[4];                  // spacing[a] * 2^level
 };
 #define SZK_GRADIENT_WORDS 9
+struct szk_composite_opts {
+    szk_map_opts win;                 // the window as the mapping's: lo, hi, scale, M = lut_n - 1, lut_n (out_type, nan_code, d_lut are not read)
+    double cutoff;
+    uint32_t axis, N;                 // the folded dimension's place among a record's four (4 - N + the caller's axis); the dimension count
+    uint32_t out_type, flags;         // SZ3HIP_COMPOSITE_RGBA*; SZ3HIP_COMPOSITE_* (LEVEL_OPACITY is worked into the boxes' s on the host)
+    const float *d_lut;               // device, win.lut_n * 4 floats
+};
+struct szk_composite_box {            // a box's output and its opacity correction; dstr holds its N entries in the LAST N of four places
+    void *dst;                        // device, the view's element [0, .., 0]
+    int64_t dstr[4];                  // in OUTPUT elements; 0 where the output's extent is 1 (the axis included)
+    uint64_t s;                       // squarings of 1 - a: level_bias + (LEVEL_OPACITY ? the box's level : 0), at most 30
+};
+#define SZK_COMPOSITE_WORDS 6
 struct szk_region_sink {
     szk_reduce_part *partials;
     void *d_stats;
@@ -569,7 +597,14 @@ struct szk_region_sink {
     szk_gradient_opts grd;
     const szk_gradient_box *grd_boxes;
     uint64_t grd_threads;
+    szk_composite_opts cmp;
+    const szk_composite_box *cmp_boxes;
+    uint64_t cmp_threads;
+    bool cmp_rows;
 };
+// the compositing's one launch over n records in device memory, the boxes' entries behind them (one box: record and entry by value)
+int szk_launch_region_composite(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
+                                uint32_t n, const szk_region_sink *sink, hipStream_t s);
 // the gradient's one launch over n records in device memory, the boxes' entries behind them (one box: record and entry by value)
 int szk_launch_region_gradient(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value,
                                uint32_t n, const szk_region_sink *sink, hipStream_t s);
@@ -600,7 +635,8 @@ uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n);
 // real views in output elements, one launch, the request's count; a sampling sink (kind SZK_SINK_SAMPLE): outs[i].dst is i, one launch, the
 // request's count, table_words with room for n * SZK_SAMPLE_WORDS more; a projecting sink (kind SZK_SINK_PROJECT): outs are the real views of
 // the collapsed boxes in output elements, one launch, the request's count; a gradient sink (kind SZK_SINK_GRADIENT): outs[i].dst is i, one
-// launch, the request's count, table_words with room for n * SZK_GRADIENT_WORDS more
+// launch, the request's count, table_words with room for n * SZK_GRADIENT_WORDS more; a compositing sink (kind SZK_SINK_COMPOSITE): as the
+// gradient's, with room for n * SZK_COMPOSITE_WORDS more
 int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                                 const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                                 void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,

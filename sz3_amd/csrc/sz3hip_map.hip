@@ -23,14 +23,8 @@ namespace {
 static_assert(sizeof(sz3hip_map_opts) == 48 && sizeof(sz3hip_map_plan) == 40, "the header's sizes");
 using Box = szk_region_gather_strided_box;
 
-// the code of a value in the window: sz3hip_reduce.hip's r_slot with nbins = M + 1, the outer slots folded into the end codes
-__device__ __forceinline__ uint32_t map_code(double x, const szk_map_opts &o) {
-    if (x != x) return o.nan_code;
-    if (x < o.lo) return 0;
-    if (x >= o.hi) return o.M;
-    const uint64_t k = (uint64_t)((x - o.lo) * o.scale);
-    return (uint32_t)(k < (uint64_t)o.M ? k : (uint64_t)o.M);
-}
+// the code of a value in the window (szk_map_code, sz3hip_kernels.h: the compositing's too)
+__device__ __forceinline__ uint32_t map_code(double x, const szk_map_opts &o) { return szk_map_code(x, o); }
 __device__ __forceinline__ float to_float(float v) { return v; }
 __device__ __forceinline__ float to_float(double v) { return (float)v; }
 __device__ __forceinline__ uint32_t float_bits(float f) {

@@ -828,6 +828,19 @@ static bool region_sink_tail(const szk_region_sink *sink, uint32_t n, uint64_t *
         }
         return true;
     }
+    if (sink && sink->kind == SZK_SINK_COMPOSITE) {  // (the boxes' entries in the RECORDS' order, as the gradient's)
+        constexpr uint64_t RW = SZK_WORDS(szk_region_gather_strided_box);
+        const uint64_t words = (uint64_t)n * SZK_COMPOSITE_WORDS;
+        if (!sink->cmp_boxes || *w < (uint64_t)n * RW || words > table_words || *w > table_words - words) return false;
+        const uint64_t recs = *w - (uint64_t)n * RW;
+        for (uint32_t r = 0; r < n; r++) {
+            szk_region_gather_strided_box b;
+            memcpy(&b, h_table + recs + r * RW, sizeof(b));
+            memcpy(h_table + *w, sink->cmp_boxes + (uintptr_t)b.dst, sizeof(szk_composite_box));
+            *w += SZK_COMPOSITE_WORDS;
+        }
+        return true;
+    }
     if (!sink || sink->kind != SZK_SINK_SELECT) return true;
     const uint64_t words = (uint64_t)n * SZK_SELECT_OUT_WORDS;
     if (!sink->sel_outs || words > table_words || *w > table_words - words) return false;
@@ -859,6 +872,11 @@ static int region_sink_launch(uint32_t *issued, const T *src, const szk_region_g
     }
     if (sink->kind == SZK_SINK_GRADIENT) {  // (one launch, per group where the request runs group by group; no final)
         if (szk_launch_region_gradient(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
+        region_count(issued);
+        return 0;
+    }
+    if (sink->kind == SZK_SINK_COMPOSITE) {  // (one launch, per group where the request runs group by group; no final)
+        if (szk_launch_region_composite(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
         region_count(issued);
         return 0;
     }
@@ -1069,7 +1087,7 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
         l.most = most;
         seq.push_back(l);
         // (a sampling's queries ride with every group's records; a selection's outputs with the request's one final)
-        if ((sink_final || (sink && (sink->kind == SZK_SINK_SAMPLE || sink->kind == SZK_SINK_GRADIENT))) && !region_sink_tail(sink, n, h_table, &w, table_words)) return -1;
+        if ((sink_final || (sink && (sink->kind == SZK_SINK_SAMPLE || sink->kind == SZK_SINK_GRADIENT || sink->kind == SZK_SINK_COMPOSITE))) && !region_sink_tail(sink, n, h_table, &w, table_words)) return -1;
     }
     // the chain's steps, behind the boxes' records: the chained launches in their order, a pass's shared part in front of its step(s)
     uint64_t steps_off = 0;
@@ -1381,7 +1399,8 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
             oo.push_back(outs[order[at]]);
         }
         const uint64_t need = szk_region_request_table_words(gg.data(), (uint32_t)gg.size()) + (sink && sink->kind == SZK_SINK_SAMPLE ? gg.size() * SZK_SAMPLE_WORDS : 0) +
-                              (sink && sink->kind == SZK_SINK_GRADIENT ? gg.size() * SZK_GRADIENT_WORDS : 0);
+                              (sink && sink->kind == SZK_SINK_GRADIENT ? gg.size() * SZK_GRADIENT_WORDS : 0) +
+                              (sink && sink->kind == SZK_SINK_COMPOSITE ? gg.size() * SZK_COMPOSITE_WORDS : 0);
         if (need > table_words || used > table_words - need) return -1;
         uint32_t issued = 0;
         const int rc = run_region_multi<T>(ip, gg.data(), (uint32_t)gg.size(), scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, nullptr,
@@ -1391,7 +1410,8 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
         total += issued;
         most_levels = std::max(most_levels, (uint32_t)gg[0].n_levels);
     }
-    if (sink && sink->kind != SZK_SINK_MAP && sink->kind != SZK_SINK_SAMPLE && sink->kind != SZK_SINK_PROJECT && sink->kind != SZK_SINK_GRADIENT) {  // ONE final for the request: the boxes' records once more, in the request's order, behind the groups' stretches
+    if (sink && sink->kind != SZK_SINK_MAP && sink->kind != SZK_SINK_SAMPLE && sink->kind != SZK_SINK_PROJECT && sink->kind != SZK_SINK_GRADIENT &&
+        sink->kind != SZK_SINK_COMPOSITE) {  // ONE final for the request: the boxes' records once more, in the request's order, behind the groups' stretches
         uint64_t need = (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box), most = 0;
         if (need > table_words || used > table_words - need) return -1;
         for (uint32_t i = 0; i < n; i++) {
@@ -1434,6 +1454,10 @@ int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_para
             if ((uintptr_t)outs[i].dst != i) return -1;
     } else if (sink && sink->kind == SZK_SINK_GRADIENT) {  // (as the sampling's)
         if (!sink->grd_boxes) return -1;
+        for (uint32_t i = 0; outs && i < n; i++)
+            if ((uintptr_t)outs[i].dst != i) return -1;
+    } else if (sink && sink->kind == SZK_SINK_COMPOSITE) {  // (as the gradient's)
+        if (!sink->cmp_boxes) return -1;
         for (uint32_t i = 0; outs && i < n; i++)
             if ((uintptr_t)outs[i].dst != i) return -1;
     } else if (sink && sink->kind == SZK_SINK_SELECT) {

@@ -26,6 +26,8 @@
 // sz3hip_stream_gradient takes the request's own boxes and leaves their derivatives by central differences — one axis,
 // the squared magnitude, the magnitude or the vector — in views of OUTPUT elements: the same geometry and sequence with one differentiating
 // launch (sz3hip_gradient.hip) in the gather's place; sz3hip_gradient_device is that gradient over one plain view.
+// sz3hip_stream_composite takes the request's own boxes and leaves each folded front to back along one axis through an
+// RGBA table — one compositing launch (sz3hip_composite.hip) in the gather's place; sz3hip_composite_device is that fold over one plain view.
 // A handle serves one request at a time; it is not thread-safe.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1399,28 +1401,36 @@ int project_axis(const sz3hip_project_opts *opts, int N, szk_project_opts *po) {
     po->N = (uint32_t)N;
     return 0;
 }
-// the views of the collapsed boxes — the requests with extent 1 at the axis, by the mapping's rules with the output element's size — and the
-// sink: a thread per output point of the largest box; the body through LDS where the axis is every box's fastest dimension that counts
-int project_views(int N, uint32_t axis, const sz3hip_tile_req *reqs, uint32_t n, szk_region_sink *sink, std::vector<ReqView> &vs) {
-    const bool index_op = project_index_op(sink->prj.op);
+// the views of the collapsed boxes — the requests with extent 1 at the axis, by the mapping's rules with the output element's size osz;
+// *threads: the largest box's output points; *rows: the axis is every box's fastest dimension that counts; *out_points (or NULL): their sum
+int collapsed_views(int N, uint32_t axis, const sz3hip_tile_req *reqs, uint32_t n, size_t osz, std::vector<ReqView> &vs, uint64_t *threads, bool *rows,
+                    uint64_t *out_points) {
     std::vector<sz3hip_tile_req> flat(reqs, reqs + n);
-    for (uint32_t i = 0; i < n; i++) {
-        if (index_op && reqs[i].box.ext[axis] > 0xFFFFFFFFull)
-            return fail(SZ3HIP_EINVAL, "box %u: the extent along the axis (%llu) is beyond an index op's uint32_t (2^32 - 1 at most)", i, (unsigned long long)reqs[i].box.ext[axis]);
-        flat[i].box.ext[axis] = 1;
-    }
-    const int rc = map_views(N, flat.data(), n, project_out_bytes(sink->prj), vs);
+    for (uint32_t i = 0; i < n; i++) flat[i].box.ext[axis] = 1;
+    const int rc = map_views(N, flat.data(), n, osz, vs);
     if (rc) return rc;
-    sink->kind = SZK_SINK_PROJECT;
-    sink->prj_threads = 1;
-    sink->prj_rows = true;
+    *threads = 1;
+    *rows = true;
+    if (out_points) *out_points = 0;
     for (uint32_t i = 0; i < n; i++) {
         uint64_t outs = 1;
         for (int j = 0; j < N; j++) outs *= flat[i].box.ext[j];
-        sink->prj_threads = std::max(sink->prj_threads, outs);
-        for (int j = (int)axis + 1; j < N; j++) sink->prj_rows = sink->prj_rows && reqs[i].box.ext[j] == 1;
+        *threads = std::max(*threads, outs);
+        if (out_points) *out_points += outs;
+        for (int j = (int)axis + 1; j < N; j++) *rows = *rows && reqs[i].box.ext[j] == 1;
         vs[i].str[axis] = 0;  // (not read)
     }
+    return 0;
+}
+// ... and the projecting sink: a thread per output point of the largest box; the body through LDS where the axis is the fastest that counts
+int project_views(int N, uint32_t axis, const sz3hip_tile_req *reqs, uint32_t n, szk_region_sink *sink, std::vector<ReqView> &vs) {
+    const bool index_op = project_index_op(sink->prj.op);
+    for (uint32_t i = 0; i < n; i++)
+        if (index_op && reqs[i].box.ext[axis] > 0xFFFFFFFFull)
+            return fail(SZ3HIP_EINVAL, "box %u: the extent along the axis (%llu) is beyond an index op's uint32_t (2^32 - 1 at most)", i, (unsigned long long)reqs[i].box.ext[axis]);
+    const int rc = collapsed_views(N, axis, reqs, n, project_out_bytes(sink->prj), vs, &sink->prj_threads, &sink->prj_rows, nullptr);
+    if (rc) return rc;
+    sink->kind = SZK_SINK_PROJECT;
     return 0;
 }
 }  // namespace
@@ -1742,6 +1752,197 @@ extern "C" int sz3hip_gradient_device(int dataType, int N, const uint64_t *dims,
     DeviceScope scope;
     HIPCHK(hipSetDevice(dev));
     if (szk_launch_region_gradient(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the gradient could not be launched");
+    return 0;
+}
+
+// ---- boxes composited along an axis: front to back through an RGBA table ------------------------------------------------------
+namespace {
+size_t composite_out_bytes(const szk_composite_opts &co) { return co.out_type == SZ3HIP_COMPOSITE_RGBA32F ? 16 : 4; }
+int composite_opts_check(const sz3hip_composite_opts *opts, szk_composite_opts *co) {
+    memset(co, 0, sizeof(*co));
+    if (!opts) return fail(SZ3HIP_EINVAL, "NULL argument (opts): a compositing needs its window, axis and table");
+    if (opts->out_type > SZ3HIP_COMPOSITE_RGBA8)
+        return fail(SZ3HIP_EINVAL, "the options' out_type (%u) is not SZ3HIP_COMPOSITE_RGBA32F or SZ3HIP_COMPOSITE_RGBA8 (0, 1)", opts->out_type);
+    const uint32_t known = SZ3HIP_COMPOSITE_REVERSE | SZ3HIP_COMPOSITE_LEVEL_OPACITY | SZ3HIP_COMPOSITE_ACCUMULATE;
+    if (opts->flags & ~known)
+        return fail(SZ3HIP_EINVAL, "the options' flags (0x%x) hold bits beyond SZ3HIP_COMPOSITE_REVERSE | _LEVEL_OPACITY | _ACCUMULATE", opts->flags);
+    if (opts->reserved) return fail(SZ3HIP_EINVAL, "the options' reserved word is %u, not 0", opts->reserved);
+    if (!(fabs(opts->lo) < INFINITY) || !(fabs(opts->hi) < INFINITY)) return fail(SZ3HIP_EINVAL, "the window [%g, %g) is not finite", opts->lo, opts->hi);
+    if (!(opts->hi > opts->lo)) return fail(SZ3HIP_EINVAL, "the window [%g, %g) is empty: hi must be above lo", opts->lo, opts->hi);
+    if (!(fabs(opts->hi - opts->lo) < INFINITY)) return fail(SZ3HIP_EINVAL, "the window [%g, %g) is too wide: hi - lo is not finite", opts->lo, opts->hi);
+    if (!(opts->cutoff > 0.0)) return fail(SZ3HIP_EINVAL, "the options' cutoff (%g) is not above 0 (+Inf never stops a column)", opts->cutoff);
+    if (opts->lut_n < 2 || opts->lut_n > SZ3HIP_MAX_LUT) return fail(SZ3HIP_EINVAL, "the table has %u entries: 2 .. %d are supported", opts->lut_n, SZ3HIP_MAX_LUT);
+    if (!opts->d_lut) return fail(SZ3HIP_EINVAL, "the table (d_lut) is NULL");
+    if ((uintptr_t)opts->d_lut % 16) return fail(SZ3HIP_EINVAL, "the table (d_lut) is not aligned to its 16-byte entries");
+    if (opts->level_bias > 30) return fail(SZ3HIP_EINVAL, "the options' level_bias is %u: an opacity is squared 30 times at most", opts->level_bias);
+    if ((opts->flags & SZ3HIP_COMPOSITE_ACCUMULATE) && opts->out_type != SZ3HIP_COMPOSITE_RGBA32F)
+        return fail(SZ3HIP_EINVAL, "SZ3HIP_COMPOSITE_ACCUMULATE reads the output's four floats: it takes SZ3HIP_COMPOSITE_RGBA32F, not RGBA8");
+    co->win.lo = opts->lo;
+    co->win.hi = opts->hi;
+    co->win.M = opts->lut_n - 1;
+    co->win.scale = (double)(co->win.M + 1) / (opts->hi - opts->lo);
+    co->win.lut_n = opts->lut_n;
+    co->cutoff = opts->cutoff;
+    co->out_type = opts->out_type;
+    co->flags = opts->flags;
+    co->d_lut = static_cast<const float *>(opts->d_lut);
+    return 0;
+}
+// ... and what needs the dimension count: the axis, counted in a record's four places from here on
+int composite_axis(const sz3hip_composite_opts *opts, int N, szk_composite_opts *co) {
+    if (opts->axis >= (uint32_t)N) return fail(SZ3HIP_EINVAL, "the options' axis (%u) is not one of the %d dimensions (0 .. %d)", opts->axis, N, N - 1);
+    co->axis = opts->axis + (uint32_t)(4 - N);
+    co->N = (uint32_t)N;
+    return 0;
+}
+// every box's squarings, the views of the collapsed boxes (the projection's way) and the sink with every box's table entry (boxes: n
+// entries, in the request's order)
+int composite_views(int N, const sz3hip_composite_opts *opts, const sz3hip_tile_req *reqs, uint32_t n, szk_region_sink *sink, std::vector<szk_composite_box> &boxes,
+                    uint64_t *out_points) {
+    boxes.assign(n, szk_composite_box());
+    for (uint32_t i = 0; i < n; i++) {
+        memset(&boxes[i], 0, sizeof(boxes[i]));
+        const uint64_t s = (uint64_t)opts->level_bias + ((opts->flags & SZ3HIP_COMPOSITE_LEVEL_OPACITY) && reqs[i].level > 0 ? (uint64_t)reqs[i].level : 0);
+        if (s > 30)
+            return fail(SZ3HIP_EINVAL, "box %u: level_bias (%u) and the box's level (%d) make %llu squarings: an opacity is squared 30 times at most", i, opts->level_bias,
+                        reqs[i].level, (unsigned long long)s);
+        boxes[i].s = s;
+    }
+    std::vector<ReqView> vs;
+    const int rc = collapsed_views(N, opts->axis, reqs, n, composite_out_bytes(sink->cmp), vs, &sink->cmp_threads, &sink->cmp_rows, out_points);
+    if (rc) return rc;
+    sink->kind = SZK_SINK_COMPOSITE;
+    for (uint32_t i = 0; i < n; i++) {
+        boxes[i].dst = reqs[i].d_out;
+        for (int j = 0; j < N; j++) boxes[i].dstr[4 - N + j] = j != (int)opts->axis && reqs[i].box.ext[j] > 1 ? vs[i].str[j] : 0;
+    }
+    sink->cmp_boxes = boxes.data();
+    return 0;
+}
+}  // namespace
+
+extern "C" int sz3hip_composite_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_composite_opts *opts,
+                                         sz3hip_composite_plan *out) {
+    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_composite_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
+    int rc = dtype_check(dataType);
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    if (rc || (rc = request_args("sz3hip_composite_plan_for", reqs, n)) || (rc = composite_opts_check(opts, &sink.cmp))) return rc;
+    std::vector<szk_region_geom> gs;
+    std::vector<szk_composite_box> boxes;
+    uint64_t out_points = 0;
+    memset(out, 0, sizeof(*out));
+    if ((rc = szi_request_geometry_conf(conf, reqs, n, gs, &out->scratch_elems)) || (rc = composite_axis(opts, conf->N, &sink.cmp)) ||
+        (rc = composite_views(conf->N, opts, reqs, n, &sink, boxes, &out_points))) {
+        memset(out, 0, sizeof(*out));
+        return rc;
+    }
+    out->n = n;
+    out->finest_level = out->coarsest_level = reqs[0].level;
+    for (uint32_t i = 0; i < n; i++) {
+        out->finest_level = std::min(out->finest_level, reqs[i].level);
+        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
+        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
+        out->points += gs[i].points;
+    }
+    out->out_points = out_points;
+    out->out_elem_bytes = (uint32_t)composite_out_bytes(sink.cmp);
+    return 0;
+}
+
+extern "C" int sz3hip_stream_composite(sz3hip_stream *h, const sz3hip_tile_req *reqs, uint32_t n, const sz3hip_composite_opts *opts, void *stream) {
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_composite: no handle");
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    int rc = request_args("sz3hip_stream_composite", reqs, n);
+    if (rc || (rc = composite_opts_check(opts, &sink.cmp))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    std::vector<szk_region_geom> gs;
+    std::vector<szk_composite_box> boxes;
+    uint64_t elems = 0, words = 0;
+    const int N = h->fast ? h->codes.ip.N : h->N;
+    // (behind the boxes' records: every box's entry, in the table's one copy)
+    const uint64_t tail = (uint64_t)n * SZK_COMPOSITE_WORDS;
+    if (!h->fast) {
+        if ((rc = full_boxes_check(h, reqs, n))) return rc;
+        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
+    } else {
+        const szk_interp_params &ip = h->codes.ip;
+        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
+        words = szk_region_request_table_words(gs.data(), n) + tail;
+    }
+    if ((rc = composite_axis(opts, N, &sink.cmp)) || (rc = composite_views(N, opts, reqs, n, &sink, boxes, nullptr))) return rc;
+    std::vector<sz3hip_tile_req> tr(reqs, reqs + n);
+    for (uint32_t i = 0; i < n; i++) tr[i].d_out = (void *)(uintptr_t)i;  // (the `dst` word: the box's index in the request)
+    HIPCHK(hipSetDevice(h->device));
+    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    const uint32_t chain_points = sz3hip_debug_get_chain_points();
+    uint32_t chain_levels = 0, launches = 0, levels = 0;
+    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
+    int lr;
+    if (!h->fast) {
+        std::vector<szk_region_gather_strided_box> full_recs(n);
+        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
+        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
+        launches = 1;
+    } else {
+        std::vector<szk_region_out> ro(n);
+        for (uint32_t i = 0; i < n; i++) {
+            memset(&ro[i], 0, sizeof(ro[i]));
+            ro[i].dst = tr[i].d_out;
+        }
+        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
+                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, ro.data(), h->h_table,
+                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
+    }
+    HIPCHK(hipEventRecord(h->ev_req, s));
+    h->req_pending = true;
+    h->last_stream = s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's compositing could not be launched (%d)", lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+extern "C" int sz3hip_composite_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_composite_opts *opts,
+                                       void *d_out, const int64_t *strides_out, void *stream) {
+    int rc = dtype_check(dataType);
+    if (rc) return rc;
+    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++)
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+    szk_region_sink sink;
+    memset(&sink, 0, sizeof(sink));
+    if ((rc = composite_opts_check(opts, &sink.cmp)) || (rc = composite_axis(opts, N, &sink.cmp))) return rc;  // (the options before any pointer)
+    if (!d_out) return fail(SZ3HIP_EINVAL, "sz3hip_composite_device: NULL argument (d_out)");
+    uint64_t str[4] = {0, 0, 0, 0};
+    int dev = 0;
+    if ((rc = szi_dev_view_strides(N, dims, strides_in, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
+    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    sz3hip_tile_req q;  // the output as a request's view of the whole array, at level 0
+    memset(&q, 0, sizeof(q));
+    for (int i = 0; i < N; i++) {
+        q.box.ext[i] = dims[i];
+        q.strides[i] = strides_out ? strides_out[i] : 0;
+    }
+    q.d_out = d_out;
+    std::vector<szk_composite_box> boxes;
+    if ((rc = composite_views(N, opts, &q, 1, &sink, boxes, nullptr))) return rc;
+    szk_region_gather_strided_box rec;
+    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);
+    hipStream_t s = (hipStream_t)stream;
+    DeviceScope scope;
+    HIPCHK(hipSetDevice(dev));
+    if (szk_launch_region_composite(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the compositing could not be launched");
     return 0;
 }
 
