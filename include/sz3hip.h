@@ -275,8 +275,12 @@ int sz3hip_tiles_plan_for(const sz3hip_config *conf, int level, const sz3hip_box
 int sz3hip_decompress_tiles_to_device(sz3hip_config *conf, int dataType, const char *cmpData, size_t cmpSize, int level, const sz3hip_box *boxes,
                                       uint32_t n, void *const *d_outs, void *stream);
 /* (test and measurement hook) the strided gather alone: the view (N extents, element strides) of d_in into the contiguous d_out on stream,
- * integers widened to f64 as the compress call does; asynchronous */
+ * integers widened to f64 as the compress call does; asynchronous (the 64-bit integer types: the call waits for the launch).
+ * sz3hip_debug_scatter is its mirror, the strided scatter alone: the contiguous d_in (N extents; f64 for the integer types, narrowed by
+ * rint and a clamp to the type's range as the decompress call does; the float types are copied) into the view of d_out, which passes the
+ * rules of an output first (no negative stride, no elements that overlap: SZ3HIP_EINVAL before any launch); asynchronous */
 int sz3hip_debug_gather(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream);
+int sz3hip_debug_scatter(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream);
 /* The question that follows a round trip in device memory — is the decoded array within the bound, what PSNR did it get — answered where
  * the arrays lie: the numbers of the reference's verify<T> (utils/Statistic.hpp:79-137: Min, Max, range, max absolute error, max point-wise
  * relative error, PSNR, NRMSE, normError, normErr_norm, acEff) for two arrays in device memory, each read once by one reduction kernel

@@ -2621,7 +2621,32 @@ extern "C" int sz3hip_debug_gather(int dataType, const void *d_in, int N, const 
     DevArray d;
     int rc = dev_array(&c, strides, d_in, false, &d);
     if (rc) return rc;
-    if (szk_launch_gather(dataType, 1, d_in, &d.view, d_out, nullptr, (hipStream_t)stream)) return fail(SZ3HIP_EHIP, "gather kernel failed");
+    // (the widening of a 64-bit type raises the 2^53 flag through its pointer: the hook gives it a word of its own and waits for the launch)
+    uint32_t *flag = nullptr;
+    DeviceGuard guard;
+    if (dataType >= SZ3HIP_UINT64 && (hipSetDevice(d.device) != hipSuccess || hipMalloc((void **)&flag, sizeof(uint32_t)) != hipSuccess))
+        return fail(SZ3HIP_EHIP, "no device word for the 2^53 flag");
+    rc = szk_launch_gather(dataType, 1, d_in, &d.view, d_out, flag, (hipStream_t)stream);
+    if (flag) {
+        (void)hipStreamSynchronize((hipStream_t)stream);
+        (void)hipFree(flag);
+    }
+    if (rc) return fail(SZ3HIP_EHIP, "gather kernel failed");
+    return 0;
+}
+// its mirror: the contiguous d_in (f64 for the integer types, T for the float types) into the view of d_out, under dev_view's output rules
+extern "C" int sz3hip_debug_scatter(int dataType, const void *d_in, int N, const uint64_t *dims, const int64_t *strides, void *d_out, void *stream) {
+    if (!dtype_ok(dataType) || N < 1 || N > 4) return fail(SZ3HIP_EINVAL, "bad arguments");
+    sz3hip_config c;
+    memset(&c, 0, sizeof(c));
+    c.N = N;
+    for (int i = 0; i < N; i++) c.dims[i] = dims[i];
+    DevArray d;
+    int rc = dev_array(&c, strides, d_out, true, &d);
+    if (rc) return rc;
+    int dev_in = 0;
+    if ((rc = dev_pointer(d_in, &dev_in))) return rc;
+    if (szk_launch_scatter(dataType, 1, d_in, d_out, &d.view, (hipStream_t)stream)) return fail(SZ3HIP_EHIP, "scatter kernel failed");
     return 0;
 }
 

@@ -11,7 +11,8 @@ import sys
 import pytest
 
 import sz3_amd
-from sweep_seeds import PARTIAL_SWEEP_N, PARTIAL_SWEEP_SEEDS, SAMPLED_SWEEP_N, SAMPLED_SWEEP_SEEDS, WIDEBOOK_SWEEP_N, WIDEBOOK_SWEEP_SEEDS
+from sweep_seeds import (DEVICE_VIEW_SWEEP_N, DEVICE_VIEW_SWEEP_SEEDS, PARTIAL_SWEEP_N, PARTIAL_SWEEP_SEEDS, SAMPLED_SWEEP_N, SAMPLED_SWEEP_SEEDS,
+                         WIDEBOOK_SWEEP_N, WIDEBOOK_SWEEP_SEEDS)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -196,4 +197,17 @@ def test_wide_book_sweep(seed):
     on the picked chunks, the decode bit for bit), then the context's second call, one encoder form and one decoder form byte for byte. The same
     seeds pass the model's premises and the coverage floors in test_widebook_sweep_cpu.py."""
     out = _run("widebook_sweep.py", seed, WIDEBOOK_SWEEP_N)
+    assert "failures 0" in out, out[-3000:]
+
+
+@pytest.mark.parametrize("seed", DEVICE_VIEW_SWEEP_SEEDS)
+def test_device_view_sweep(seed):
+    """tests/checks/device_view_sweep.py: per seed 24 drawn cases of the device-memory calls — the ten element types, ranks
+    1 .. 4 at the row walker's inner extents, an input view and another output view (sub-ranges, steps of 2 and 3, permuted memory orders, stride-0
+    axes, interleaved fields, bases misaligned or in whole 8- / 16-byte units), every algorithm, the bound modes, stock format, conf.openmp slabs
+    and pipelined pieces, non-finite values and integers at their type's ends: the gather hook against numpy's view, the view's container against
+    its contiguous copy's and the host API's, the input untouched, the decode's whole allocation against the host decode scattered by numpy, the
+    mode's bound, and the coarse call into a drawn view. The same seeds pass their premises and the coverage floors in
+    test_device_view_sweep_cpu.py."""
+    out = _run("device_view_sweep.py", seed, DEVICE_VIEW_SWEEP_N)
     assert "failures 0" in out, out[-3000:]
