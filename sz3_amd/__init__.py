@@ -1070,26 +1070,40 @@ def reduce_plan(conf, dtype, items, bins=0, lo=0.0, hi=0.0):
     return {k: int(getattr(plan, k)) for k, _ in _CReducePlan._fields_}
 
 
+def _points_tensor(fn, tensor, ndim=(0, None), what="the tensor is empty"):
+    """what reduce_stats, select_points and the *_points functions ask of their input first: a torch tensor on a HIP device, of a supported
+    dtype, not empty and of ndim[0] .. ndim[1] dimensions (None: any number); fn: the caller's name, for the messages. Returns the dtype's name."""
+    if not _is_tensor(tensor):
+        raise TypeError("%s takes a torch tensor on a HIP device (got %s)" % (fn, type(tensor).__name__))
+    if not _gpu_tensor(tensor):
+        raise ValueError("%s: the tensor must be on a HIP device (it is on %s)" % (fn, tensor.device))
+    name = str(tensor.dtype).replace("torch.", "")
+    if name not in _SZ_TYPES:
+        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
+    if tensor.numel() == 0 or tensor.dim() < ndim[0] or (ndim[1] is not None and tensor.dim() > ndim[1]):
+        raise ValueError("%s: %s" % (fn, what))
+    return name
+
+
+def _points_view(fn, tensor, out=None, axis=None):
+    """... and the view a _device call gets: the dimensions above size 1 (and `axis`, where one is kept whatever its size), at most 4.
+    Returns their indices, N, the extents, the input's strides and (out given) the output's."""
+    keep = [i for i, d in enumerate(tensor.shape) if int(d) != 1 or i == axis]
+    if len(keep) > 4:
+        raise ValueError("%s: %d dimensions above size 1%s (at most 4 are supported)" % (fn, len(keep), "" if axis is None else ", the axis included"))
+    dims = [int(tensor.shape[i]) for i in keep] or [1]
+    sin = [int(tensor.stride(i)) for i in keep] or [1]
+    sout = None if out is None else [int(out.stride(i)) for i in keep] or [1]
+    return keep, len(dims), dims, sin, sout
+
+
 def reduce_stats(tensor, bins=0, lo=0.0, hi=0.0, stream=None):
     """min, max, their places, shifted moments and (bins > 0) a histogram over [lo, hi) of one float32 / float64 torch tensor on a HIP device
     (sz3hip_reduce_device): the reduction Stream.reduce runs per box, over a plain view — any strides that are not negative, size-1
     dimensions dropped, at most 4 left; indices are row-major over the tensor's shape. Asynchronous on `stream`; returns a ReduceResult
     of one row."""
-    if not _is_tensor(tensor):
-        raise TypeError("reduce_stats takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
-    if not _gpu_tensor(tensor):
-        raise ValueError("reduce_stats: the tensor must be on a HIP device (it is on %s)" % tensor.device)
-    name = str(tensor.dtype).replace("torch.", "")
-    if name not in _SZ_TYPES:
-        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
-    if tensor.numel() == 0:
-        raise ValueError("reduce_stats: the tensor is empty")
-    keep = [i for i, d in enumerate(tensor.shape) if int(d) != 1]
-    if len(keep) > 4:
-        raise ValueError("reduce_stats: %d dimensions above size 1 (at most 4 are supported)" % len(keep))
-    dims = [int(tensor.shape[i]) for i in keep] or [1]
-    strides = [int(tensor.stride(i)) for i in keep] or [1]
-    N = len(dims)
+    name = _points_tensor("reduce_stats", tensor)
+    _, N, dims, strides, _ = _points_view("reduce_stats", tensor)
     res = _reduce_result(1, bins, tensor.device)
     opts = _reduce_opts(bins, lo, hi)
     _check(lib().sz3hip_reduce_device(_SZ_TYPES[name], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*strides), C.byref(opts),
@@ -1187,21 +1201,8 @@ def select_points(tensor, lo, hi, capacity, invert=False, nan=False, values=True
     Stream.select runs per box, over a plain view — any strides that are not negative, size-1 dimensions dropped, at most 4 left; indices
     are row-major over the tensor's shape. invert: the points outside the range; nan: NaN points too. Asynchronous on `stream`; returns a
     SelectResult of one box."""
-    if not _is_tensor(tensor):
-        raise TypeError("select_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
-    if not _gpu_tensor(tensor):
-        raise ValueError("select_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
-    name = str(tensor.dtype).replace("torch.", "")
-    if name not in _SZ_TYPES:
-        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
-    if tensor.numel() == 0:
-        raise ValueError("select_points: the tensor is empty")
-    keep = [i for i, d in enumerate(tensor.shape) if int(d) != 1]
-    if len(keep) > 4:
-        raise ValueError("select_points: %d dimensions above size 1 (at most 4 are supported)" % len(keep))
-    dims = [int(tensor.shape[i]) for i in keep] or [1]
-    strides = [int(tensor.stride(i)) for i in keep] or [1]
-    N = len(dims)
+    name = _points_tensor("select_points", tensor)
+    _, N, dims, strides, _ = _points_view("select_points", tensor)
     caps = _select_caps(capacity, 1)
     res = _select_result(caps, values, tensor.dtype, tensor.device)
     opts = _select_opts(lo, hi, invert, nan)
@@ -1259,7 +1260,7 @@ def _map_reqs(N, items, shapes, arr, name, device, alloc):
         reqs[i].level = int(it[0])
         reqs[i].box = arr[i]
         if t is not None:
-            if str(t.dtype) != "torch." + name or tuple(t.shape) != shape or (alloc and (not _gpu_tensor(t) or t.device != device)):
+            if (alloc and not _gpu_tensor(t)) or str(t.dtype) != "torch." + name or tuple(t.shape) != shape or (alloc and t.device != device):
                 raise ValueError("item %d: out must be a %s tensor of the box's shape %s%s" % (i, name, shape, " on %s" % device if alloc else ""))
             reqs[i].d_out = t.data_ptr()
             reqs[i].strides[:N] = [int(v) for v in t.stride()]
@@ -1299,28 +1300,14 @@ def map_points(tensor, out_type, lo=0.0, hi=0.0, nan_code=0, lut=None, out=None,
     point becomes nan_code itself). `out`: a tensor of the input's shape and of dtype uint8 / int16 (u16's two bytes: torch's uint16 is
     not a working storage type) / float16 / float32 / int32, any view whose strides nest in row-major order (default: allocated,
     contiguous). Asynchronous on `stream`; returns `out`."""
-    if not _is_tensor(tensor):
-        raise TypeError("map_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
-    if not _gpu_tensor(tensor):
-        raise ValueError("map_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
-    tname = str(tensor.dtype).replace("torch.", "")
-    if tname not in _SZ_TYPES:
-        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
-    if tensor.numel() == 0:
-        raise ValueError("map_points: the tensor is empty")
+    tname = _points_tensor("map_points", tensor)
     import torch
     code, name = _map_type(out_type)
     if out is None:
         out = torch.empty(tuple(tensor.shape), dtype=getattr(torch, name), device=tensor.device)
     if not _gpu_tensor(out) or str(out.dtype) != "torch." + name or tuple(out.shape) != tuple(tensor.shape) or out.device != tensor.device:
         raise ValueError("map_points: out must be a %s tensor of the input's shape %s on %s" % (name, tuple(tensor.shape), tensor.device))
-    keep = [i for i, d in enumerate(tensor.shape) if int(d) != 1]
-    if len(keep) > 4:
-        raise ValueError("map_points: %d dimensions above size 1 (at most 4 are supported)" % len(keep))
-    dims = [int(tensor.shape[i]) for i in keep] or [1]
-    sin = [int(tensor.stride(i)) for i in keep] or [1]
-    sout = [int(out.stride(i)) for i in keep] or [1]
-    N = len(dims)
+    _, N, dims, sin, sout = _points_view("map_points", tensor, out)
     opts = _map_opts(code, lo, hi, nan_code, lut)
     _check(lib().sz3hip_map_device(_SZ_TYPES[tname], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*sin), C.byref(opts), out.data_ptr(),
                                    (C.c_int64 * N)(*sout), _stream_handle(tensor.device, stream)))
@@ -1431,15 +1418,7 @@ def sample_points(tensor, query, mode="linear", clamp=False, fill=float("nan"), 
     counts). mode "nearest": the nearest point's bytes; "linear": the multilinear interpolation in double, rounded once. A query outside
     [0, size - 1] yields `fill`, or is clamped (clamp=True); a NaN coordinate always yields `fill`. Asynchronous on `stream`; returns a
     tensor of the input's dtype: (n,) for coordinates, of shape `counts` for a lattice."""
-    if not _is_tensor(tensor):
-        raise TypeError("sample_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
-    if not _gpu_tensor(tensor):
-        raise ValueError("sample_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
-    name = str(tensor.dtype).replace("torch.", "")
-    if name not in _SZ_TYPES:
-        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
-    if tensor.numel() == 0:
-        raise ValueError("sample_points: the tensor is empty")
+    name = _points_tensor("sample_points", tensor)
     N = tensor.dim()
     if not 1 <= N <= 4:
         raise ValueError("sample_points: %d dimensions (1 .. 4 are supported)" % N)
@@ -1524,15 +1503,7 @@ def project_points(tensor, op, axis, out_dtype=None, fill=float("nan"), out=None
     argmax). The sum is the sequential fold in double along the axis, rounded once. `out`: a tensor of the input's shape with 1 at `axis`,
     any view whose strides nest in row-major order (default: allocated, contiguous). Asynchronous on `stream`; returns `out`. One number
     about a long 1-D tensor is reduce_stats' work: a 1-D projection is one lane's."""
-    if not _is_tensor(tensor):
-        raise TypeError("project_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
-    if not _gpu_tensor(tensor):
-        raise ValueError("project_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
-    tname = str(tensor.dtype).replace("torch.", "")
-    if tname not in _SZ_TYPES:
-        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
-    if tensor.numel() == 0 or tensor.dim() == 0:
-        raise ValueError("project_points: the tensor is empty or has no dimension")
+    tname = _points_tensor("project_points", tensor, (1, None), "the tensor is empty or has no dimension")
     import torch
     opts, name = _project_opts(op, axis, tensor.dim(), tname, out_dtype, fill)
     axis = int(opts.axis)
@@ -1541,13 +1512,7 @@ def project_points(tensor, op, axis, out_dtype=None, fill=float("nan"), out=None
         out = torch.empty(shape, dtype=getattr(torch, name), device=tensor.device)
     if not _gpu_tensor(out) or str(out.dtype) != "torch." + name or tuple(out.shape) != shape or out.device != tensor.device:
         raise ValueError("project_points: out must be a %s tensor of shape %s on %s" % (name, shape, tensor.device))
-    keep = [i for i, d in enumerate(tensor.shape) if int(d) != 1 or i == axis]
-    if len(keep) > 4:
-        raise ValueError("project_points: %d dimensions above size 1, the axis included (at most 4 are supported)" % len(keep))
-    dims = [int(tensor.shape[i]) for i in keep]
-    sin = [int(tensor.stride(i)) for i in keep]
-    sout = [int(out.stride(i)) for i in keep]
-    N = len(dims)
+    keep, N, dims, sin, sout = _points_view("project_points", tensor, out, axis)
     opts.axis = keep.index(axis)
     _check(lib().sz3hip_project_device(_SZ_TYPES[tname], N, (C.c_uint64 * N)(*dims), tensor.data_ptr(), (C.c_int64 * N)(*sin), C.byref(opts), out.data_ptr(),
                                        (C.c_int64 * N)(*sout), _stream_handle(tensor.device, stream)))
@@ -1669,15 +1634,7 @@ def gradient_points(tensor, op, axis=0, spacing=None, out_dtype=None, interior=F
     difference. `out`: a tensor of the output's shape, any view whose strides nest in row-major order (default: allocated, contiguous);
     a vector output must have its last dimension contiguous and its other strides divisible by the component count. Asynchronous on
     `stream`; returns `out`."""
-    if not _is_tensor(tensor):
-        raise TypeError("gradient_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
-    if not _gpu_tensor(tensor):
-        raise ValueError("gradient_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
-    tname = str(tensor.dtype).replace("torch.", "")
-    if tname not in _SZ_TYPES:
-        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
-    if tensor.numel() == 0 or not 1 <= tensor.dim() <= 4:
-        raise ValueError("gradient_points: the tensor is empty or does not have 1 .. 4 dimensions")
+    tname = _points_tensor("gradient_points", tensor, (1, 4), "the tensor is empty or does not have 1 .. 4 dimensions")
     import torch
     N = tensor.dim()
     opts, name = _gradient_opts(op, axis, N, tname, spacing, out_dtype, interior)
@@ -1787,15 +1744,7 @@ def composite_points(tensor, axis, lut, lo, hi, out_type="rgba32f", reverse=Fals
     plus a last dimension 4 (premultiplied colours, opacity) — a given `out` must have that dimension contiguous and its other strides
     divisible by 4; accumulate: the fold starts from what `out` holds. "rgba8": an int32 tensor, byte 0 = r .. byte 3 = a. Asynchronous
     on `stream`; returns `out`."""
-    if not _is_tensor(tensor):
-        raise TypeError("composite_points takes a torch tensor on a HIP device (got %s)" % type(tensor).__name__)
-    if not _gpu_tensor(tensor):
-        raise ValueError("composite_points: the tensor must be on a HIP device (it is on %s)" % tensor.device)
-    tname = str(tensor.dtype).replace("torch.", "")
-    if tname not in _SZ_TYPES:
-        raise TypeError("sz3_amd supports float32 / float64 and 8 ... 64-bit integers (got %s)" % tensor.dtype)
-    if tensor.numel() == 0 or not 1 <= tensor.dim() <= 4:
-        raise ValueError("composite_points: the tensor is empty or does not have 1 .. 4 dimensions")
+    tname = _points_tensor("composite_points", tensor, (1, 4), "the tensor is empty or does not have 1 .. 4 dimensions")
     import torch
     N = tensor.dim()
     opts, name = _composite_opts(axis, N, lut, lo, hi, out_type, reverse, False, accumulate, cutoff, level_bias)
@@ -1896,18 +1845,7 @@ class Stream:
             raise ValueError("an item is (level, lo, shape) or (level, lo, shape, out)")
         N = self.conf.N
         arr, shapes = _boxes(N, [(it[1], it[2]) for it in items])
-        import torch
-        reqs = (_CTileReq * max(len(items), 1))()
-        outs = []
-        for i, (it, shape) in enumerate(zip(items, shapes)):
-            t = it[3] if len(it) == 4 and it[3] is not None else torch.empty(shape, dtype=getattr(torch, self.dtype.name), device=self.device)
-            if not _gpu_tensor(t) or _np_dtype(t.dtype) != self.dtype or tuple(t.shape) != shape or t.device != self.device:
-                raise ValueError("item %d: out must be a %s tensor of the box's shape %s on %s" % (i, self.dtype, shape, self.device))
-            outs.append(t)
-            reqs[i].level = int(it[0])
-            reqs[i].box = arr[i]
-            reqs[i].d_out = t.data_ptr()
-            reqs[i].strides[:N] = [int(v) for v in t.stride()]
+        reqs, outs = _map_reqs(N, items, shapes, arr, self.dtype.name, self.device, True)
         _check(lib().sz3hip_stream_request(self._h, reqs, len(items), _stream_handle(self.device, stream)))
         return outs
 

@@ -629,25 +629,37 @@ int szk_launch_region_reduce(int dtype, const void *d_src, const struct szk_regi
 int szk_launch_region_reduce_final(int dtype, const void *d_src, const struct szk_region_gather_strided_box *d_recs, const struct szk_region_gather_strided_box *rec_by_value, uint32_t n,
                                    const szk_region_sink *sink, hipStream_t s);
 uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n);
-// sink non-null: the request reduces (outs[i].dst: box i's SZK_REDUCE_DST word, cast; the strides are not read) — reduce and final stand
-// in the strided gather's place, *launches is the request's count plus one; a selecting sink (kind SZK_SINK_SELECT): count, scan and write,
-// the request's count plus two, table_words with room for n * SZK_SELECT_OUT_WORDS more; a mapping sink (kind SZK_SINK_MAP): outs are the
-// real views in output elements, one launch, the request's count; a sampling sink (kind SZK_SINK_SAMPLE): outs[i].dst is i, one launch, the
-// request's count, table_words with room for n * SZK_SAMPLE_WORDS more; a projecting sink (kind SZK_SINK_PROJECT): outs are the real views of
-// the collapsed boxes in output elements, one launch, the request's count; a gradient sink (kind SZK_SINK_GRADIENT): outs[i].dst is i, one
-// launch, the request's count, table_words with room for n * SZK_GRADIENT_WORDS more; a compositing sink (kind SZK_SINK_COMPOSITE): as the
-// gradient's, with room for n * SZK_COMPOSITE_WORDS more
+// ---- the sink table (sz3hip_region.hip): what the launchers' host code and a handle's submit path know about a sink, one entry per kind ----
+#define SZK_DST_VIEW 0   // a record's `dst` word: the box's real view, with `dstr`
+#define SZK_DST_INDEX 1  // ... the box's index in the request (`dstr` is not read)
+#define SZK_DST_PART 2   // ... SZK_REDUCE_DST(the box's first partial record, its index)
+typedef int (*szk_sink_launch_fn)(int dtype, const void *d_src, const szk_region_gather_strided_box *d_recs, uint32_t n, uint64_t most_total,
+                                  const szk_region_sink *sink, hipStream_t s);
+struct szk_sink_desc {
+    uint32_t box_words;   // words per box behind the records of EVERY launch, in the RECORDS' order (a record's `dst` word names its box)
+    uint32_t flat_words;  // words per box behind the records of the final's launch only, flat in the REQUEST's order
+    const void *(*entries)(const szk_region_sink *);  // the HOST array those words are copied from (null: nothing rides behind the records)
+    int dst;              // SZK_DST_*
+    uint32_t final_launches;  // 0: complete per level group, `launch` alone; else `final` stands once per request and issues this many
+    szk_sink_launch_fn launch, final;
+    bool (*ready)(const szk_region_sink *);  // the device pointers the launches read are set (null: none beyond `entries`)
+};
+const szk_sink_desc &szk_sink(const szk_region_sink *sink);  // (null: the strided gather — real views, nothing rides, no launch of a sink's)
+// the words a request's table needs with this sink: the boxes' records alone (gs null: a handle that keeps the full array) or the
+// request's table with — for a sink that has a final — the records once more; behind them what the sink's entry says rides
+uint64_t szk_sink_table_words(const szk_region_sink *sink, const szk_region_geom *gs, uint32_t n);
+// sink non-null: the sink's launches stand in the strided gather's place; outs[i].dst, the room in table_words and *launches (the
+// request's count, plus the final's launches) are what the sink table says
 int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_params *ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems,
                                                 const uint8_t *payload, uint64_t vout_idx_off, uint64_t vout_val_off, uint64_t n_vout, const uint16_t *codes,
                                                 void *scratch, const szk_region_out *outs, uint64_t *h_table, uint64_t *d_table, uint64_t table_words,
                                                 hipEvent_t copied, hipStream_t s, uint32_t chain_points, uint32_t *chain_levels, uint32_t *launches, uint32_t *levels,
                                                 const szk_region_sink *sink = nullptr);
 // n strided boxes of one array into n strided views in one launch (the gather of szk_launch_gather with a strided destination, per box): recs
-// are copied through h_table into d_table (n * 15 words) in front of the launch, `copied` recorded behind the copy. sink non-null: the boxes are
-// reduced instead (recs[i].dst: box i's SZK_REDUCE_DST word), two launches — or selected, three launches, the boxes' outputs (n * 3 words)
-// behind the records in the same copy
+// are copied through h_table into d_table (n * 15 words) in front of the launch, `copied` recorded behind the copy. sink non-null: the sink's
+// launch and final in the gather's place, what the sink table says rides behind the records in the same copy. *launches: what was issued
 int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gather_strided_box *recs, uint32_t n, uint64_t *h_table, uint64_t *d_table,
-                            uint64_t table_words, hipEvent_t copied, hipStream_t s, const szk_region_sink *sink = nullptr);
+                            uint64_t table_words, hipEvent_t copied, hipStream_t s, const szk_region_sink *sink = nullptr, uint32_t *launches = nullptr);
 uint64_t szk_region_launches(void);  // test hook: kernel launches the box reconstructions issued so far, single and multi
 
 int szk_launch_profile_blocks(int dtype, const void *d_in, int N, const uint64_t *dims, uint64_t bs, uint64_t stride, double abseb,

@@ -800,100 +800,64 @@ static void region_launch(uint32_t *issued, void (*kernel)(KA...), dim3 grid, ui
     region_count(issued);
 }
 
-// a selecting request's outputs ride in the table's one copy, directly behind the n boxes' records at the cursor *w (any other sink: nothing)
-static bool region_sink_tail(const szk_region_sink *sink, uint32_t n, uint64_t *h_table, uint64_t *w, uint64_t table_words) {
-    if (sink && sink->kind == SZK_SINK_SAMPLE) {  // (the queries in the RECORDS' order: a record's `dst` word names its box in the request)
-        constexpr uint64_t RW = SZK_WORDS(szk_region_gather_strided_box);
-        const uint64_t words = (uint64_t)n * SZK_SAMPLE_WORDS;
-        if (!sink->smp_queries || *w < (uint64_t)n * RW || words > table_words || *w > table_words - words) return false;
-        const uint64_t recs = *w - (uint64_t)n * RW;
-        for (uint32_t r = 0; r < n; r++) {
-            szk_region_gather_strided_box b;
-            memcpy(&b, h_table + recs + r * RW, sizeof(b));
-            memcpy(h_table + *w, sink->smp_queries + (uintptr_t)b.dst, sizeof(szk_sample_query));
-            *w += SZK_SAMPLE_WORDS;
-        }
-        return true;
+// the sink table (sz3hip_kernels.h), in the order of SZK_SINK_*; the launch functions of the sinks' files behind the one signature
+#define SINK_FN(call)                                                                                                                          \
+    [](int dtype, const void *src, const szk_region_gather_strided_box *d_recs, uint32_t n, uint64_t most, const szk_region_sink *sink, hipStream_t s) -> int { \
+        (void)most;                                                                                                                            \
+        return call;                                                                                                                           \
     }
-    if (sink && sink->kind == SZK_SINK_GRADIENT) {  // (the boxes' entries in the RECORDS' order, as the sampling's queries)
-        constexpr uint64_t RW = SZK_WORDS(szk_region_gather_strided_box);
-        const uint64_t words = (uint64_t)n * SZK_GRADIENT_WORDS;
-        if (!sink->grd_boxes || *w < (uint64_t)n * RW || words > table_words || *w > table_words - words) return false;
-        const uint64_t recs = *w - (uint64_t)n * RW;
-        for (uint32_t r = 0; r < n; r++) {
-            szk_region_gather_strided_box b;
-            memcpy(&b, h_table + recs + r * RW, sizeof(b));
-            memcpy(h_table + *w, sink->grd_boxes + (uintptr_t)b.dst, sizeof(szk_gradient_box));
-            *w += SZK_GRADIENT_WORDS;
-        }
-        return true;
+#define SINK_ARRAY(field) [](const szk_region_sink *k) -> const void * { return k->field; }
+// (complete per level group: one launch, no final — DESIGN.md sections 19, 20, 21, 23, 26)
+#define SINK_PER_GROUP(words, array, dst, launch) {words, 0, array, dst, 0, SINK_FN(launch(dtype, src, d_recs, nullptr, n, sink, s)), nullptr, nullptr}
+static const szk_sink_desc g_sinks[] = {
+    // REDUCE: the reduction, then — once per request — the final fold
+    {0, 0, nullptr, SZK_DST_PART, 1, SINK_FN(szk_launch_region_reduce(dtype, src, d_recs, nullptr, n, most, sink, s)),
+     SINK_FN(szk_launch_region_reduce_final(dtype, src, d_recs, nullptr, n, sink, s)),
+     [](const szk_region_sink *k) { return k->partials && k->d_stats && (!k->hist.nbins || k->d_hist); }},
+    // SELECT: the count, then — once per request — scan and write, with every box's d_index, d_value and capacity
+    {0, SZK_SELECT_OUT_WORDS, SINK_ARRAY(sel_outs), SZK_DST_PART, 2, SINK_FN(szk_launch_region_select_count(dtype, src, d_recs, nullptr, n, most, sink, s)),
+     SINK_FN(szk_launch_region_select_place(dtype, src, d_recs, nullptr, n, most, sink, s)), [](const szk_region_sink *k) { return k->sel_counts && k->sel_heads; }},
+    /* MAP */ SINK_PER_GROUP(0, nullptr, SZK_DST_VIEW, szk_launch_region_map),
+    /* SAMPLE */ SINK_PER_GROUP(SZK_SAMPLE_WORDS, SINK_ARRAY(smp_queries), SZK_DST_INDEX, szk_launch_region_sample),
+    /* PROJECT */ SINK_PER_GROUP(0, nullptr, SZK_DST_VIEW, szk_launch_region_project),
+    /* GRADIENT */ SINK_PER_GROUP(SZK_GRADIENT_WORDS, SINK_ARRAY(grd_boxes), SZK_DST_INDEX, szk_launch_region_gradient),
+    /* COMPOSITE */ SINK_PER_GROUP(SZK_COMPOSITE_WORDS, SINK_ARRAY(cmp_boxes), SZK_DST_INDEX, szk_launch_region_composite),
+};
+static const szk_sink_desc g_gather = {0, 0, nullptr, SZK_DST_VIEW, 0, nullptr, nullptr, nullptr};
+const szk_sink_desc &szk_sink(const szk_region_sink *sink) {
+    return !sink ? g_gather : g_sinks[(size_t)sink->kind < sizeof(g_sinks) / sizeof(g_sinks[0]) ? sink->kind : SZK_SINK_REDUCE];
+}
+
+// what rides in the table's one copy directly behind the n boxes' records at the cursor *w: the sink's per-box entries in the RECORDS' order
+// (a record's `dst` word names its box in the request), or — with the final only — its flat words in the request's order
+static bool region_sink_tail(const szk_region_sink *sink, uint32_t n, uint64_t *h_table, uint64_t *w, uint64_t table_words, bool with_final = true) {
+    constexpr uint64_t RW = SZK_WORDS(szk_region_gather_strided_box);
+    const szk_sink_desc &d = szk_sink(sink);
+    const uint64_t per = d.box_words ? d.box_words : with_final ? d.flat_words : 0, words = (uint64_t)n * per;
+    if (!words) return true;
+    const char *from = static_cast<const char *>(d.entries(sink));
+    if (!from || words > table_words || *w > table_words - words || (d.box_words && *w < (uint64_t)n * RW)) return false;
+    if (!d.box_words) memcpy(h_table + *w, from, words * 8);
+    for (uint32_t r = 0; d.box_words && r < n; r++) {
+        szk_region_gather_strided_box b;
+        memcpy(&b, h_table + *w - (uint64_t)n * RW + r * RW, sizeof(b));
+        memcpy(h_table + *w + r * per, from + (uintptr_t)b.dst * per * 8, per * 8);
     }
-    if (sink && sink->kind == SZK_SINK_COMPOSITE) {  // (the boxes' entries in the RECORDS' order, as the gradient's)
-        constexpr uint64_t RW = SZK_WORDS(szk_region_gather_strided_box);
-        const uint64_t words = (uint64_t)n * SZK_COMPOSITE_WORDS;
-        if (!sink->cmp_boxes || *w < (uint64_t)n * RW || words > table_words || *w > table_words - words) return false;
-        const uint64_t recs = *w - (uint64_t)n * RW;
-        for (uint32_t r = 0; r < n; r++) {
-            szk_region_gather_strided_box b;
-            memcpy(&b, h_table + recs + r * RW, sizeof(b));
-            memcpy(h_table + *w, sink->cmp_boxes + (uintptr_t)b.dst, sizeof(szk_composite_box));
-            *w += SZK_COMPOSITE_WORDS;
-        }
-        return true;
-    }
-    if (!sink || sink->kind != SZK_SINK_SELECT) return true;
-    const uint64_t words = (uint64_t)n * SZK_SELECT_OUT_WORDS;
-    if (!sink->sel_outs || words > table_words || *w > table_words - words) return false;
-    memcpy(h_table + *w, sink->sel_outs, words * 8);
     *w += words;
     return true;
 }
 
-// a reducing request's launches in the gather's place: the reduction over the boxes' records, then — unless the caller
-// issues it once for several groups — the final
+// a sink's launches in the gather's place: its launch over the boxes' records, then — unless the caller issues it once for several groups —
+// its final
 template <typename T>
 static int region_sink_launch(uint32_t *issued, const T *src, const szk_region_gather_strided_box *d_recs, uint32_t n, uint64_t most, const szk_region_sink *sink,
                               bool with_final, hipStream_t s) {
-    const int dtype = sizeof(T) == 4 ? 0 : 1;
-    if (sink->kind == SZK_SINK_MAP) {  // (one launch, per group where the request runs group by group; no final)
-        if (szk_launch_region_map(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
-        region_count(issued);
-        return 0;
-    }
-    if (sink->kind == SZK_SINK_SAMPLE) {  // (one launch, per group where the request runs group by group; no final)
-        if (szk_launch_region_sample(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
-        region_count(issued);
-        return 0;
-    }
-    if (sink->kind == SZK_SINK_PROJECT) {  // (one launch, per group where the request runs group by group; no final, no tail)
-        if (szk_launch_region_project(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
-        region_count(issued);
-        return 0;
-    }
-    if (sink->kind == SZK_SINK_GRADIENT) {  // (one launch, per group where the request runs group by group; no final)
-        if (szk_launch_region_gradient(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
-        region_count(issued);
-        return 0;
-    }
-    if (sink->kind == SZK_SINK_COMPOSITE) {  // (one launch, per group where the request runs group by group; no final)
-        if (szk_launch_region_composite(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
-        region_count(issued);
-        return 0;
-    }
-    if (sink->kind == SZK_SINK_SELECT) {  // (the count, then — once per request — scan and write)
-        if (szk_launch_region_select_count(dtype, src, d_recs, nullptr, n, most, sink, s)) return -2;
-        region_count(issued);
-        if (!with_final) return 0;
-        if (szk_launch_region_select_place(dtype, src, d_recs, nullptr, n, most, sink, s)) return -2;
-        region_count(issued);
-        region_count(issued);
-        return 0;
-    }
-    if (szk_launch_region_reduce(dtype, src, d_recs, nullptr, n, most, sink, s)) return -2;
+    const szk_sink_desc &d = szk_sink(sink);
+    if (d.launch(sizeof(T) == 4 ? 0 : 1, src, d_recs, n, most, sink, s)) return -2;
     region_count(issued);
-    if (!with_final) return 0;
-    if (szk_launch_region_reduce_final(dtype, src, d_recs, nullptr, n, sink, s)) return -2;
-    region_count(issued);
+    if (!d.final_launches || !with_final) return 0;
+    if (d.final(sizeof(T) == 4 ? 0 : 1, src, d_recs, n, most, sink, s)) return -2;
+    for (uint32_t k = 0; k < d.final_launches; k++) region_count(issued);
     return 0;
 }
 
@@ -1086,8 +1050,8 @@ static int run_region_multi(const szk_interp_params &ip, const szk_region_geom *
         if (!region_grid(most, &l.gx)) return -1;
         l.most = most;
         seq.push_back(l);
-        // (a sampling's queries ride with every group's records; a selection's outputs with the request's one final)
-        if ((sink_final || (sink && (sink->kind == SZK_SINK_SAMPLE || sink->kind == SZK_SINK_GRADIENT || sink->kind == SZK_SINK_COMPOSITE))) && !region_sink_tail(sink, n, h_table, &w, table_words)) return -1;
+        // (a sink's per-box entries ride with every group's records; its flat words with the request's one final)
+        if (!region_sink_tail(sink, n, h_table, &w, table_words, sink_final)) return -1;
     }
     // the chain's steps, behind the boxes' records: the chained launches in their order, a pass's shared part in front of its step(s)
     uint64_t steps_off = 0;
@@ -1217,6 +1181,11 @@ uint64_t szk_region_request_table_words(const szk_region_geom *gs, uint32_t n) {
                  nl * SZK_WORDS(szk_region_regrid_box) + nl * N * SZK_WORDS(szk_region_pass_mixed_box) + SZK_WORDS(szk_region_gather_strided_box);
     // (one level, or level group by level group: the one-level sequence's chain parts, once per level)
     return words + (uint64_t)__builtin_popcountll(kinds) * (nl * N * SZK_WORDS(szk_region_pass_shared) + (1 + nl * (1 + 2 * N)) * SZK_WORDS(szk_chain_step));
+}
+uint64_t szk_sink_table_words(const szk_region_sink *sink, const szk_region_geom *gs, uint32_t n) {
+    const szk_sink_desc &d = szk_sink(sink);
+    const uint64_t recs = (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box);
+    return (gs ? szk_region_request_table_words(gs, n) + (d.final_launches ? recs : 0) : recs) + (uint64_t)n * (d.box_words + d.flat_words);
 }
 template <typename T>
 static int run_region_mixed(const szk_interp_params &ip, const szk_region_geom *gs, uint32_t n, uint64_t scratch_elems, const uint8_t *payload,
@@ -1386,6 +1355,7 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
         if (rc != -4) return rc;  // (-4: a pass's arguments are not one for all boxes; nothing was copied or launched)
     }
     // level group by level group, every group with a stretch of the table of its own (no wait between the groups' copies)
+    const szk_sink_desc &sd = szk_sink(sink);
     std::vector<uint32_t> order(n);
     for (uint32_t i = 0; i < n; i++) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return gs[a].shift < gs[b].shift; });
@@ -1398,9 +1368,7 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
             gg.push_back(gs[order[at]]);
             oo.push_back(outs[order[at]]);
         }
-        const uint64_t need = szk_region_request_table_words(gg.data(), (uint32_t)gg.size()) + (sink && sink->kind == SZK_SINK_SAMPLE ? gg.size() * SZK_SAMPLE_WORDS : 0) +
-                              (sink && sink->kind == SZK_SINK_GRADIENT ? gg.size() * SZK_GRADIENT_WORDS : 0) +
-                              (sink && sink->kind == SZK_SINK_COMPOSITE ? gg.size() * SZK_COMPOSITE_WORDS : 0);
+        const uint64_t need = szk_region_request_table_words(gg.data(), (uint32_t)gg.size()) + gg.size() * sd.box_words;
         if (need > table_words || used > table_words - need) return -1;
         uint32_t issued = 0;
         const int rc = run_region_multi<T>(ip, gg.data(), (uint32_t)gg.size(), scratch_elems, payload, vout_idx_off, vout_val_off, n_vout, codes, scratch, nullptr,
@@ -1410,8 +1378,7 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
         total += issued;
         most_levels = std::max(most_levels, (uint32_t)gg[0].n_levels);
     }
-    if (sink && sink->kind != SZK_SINK_MAP && sink->kind != SZK_SINK_SAMPLE && sink->kind != SZK_SINK_PROJECT && sink->kind != SZK_SINK_GRADIENT &&
-        sink->kind != SZK_SINK_COMPOSITE) {  // ONE final for the request: the boxes' records once more, in the request's order, behind the groups' stretches
+    if (sd.final_launches) {  // ONE final for the request: the boxes' records once more, in the request's order, behind the groups' stretches
         uint64_t need = (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box), most = 0;
         if (need > table_words || used > table_words - need) return -1;
         for (uint32_t i = 0; i < n; i++) {
@@ -1420,17 +1387,14 @@ static int run_region_request(const szk_interp_params &ip, const szk_region_geom
             memcpy(h_table + used + (uint64_t)i * SZK_WORDS(szk_region_gather_strided_box), &r, sizeof(r));
             most = std::max(most, r.total);
         }
-        need += used;  // (the cursor behind the records; a selection's outputs follow them)
+        need += used;  // (the cursor behind the records; the sink's flat words follow them)
         if (!region_sink_tail(sink, n, h_table, &need, table_words)) return -1;
         need -= used;
         if (hipMemcpyAsync(d_table + used, h_table + used, need * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -2;
         if (hipEventRecord(copied, s) != hipSuccess) return -2;
         const szk_region_gather_strided_box *d_recs = reinterpret_cast<const szk_region_gather_strided_box *>(d_table + used);
-        if (sink->kind == SZK_SINK_SELECT) {  // (the groups counted; scan and write once, over all boxes)
-            if (szk_launch_region_select_place(sizeof(T) == 4 ? 0 : 1, scratch, d_recs, nullptr, n, most, sink, s)) return -2;
-            region_count(&total);
-        } else if (szk_launch_region_reduce_final(sizeof(T) == 4 ? 0 : 1, scratch, d_recs, nullptr, n, sink, s)) return -2;
-        region_count(&total);
+        if (sd.final(sizeof(T) == 4 ? 0 : 1, scratch, d_recs, n, most, sink, s)) return -2;  // (the groups ran the sink's launch; its final once, over all boxes)
+        for (uint32_t k = 0; k < sd.final_launches; k++) region_count(&total);
     }
     if (launches) *launches = total;
     if (levels) *levels = most_levels;
@@ -1445,31 +1409,16 @@ int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_para
     if (chain_levels) *chain_levels = 0;
     if (launches) *launches = 0;
     if (levels) *levels = 0;
-    if (sink && (sink->kind == SZK_SINK_MAP || sink->kind == SZK_SINK_PROJECT)) {  // (the views are real: every box's destination)
-        for (uint32_t i = 0; outs && i < n; i++)
-            if (!outs[i].dst) return -1;
-    } else if (sink && sink->kind == SZK_SINK_SAMPLE) {  // (every box's `dst` word is its index in the request)
-        if (!sink->smp_queries) return -1;
-        for (uint32_t i = 0; outs && i < n; i++)
-            if ((uintptr_t)outs[i].dst != i) return -1;
-    } else if (sink && sink->kind == SZK_SINK_GRADIENT) {  // (as the sampling's)
-        if (!sink->grd_boxes) return -1;
-        for (uint32_t i = 0; outs && i < n; i++)
-            if ((uintptr_t)outs[i].dst != i) return -1;
-    } else if (sink && sink->kind == SZK_SINK_COMPOSITE) {  // (as the gradient's)
-        if (!sink->cmp_boxes) return -1;
-        for (uint32_t i = 0; outs && i < n; i++)
-            if ((uintptr_t)outs[i].dst != i) return -1;
-    } else if (sink && sink->kind == SZK_SINK_SELECT) {
-        if (!sink->sel_counts || !sink->sel_heads || !sink->sel_outs) return -1;
-    } else if (sink && (!sink->partials || !sink->d_stats || (sink->hist.nbins && !sink->d_hist))) return -1;
     if (n < 1 || n > 65535 || !gs || !outs || !h_table || !d_table) return -1;
+    const szk_sink_desc &sd = szk_sink(sink);  // (what the sink's row asks of the sink and of every box's `dst` word)
+    if (sink && ((sd.entries && !sd.entries(sink)) || (sd.ready && !sd.ready(sink)))) return -1;
+    for (uint32_t i = 0; i < n; i++)
+        if (sd.dst == SZK_DST_VIEW ? !outs[i].dst : sd.dst == SZK_DST_INDEX && (uintptr_t)outs[i].dst != i) return -1;
     for (uint32_t i = 0; i < n; i++) {  // one stream: every box on the grid of its own level
         const szk_region_geom &g = gs[i];
         if (g.N != ip->N || g.nbuf < 1 || g.nbuf > SZK_REGION_MAX_LEVELS || g.n_levels < 0 || g.n_levels > g.nbuf || g.shift < 0 || g.shift > 30) return -1;
         for (int j = 0; j < ip->N; j++)
             if (g.full[j] != ip->dims[j] || g.dims[j] != ((ip->dims[j] - 1) >> g.shift) + 1) return -1;
-        if (!sink && !outs[i].dst) return -1;
         if (g.shift == gs[0].shift) {  // (the one-level sequence's conditions, for the boxes of a level)
             if (g.n_levels != gs[0].n_levels || g.nbuf != gs[0].nbuf || g.anchor != gs[0].anchor) return -1;
         }
@@ -1481,7 +1430,8 @@ int szk_launch_interp_decompress_region_request(int dtype, const szk_interp_para
 }
 
 int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gather_strided_box *recs, uint32_t n, uint64_t *h_table, uint64_t *d_table,
-                            uint64_t table_words, hipEvent_t copied, hipStream_t s, const szk_region_sink *sink) {
+                            uint64_t table_words, hipEvent_t copied, hipStream_t s, const szk_region_sink *sink, uint32_t *launches) {
+    if (launches) *launches = 0;
     if (n < 1 || n > 65535 || !d_src || !recs || !h_table || !d_table || (uint64_t)n * SZK_WORDS(szk_region_gather_strided_box) > table_words) return -1;
     uint64_t most = 0;
     for (uint32_t i = 0; i < n; i++) most = std::max(most, recs[i].total);
@@ -1494,10 +1444,10 @@ int szk_launch_gather_boxes(int dtype, const void *d_src, const szk_region_gathe
     if (hipEventRecord(copied, s) != hipSuccess) return -2;
     const szk_region_gather_strided_box *d_recs = reinterpret_cast<const szk_region_gather_strided_box *>(d_table);
     if (sink)
-        return dtype == 0 ? region_sink_launch<float>(nullptr, (const float *)d_src, d_recs, n, most, sink, true, s)
-                          : region_sink_launch<double>(nullptr, (const double *)d_src, d_recs, n, most, sink, true, s);
-    if (dtype == 0) region_launch(nullptr, k_region_gather_strided<float>, dim3(gx, n), 256, s, (const float *)d_src, d_recs);
-    else region_launch(nullptr, k_region_gather_strided<double>, dim3(gx, n), 256, s, (const double *)d_src, d_recs);
+        return dtype == 0 ? region_sink_launch<float>(launches, (const float *)d_src, d_recs, n, most, sink, true, s)
+                          : region_sink_launch<double>(launches, (const double *)d_src, d_recs, n, most, sink, true, s);
+    if (dtype == 0) region_launch(launches, k_region_gather_strided<float>, dim3(gx, n), 256, s, (const float *)d_src, d_recs);
+    else region_launch(launches, k_region_gather_strided<double>, dim3(gx, n), 256, s, (const double *)d_src, d_recs);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -300,71 +300,6 @@ extern "C" int sz3hip_stream_stats(const sz3hip_stream *h, struct sz3hip_stream_
     return 0;
 }
 
-extern "C" int sz3hip_stream_tiles(sz3hip_stream *h, int level, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, void *stream) {
-    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_tiles: no handle");
-    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
-    int rc = szi_boxes_args("sz3hip_stream_tiles", boxes, n, d_outs, "d_outs");
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceScope scope;
-    if (!h->fast) {  // strided gathers out of the resident array (nothing of it is written after open: no ordering between requests is needed)
-        if ((rc = boxes_on_grid(h, level, boxes, n)) || (rc = szi_boxes_outputs_check(h->N, boxes, n, d_outs, tsize(h->dtype)))) return rc;
-        HIPCHK(hipSetDevice(h->device));
-        uint64_t str[4] = {0, 0, 0, 0}, run = 1;
-        for (int i = h->N - 1; i >= 0; i--) {
-            str[i] = run;
-            run *= h->dims[i];
-        }
-        for (uint32_t b = 0; b < n; b++) {
-            szk_view gv;
-            memset(&gv, 0, sizeof(gv));
-            uint64_t corner = 0;
-            for (int q = 0; q < 4; q++) {
-                const int i = q - (4 - h->N);
-                gv.dims[q] = i >= 0 ? boxes[b].ext[i] : 1;
-                gv.str[q] = i >= 0 && boxes[b].ext[i] > 1 ? (int64_t)(str[i] << level) : 0;
-                if (i >= 0) corner += (boxes[b].lo[i] << level) * str[i];
-            }
-            if (szk_launch_gather(h->dtype, 0, (const char *)h->d_full + corner * tsize(h->dtype), &gv, d_outs[b], nullptr, s)) return fail(SZ3HIP_EHIP, "gather kernel failed");
-        }
-        h->launches_last = n;
-        h->chain_last = h->levels_last = 0;
-        h->chain_points_last = sz3hip_debug_get_chain_points();
-        h->requests++;
-        return 0;
-    }
-    // every box and every output before anything is launched or written (boxes_prepare of sz3hip_api.cpp, on the handle's arrays)
-    const szk_interp_params &ip = h->codes.ip;
-    std::vector<szk_region_geom> gs;
-    uint64_t elems = 0;
-    if ((rc = szi_boxes_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, level, boxes, n, gs, &elems))) return rc;
-    if ((rc = szi_boxes_outputs_check(ip.N, boxes, n, d_outs, tsize(h->dtype)))) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    if ((rc = region_reserve(h, elems)) || (rc = table_reserve(h, szk_region_multi_table_words(gs.data(), n)))) return rc;
-    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
-        HIPCHK(hipEventSynchronize(h->ev_table));
-        h->table_pending = false;
-    }
-    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
-    const uint32_t chain_points = sz3hip_debug_get_chain_points();
-    uint32_t chain_levels = 0, launches = 0;
-    h->table_pending = true;  // (the launcher records ev_table behind the table's copy)
-    // (the lists are the handle's own arrays: handed over as offsets from a null base, as a stock stream's are)
-    const int lr = szk_launch_interp_decompress_region_multi(h->dtype, &ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx, (uint64_t)(uintptr_t)h->codes.d_vval,
-                                                             h->codes.n_vout, h->codes.d_codes, h->d_region, d_outs, h->h_table, h->d_table, h->table_cap, h->ev_table, s,
-                                                             chain_points, &chain_levels, &launches);
-    HIPCHK(hipEventRecord(h->ev_req, s));
-    h->req_pending = true;
-    h->last_stream = s;
-    if (lr) return fail(SZ3HIP_EHIP, "the stream's reconstruction could not be launched (%d)", lr);
-    h->launches_last = launches;
-    h->chain_last = chain_levels;
-    h->levels_last = (uint32_t)gs[0].n_levels;
-    h->chain_points_last = chain_points;
-    h->requests++;
-    return 0;
-}
-
 // ---- boxes of several levels in one request, into strided views ----------------------------------------------------------
 namespace {
 struct ReqView {
@@ -490,14 +425,11 @@ void szi_view_record(int N, const uint64_t *ext, const uint64_t *str, uint64_t c
     }
 }
 
-extern "C" int sz3hip_request_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, sz3hip_request_plan *out) {
-    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_request_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
-    int rc = dtype_check(dataType);
-    if (rc || (rc = request_args("sz3hip_request_plan_for", reqs, n))) return rc;
-    std::vector<szk_region_geom> gs;
-    std::vector<ReqView> vs;
-    memset(out, 0, sizeof(*out));
-    if ((rc = szi_request_geometry_conf(conf, reqs, n, gs, &out->scratch_elems)) || (rc = request_views(conf->N, reqs, n, tsize(dataType), vs))) return rc;
+// ---- what every call of a kind shares: the plans' prefix, a handle's one submit path, the _device calls' view ------------
+namespace {
+// the plan structs' shared prefix: sz3hip_request_plan's fields in front of scratch_elems (that one is the call's own)
+template <typename Plan, typename Req>
+void plan_prefix(Plan *out, const Req *reqs, uint32_t n, const std::vector<szk_region_geom> &gs) {
     out->n = n;
     out->finest_level = out->coarsest_level = reqs[0].level;
     for (uint32_t i = 0; i < n; i++) {
@@ -506,6 +438,173 @@ extern "C" int sz3hip_request_plan_for(const sz3hip_config *conf, int dataType, 
         out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
         out->points += gs[i].points;
     }
+}
+
+// One request of a handle, whatever its sink. The handle's pinned table, scratch and device table are shared by all of them: submit_begin
+// and submit_launch are the one place that orders a request behind the previous one. Between submit_boxes and submit_begin a call runs the
+// checks of its own that need the dimension count; nothing is reserved, waited for or launched before all of them passed.
+struct Submit {
+    sz3hip_stream *h;
+    hipStream_t s;
+    DeviceScope scope;
+    int N;                                  // the stream's dimension count
+    const sz3hip_tile_req *reqs = nullptr;  // the boxes; d_out and strides count where the sink's `dst` word is the view (SZK_DST_VIEW)
+    uint32_t n = 0;
+    std::vector<szk_region_geom> gs;        // fast: the boxes' geometry and the level buffers' elements
+    uint64_t elems = 0;
+    void *const *d_outs = nullptr;          // sz3hip_stream_tiles: boxes of one level into contiguous arrays, the multi launcher's form
+    Submit(sz3hip_stream *h_, void *stream) : h(h_), s((hipStream_t)stream), N(h_->fast ? h_->codes.ip.N : h_->N) {}
+};
+// every box on the grid of its own level: the geometry, or — a handle that keeps the full array — the checks alone
+int submit_boxes(Submit &sub, const sz3hip_tile_req *reqs, uint32_t n) {
+    sub.reqs = reqs;
+    sub.n = n;
+    if (!sub.h->fast) return full_boxes_check(sub.h, reqs, n);
+    const szk_interp_params &ip = sub.h->codes.ip;
+    return szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, sub.gs, &sub.elems);
+}
+// the device; the scratch (`scratch` elements: the level buffers and what the sink keeps behind them) and the table's room (the sink
+// table's); then the two waits
+int submit_begin(Submit &sub, const szk_region_sink *sink, uint64_t scratch) {
+    sz3hip_stream *h = sub.h;
+    const uint64_t words = sub.d_outs ? szk_region_multi_table_words(sub.gs.data(), sub.n) : szk_sink_table_words(sink, h->fast ? sub.gs.data() : nullptr, sub.n);
+    int rc;
+    HIPCHK(hipSetDevice(h->device));
+    if ((rc = region_reserve(h, scratch)) || (rc = table_reserve(h, words))) return rc;
+    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
+        HIPCHK(hipEventSynchronize(h->ev_table));
+        h->table_pending = false;
+    }
+    if (h->req_pending && sub.s != h->last_stream) HIPCHK(hipStreamWaitEvent(sub.s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
+    return 0;
+}
+// the one launcher call and what follows it. vs: the boxes' views where the sink reads them (null: no strides); first: box i's first
+// partial record where the `dst` word carries it (SZK_DST_PART). ev_req is recorded and the handle marked even when the launcher fails
+// (part of the sequence may be issued); the statistics change on success only. what: the call's noun in the failure's message
+int submit_launch(Submit &sub, const char *what, const szk_region_sink *sink, const std::vector<ReqView> *vs, const uint64_t *first) {
+    sz3hip_stream *h = sub.h;
+    const uint32_t n = sub.n, chain_points = sz3hip_debug_get_chain_points();
+    const int dst = szk_sink(sink).dst;
+    auto dst_word = [&](uint32_t i) { return dst == SZK_DST_VIEW ? sub.reqs[i].d_out : (void *)(uintptr_t)(dst == SZK_DST_INDEX ? (uint64_t)i : SZK_REDUCE_DST(first[i], i)); };
+    uint32_t chain_levels = 0, launches = 0, levels = 0;
+    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
+    // (fast: the lists are the handle's own arrays, handed over as offsets from a null base, as a stock stream's are)
+    const szi_stream_codes &c = h->codes;
+    const uint64_t vidx = (uint64_t)(uintptr_t)c.d_vidx, vval = (uint64_t)(uintptr_t)c.d_vval;
+    int lr;
+    if (sub.d_outs) {
+        levels = (uint32_t)sub.gs[0].n_levels;
+        lr = szk_launch_interp_decompress_region_multi(h->dtype, &c.ip, sub.gs.data(), n, sub.elems, nullptr, vidx, vval, c.n_vout, c.d_codes, h->d_region, sub.d_outs, h->h_table,
+                                                       h->d_table, h->table_cap, h->ev_table, sub.s, chain_points, &chain_levels, &launches);
+    } else if (!h->fast) {
+        std::vector<szk_region_gather_strided_box> full_recs(n);
+        for (uint32_t i = 0; i < n; i++) {
+            full_record(h, sub.reqs[i], vs ? (*vs)[i].str : nullptr, &full_recs[i]);
+            full_recs[i].dst = dst_word(i);
+        }
+        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, sub.s, sink, &launches);
+    } else {
+        std::vector<szk_region_out> outs(n);
+        for (uint32_t i = 0; i < n; i++) {
+            outs[i].dst = dst_word(i);
+            for (int j = 0; j < 4; j++) outs[i].str[j] = vs && j < sub.N ? (*vs)[i].str[j] : 0;
+        }
+        lr = szk_launch_interp_decompress_region_request(h->dtype, &c.ip, sub.gs.data(), n, sub.elems, nullptr, vidx, vval, c.n_vout, c.d_codes, h->d_region, outs.data(), h->h_table,
+                                                         h->d_table, h->table_cap, h->ev_table, sub.s, chain_points, &chain_levels, &launches, &levels, sink);
+    }
+    HIPCHK(hipEventRecord(h->ev_req, sub.s));
+    h->req_pending = true;
+    h->last_stream = sub.s;
+    if (lr) return fail(SZ3HIP_EHIP, "the stream's %s could not be launched (%d)", what, lr);
+    h->launches_last = launches;
+    h->chain_last = chain_levels;
+    h->levels_last = levels;
+    h->chain_points_last = chain_points;
+    h->requests++;
+    return 0;
+}
+
+// a _device call's arguments in front of its own: the type and the extents ...
+int device_dims(int dataType, int N, const uint64_t *dims) {
+    const int rc = dtype_check(dataType);
+    if (rc) return rc;
+    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
+    for (int i = 0; i < N; i++)
+        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
+    return 0;
+}
+// ... and behind them: the input view's strides, device and alignment; the output (where the call has one) as a request's view of the whole
+// array at level 0, for the request's own view checks
+struct DeviceView {
+    uint64_t str[4] = {0, 0, 0, 0};
+    int dev = 0;
+    sz3hip_tile_req q;
+};
+int device_view(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, void *d_out, const int64_t *strides_out, DeviceView *v) {
+    int rc;
+    if ((rc = szi_dev_view_strides(N, dims, strides_in, v->str)) || (rc = szi_dev_pointer(d_in, &v->dev))) return rc;
+    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    memset(&v->q, 0, sizeof(v->q));
+    for (int i = 0; i < N; i++) {
+        v->q.box.ext[i] = dims[i];
+        v->q.strides[i] = strides_out ? strides_out[i] : 0;
+    }
+    v->q.d_out = d_out;
+    return 0;
+}
+}  // namespace
+
+extern "C" int sz3hip_stream_tiles(sz3hip_stream *h, int level, const sz3hip_box *boxes, uint32_t n, void *const *d_outs, void *stream) {
+    if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_tiles: no handle");
+    if (level < 0 || level > 30) return fail(SZ3HIP_EINVAL, "tile level %d is outside 0 .. 30", level);
+    int rc = szi_boxes_args("sz3hip_stream_tiles", boxes, n, d_outs, "d_outs");
+    if (rc) return rc;
+    Submit sub(h, stream);
+    hipStream_t s = sub.s;
+    if (!h->fast) {  // strided gathers out of the resident array (nothing of it is written after open: no ordering between requests is needed)
+        if ((rc = boxes_on_grid(h, level, boxes, n)) || (rc = szi_boxes_outputs_check(h->N, boxes, n, d_outs, tsize(h->dtype)))) return rc;
+        HIPCHK(hipSetDevice(h->device));
+        uint64_t str[4] = {0, 0, 0, 0}, run = 1;
+        for (int i = h->N - 1; i >= 0; i--) {
+            str[i] = run;
+            run *= h->dims[i];
+        }
+        for (uint32_t b = 0; b < n; b++) {
+            szk_view gv;
+            memset(&gv, 0, sizeof(gv));
+            uint64_t corner = 0;
+            for (int q = 0; q < 4; q++) {
+                const int i = q - (4 - h->N);
+                gv.dims[q] = i >= 0 ? boxes[b].ext[i] : 1;
+                gv.str[q] = i >= 0 && boxes[b].ext[i] > 1 ? (int64_t)(str[i] << level) : 0;
+                if (i >= 0) corner += (boxes[b].lo[i] << level) * str[i];
+            }
+            if (szk_launch_gather(h->dtype, 0, (const char *)h->d_full + corner * tsize(h->dtype), &gv, d_outs[b], nullptr, s)) return fail(SZ3HIP_EHIP, "gather kernel failed");
+        }
+        h->launches_last = n;
+        h->chain_last = h->levels_last = 0;
+        h->chain_points_last = sz3hip_debug_get_chain_points();
+        h->requests++;
+        return 0;
+    }
+    // every box and every output before anything is launched or written (boxes_prepare of sz3hip_api.cpp, on the handle's arrays)
+    const szk_interp_params &ip = h->codes.ip;
+    sub.n = n;
+    sub.d_outs = d_outs;
+    if ((rc = szi_boxes_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, level, boxes, n, sub.gs, &sub.elems))) return rc;
+    if ((rc = szi_boxes_outputs_check(ip.N, boxes, n, d_outs, tsize(h->dtype))) || (rc = submit_begin(sub, nullptr, sub.elems))) return rc;
+    return submit_launch(sub, "reconstruction", nullptr, nullptr, nullptr);
+}
+
+extern "C" int sz3hip_request_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_tile_req *reqs, uint32_t n, sz3hip_request_plan *out) {
+    if (!conf || !out) return fail(SZ3HIP_EINVAL, "sz3hip_request_plan_for: NULL argument (%s)", !conf ? "conf" : "out");
+    int rc = dtype_check(dataType);
+    if (rc || (rc = request_args("sz3hip_request_plan_for", reqs, n))) return rc;
+    std::vector<szk_region_geom> gs;
+    std::vector<ReqView> vs;
+    memset(out, 0, sizeof(*out));
+    if ((rc = szi_request_geometry_conf(conf, reqs, n, gs, &out->scratch_elems)) || (rc = request_views(conf->N, reqs, n, tsize(dataType), vs))) return rc;
+    plan_prefix(out, reqs, n, gs);
     return 0;
 }
 
@@ -513,57 +612,10 @@ extern "C" int sz3hip_stream_request(sz3hip_stream *h, const sz3hip_tile_req *re
     if (!h) return fail(SZ3HIP_EINVAL, "sz3hip_stream_request: no handle");
     int rc = request_args("sz3hip_stream_request", reqs, n);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceScope scope;
+    Submit sub(h, stream);
     std::vector<ReqView> vs;
-    std::vector<szk_region_geom> gs;
-    uint64_t elems = 0, words = 0;
-    std::vector<szk_region_gather_strided_box> full_recs;  // a handle that keeps the full array
-    if (!h->fast) {
-        if ((rc = full_boxes_check(h, reqs, n)) || (rc = request_views(h->N, reqs, n, tsize(h->dtype), vs))) return rc;
-        full_recs.resize(n);
-        for (uint32_t b = 0; b < n; b++) full_record(h, reqs[b], vs[b].str, &full_recs[b]);
-        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
-    } else {
-        const szk_interp_params &ip = h->codes.ip;
-        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
-        if ((rc = request_views(ip.N, reqs, n, tsize(h->dtype), vs))) return rc;
-        words = szk_region_request_table_words(gs.data(), n);
-    }
-    HIPCHK(hipSetDevice(h->device));
-    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
-    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
-        HIPCHK(hipEventSynchronize(h->ev_table));
-        h->table_pending = false;
-    }
-    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
-    const uint32_t chain_points = sz3hip_debug_get_chain_points();
-    uint32_t chain_levels = 0, launches = 0, levels = 0;
-    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
-    int lr;
-    if (!h->fast) {
-        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s);
-        launches = 1;
-    } else {
-        std::vector<szk_region_out> outs(n);
-        for (uint32_t i = 0; i < n; i++) {
-            outs[i].dst = reqs[i].d_out;
-            for (int j = 0; j < 4; j++) outs[i].str[j] = j < h->codes.ip.N ? vs[i].str[j] : 0;
-        }
-        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
-                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, outs.data(), h->h_table,
-                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels);
-    }
-    HIPCHK(hipEventRecord(h->ev_req, s));
-    h->req_pending = true;
-    h->last_stream = s;
-    if (lr) return fail(SZ3HIP_EHIP, "the stream's reconstruction could not be launched (%d)", lr);
-    h->launches_last = launches;
-    h->chain_last = chain_levels;
-    h->levels_last = levels;
-    h->chain_points_last = chain_points;
-    h->requests++;
-    return 0;
+    if ((rc = submit_boxes(sub, reqs, n)) || (rc = request_views(sub.N, reqs, n, tsize(h->dtype), vs)) || (rc = submit_begin(sub, nullptr, sub.elems))) return rc;
+    return submit_launch(sub, "reconstruction", nullptr, &vs, nullptr);
 }
 
 // ---- numbers about boxes, no output --------------------------------------------------------------------------------------
@@ -630,6 +682,24 @@ ReduceWs *reduce_ws(int device) {
     if (!p) p.reset(new ReduceWs);
     return p.get();
 }
+// room for `parts` records, and the call on s ordered behind the previous one (w->mu is held)
+int reduce_ws_reserve(ReduceWs *w, uint64_t parts, hipStream_t s) {
+    if (!w->ev) HIPCHK(hipEventCreateWithFlags(&w->ev, hipEventDisableTiming));
+    if (parts > w->cap) {
+        if (w->d_partials) {
+            HIPCHK(hipDeviceSynchronize());  // (an earlier call's kernels may still use them)
+            (void)hipFree(w->d_partials);
+        }
+        w->d_partials = nullptr;
+        w->cap = 0;
+        w->pending = false;
+        const uint64_t cap = std::max<uint64_t>(parts, 4096);
+        HIPCHK(hipMalloc((void **)&w->d_partials, cap * sizeof(szk_reduce_part)));
+        w->cap = cap;
+    }
+    if (w->pending && s != w->last) HIPCHK(hipStreamWaitEvent(s, w->ev, 0));
+    return 0;
+}
 }  // namespace
 
 extern "C" int sz3hip_reduce_plan_for(const sz3hip_config *conf, int dataType, const sz3hip_reduce_req *reqs, uint32_t n, const sz3hip_reduce_opts *opts,
@@ -643,14 +713,7 @@ extern "C" int sz3hip_reduce_plan_for(const sz3hip_config *conf, int dataType, c
     uint64_t elems = 0;
     memset(out, 0, sizeof(*out));
     if ((rc = szi_request_geometry_conf(conf, tr.data(), n, gs, &elems))) return rc;
-    out->n = n;
-    out->finest_level = out->coarsest_level = reqs[0].level;
-    for (uint32_t i = 0; i < n; i++) {
-        out->finest_level = std::min(out->finest_level, reqs[i].level);
-        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
-        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
-        out->points += gs[i].points;
-    }
+    plan_prefix(out, reqs, n, gs);
     out->partials = reduce_partials(tr.data(), n, conf->N, nullptr);
     out->scratch_elems = reduce_scratch_elems(elems, out->partials, tsize(dataType));
     out->hist_words = (uint64_t)n * (hh.nbins ? hh.nbins + 2 : 0);
@@ -666,104 +729,39 @@ extern "C" int sz3hip_stream_reduce(sz3hip_stream *h, const sz3hip_reduce_req *r
     memset(&sink, 0, sizeof(sink));
     int rc = reduce_args("sz3hip_stream_reduce", reqs, n, d_stats, "d_stats", tr);
     if (rc || (rc = reduce_opts(opts, d_hist, true, &sink.hist))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceScope scope;
-    std::vector<szk_region_geom> gs;
+    Submit sub(h, stream);
     std::vector<uint64_t> first;
-    uint64_t elems = 0, words = 0;
-    const int N = h->fast ? h->codes.ip.N : h->N;
-    if (!h->fast) {
-        if ((rc = full_boxes_check(h, tr.data(), n))) return rc;
-        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
-    } else {
-        const szk_interp_params &ip = h->codes.ip;
-        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, tr.data(), n, gs, &elems))) return rc;
-        // (behind a request's table: the boxes' records once more, for the final of a request served level group by level group)
-        words = szk_region_request_table_words(gs.data(), n) + (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
-    }
-    const uint64_t partials = reduce_partials(tr.data(), n, N, &first);
+    if ((rc = submit_boxes(sub, tr.data(), n))) return rc;
+    const uint64_t partials = reduce_partials(tr.data(), n, sub.N, &first);
     if (partials >= (1ull << 40)) return fail(SZ3HIP_EINVAL, "the boxes hold too many points for one reducing request");
-    for (uint32_t i = 0; i < n; i++) tr[i].d_out = (void *)(uintptr_t)SZK_REDUCE_DST(first[i], i);  // (a reducing request's `dst` word)
-    HIPCHK(hipSetDevice(h->device));
-    if ((rc = region_reserve(h, reduce_scratch_elems(elems, partials, tsize(h->dtype)))) || (rc = table_reserve(h, words))) return rc;
-    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
-        HIPCHK(hipEventSynchronize(h->ev_table));
-        h->table_pending = false;
-    }
-    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
-    sink.partials = reinterpret_cast<szk_reduce_part *>((char *)h->d_region + reduce_part_base(elems, tsize(h->dtype)) * tsize(h->dtype));
+    if ((rc = submit_begin(sub, &sink, reduce_scratch_elems(sub.elems, partials, tsize(h->dtype))))) return rc;
+    sink.partials = reinterpret_cast<szk_reduce_part *>((char *)h->d_region + reduce_part_base(sub.elems, tsize(h->dtype)) * tsize(h->dtype));
     sink.d_stats = d_stats;
     sink.d_hist = sink.hist.nbins ? d_hist : nullptr;
-    if (sink.hist.nbins) HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)n * (sink.hist.nbins + 2) * 8, s));
-    const uint32_t chain_points = sz3hip_debug_get_chain_points();
-    uint32_t chain_levels = 0, launches = 0, levels = 0;
-    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
-    int lr;
-    if (!h->fast) {
-        std::vector<szk_region_gather_strided_box> full_recs(n);
-        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
-        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
-        launches = 2;
-    } else {
-        std::vector<szk_region_out> outs(n);
-        for (uint32_t i = 0; i < n; i++) {
-            memset(&outs[i], 0, sizeof(outs[i]));
-            outs[i].dst = tr[i].d_out;
-        }
-        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
-                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, outs.data(), h->h_table,
-                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
-    }
-    HIPCHK(hipEventRecord(h->ev_req, s));
-    h->req_pending = true;
-    h->last_stream = s;
-    if (lr) return fail(SZ3HIP_EHIP, "the stream's reduction could not be launched (%d)", lr);
-    h->launches_last = launches;
-    h->chain_last = chain_levels;
-    h->levels_last = levels;
-    h->chain_points_last = chain_points;
-    h->requests++;
-    return 0;
+    if (sink.hist.nbins) HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)n * (sink.hist.nbins + 2) * 8, sub.s));
+    return submit_launch(sub, "reduction", &sink, nullptr, first.data());
 }
 
 extern "C" int sz3hip_reduce_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_reduce_opts *opts,
                                     sz3hip_box_stats *d_stats, uint64_t *d_hist, void *stream) {
-    int rc = dtype_check(dataType);
+    int rc = device_dims(dataType, N, dims);
     if (rc) return rc;
-    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
-    for (int i = 0; i < N; i++)
-        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
     if (!d_stats) return fail(SZ3HIP_EINVAL, "sz3hip_reduce_device: NULL argument (d_stats)");
     szk_region_sink sink;
     memset(&sink, 0, sizeof(sink));
     if ((rc = reduce_opts(opts, d_hist, true, &sink.hist))) return rc;
-    uint64_t str[4] = {0, 0, 0, 0};
-    int dev = 0;
-    if ((rc = szi_dev_view_strides(N, dims, strides, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
-    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    DeviceView v;
+    if ((rc = device_view(dataType, N, dims, d_in, strides, nullptr, nullptr, &v))) return rc;
     szk_region_gather_strided_box rec;
-    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);  // (dst word 0: the view's first partial record)
+    szi_view_record(N, dims, v.str, 0, nullptr, nullptr, &rec);  // (dst word 0: the view's first partial record)
     const uint64_t partials = szk_reduce_chunks(rec.total);
     if (partials >= (1ull << 40)) return fail(SZ3HIP_EINVAL, "the view holds too many points for one reduction");
     hipStream_t s = (hipStream_t)stream;
     DeviceScope scope;
-    HIPCHK(hipSetDevice(dev));
-    ReduceWs *w = reduce_ws(dev);
+    HIPCHK(hipSetDevice(v.dev));
+    ReduceWs *w = reduce_ws(v.dev);
     std::lock_guard<std::mutex> lock(w->mu);
-    if (!w->ev) HIPCHK(hipEventCreateWithFlags(&w->ev, hipEventDisableTiming));
-    if (partials > w->cap) {
-        if (w->d_partials) {
-            HIPCHK(hipDeviceSynchronize());  // (an earlier call's kernels may still use them)
-            (void)hipFree(w->d_partials);
-        }
-        w->d_partials = nullptr;
-        w->cap = 0;
-        w->pending = false;
-        const uint64_t cap = std::max<uint64_t>(partials, 4096);
-        HIPCHK(hipMalloc((void **)&w->d_partials, cap * sizeof(szk_reduce_part)));
-        w->cap = cap;
-    }
-    if (w->pending && s != w->last) HIPCHK(hipStreamWaitEvent(s, w->ev, 0));
+    if ((rc = reduce_ws_reserve(w, partials, s))) return rc;
     sink.partials = w->d_partials;
     sink.d_stats = d_stats;
     sink.d_hist = sink.hist.nbins ? d_hist : nullptr;
@@ -837,14 +835,7 @@ extern "C" int sz3hip_select_plan_for(const sz3hip_config *conf, int dataType, c
     uint64_t elems = 0;
     memset(out, 0, sizeof(*out));
     if ((rc = szi_request_geometry_conf(conf, tr.data(), n, gs, &elems))) return rc;
-    out->n = n;
-    out->finest_level = out->coarsest_level = reqs[0].level;
-    for (uint32_t i = 0; i < n; i++) {
-        out->finest_level = std::min(out->finest_level, reqs[i].level);
-        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
-        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
-        out->points += gs[i].points;
-    }
+    plan_prefix(out, reqs, n, gs);
     out->partials = reduce_partials(tr.data(), n, conf->N, nullptr);
     out->scratch_elems = select_scratch_elems(elems, out->partials, tsize(dataType));
     return 0;
@@ -860,113 +851,46 @@ extern "C" int sz3hip_stream_select(sz3hip_stream *h, const sz3hip_select_req *r
     sink.kind = SZK_SINK_SELECT;
     int rc = select_args("sz3hip_stream_select", reqs, n, tsize(h->dtype), tr);
     if (rc || (rc = select_opts(opts, &sink.sel))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceScope scope;
-    std::vector<szk_region_geom> gs;
+    Submit sub(h, stream);
     std::vector<uint64_t> first;
-    uint64_t elems = 0, words = 0;
-    const int N = h->fast ? h->codes.ip.N : h->N;
-    // (behind the boxes' records: every box's d_index, d_value and capacity, in the table's one copy)
-    const uint64_t tail = (uint64_t)n * SZK_SELECT_OUT_WORDS;
-    if (!h->fast) {
-        if ((rc = full_boxes_check(h, tr.data(), n))) return rc;
-        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
-    } else {
-        const szk_interp_params &ip = h->codes.ip;
-        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, tr.data(), n, gs, &elems))) return rc;
-        // (behind a request's table: the boxes' records once more, for scan and write of a request served level group by level group)
-        words = szk_region_request_table_words(gs.data(), n) + (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
-    }
-    const uint64_t partials = reduce_partials(tr.data(), n, N, &first);
+    if ((rc = submit_boxes(sub, tr.data(), n))) return rc;
+    const uint64_t partials = reduce_partials(tr.data(), n, sub.N, &first);
     if (partials >= (1ull << 40)) return fail(SZ3HIP_EINVAL, "the boxes hold too many points for one selecting request");
-    std::vector<uint64_t> outs(tail);
+    std::vector<uint64_t> outs((size_t)n * SZK_SELECT_OUT_WORDS);  // (every box's d_index, d_value and capacity: they ride behind the final's records)
     for (uint32_t i = 0; i < n; i++) {
-        tr[i].d_out = (void *)(uintptr_t)SZK_REDUCE_DST(first[i], i);  // (the `dst` word, as a reducing request's)
         outs[i * SZK_SELECT_OUT_WORDS] = (uint64_t)(uintptr_t)reqs[i].d_index;
         outs[i * SZK_SELECT_OUT_WORDS + 1] = (uint64_t)(uintptr_t)reqs[i].d_value;
         outs[i * SZK_SELECT_OUT_WORDS + 2] = reqs[i].capacity;
     }
-    HIPCHK(hipSetDevice(h->device));
-    if ((rc = region_reserve(h, select_scratch_elems(elems, partials, tsize(h->dtype)))) || (rc = table_reserve(h, words))) return rc;
-    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
-        HIPCHK(hipEventSynchronize(h->ev_table));
-        h->table_pending = false;
-    }
-    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
-    sink.sel_counts = reinterpret_cast<uint64_t *>((char *)h->d_region + reduce_part_base(elems, tsize(h->dtype)) * tsize(h->dtype));
+    if ((rc = submit_begin(sub, &sink, select_scratch_elems(sub.elems, partials, tsize(h->dtype))))) return rc;
+    sink.sel_counts = reinterpret_cast<uint64_t *>((char *)h->d_region + reduce_part_base(sub.elems, tsize(h->dtype)) * tsize(h->dtype));
     sink.sel_heads = d_heads;
     sink.sel_outs = outs.data();
-    const uint32_t chain_points = sz3hip_debug_get_chain_points();
-    uint32_t chain_levels = 0, launches = 0, levels = 0;
-    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
-    int lr;
-    if (!h->fast) {
-        std::vector<szk_region_gather_strided_box> full_recs(n);
-        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
-        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
-        launches = 3;
-    } else {
-        std::vector<szk_region_out> ro(n);
-        for (uint32_t i = 0; i < n; i++) {
-            memset(&ro[i], 0, sizeof(ro[i]));
-            ro[i].dst = tr[i].d_out;
-        }
-        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
-                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, ro.data(), h->h_table,
-                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
-    }
-    HIPCHK(hipEventRecord(h->ev_req, s));
-    h->req_pending = true;
-    h->last_stream = s;
-    if (lr) return fail(SZ3HIP_EHIP, "the stream's selection could not be launched (%d)", lr);
-    h->launches_last = launches;
-    h->chain_last = chain_levels;
-    h->levels_last = levels;
-    h->chain_points_last = chain_points;
-    h->requests++;
-    return 0;
+    return submit_launch(sub, "selection", &sink, nullptr, first.data());
 }
 
 extern "C" int sz3hip_select_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_select_opts *opts,
                                     uint64_t *d_index, void *d_value, uint64_t capacity, sz3hip_select_head *d_head, void *stream) {
-    int rc = dtype_check(dataType);
+    int rc = device_dims(dataType, N, dims);
     if (rc) return rc;
-    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
-    for (int i = 0; i < N; i++)
-        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
     if (!d_head) return fail(SZ3HIP_EINVAL, "sz3hip_select_device: NULL argument (d_head)");
     szk_region_sink sink;
     memset(&sink, 0, sizeof(sink));
     sink.kind = SZK_SINK_SELECT;
     if ((rc = select_opts(opts, &sink.sel)) || (rc = select_out("", d_index, d_value, capacity, tsize(dataType)))) return rc;
-    uint64_t str[4] = {0, 0, 0, 0};
-    int dev = 0;
-    if ((rc = szi_dev_view_strides(N, dims, strides, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
-    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    DeviceView v;
+    if ((rc = device_view(dataType, N, dims, d_in, strides, nullptr, nullptr, &v))) return rc;
     szk_region_gather_strided_box rec;
-    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);  // (dst word 0: the view's first chunk record)
+    szi_view_record(N, dims, v.str, 0, nullptr, nullptr, &rec);  // (dst word 0: the view's first chunk record)
     const uint64_t partials = szk_reduce_chunks(rec.total);
     if (partials >= (1ull << 40)) return fail(SZ3HIP_EINVAL, "the view holds too many points for one selection");
     const uint64_t parts = (partials * 8 + sizeof(szk_reduce_part) - 1) / sizeof(szk_reduce_part);  // (the workspace counts reduce records)
     hipStream_t s = (hipStream_t)stream;
     DeviceScope scope;
-    HIPCHK(hipSetDevice(dev));
-    ReduceWs *w = reduce_ws(dev);
+    HIPCHK(hipSetDevice(v.dev));
+    ReduceWs *w = reduce_ws(v.dev);
     std::lock_guard<std::mutex> lock(w->mu);
-    if (!w->ev) HIPCHK(hipEventCreateWithFlags(&w->ev, hipEventDisableTiming));
-    if (parts > w->cap) {
-        if (w->d_partials) {
-            HIPCHK(hipDeviceSynchronize());  // (an earlier call's kernels may still use them)
-            (void)hipFree(w->d_partials);
-        }
-        w->d_partials = nullptr;
-        w->cap = 0;
-        w->pending = false;
-        const uint64_t cap = std::max<uint64_t>(parts, 4096);
-        HIPCHK(hipMalloc((void **)&w->d_partials, cap * sizeof(szk_reduce_part)));
-        w->cap = cap;
-    }
-    if (w->pending && s != w->last) HIPCHK(hipStreamWaitEvent(s, w->ev, 0));
+    if ((rc = reduce_ws_reserve(w, parts, s))) return rc;
     const uint64_t out3[SZK_SELECT_OUT_WORDS] = {(uint64_t)(uintptr_t)d_index, (uint64_t)(uintptr_t)d_value, capacity};
     sink.sel_counts = reinterpret_cast<uint64_t *>(w->d_partials);
     sink.sel_heads = d_head;
@@ -1051,14 +975,7 @@ extern "C" int sz3hip_map_plan_for(const sz3hip_config *conf, int dataType, cons
     memset(out, 0, sizeof(*out));
     const size_t osz = szk_map_out_bytes(mo.out_type);
     if ((rc = szi_request_geometry_conf(conf, reqs, n, gs, &out->scratch_elems)) || (rc = map_views(conf->N, reqs, n, osz, vs))) return rc;
-    out->n = n;
-    out->finest_level = out->coarsest_level = reqs[0].level;
-    for (uint32_t i = 0; i < n; i++) {
-        out->finest_level = std::min(out->finest_level, reqs[i].level);
-        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
-        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
-        out->points += gs[i].points;
-    }
+    plan_prefix(out, reqs, n, gs);
     out->out_elem_bytes = osz;
     return 0;
 }
@@ -1070,90 +987,32 @@ extern "C" int sz3hip_stream_map(sz3hip_stream *h, const sz3hip_tile_req *reqs, 
     int rc = request_args("sz3hip_stream_map", reqs, n);
     if (rc || (rc = map_opts_check(opts, &sink.map))) return rc;
     const size_t osz = szk_map_out_bytes(sink.map.out_type);
-    hipStream_t s = (hipStream_t)stream;
-    DeviceScope scope;
+    Submit sub(h, stream);
     std::vector<ReqView> vs;
-    std::vector<szk_region_geom> gs;
-    uint64_t elems = 0, words = 0;
-    const int N = h->fast ? h->codes.ip.N : h->N;
-    if (!h->fast) {
-        if ((rc = full_boxes_check(h, reqs, n)) || (rc = map_views(N, reqs, n, osz, vs))) return rc;
-        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
-    } else {
-        const szk_interp_params &ip = h->codes.ip;
-        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
-        if ((rc = map_views(N, reqs, n, osz, vs))) return rc;
-        words = szk_region_request_table_words(gs.data(), n);
-    }
-    map_sink(&sink, N, reqs, n, vs);
-    HIPCHK(hipSetDevice(h->device));
-    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
-    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
-        HIPCHK(hipEventSynchronize(h->ev_table));
-        h->table_pending = false;
-    }
-    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
-    const uint32_t chain_points = sz3hip_debug_get_chain_points();
-    uint32_t chain_levels = 0, launches = 0, levels = 0;
-    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
-    int lr;
-    if (!h->fast) {
-        std::vector<szk_region_gather_strided_box> full_recs(n);
-        for (uint32_t b = 0; b < n; b++) full_record(h, reqs[b], vs[b].str, &full_recs[b]);
-        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
-        launches = 1;
-    } else {
-        std::vector<szk_region_out> outs(n);
-        for (uint32_t i = 0; i < n; i++) {
-            outs[i].dst = reqs[i].d_out;
-            for (int j = 0; j < 4; j++) outs[i].str[j] = j < N ? vs[i].str[j] : 0;
-        }
-        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
-                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, outs.data(), h->h_table,
-                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
-    }
-    HIPCHK(hipEventRecord(h->ev_req, s));
-    h->req_pending = true;
-    h->last_stream = s;
-    if (lr) return fail(SZ3HIP_EHIP, "the stream's mapping could not be launched (%d)", lr);
-    h->launches_last = launches;
-    h->chain_last = chain_levels;
-    h->levels_last = levels;
-    h->chain_points_last = chain_points;
-    h->requests++;
-    return 0;
+    if ((rc = submit_boxes(sub, reqs, n)) || (rc = map_views(sub.N, reqs, n, osz, vs))) return rc;
+    map_sink(&sink, sub.N, reqs, n, vs);
+    if ((rc = submit_begin(sub, &sink, sub.elems))) return rc;
+    return submit_launch(sub, "mapping", &sink, &vs, nullptr);
 }
 
 extern "C" int sz3hip_map_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_map_opts *opts,
                                  void *d_out, const int64_t *strides_out, void *stream) {
-    int rc = dtype_check(dataType);
+    int rc = device_dims(dataType, N, dims);
     if (rc) return rc;
-    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
-    for (int i = 0; i < N; i++)
-        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
     if (!d_out) return fail(SZ3HIP_EINVAL, "sz3hip_map_device: NULL argument (d_out)");
     szk_region_sink sink;
     memset(&sink, 0, sizeof(sink));
     if ((rc = map_opts_check(opts, &sink.map))) return rc;
-    uint64_t str[4] = {0, 0, 0, 0};
-    int dev = 0;
-    if ((rc = szi_dev_view_strides(N, dims, strides_in, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
-    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
-    sz3hip_tile_req q;  // the output as a request's view of the whole array
-    memset(&q, 0, sizeof(q));
-    for (int i = 0; i < N; i++) {
-        q.box.ext[i] = dims[i];
-        q.strides[i] = strides_out ? strides_out[i] : 0;
-    }
-    q.d_out = d_out;
+    DeviceView v;
+    if ((rc = device_view(dataType, N, dims, d_in, strides_in, d_out, strides_out, &v))) return rc;
     std::vector<ReqView> vs;
-    if ((rc = map_views(N, &q, 1, szk_map_out_bytes(sink.map.out_type), vs))) return rc;
-    map_sink(&sink, N, &q, 1, vs);
+    if ((rc = map_views(N, &v.q, 1, szk_map_out_bytes(sink.map.out_type), vs))) return rc;
+    map_sink(&sink, N, &v.q, 1, vs);
     szk_region_gather_strided_box rec;
-    szi_view_record(N, dims, str, 0, d_out, vs[0].str, &rec);
+    szi_view_record(N, dims, v.str, 0, d_out, vs[0].str, &rec);
     hipStream_t s = (hipStream_t)stream;
     DeviceScope scope;
-    HIPCHK(hipSetDevice(dev));
+    HIPCHK(hipSetDevice(v.dev));
     if (szk_launch_region_map(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the mapping could not be launched");
     return 0;
 }
@@ -1260,15 +1119,8 @@ extern "C" int sz3hip_sample_plan_for(const sz3hip_config *conf, int dataType, c
     std::vector<szk_region_geom> gs;
     memset(out, 0, sizeof(*out));
     if ((rc = szi_request_geometry_conf(conf, tr.data(), n, gs, &out->scratch_elems)) || (rc = sample_lattices(reqs, n, conf->N))) return rc;
-    out->n = n;
-    out->finest_level = out->coarsest_level = reqs[0].level;
-    for (uint32_t i = 0; i < n; i++) {
-        out->finest_level = std::min(out->finest_level, reqs[i].level);
-        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
-        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
-        out->points += gs[i].points;
-        out->queries += reqs[i].n_points;
-    }
+    plan_prefix(out, reqs, n, gs);
+    for (uint32_t i = 0; i < n; i++) out->queries += reqs[i].n_points;
     return 0;
 }
 
@@ -1280,76 +1132,24 @@ extern "C" int sz3hip_stream_sample(sz3hip_stream *h, const sz3hip_sample_req *r
     sink.kind = SZK_SINK_SAMPLE;
     int rc = sample_opts_check(opts, &sink.smp);
     if (rc || (rc = sample_args("sz3hip_stream_sample", reqs, n, tsize(h->dtype), tsize((int)sink.smp.coord_type), tr))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceScope scope;
-    std::vector<szk_region_geom> gs;
-    uint64_t elems = 0, words = 0;
-    const int N = h->fast ? h->codes.ip.N : h->N;
-    // (behind the boxes' records: every box's queries, in the table's one copy)
-    const uint64_t tail = (uint64_t)n * SZK_SAMPLE_WORDS;
-    if (!h->fast) {
-        if ((rc = full_boxes_check(h, tr.data(), n))) return rc;
-        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
-    } else {
-        const szk_interp_params &ip = h->codes.ip;
-        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, tr.data(), n, gs, &elems))) return rc;
-        words = szk_region_request_table_words(gs.data(), n) + tail;
-    }
-    if ((rc = sample_lattices(reqs, n, N))) return rc;
+    Submit sub(h, stream);
+    if ((rc = submit_boxes(sub, tr.data(), n)) || (rc = sample_lattices(reqs, n, sub.N))) return rc;
     std::vector<szk_sample_query> queries(n);
-    sink.smp.N = (uint32_t)N;
+    sink.smp.N = (uint32_t)sub.N;
     sink.smp_threads = 1;
     for (uint32_t i = 0; i < n; i++) {
-        tr[i].d_out = (void *)(uintptr_t)i;  // (the `dst` word: the box's index in the request)
-        sample_query_words(reqs[i], N, &queries[i]);
+        sample_query_words(reqs[i], sub.N, &queries[i]);
         sink.smp_threads = std::max(sink.smp_threads, reqs[i].n_points);
     }
     sink.smp_queries = queries.data();
-    HIPCHK(hipSetDevice(h->device));
-    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
-    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
-        HIPCHK(hipEventSynchronize(h->ev_table));
-        h->table_pending = false;
-    }
-    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
-    const uint32_t chain_points = sz3hip_debug_get_chain_points();
-    uint32_t chain_levels = 0, launches = 0, levels = 0;
-    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
-    int lr;
-    if (!h->fast) {
-        std::vector<szk_region_gather_strided_box> full_recs(n);
-        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
-        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
-        launches = 1;
-    } else {
-        std::vector<szk_region_out> ro(n);
-        for (uint32_t i = 0; i < n; i++) {
-            memset(&ro[i], 0, sizeof(ro[i]));
-            ro[i].dst = tr[i].d_out;
-        }
-        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
-                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, ro.data(), h->h_table,
-                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
-    }
-    HIPCHK(hipEventRecord(h->ev_req, s));
-    h->req_pending = true;
-    h->last_stream = s;
-    if (lr) return fail(SZ3HIP_EHIP, "the stream's sampling could not be launched (%d)", lr);
-    h->launches_last = launches;
-    h->chain_last = chain_levels;
-    h->levels_last = levels;
-    h->chain_points_last = chain_points;
-    h->requests++;
-    return 0;
+    if ((rc = submit_begin(sub, &sink, sub.elems))) return rc;
+    return submit_launch(sub, "sampling", &sink, nullptr, nullptr);
 }
 
 extern "C" int sz3hip_sample_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides, const sz3hip_sample_opts *opts,
                                     const sz3hip_sample_req *query, void *stream) {
-    int rc = dtype_check(dataType);
+    int rc = device_dims(dataType, N, dims);
     if (rc) return rc;
-    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
-    for (int i = 0; i < N; i++)
-        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
     if (!query) return fail(SZ3HIP_EINVAL, "sz3hip_sample_device: NULL argument (query)");
     szk_region_sink sink;
     memset(&sink, 0, sizeof(sink));
@@ -1359,12 +1159,10 @@ extern "C" int sz3hip_sample_device(int dataType, int N, const uint64_t *dims, c
     for (int j = 0; j < 4; j++) zero = zero && query->box.lo[j] == 0 && query->box.ext[j] == 0;
     if (!zero) return fail(SZ3HIP_EINVAL, "the query's level, reserved word and box must be 0: the view is the box");
     if ((rc = sample_query_args("", *query, tsize(dataType), tsize((int)sink.smp.coord_type))) || (rc = sample_query_lattice("", *query, N))) return rc;
-    uint64_t str[4] = {0, 0, 0, 0};
-    int dev = 0;
-    if ((rc = szi_dev_view_strides(N, dims, strides, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
-    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
+    DeviceView v;
+    if ((rc = device_view(dataType, N, dims, d_in, strides, nullptr, nullptr, &v))) return rc;
     szk_region_gather_strided_box rec;
-    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);
+    szi_view_record(N, dims, v.str, 0, nullptr, nullptr, &rec);
     szk_sample_query q;
     sample_query_words(*query, N, &q);
     sink.smp.N = (uint32_t)N;
@@ -1372,7 +1170,7 @@ extern "C" int sz3hip_sample_device(int dataType, int N, const uint64_t *dims, c
     sink.smp_queries = &q;
     hipStream_t s = (hipStream_t)stream;
     DeviceScope scope;
-    HIPCHK(hipSetDevice(dev));
+    HIPCHK(hipSetDevice(v.dev));
     if (szk_launch_region_sample(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the sampling could not be launched");
     return 0;
 }
@@ -1450,13 +1248,8 @@ extern "C" int sz3hip_project_plan_for(const sz3hip_config *conf, int dataType, 
         memset(out, 0, sizeof(*out));
         return rc;
     }
-    out->n = n;
-    out->finest_level = out->coarsest_level = reqs[0].level;
+    plan_prefix(out, reqs, n, gs);
     for (uint32_t i = 0; i < n; i++) {
-        out->finest_level = std::min(out->finest_level, reqs[i].level);
-        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
-        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
-        out->points += gs[i].points;
         uint64_t outs = 1;
         for (int j = 0; j < conf->N; j++) outs *= j == (int)opts->axis ? 1 : reqs[i].box.ext[j];
         out->out_points += outs;
@@ -1471,88 +1264,30 @@ extern "C" int sz3hip_stream_project(sz3hip_stream *h, const sz3hip_tile_req *re
     memset(&sink, 0, sizeof(sink));
     int rc = request_args("sz3hip_stream_project", reqs, n);
     if (rc || (rc = project_opts_check(opts, &sink.prj))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceScope scope;
+    Submit sub(h, stream);
     std::vector<ReqView> vs;
-    std::vector<szk_region_geom> gs;
-    uint64_t elems = 0, words = 0;
-    const int N = h->fast ? h->codes.ip.N : h->N;
-    if (!h->fast) {
-        if ((rc = full_boxes_check(h, reqs, n))) return rc;
-        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8);
-    } else {
-        const szk_interp_params &ip = h->codes.ip;
-        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
-        words = szk_region_request_table_words(gs.data(), n);
-    }
-    if ((rc = project_axis(opts, N, &sink.prj)) || (rc = project_views(N, opts->axis, reqs, n, &sink, vs))) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
-    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
-        HIPCHK(hipEventSynchronize(h->ev_table));
-        h->table_pending = false;
-    }
-    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
-    const uint32_t chain_points = sz3hip_debug_get_chain_points();
-    uint32_t chain_levels = 0, launches = 0, levels = 0;
-    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
-    int lr;
-    if (!h->fast) {
-        std::vector<szk_region_gather_strided_box> full_recs(n);
-        for (uint32_t b = 0; b < n; b++) full_record(h, reqs[b], vs[b].str, &full_recs[b]);
-        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
-        launches = 1;
-    } else {
-        std::vector<szk_region_out> outs(n);
-        for (uint32_t i = 0; i < n; i++) {
-            outs[i].dst = reqs[i].d_out;
-            for (int j = 0; j < 4; j++) outs[i].str[j] = j < N ? vs[i].str[j] : 0;
-        }
-        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
-                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, outs.data(), h->h_table,
-                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
-    }
-    HIPCHK(hipEventRecord(h->ev_req, s));
-    h->req_pending = true;
-    h->last_stream = s;
-    if (lr) return fail(SZ3HIP_EHIP, "the stream's projection could not be launched (%d)", lr);
-    h->launches_last = launches;
-    h->chain_last = chain_levels;
-    h->levels_last = levels;
-    h->chain_points_last = chain_points;
-    h->requests++;
-    return 0;
+    if ((rc = submit_boxes(sub, reqs, n)) || (rc = project_axis(opts, sub.N, &sink.prj)) || (rc = project_views(sub.N, opts->axis, reqs, n, &sink, vs))) return rc;
+    if ((rc = submit_begin(sub, &sink, sub.elems))) return rc;
+    return submit_launch(sub, "projection", &sink, &vs, nullptr);
 }
 
 extern "C" int sz3hip_project_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_project_opts *opts,
                                      void *d_out, const int64_t *strides_out, void *stream) {
-    int rc = dtype_check(dataType);
+    int rc = device_dims(dataType, N, dims);
     if (rc) return rc;
-    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
-    for (int i = 0; i < N; i++)
-        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
     if (!d_out) return fail(SZ3HIP_EINVAL, "sz3hip_project_device: NULL argument (d_out)");
     szk_region_sink sink;
     memset(&sink, 0, sizeof(sink));
     if ((rc = project_opts_check(opts, &sink.prj)) || (rc = project_axis(opts, N, &sink.prj))) return rc;
-    uint64_t str[4] = {0, 0, 0, 0};
-    int dev = 0;
-    if ((rc = szi_dev_view_strides(N, dims, strides_in, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
-    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
-    sz3hip_tile_req q;  // the output as a request's view of the whole array
-    memset(&q, 0, sizeof(q));
-    for (int i = 0; i < N; i++) {
-        q.box.ext[i] = dims[i];
-        q.strides[i] = strides_out ? strides_out[i] : 0;
-    }
-    q.d_out = d_out;
+    DeviceView v;
+    if ((rc = device_view(dataType, N, dims, d_in, strides_in, d_out, strides_out, &v))) return rc;
     std::vector<ReqView> vs;
-    if ((rc = project_views(N, opts->axis, &q, 1, &sink, vs))) return rc;
+    if ((rc = project_views(N, opts->axis, &v.q, 1, &sink, vs))) return rc;
     szk_region_gather_strided_box rec;
-    szi_view_record(N, dims, str, 0, d_out, vs[0].str, &rec);
+    szi_view_record(N, dims, v.str, 0, d_out, vs[0].str, &rec);
     hipStream_t s = (hipStream_t)stream;
     DeviceScope scope;
-    HIPCHK(hipSetDevice(dev));
+    HIPCHK(hipSetDevice(v.dev));
     if (szk_launch_region_project(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the projection could not be launched");
     return 0;
 }
@@ -1646,14 +1381,7 @@ extern "C" int sz3hip_gradient_plan_for(const sz3hip_config *conf, int dataType,
         memset(out, 0, sizeof(*out));
         return rc;
     }
-    out->n = n;
-    out->finest_level = out->coarsest_level = reqs[0].level;
-    for (uint32_t i = 0; i < n; i++) {
-        out->finest_level = std::min(out->finest_level, reqs[i].level);
-        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
-        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
-        out->points += gs[i].points;
-    }
+    plan_prefix(out, reqs, n, gs);
     out->out_points = out_points;
     out->out_elem_bytes = (uint32_t)gradient_out_bytes(sink.grd);
     return 0;
@@ -1665,92 +1393,30 @@ extern "C" int sz3hip_stream_gradient(sz3hip_stream *h, const sz3hip_tile_req *r
     memset(&sink, 0, sizeof(sink));
     int rc = request_args("sz3hip_stream_gradient", reqs, n);
     if (rc || (rc = gradient_opts_check(opts, &sink.grd))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceScope scope;
-    std::vector<szk_region_geom> gs;
+    Submit sub(h, stream);
     std::vector<szk_gradient_box> boxes;
-    uint64_t elems = 0, words = 0;
-    const int N = h->fast ? h->codes.ip.N : h->N;
-    // (behind the boxes' records: every box's entry, in the table's one copy)
-    const uint64_t tail = (uint64_t)n * SZK_GRADIENT_WORDS;
-    if (!h->fast) {
-        if ((rc = full_boxes_check(h, reqs, n))) return rc;
-        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
-    } else {
-        const szk_interp_params &ip = h->codes.ip;
-        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
-        words = szk_region_request_table_words(gs.data(), n) + tail;
-    }
-    if ((rc = gradient_axis(opts, N, &sink.grd)) || (rc = gradient_views(N, opts, reqs, n, &sink, boxes, nullptr))) return rc;
-    std::vector<sz3hip_tile_req> tr(reqs, reqs + n);
-    for (uint32_t i = 0; i < n; i++) tr[i].d_out = (void *)(uintptr_t)i;  // (the `dst` word: the box's index in the request)
-    HIPCHK(hipSetDevice(h->device));
-    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
-    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
-        HIPCHK(hipEventSynchronize(h->ev_table));
-        h->table_pending = false;
-    }
-    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
-    const uint32_t chain_points = sz3hip_debug_get_chain_points();
-    uint32_t chain_levels = 0, launches = 0, levels = 0;
-    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
-    int lr;
-    if (!h->fast) {
-        std::vector<szk_region_gather_strided_box> full_recs(n);
-        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
-        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
-        launches = 1;
-    } else {
-        std::vector<szk_region_out> ro(n);
-        for (uint32_t i = 0; i < n; i++) {
-            memset(&ro[i], 0, sizeof(ro[i]));
-            ro[i].dst = tr[i].d_out;
-        }
-        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
-                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, ro.data(), h->h_table,
-                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
-    }
-    HIPCHK(hipEventRecord(h->ev_req, s));
-    h->req_pending = true;
-    h->last_stream = s;
-    if (lr) return fail(SZ3HIP_EHIP, "the stream's gradient could not be launched (%d)", lr);
-    h->launches_last = launches;
-    h->chain_last = chain_levels;
-    h->levels_last = levels;
-    h->chain_points_last = chain_points;
-    h->requests++;
-    return 0;
+    if ((rc = submit_boxes(sub, reqs, n)) || (rc = gradient_axis(opts, sub.N, &sink.grd)) || (rc = gradient_views(sub.N, opts, reqs, n, &sink, boxes, nullptr))) return rc;
+    if ((rc = submit_begin(sub, &sink, sub.elems))) return rc;
+    return submit_launch(sub, "gradient", &sink, nullptr, nullptr);
 }
 
 extern "C" int sz3hip_gradient_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_gradient_opts *opts,
                                       void *d_out, const int64_t *strides_out, void *stream) {
-    int rc = dtype_check(dataType);
+    int rc = device_dims(dataType, N, dims);
     if (rc) return rc;
-    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
-    for (int i = 0; i < N; i++)
-        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
     szk_region_sink sink;
     memset(&sink, 0, sizeof(sink));
     if ((rc = gradient_opts_check(opts, &sink.grd)) || (rc = gradient_axis(opts, N, &sink.grd))) return rc;  // (the options before any pointer)
     if (!d_out) return fail(SZ3HIP_EINVAL, "sz3hip_gradient_device: NULL argument (d_out)");
-    uint64_t str[4] = {0, 0, 0, 0};
-    int dev = 0;
-    if ((rc = szi_dev_view_strides(N, dims, strides_in, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
-    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
-    sz3hip_tile_req q;  // the output as a request's view of the whole array, at level 0
-    memset(&q, 0, sizeof(q));
-    for (int i = 0; i < N; i++) {
-        q.box.ext[i] = dims[i];
-        q.strides[i] = strides_out ? strides_out[i] : 0;
-    }
-    q.d_out = d_out;
+    DeviceView v;
+    if ((rc = device_view(dataType, N, dims, d_in, strides_in, d_out, strides_out, &v))) return rc;
     std::vector<szk_gradient_box> boxes;
-    if ((rc = gradient_views(N, opts, &q, 1, &sink, boxes, nullptr))) return rc;
+    if ((rc = gradient_views(N, opts, &v.q, 1, &sink, boxes, nullptr))) return rc;
     szk_region_gather_strided_box rec;
-    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);
+    szi_view_record(N, dims, v.str, 0, nullptr, nullptr, &rec);
     hipStream_t s = (hipStream_t)stream;
     DeviceScope scope;
-    HIPCHK(hipSetDevice(dev));
+    HIPCHK(hipSetDevice(v.dev));
     if (szk_launch_region_gradient(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the gradient could not be launched");
     return 0;
 }
@@ -1837,14 +1503,7 @@ extern "C" int sz3hip_composite_plan_for(const sz3hip_config *conf, int dataType
         memset(out, 0, sizeof(*out));
         return rc;
     }
-    out->n = n;
-    out->finest_level = out->coarsest_level = reqs[0].level;
-    for (uint32_t i = 0; i < n; i++) {
-        out->finest_level = std::min(out->finest_level, reqs[i].level);
-        out->coarsest_level = std::max(out->coarsest_level, reqs[i].level);
-        out->n_levels = std::max(out->n_levels, (int32_t)gs[i].n_levels);
-        out->points += gs[i].points;
-    }
+    plan_prefix(out, reqs, n, gs);
     out->out_points = out_points;
     out->out_elem_bytes = (uint32_t)composite_out_bytes(sink.cmp);
     return 0;
@@ -1856,92 +1515,30 @@ extern "C" int sz3hip_stream_composite(sz3hip_stream *h, const sz3hip_tile_req *
     memset(&sink, 0, sizeof(sink));
     int rc = request_args("sz3hip_stream_composite", reqs, n);
     if (rc || (rc = composite_opts_check(opts, &sink.cmp))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DeviceScope scope;
-    std::vector<szk_region_geom> gs;
+    Submit sub(h, stream);
     std::vector<szk_composite_box> boxes;
-    uint64_t elems = 0, words = 0;
-    const int N = h->fast ? h->codes.ip.N : h->N;
-    // (behind the boxes' records: every box's entry, in the table's one copy)
-    const uint64_t tail = (uint64_t)n * SZK_COMPOSITE_WORDS;
-    if (!h->fast) {
-        if ((rc = full_boxes_check(h, reqs, n))) return rc;
-        words = (uint64_t)n * (sizeof(szk_region_gather_strided_box) / 8) + tail;
-    } else {
-        const szk_interp_params &ip = h->codes.ip;
-        if ((rc = szi_request_geometry(ip.N, ip.dims, ip.interp_id, ip.direction, ip.anchor_stride, reqs, n, gs, &elems))) return rc;
-        words = szk_region_request_table_words(gs.data(), n) + tail;
-    }
-    if ((rc = composite_axis(opts, N, &sink.cmp)) || (rc = composite_views(N, opts, reqs, n, &sink, boxes, nullptr))) return rc;
-    std::vector<sz3hip_tile_req> tr(reqs, reqs + n);
-    for (uint32_t i = 0; i < n; i++) tr[i].d_out = (void *)(uintptr_t)i;  // (the `dst` word: the box's index in the request)
-    HIPCHK(hipSetDevice(h->device));
-    if ((h->fast && (rc = region_reserve(h, elems))) || (rc = table_reserve(h, words))) return rc;
-    if (h->table_pending) {  // the previous request's copy of the pinned table, whatever stream it ran on
-        HIPCHK(hipEventSynchronize(h->ev_table));
-        h->table_pending = false;
-    }
-    if (h->req_pending && s != h->last_stream) HIPCHK(hipStreamWaitEvent(s, h->ev_req, 0));  // (the scratch and the device table are still the previous request's)
-    const uint32_t chain_points = sz3hip_debug_get_chain_points();
-    uint32_t chain_levels = 0, launches = 0, levels = 0;
-    h->table_pending = true;  // (the launchers record ev_table behind the table's copy)
-    int lr;
-    if (!h->fast) {
-        std::vector<szk_region_gather_strided_box> full_recs(n);
-        for (uint32_t b = 0; b < n; b++) full_record(h, tr[b], nullptr, &full_recs[b]);
-        lr = szk_launch_gather_boxes(h->dtype, h->d_full, full_recs.data(), n, h->h_table, h->d_table, h->table_cap, h->ev_table, s, &sink);
-        launches = 1;
-    } else {
-        std::vector<szk_region_out> ro(n);
-        for (uint32_t i = 0; i < n; i++) {
-            memset(&ro[i], 0, sizeof(ro[i]));
-            ro[i].dst = tr[i].d_out;
-        }
-        lr = szk_launch_interp_decompress_region_request(h->dtype, &h->codes.ip, gs.data(), n, elems, nullptr, (uint64_t)(uintptr_t)h->codes.d_vidx,
-                                                         (uint64_t)(uintptr_t)h->codes.d_vval, h->codes.n_vout, h->codes.d_codes, h->d_region, ro.data(), h->h_table,
-                                                         h->d_table, h->table_cap, h->ev_table, s, chain_points, &chain_levels, &launches, &levels, &sink);
-    }
-    HIPCHK(hipEventRecord(h->ev_req, s));
-    h->req_pending = true;
-    h->last_stream = s;
-    if (lr) return fail(SZ3HIP_EHIP, "the stream's compositing could not be launched (%d)", lr);
-    h->launches_last = launches;
-    h->chain_last = chain_levels;
-    h->levels_last = levels;
-    h->chain_points_last = chain_points;
-    h->requests++;
-    return 0;
+    if ((rc = submit_boxes(sub, reqs, n)) || (rc = composite_axis(opts, sub.N, &sink.cmp)) || (rc = composite_views(sub.N, opts, reqs, n, &sink, boxes, nullptr))) return rc;
+    if ((rc = submit_begin(sub, &sink, sub.elems))) return rc;
+    return submit_launch(sub, "compositing", &sink, nullptr, nullptr);
 }
 
 extern "C" int sz3hip_composite_device(int dataType, int N, const uint64_t *dims, const void *d_in, const int64_t *strides_in, const sz3hip_composite_opts *opts,
                                        void *d_out, const int64_t *strides_out, void *stream) {
-    int rc = dtype_check(dataType);
+    int rc = device_dims(dataType, N, dims);
     if (rc) return rc;
-    if (N < 1 || N > 4 || !dims) return fail(SZ3HIP_EINVAL, "the dimension count is %d: 1 .. 4 extents are supported", N);
-    for (int i = 0; i < N; i++)
-        if (dims[i] == 0) return fail(SZ3HIP_EINVAL, "dimension %d has extent 0", i);
     szk_region_sink sink;
     memset(&sink, 0, sizeof(sink));
     if ((rc = composite_opts_check(opts, &sink.cmp)) || (rc = composite_axis(opts, N, &sink.cmp))) return rc;  // (the options before any pointer)
     if (!d_out) return fail(SZ3HIP_EINVAL, "sz3hip_composite_device: NULL argument (d_out)");
-    uint64_t str[4] = {0, 0, 0, 0};
-    int dev = 0;
-    if ((rc = szi_dev_view_strides(N, dims, strides_in, str)) || (rc = szi_dev_pointer(d_in, &dev))) return rc;
-    if ((uintptr_t)d_in % tsize(dataType)) return fail(SZ3HIP_EINVAL, "an array is not aligned to its element size (%zu bytes)", tsize(dataType));
-    sz3hip_tile_req q;  // the output as a request's view of the whole array, at level 0
-    memset(&q, 0, sizeof(q));
-    for (int i = 0; i < N; i++) {
-        q.box.ext[i] = dims[i];
-        q.strides[i] = strides_out ? strides_out[i] : 0;
-    }
-    q.d_out = d_out;
+    DeviceView v;
+    if ((rc = device_view(dataType, N, dims, d_in, strides_in, d_out, strides_out, &v))) return rc;
     std::vector<szk_composite_box> boxes;
-    if ((rc = composite_views(N, opts, &q, 1, &sink, boxes, nullptr))) return rc;
+    if ((rc = composite_views(N, opts, &v.q, 1, &sink, boxes, nullptr))) return rc;
     szk_region_gather_strided_box rec;
-    szi_view_record(N, dims, str, 0, nullptr, nullptr, &rec);
+    szi_view_record(N, dims, v.str, 0, nullptr, nullptr, &rec);
     hipStream_t s = (hipStream_t)stream;
     DeviceScope scope;
-    HIPCHK(hipSetDevice(dev));
+    HIPCHK(hipSetDevice(v.dev));
     if (szk_launch_region_composite(dataType, d_in, nullptr, &rec, 1, &sink, s)) return fail(SZ3HIP_EHIP, "the compositing could not be launched");
     return 0;
 }

@@ -498,3 +498,73 @@ def test_refusals_on_a_fallback_handle():
         torch.cuda.synchronize()
         assert all(bool((o == SENTINEL).all()) for o in outs)
         same(ask(st, 1, FB_BOXES[1]), full, 1, FB_BOXES[1])
+
+
+# ---- 10. different sinks interleaved on one handle: the one submit path orders request after reduce after map ... ----------------------------------
+def sink_calls(items, level1_box, lo, hi, lut):
+    """(name, extra launches beyond the request's own, call(st, stream)): every request call of a handle on the same three boxes, then tiles"""
+    a, b = lo + 0.25 * (hi - lo), lo + 0.5 * (hi - lo)
+    lattice = ((0.4, 0.6, 0.3), [(0.7, 0.5, 1.3)], (5,))  # five points along a line, nearest: the points' bytes
+    return [
+        ("request", 0, lambda st, s: st.request(items, stream=s)),
+        ("reduce", 1, lambda st, s: st.reduce(items, bins=8, lo=lo, hi=hi, stream=s)),
+        ("map", 0, lambda st, s: st.map(items, "u8", lo, hi, stream=s)),
+        ("select", 2, lambda st, s: st.select(items, a, b, 64, stream=s)),
+        ("sample", 0, lambda st, s: st.sample(items, [lattice] * len(items), mode="nearest", stream=s)),
+        ("project", 0, lambda st, s: st.project(items, "max", 1, stream=s)),
+        ("gradient", 0, lambda st, s: st.gradient(items, "mag", stream=s)),
+        ("composite", 0, lambda st, s: st.composite(items, 1, lut, lo, hi, out_type="rgba8", stream=s)),
+        ("tiles", None, lambda st, s: st.tiles(1, [level1_box], stream=s)),
+    ]
+
+
+def result_bytes(res):
+    """a call's result as bytes, after the device was waited for: tensors as they are, a reduction's records and histogram, a selection's counts
+    and its written indices and values (the rest of a selection's arrays is not set)"""
+    if isinstance(res, sz3_amd.ReduceResult):
+        return [x.tobytes() for x in res.numpy()]
+    if isinstance(res, sz3_amd.SelectResult):
+        return [np.int64(count).tobytes() + ix.tobytes() + v.tobytes() for count, ix, v in res.numpy()]
+    return [raw(t).tobytes() for t in res]
+
+
+@pytest.mark.parametrize("fast", [True, False], ids=["fast", "full_array"])
+def test_sinks_interleaved_on_two_streams(fast):
+    from test_gpu_request import mixed  # (that module imports this one)
+    shape = (65, 47, 130) if fast else (40, 48, 56)
+    if fast:
+        a, blob, full, conf = case(shape)
+    else:
+        blob = container(smooth(shape), conf_for(shape, **dict(FALLBACKS[0][1])))
+        full, conf = sz3_amd.decompress(blob, np.float32, device=DEV)
+    items = mixed(shape, (0, 1, 2))[6:9]  # the origin-corner boxes of levels 0, 1 and 2: every extent is above 2
+    assert [it[0] for it in items] == [0, 1, 2] and all(e > 2 for it in items for e in it[2])
+    lo, hi = float(full.min()), float(full.max())
+    lut = torch.linspace(0.05, 0.6, 64, device=DEV).reshape(16, 4).contiguous()
+    calls = sink_calls(items, tile_boxes(coarse_shape(shape, 1))[2], lo, hi, lut)
+    alone = []
+    for name, extra, call in calls:  # every call alone on a fresh handle, with a synchronise behind it
+        with sz3_amd.open_stream(blob, np.float32, device=DEV) as st:
+            res = call(st, None)
+            torch.cuda.synchronize()
+            alone.append(result_bytes(res))
+    s1, s2 = torch.cuda.Stream(device=DEV), torch.cuda.Stream(device=DEV)
+    with sz3_amd.open_stream(blob, np.float32, device=DEV) as st:
+        assert st.stats()["fast"] == (1 if fast else 0)
+        before = st.stats()["requests"]
+        torch.cuda.synchronize()
+        got, own = [], None
+        for turn in range(2):  # the whole sequence twice, the streams alternating, no host synchronisation anywhere
+            for i, (name, extra, call) in enumerate(calls):
+                got.append(call(st, s1 if (turn * len(calls) + i) % 2 == 0 else s2))
+                launches = st.stats()["launches_last_request"]
+                if name == "request":
+                    own = launches
+                    assert own >= 1 and (fast or own == 1)
+                elif extra is not None:
+                    assert launches == own + extra, "%s: %d launches, the request's own are %d" % (name, launches, own)
+        assert st.stats()["requests"] == before + 2 * len(calls)
+        torch.cuda.synchronize()
+        for j, res in enumerate(got):
+            name = calls[j % len(calls)][0]
+            assert result_bytes(res) == alone[j % len(calls)], "%s (call %d of the interleaved sequence) differs from the call alone on a fresh handle" % (name, j)
