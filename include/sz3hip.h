@@ -1010,6 +1010,9 @@ int sz3hip_debug_decode_info(sz3hip_ctx *ctx, uint32_t *out4);
 /* the last stock Huffman decode of this process: *passes = restart-point passes launched (0 if none),
    *route = 0 device, 1 host by the switch, 2 host after the pass cap, 3 single symbol (no bit stream) */
 void sz3hip_debug_stock_huffman(int *passes, int *route);
+/* the last block-stream decode of this process (predictor sets with Lorenzo-2 / regression): which decoder form ran, over how many
+   slots, workgroups and tiles, and whether the retry was taken — out[enum sz3hip_blkdec_word], sz3hip_debug.h; all 0 before the first */
+void sz3hip_debug_blkdec_last(uint32_t out[8]);
 /* test hook: non-zero routes every shape through the generic (any-shape) stage-1 kernel instead of the tuned one */
 void sz3hip_debug_force_generic(int on);
 /* development switches (bit mask, process-wide; 0 = product behaviour): an OR of enum sz3hip_dbg, sz3hip_debug.h, which says what each bit gates */

@@ -99,4 +99,33 @@ enum sz3hip_dbg2 {
     SZ3HIP_DBG2_MAP_PLAIN_STORES = 4       /* szk_launch_region_map: one-byte and two-byte texels by a thread per point (k_region_map), not by the form in which a lane maps four / two consecutive x points and issues one 32-bit store (k_region_map_packed) */
 };
 
+/* What the block decoder did, sz3hip_debug_blkdec_last(): the branch of blk_decompress_impl a pass took, one name per branch. The
+ * values are ABI like the switches'. */
+enum sz3hip_blkdec_form {
+    SZ3HIP_BLKDEC_FORM_NONE = 0,           /* no block stream has been decoded in this process */
+    SZ3HIP_BLKDEC_FORM_FRONTS_4D = 1,      /* 4-D: a launch per front of blocks (k_blk4_decode) */
+    SZ3HIP_BLKDEC_FORM_SCAN2_1D = 2,       /* 1-D, second-order Lorenzo in the set: the scan of affine maps (k_blkn2_tile, k_blkn2_top, k_blkn2_apply) */
+    SZ3HIP_BLKDEC_FORM_WAVE_2D = 3,        /* 2-D, one launch for the chain of fronts (k_blkn_wave2) */
+    SZ3HIP_BLKDEC_FORM_SCAN_1D = 4,        /* 1-D, first-order sets: the scan of the blocks' sums (k_blkn_scan_tile, k_blkn_scan_top, k_blkn_apply1*) */
+    SZ3HIP_BLKDEC_FORM_FRONTS2_2D = 5,     /* 2-D, second-order Lorenzo in the set: a block per wave, a launch per front (k_blkn_decode2s) */
+    SZ3HIP_BLKDEC_FORM_GROUPS_2D = 6,      /* 2-D: groups of 4 x 4 blocks, a launch per front (k_blkn_decode2g) */
+    SZ3HIP_BLKDEC_FORM_FRONTS_2D = 7,      /* 2-D: a block per wave, a launch per front (k_blkn_decode2) */
+    SZ3HIP_BLKDEC_FORM_WAVE_3D = 8,        /* 3-D blocks of 6^3, one launch for the chain of fronts (k_blk_wave3) */
+    SZ3HIP_BLKDEC_FORM_GROUPS_3_3D = 9,    /* 3-D blocks of 6^3: groups of 3 x 3 x 3 blocks in closed form, a launch per front (k_blk_decode_gf) */
+    SZ3HIP_BLKDEC_FORM_GROUPS_2_3D = 10,   /* lab build, 3-D blocks of 6^3: groups of 2 x 2 x 2 blocks, line scans, a launch per front (k_blk_decode_g) */
+    SZ3HIP_BLKDEC_FORM_FRONTS_3D = 11      /* 3-D: a block per wave, a launch per front (k_blk_decode) */
+};
+
+/* The words of sz3hip_debug_blkdec_last(). [0] .. [3] and [5] describe the first pass of the last szk_launch_blk_decompress of this
+ * process, under the flags the caller had set. */
+enum sz3hip_blkdec_word {
+    SZ3HIP_BLKDEC_WORD_FORM = 0,           /* enum sz3hip_blkdec_form */
+    SZ3HIP_BLKDEC_WORD_NSLOTS = 1,         /* the groups the form hands out (WAVE_2D, GROUPS_2D, WAVE_3D, GROUPS_3_3D, GROUPS_2_3D); the blocks for every other form */
+    SZ3HIP_BLKDEC_WORD_WORKGROUPS = 2,     /* WAVE_2D / WAVE_3D: the workgroups of the one launch, each taking tickets until none is left (more slots than workgroups: some take a second one); else 0 */
+    SZ3HIP_BLKDEC_WORD_TILES = 3,          /* SCAN_1D / SCAN2_1D: the tiles of 1024 blocks the top scan runs over, 1024 to a step of its loop; else 0 */
+    SZ3HIP_BLKDEC_WORD_RETRIED = 4,        /* 1: a one-launch form was followed by the retry through the launch-per-front decoders (a flag poll gave up, or SZ3HIP_DBG_BLKDEC_FORCE_RETRY) */
+    SZ3HIP_BLKDEC_WORD_ROWS = 5,           /* SCAN_1D / SCAN2_1D: 1 four blocks per wave (the *_rows kernels), 0 a wave per block; else 0 */
+    SZ3HIP_BLKDEC_WORD_RETRY_FORM = 6      /* the form the retry took, SZ3HIP_BLKDEC_FORM_NONE without one; [7] is reserved (0) */
+};
+
 #endif

@@ -88,6 +88,23 @@ class Dbg2(enum.IntFlag):
     MAP_PLAIN_STORES = 4
 
 
+class BlkDecForm(enum.IntEnum):
+    """The block decoder's forms (debug_blkdec_last): enum sz3hip_blkdec_form of include/sz3hip_debug.h without the
+    SZ3HIP_BLKDEC_FORM_ prefix, same values."""
+    NONE = 0
+    FRONTS_4D = 1
+    SCAN2_1D = 2
+    WAVE_2D = 3
+    SCAN_1D = 4
+    FRONTS2_2D = 5
+    GROUPS_2D = 6
+    FRONTS_2D = 7
+    WAVE_3D = 8
+    GROUPS_3_3D = 9
+    GROUPS_2_3D = 10
+    FRONTS_3D = 11
+
+
 class SZ3HipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("sz3hip error %d: %s" % (code, msg))
@@ -400,6 +417,8 @@ def lib():
     L.sz3hip_debug_region_launches.argtypes = []
     L.sz3hip_debug_tile_units.restype = None
     L.sz3hip_debug_tile_units.argtypes = [P(C.c_uint64), P(C.c_uint64)]
+    L.sz3hip_debug_blkdec_last.restype = None
+    L.sz3hip_debug_blkdec_last.argtypes = [P(C.c_uint32)]
     L.sz3hip_debug_stock_huffman.restype = None
     L.sz3hip_debug_stock_huffman.argtypes = [P(C.c_int), P(C.c_int)]
     L.sz3hip_debug_region_fast_calls.restype = C.c_uint64
@@ -858,6 +877,17 @@ def debug_stock_huffman():
     p, r = C.c_int(0), C.c_int(0)
     lib().sz3hip_debug_stock_huffman(C.byref(p), C.byref(r))
     return int(p.value), int(r.value)
+
+
+def debug_blkdec_last():
+    """what this process's last block-stream decode did (sz3hip_debug_blkdec_last; the words of enum sz3hip_blkdec_word): a dict of
+    form (BlkDecForm: the branch the first pass took), nslots (groups handed out, or blocks), workgroups (of a one-launch form, else
+    0), tiles (of the 1-D top scan, else 0), retried (the retry through the launch-per-front decoders followed), rows (1-D: four
+    blocks per wave) and retry_form (BlkDecForm.NONE without a retry)"""
+    w = (C.c_uint32 * 8)()
+    lib().sz3hip_debug_blkdec_last(w)
+    return dict(form=BlkDecForm(w[0]), nslots=int(w[1]), workgroups=int(w[2]), tiles=int(w[3]), retried=bool(w[4]), rows=bool(w[5]),
+                retry_form=BlkDecForm(w[6]))
 
 
 def _decompress_partial(name, blob, dtype, probe_args, shape_of, out, device, stream):

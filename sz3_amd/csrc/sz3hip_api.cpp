@@ -2698,6 +2698,9 @@ extern "C" void sz3hip_debug_flags(int flags) {
 }
 extern "C" void sz3hip_debug_flags2(int flags) { szk_dbg_flags2 = flags; }
 extern "C" int sz3hip_last_encode_launches(void) { return szk_encode_launches; }
+extern "C" void sz3hip_debug_blkdec_last(uint32_t out[8]) {
+    for (int i = 0; i < 8; i++) out[i] = szk_blkdec_last[i];
+}
 extern "C" int sz3hip_debug_codebook_info(sz3hip_ctx *ctx, uint64_t *out16) {
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipDeviceSynchronize());

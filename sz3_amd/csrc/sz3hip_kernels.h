@@ -841,5 +841,6 @@ extern int szk_force_generic;
 extern int szk_dbg_flags;
 extern int szk_dbg_flags2;       // sz3hip_debug_flags2(): an OR of enum sz3hip_dbg2
 extern int szk_encode_launches;  // launches the last szk_launch_encode enqueued, the packer's included
+extern uint32_t szk_blkdec_last[8];  // sz3hip_debug_blkdec_last(): what the last szk_launch_blk_decompress did (enum sz3hip_blkdec_word)
 
 #endif

@@ -5635,13 +5635,19 @@ int szk_launch_blk_side(const szk_blk_params *p, const szk_blk_scratch *sc, cons
     SZK_CHECK_LAUNCH();
     return 0;
 }
+// what a pass of blk_decompress_impl did, for sz3hip_debug_blkdec_last (host bookkeeping only): the branch taken and its sizes
+struct blkdec_note {
+    uint32_t form = SZ3HIP_BLKDEC_FORM_NONE, nslots = 0, workgroups = 0, tiles = 0, rows = 0;
+};
+uint32_t szk_blkdec_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 // (dbg = the debug flags in force: the caller's retry ORs in the switches that take the launch-per-front decoders; *ctl_out: the
-// control words of a one-launch decoder, when one was taken — [1] is raised by a flag poll that gave up)
+// control words of a one-launch decoder, when one was taken — [1] is raised by a flag poll that gave up; *note: what the pass did)
 static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, const szk_blk_params *p, const szk_blk_scratch *sc,
                                const uint8_t *payload, const szh_header *h, const szh_offsets *o, int64_t *coef_by_rank, hipStream_t s,
-                               hipEvent_t side_done, const int dbg, uint32_t **ctl_out) {
+                               hipEvent_t side_done, const int dbg, uint32_t **ctl_out, blkdec_note *note) {
     *ctl_out = nullptr;
     const uint32_t nblocks = blk_count_blocks(p);
+    note->nslots = nblocks;  // (the forms by groups overwrite it)
     // (k_blk_local3v reads the codes themselves: the far deltas alone go to the work array; SZ3HIP_DBG_BLKDEC_LOCAL_EXPANDED: the expanded copy and the
     // wave-per-block pass)
     const bool fusedv = p->ndim == 3 && p->B == 6 && p->carry && !(dbg & (SZ3HIP_DBG_BLKDEC_GROUPS_3 | SZ3HIP_DBG_BLKDEC_PER_FRONT | SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE | SZ3HIP_DBG_BLKDEC_LOCAL_EXPANDED));
@@ -5654,6 +5660,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
     if (p->ndim == 4) {  // fronts of blocks, bw + bz + by + bx = const
         const uint32_t g4 = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 3) / 4);
         const uint32_t ndiag = p->nbw + p->nb[0] + p->nb[1] + p->nb[2] - 3, gfront = p->nbw * p->nb[0] * p->nb[1];
+        note->form = SZ3HIP_BLKDEC_FORM_FRONTS_4D;
 #define BLK4_DEC(T)                                                                                                                   \
     do {                                                                                                                              \
         hipLaunchKernelGGL(k_blk4_pre<T>, dim3(g4), dim3(256), 0, s, codes, d_out, *p, nblocks, sc->rank, coef_by_rank);               \
@@ -5673,6 +5680,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
         // blocks of up to 128 values, a multiple of 8: four blocks per wave (SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK: a wave per block)
         const bool rows = p->B <= 128 && p->B % 8 == 0 && !(dbg & SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK);
         const uint32_t grow = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 15) / 16);
+        note->form = SZ3HIP_BLKDEC_FORM_SCAN2_1D, note->tiles = ntiles, note->rows = rows;
 #define BLKN2_DEC(T, QT)                                                                                                                          \
     do {                                                                                                                                          \
         if (rows) hipLaunchKernelGGL(k_blkn2_pre_rows<T>, dim3(grow), dim3(256), 0, s, codes, p->qwork, d_out, *p, nblocks, sc->rank, coef_by_rank); \
@@ -5696,6 +5704,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
         if (hipMemsetAsync(ctl, 0, (4 + (size_t)nslots) * 4, s) != hipSuccess) return -1;
         *ctl_out = ctl;
         const uint32_t gw = (uint32_t)std::min<uint64_t>(nslots, dtype == 0 ? 2048 : 1024);
+        note->form = SZ3HIP_BLKDEC_FORM_WAVE_2D, note->nslots = (uint32_t)nslots, note->workgroups = gw;
         if (dtype == 0) {
             hipLaunchKernelGGL(k_blkn_pre<float>, dim3(gpre), dim3(256), 0, s, codes, p->qwork, d_out, *p, nblocks, sc->rank, coef_by_rank, 1);
             hipLaunchKernelGGL(k_blkn_wave2<float>, dim3(gw), dim3(256), 0, s, codes, p->qwork, d_out, *p, ctl, (uint32_t)nslots);
@@ -5724,6 +5733,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
             // blocks of up to 128 values, a multiple of 8: four blocks per wave (SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK: a wave per block)
             const bool rows = p->B <= 128 && p->B % 8 == 0 && !(dbg & SZ3HIP_DBG_BLK_1D_WAVE_PER_BLOCK);
             const uint32_t grow = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 15) / 16);
+            note->form = SZ3HIP_BLKDEC_FORM_SCAN_1D, note->tiles = ntiles, note->rows = rows;
             if (dtype == 0) {
                 hipLaunchKernelGGL(k_blkn_scan_tile<int32_t>, dim3(ntiles), dim3(1024), 0, s, p->sel, nblocks, p->carry);
                 hipLaunchKernelGGL(k_blkn_scan_top<int32_t>, dim3(1), dim3(1024), 0, s, ntiles, (int32_t *)p->carry + 2 * (uint64_t)nblocks);
@@ -5737,6 +5747,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
             }
         } else if (p->mask & 2u) {  // second-order Lorenzo in the set: the plain form with two halo layers
             const uint32_t ndiag = p->nb[1] + p->nb[2] - 1;
+            note->form = SZ3HIP_BLKDEC_FORM_FRONTS2_2D;
             for (uint32_t d = 0; d < ndiag; d++) {
                 const uint32_t by_lo = d >= p->nb[2] ? d - (p->nb[2] - 1) : 0, by_hi = d < p->nb[1] - 1 ? d : p->nb[1] - 1;
                 const uint32_t nfront = by_hi - by_lo + 1;
@@ -5745,6 +5756,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
             }
         } else if (p->B <= 16 && !(dbg & SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE)) {  // groups of 4 x 4 blocks per workgroup, a launch per front (SZ3HIP_DBG_BLKDEC_PER_FRONT; SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE: a block per wave)
             const uint32_t ng1 = (p->nb[1] + BLKN_G - 1) / BLKN_G, ng2 = (p->nb[2] + BLKN_G - 1) / BLKN_G;
+            note->form = SZ3HIP_BLKDEC_FORM_GROUPS_2D, note->nslots = ng1 * ng2;
             for (uint32_t d = 0; d < ng1 + ng2 - 1; d++) {
                 const uint32_t gy_lo = d >= ng2 ? d - (ng2 - 1) : 0, gy_hi = d < ng1 - 1 ? d : ng1 - 1;
                 if (dtype == 0) hipLaunchKernelGGL(k_blkn_decode2g<float>, dim3(gy_hi - gy_lo + 1), dim3(256), 0, s, p->qwork, d_out, *p, d, gy_lo);
@@ -5752,6 +5764,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
             }
         } else {
             const uint32_t ndiag = p->nb[1] + p->nb[2] - 1;
+            note->form = SZ3HIP_BLKDEC_FORM_FRONTS_2D;
             for (uint32_t d = 0; d < ndiag; d++) {
                 const uint32_t by_lo = d >= p->nb[2] ? d - (p->nb[2] - 1) : 0, by_hi = d < p->nb[1] - 1 ? d : p->nb[1] - 1;
                 const uint32_t nfront = by_hi - by_lo + 1;
@@ -5771,6 +5784,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
         *ctl_out = ctl;
         const uint32_t gpre = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 3) / 4);
         const uint32_t gw = (uint32_t)std::min<uint64_t>(nslots, dtype == 0 ? 1024 : 512);
+        note->form = SZ3HIP_BLKDEC_FORM_WAVE_3D, note->nslots = (uint32_t)nslots, note->workgroups = gw;
         const bool ragged = p->d[0] % 6 || p->d[1] % 6 || p->d[2] % 6;
         const uint32_t gv = (uint32_t)std::min<uint64_t>(8192, ((uint64_t)nblocks + BLK3V_NB - 1) / BLK3V_NB);
         if (dtype == 0) {
@@ -5797,6 +5811,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
         constexpr uint32_t G = 3;
         const uint32_t ng0 = (p->nb[0] + G - 1) / G, ng1 = (p->nb[1] + G - 1) / G, ng2 = (p->nb[2] + G - 1) / G;
         const uint32_t ngd = ng0 + ng1 + ng2 - 2;
+        note->form = SZ3HIP_BLKDEC_FORM_GROUPS_3_3D, note->nslots = ng0 * ng1 * ng2;
         {
             const uint32_t gpre = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 3) / 4);
             if (dtype == 0) hipLaunchKernelGGL((k_blk_local3<float, 6, false>), dim3(gpre), dim3(256), 0, s, codes, p->qwork, d_out, *p, nblocks, sc->rank, coef_by_rank);
@@ -5815,6 +5830,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
     if (p->B == 6 && !(dbg & SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE)) {  // round 3's form (lab builds, SZ3HIP_DBG_BLKDEC_PER_FRONT): groups of 2 x 2 x 2 blocks, line scans (SZ3HIP_DBG_BLKDEC_BLOCK_PER_WAVE: a block per wave)
         const uint32_t ng0 = (p->nb[0] + 1) / 2, ng1 = (p->nb[1] + 1) / 2, ng2 = (p->nb[2] + 1) / 2;
         const uint32_t ngd = ng0 + ng1 + ng2 - 2;
+        note->form = SZ3HIP_BLKDEC_FORM_GROUPS_2_3D, note->nslots = ng0 * ng1 * ng2;
         {
             const uint32_t gpre = (uint32_t)std::min<uint64_t>(BLK_GRID, ((uint64_t)nblocks + 3) / 4);
             if (dtype == 0) hipLaunchKernelGGL((k_blk_pre3<float, 6>), dim3(gpre), dim3(256), 0, s, codes, d_out, *p, nblocks, sc->rank, coef_by_rank);
@@ -5834,6 +5850,7 @@ static int blk_decompress_impl(int dtype, const uint16_t *codes, void *d_out, co
 #endif
     {
     const uint32_t ndiag = p->nb[0] + p->nb[1] + p->nb[2] - 2;
+    note->form = SZ3HIP_BLKDEC_FORM_FRONTS_3D;
     for (uint32_t d = 0; d < ndiag; d++) {
         // blocks of the front: bz + by + bx = d; only the bz that can have a partner (by, bx) are enumerated
         const uint32_t rest = (p->nb[1] - 1) + (p->nb[2] - 1);
@@ -5880,12 +5897,26 @@ int szk_launch_blk_decompress(int dtype, const uint16_t *codes, void *d_out, con
                               const uint8_t *payload, const szh_header *h, const szh_offsets *o, int64_t *coef_by_rank, hipStream_t s,
                               hipEvent_t side_done) {
     uint32_t *ctl = nullptr;
-    int rc = blk_decompress_impl(dtype, codes, d_out, p, sc, payload, h, o, coef_by_rank, s, side_done, szk_dbg_flags, &ctl);
+    blkdec_note first, again;
+    auto record = [&](bool retried) {
+        szk_blkdec_last[SZ3HIP_BLKDEC_WORD_FORM] = first.form;
+        szk_blkdec_last[SZ3HIP_BLKDEC_WORD_NSLOTS] = first.nslots;
+        szk_blkdec_last[SZ3HIP_BLKDEC_WORD_WORKGROUPS] = first.workgroups;
+        szk_blkdec_last[SZ3HIP_BLKDEC_WORD_TILES] = first.tiles;
+        szk_blkdec_last[SZ3HIP_BLKDEC_WORD_RETRIED] = retried;
+        szk_blkdec_last[SZ3HIP_BLKDEC_WORD_ROWS] = first.rows;
+        szk_blkdec_last[SZ3HIP_BLKDEC_WORD_RETRY_FORM] = again.form;
+        szk_blkdec_last[7] = 0;
+    };
+    int rc = blk_decompress_impl(dtype, codes, d_out, p, sc, payload, h, o, coef_by_rank, s, side_done, szk_dbg_flags, &ctl, &first);
+    record(false);
     if (rc || !ctl) return rc;
     uint32_t gave_up = 0;
     if (hipMemcpyAsync(&gave_up, ctl + 1, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -1;
     if (!gave_up && !(szk_dbg_flags & SZ3HIP_DBG_BLKDEC_FORCE_RETRY)) return 0;  // (take the retry as if a poll had given up — tests)
-    return blk_decompress_impl(dtype, codes, d_out, p, sc, payload, h, o, coef_by_rank, s, nullptr, szk_dbg_flags | SZ3HIP_DBG_BLKDEC_GROUPS_3 | SZ3HIP_DBG_BLKDEC_PER_FRONT, &ctl);
+    rc = blk_decompress_impl(dtype, codes, d_out, p, sc, payload, h, o, coef_by_rank, s, nullptr, szk_dbg_flags | SZ3HIP_DBG_BLKDEC_GROUPS_3 | SZ3HIP_DBG_BLKDEC_PER_FRONT, &ctl, &again);
+    record(true);
+    return rc;
 }
 
 int szk_launch_trial_lorenzo12(int dtype, const void *d_samples, uint64_t per, uint64_t nsb, double eb, int radius, uint64_t *hist, uint64_t *counters,

@@ -418,76 +418,251 @@ def reconstruct_blocks4(h, sec, codes):
     return x, sel
 
 
-def reconstruct_blocks(h, sec, codes):
+def lorenzo_block_elementwise(q, delta, origin, extents, order):
+    """THE DEFINITION of a Lorenzo block's inverse. q: the lattice array with two zero halo layers on the low side of every axis
+    (int64, element (z, y, x) at q[z + 2, y + 2, x + 2]), filled in place for the block at `origin` = (z0, y0, x0) with `extents` =
+    (ez, ey, ex); delta: the block's residuals [ez, ey, ex]; order 1 / 2: the stencil (1, -1) / (1, -2, 1) per axis. Element by
+    element in raster order, in Python integers: q = delta - sum over the stencil's other corners of w_a w_b w_c q[z - a, y - b, x - c]."""
+    w = (1, -1) if order == 1 else (1, -2, 1)
+    m = len(w) - 1
+    (z0, y0, x0), (ez, ey, ex) = origin, extents
+    for k in range(ez):
+        for j in range(ey):
+            for i in range(ex):
+                z, y, x = z0 + k + 2, y0 + j + 2, x0 + i + 2
+                acc = int(delta[k, j, i])
+                for a in range(m + 1):
+                    for b_ in range(m + 1):
+                        for c_ in range(m + 1):
+                            if a or b_ or c_:
+                                acc -= w[a] * w[b_] * w[c_] * int(q[z - a, y - b_, x - c_])
+                q[z, y, x] = acc
+
+
+def lorenzo_block(q, delta, origin, extents, order):
+    """the same block at once, exact in int64 (tests/test_block_model_cpu.py holds the two forms equal): the block with its low-side
+    halo of `order` layers in a box of extents + order whose interior is zeroed; the box's own Lorenzo residuals by differencing
+    along each axis `order` times (a halo position's residual reads halo positions only: the zeroed interior does not reach it);
+    the interior's residuals replaced by the block's; back by cumulative sums along each axis, `order` times. What holds for a block
+    holds for any box of elements that obey one recurrence: reconstruct_blocks hands a run of blocks of one order along x over as one."""
+    m = order
+    (z0, y0, x0), (ez, ey, ex) = origin, extents
+    src = q[z0 + 2 - m:z0 + 2 + ez, y0 + 2 - m:y0 + 2 + ey, x0 + 2 - m:x0 + 2 + ex]
+    box = src.astype(np.int64)  # (a copy)
+    box[m:, m:, m:] = 0
+    for ax in range(3):
+        hi = tuple(slice(1, None) if a == ax else slice(None) for a in range(3))
+        lo = tuple(slice(0, -1) if a == ax else slice(None) for a in range(3))
+        for _ in range(m):
+            box[hi] -= box[lo].copy()
+    box[m:, m:, m:] = delta
+    for ax in range(3):
+        for _ in range(m):
+            np.cumsum(box, axis=ax, out=box)
+    src[m:, m:, m:] = box[m:, m:, m:]
+
+
+def _lattice_of(val, cc, eb, T):
+    """the lattice values a regression block leaves for its neighbours: rint(val / 2 eb), 0 where the code is 0 or the value does not
+    sit on the lattice within the bound"""
+    recip = T(1.0 / (2.0 * eb)) if T == np.float32 else 1.0 / (2.0 * eb)
+    lim = T(8388608.0) if T == np.float32 else 4503599627370496.0
+    with np.errstate(invalid="ignore", over="ignore"):
+        sc = val * recip
+        ok = np.abs(sc) < lim
+        rr = np.rint(np.where(ok, sc, 0)).astype(T)
+        bad = ~ok | ~(np.abs(rr * T(2.0 * eb) - val) <= (T(eb) if float(T(eb)) <= eb else np.nextafter(T(eb), T(0))))
+    return np.where((cc == 0) | bad, 0, rr.astype(np.int64))
+
+
+def regression_block(cc, lc, B, eb, radius, T, nd1):
+    """THE DEFINITION of a regression block: cc its codes [ez, ey, ex] (int64), lc its four coefficient lattice values ->
+    (lattice values for the neighbours, output values): pred + 2 (code - radius) eb, pred = c0 z + c1 y + c2 x + c3 in T"""
+    ez, ey, ex = cc.shape
+    step_ind, step_lin = 2.0 * (eb / nd1), 2.0 * (eb / nd1 / B)
+    rc = [T(float(lc[i]) * step_lin) for i in range(3)] + [T(float(lc[3]) * step_ind)]
+    i0, i1, i2 = np.meshgrid(np.arange(ez), np.arange(ey), np.arange(ex), indexing="ij")
+    pred = (rc[0] * i0.astype(T) + rc[1] * i1.astype(T) + rc[2] * i2.astype(T) + rc[3]).astype(T)
+    val = (pred.astype(np.float64) + (2 * (cc - radius)).astype(np.float64) * eb).astype(T)
+    return _lattice_of(val, cc, eb, T), np.where(cc == 0, 0, val)
+
+
+def regression_run(cc, lcs, B, eb, radius, T, nd1):
+    """a run of regression blocks along x at once (tests/test_block_model_cpu.py holds it equal to regression_block block by block):
+    cc the run's codes [ez, ey, ex of the run], lcs [blocks of the run, 4]; the same operations in T, element by element"""
+    ez, ey, ex = cc.shape
+    step_ind, step_lin = 2.0 * (eb / nd1), 2.0 * (eb / nd1 / B)
+    lcs = np.asarray(lcs, dtype=np.int64)
+    bi = np.arange(ex) // B
+    rc = [(lcs[:, i].astype(np.float64) * step_lin).astype(T)[bi] for i in range(3)] + [(lcs[:, 3].astype(np.float64) * step_ind).astype(T)[bi]]
+    i0 = np.arange(ez).astype(T)[:, None, None]
+    i1 = np.arange(ey).astype(T)[None, :, None]
+    i2 = (np.arange(ex) % B).astype(T)[None, None, :]
+    pred = (rc[0][None, None, :] * i0 + rc[1][None, None, :] * i1 + rc[2][None, None, :] * i2 + rc[3][None, None, :]).astype(T)
+    val = (pred.astype(np.float64) + (2 * (cc - radius)).astype(np.float64) * eb).astype(T)
+    return _lattice_of(val, cc, eb, T), np.where(cc == 0, 0, val)
+
+
+def block_positions(dims3, B):
+    """-> int64 [dz, dy, dx]: the position in the code stream of every element (blocks in raster order, raster order inside a block)"""
+    n = [np.arange(d) for d in dims3]
+    b = [v // B for v in n]                                   # block index per coordinate
+    l = [v % B for v in n]                                    # local index
+    e = [np.minimum(B, d - np.arange((d + B - 1) // B) * B) for d in dims3]  # block extents per block index
+    size = e[0][:, None, None] * e[1][None, :, None] * e[2][None, None, :]
+    start = (np.cumsum(size.reshape(-1)) - size.reshape(-1)).reshape(size.shape)
+    ey, ex = e[1][b[1]], e[2][b[2]]
+    return (start[b[0][:, None, None], b[1][None, :, None], b[2][None, None, :]]
+            + (l[0][:, None, None] * ey[None, :, None] + l[1][None, :, None]) * ex[None, None, :] + l[2][None, None, :]).astype(np.int64)
+
+
+def reconstruct_blocks(h, sec, codes, side=None):
     """numpy model of the block decoder: blocks in raster order (any order that respects the low-side dependencies works),
-    Lorenzo blocks invert their integer stencil element by element, regression blocks are pred + 2*(code - radius)*eb"""
+    Lorenzo blocks invert their integer stencil (lorenzo_block), regression blocks are pred + 2*(code - radius)*eb (regression_run);
+    a run of blocks of one kind along x is taken at once. side: parse_side's result where the caller has it already."""
     if h["ndim"] == 4:
         return reconstruct_blocks4(h, sec, codes)
     T = np.float32 if h["dtype"] == 0 else np.float64
-    Q = np.int32 if h["dtype"] == 0 else np.int64
     dz, dy, dx = h["dims"][1:]
     B, eb, radius = h["blk_edge"], h["eb"], h["radius"]
-    sel, coef = parse_side(h, sec)
+    sel, coef = side if side is not None else parse_side(h, sec)
+    codes = np.asarray(codes)
     dflat = np.where(codes == 0, 0, codes.astype(np.int64) - radius).astype(np.int64)
     dflat[sec["dout_idx"].astype(np.int64)] = sec["dout_val"]  # (outlier indices are code positions)
     # the codes are stored block by block (block raster order, raster order inside a block): back to element order
-    d = np.zeros((dz, dy, dx), dtype=np.int64)
-    c3 = np.zeros((dz, dy, dx), dtype=np.int64)
-    pos = 0
-    for z0 in range(0, dz, B):
-        for y0 in range(0, dy, B):
-            for x0 in range(0, dx, B):
-                ez, ey, ex = min(B, dz - z0), min(B, dy - y0), min(B, dx - x0)
-                m = ez * ey * ex
-                d[z0:z0 + ez, y0:y0 + ey, x0:x0 + ex] = dflat[pos:pos + m].reshape(ez, ey, ex)
-                c3[z0:z0 + ez, y0:y0 + ey, x0:x0 + ex] = codes[pos:pos + m].reshape(ez, ey, ex)
-                pos += m
+    pos = block_positions((dz, dy, dx), B)
+    d = dflat[pos]
+    c3 = codes[pos].astype(np.int64)
+    del pos
     q = np.zeros((dz + 2, dy + 2, dx + 2), dtype=np.int64)  # two zero halo layers on the low side
     out = np.zeros((dz, dy, dx), dtype=T)
-    recip = T(1.0 / (2.0 * eb)) if T == np.float32 else 1.0 / (2.0 * eb)
-    lim = T(8388608.0) if T == np.float32 else 4503599627370496.0
     nd1 = h["ndim"] + 1  # (1-D / 2-D arrays are seen as (1, 1, n) / (1, dy, dx): RegressionPredictor.hpp:22-26 divides by N + 1)
-    step_ind, step_lin = 2.0 * (eb / nd1), 2.0 * (eb / nd1 / B)
-    w1, w2 = np.array([1, -1]), np.array([1, -2, 1])
-    r = 0
+    two_eb = T(2.0 * eb)
+    nreg_before = np.concatenate([[0], np.cumsum(sel.reshape(-1) == 2)])  # (regression blocks in front of a block, raster order)
+    nbx = sel.shape[2]
     for bz in range(sel.shape[0]):
         for by in range(sel.shape[1]):
-            for bx in range(sel.shape[2]):
-                z0, y0, x0 = bz * B, by * B, bx * B
-                ez, ey, ex = min(B, dz - z0), min(B, dy - y0), min(B, dx - x0)
-                s = int(sel[bz, by, bx])
+            z0, y0 = bz * B, by * B
+            ez, ey = min(B, dz - z0), min(B, dy - y0)
+            row = sel[bz, by]
+            cut = np.flatnonzero(row[1:] != row[:-1]) + 1
+            for b0, b1 in zip(np.concatenate([[0], cut]).tolist(), np.concatenate([cut, [nbx]]).tolist()):
+                s = int(row[b0])
+                x0 = b0 * B
+                ex = min(b1 * B, dx) - x0
+                blk = (slice(z0, z0 + ez), slice(y0, y0 + ey), slice(x0, x0 + ex))
                 if s == 2:
-                    lc = coef[r]
-                    r += 1
-                    rc = [T(float(lc[i]) * step_lin) for i in range(3)] + [T(float(lc[3]) * step_ind)]
-                    i0, i1, i2 = np.meshgrid(np.arange(ez), np.arange(ey), np.arange(ex), indexing="ij")
-                    pred = (rc[0] * i0.astype(T) + rc[1] * i1.astype(T) + rc[2] * i2.astype(T) + rc[3]).astype(T)
-                    cc = c3[z0:z0 + ez, y0:y0 + ey, x0:x0 + ex].astype(np.int64)
-                    val = (pred.astype(np.float64) + (2 * (cc - radius)).astype(np.float64) * eb).astype(T)
-                    with np.errstate(invalid="ignore", over="ignore"):
-                        sc = val * recip
-                        ok = np.abs(sc) < lim
-                        rr = np.rint(np.where(ok, sc, 0)).astype(T)
-                        bad = ~ok | ~(np.abs(rr * T(2.0 * eb) - val) <= (T(eb) if float(T(eb)) <= eb else np.nextafter(T(eb), T(0))))
-                    qt = np.where((cc == 0) | bad, 0, rr.astype(np.int64))
+                    r = int(nreg_before[(bz * sel.shape[1] + by) * nbx + b0])
+                    qt, val = regression_run(c3[blk], coef[r:r + (b1 - b0)], B, eb, radius, T, nd1)
                     q[z0 + 2:z0 + 2 + ez, y0 + 2:y0 + 2 + ey, x0 + 2:x0 + 2 + ex] = qt
-                    out[z0:z0 + ez, y0:y0 + ey, x0:x0 + ex] = np.where(cc == 0, 0, val)
+                    out[blk] = val
                 else:
-                    w = w1 if s == 0 else w2
-                    m = len(w) - 1
-                    for k in range(ez):
-                        for j in range(ey):
-                            for i in range(ex):
-                                z, y, x = z0 + k + 2, y0 + j + 2, x0 + i + 2
-                                acc = int(d[z0 + k, y0 + j, x0 + i])
-                                for a in range(m + 1):
-                                    for b_ in range(m + 1):
-                                        for c_ in range(m + 1):
-                                            if a or b_ or c_:
-                                                acc -= int(w[a] * w[b_] * w[c_]) * int(q[z - a, y - b_, x - c_])
-                                q[z, y, x] = acc
-                    blk = q[z0 + 2:z0 + 2 + ez, y0 + 2:y0 + 2 + ey, x0 + 2:x0 + 2 + ex]
-                    out[z0:z0 + ez, y0:y0 + ey, x0:x0 + ex] = blk.astype(T) * T(2.0 * eb)
+                    lorenzo_block(q, d[blk], (z0, y0, x0), (ez, ey, ex), s + 1)
+                    out[blk] = q[z0 + 2:z0 + 2 + ez, y0 + 2:y0 + 2 + ey, x0 + 2:x0 + 2 + ex].astype(T) * two_eb
     x = out.reshape(-1)
     x[sec["vout_idx"].astype(np.int64)] = sec["vout_val"]
     return x, sel
+
+
+# ---- the same streams read a unit / a group of blocks at a time, for arrays of millions of values ----
+def huffman_decode_units(h, sec):
+    """huffman_decode's codes (tests/test_block_model_cpu.py holds the two equal), every unit of the stream advanced in step: a unit
+    starts at its chunk's first word or at the chunk's restart offset, and a table of 2^(longest word) entries reads a symbol at a time.
+    Checks that a unit ends where the chunk's next one starts."""
+    n = h["n"]
+    if h["max_len"] == 0:
+        return np.full(n, h["sym_min"], dtype=np.uint16)
+    lens = sec["lens"].astype(np.int64)
+    L = int(lens.max())
+    order = np.lexsort((np.arange(len(lens)), lens))  # canonical order: (len, symbol)
+    order = order[lens[order] > 0]
+    syms = (h["sym_min"] + order).astype(np.int64)
+    if h.get("esc_sym"):
+        syms[syms == h["esc_sym"]] = 0
+    span = 1 << (L - lens[order])
+    assert int(span.sum()) <= 1 << L, "the lengths are no prefix code"
+    t_sym = np.zeros(1 << L, dtype=np.uint16)
+    t_len = np.zeros(1 << L, dtype=np.int64)    # (0: no code word starts like this)
+    t_sym[:int(span.sum())] = np.repeat(syms, span)
+    t_len[:int(span.sum())] = np.repeat(lens[order], span)
+    n_chunks = h["n_chunks"]
+    offs = np.concatenate([[0], np.cumsum(sec["chunkwords"].astype(np.int64))])
+    data = np.concatenate([sec["bitstream"].view(np.uint8), np.zeros(8, np.uint8)]).astype(np.int64)  # bytes are in stream order
+    start = np.zeros((n_chunks, SUBS), dtype=np.int64)
+    start[:, 1:] = sec["subbits"].astype(np.int64)
+    pos = (32 * offs[:-1, None] + start).reshape(-1)
+    first = pos.copy()
+    count = np.clip(n - np.arange(n_chunks * SUBS, dtype=np.int64) * UNIT, 0, UNIT)
+    out = np.zeros(n_chunks * CHUNK, dtype=np.uint16)
+    base = np.arange(n_chunks * SUBS, dtype=np.int64) * UNIT
+    for i in range(UNIT):
+        act = np.flatnonzero(count > i)
+        if not act.size:
+            break
+        p = pos[act]
+        by = p >> 3
+        v = (data[by] << 24) | (data[by + 1] << 16) | (data[by + 2] << 8) | data[by + 3]
+        win = (v >> (32 - L - (p & 7))) & ((1 << L) - 1)
+        l = t_len[win]
+        if not l.all():
+            raise ValueError("bad code in unit %d" % int(act[np.flatnonzero(l == 0)[0]]))
+        out[base[act] + i] = t_sym[win]
+        pos[act] = p + l
+    ends = pos.reshape(n_chunks, SUBS)
+    if not np.array_equal(ends[:, :-1] - first.reshape(n_chunks, SUBS)[:, :1], start[:, 1:]):
+        raise ValueError("a restart offset is not where its unit's first symbol starts")
+    if not np.array_equal((ends[:, -1] - 32 * offs[:-1] + 31) >> 5, sec["chunkwords"].astype(np.int64)):
+        raise ValueError("a chunk's word count is not its bits' count")
+    return out[:n]
+
+
+def parse_side_groups(h, sec):
+    """parse_side's result (tests/test_block_model_cpu.py holds the two equal), the groups of 64 regression blocks advanced in step"""
+    side = sec["side"].tobytes()
+    coding, sel_bits, nblocks, nreg = struct.unpack_from("<IIQQ", side, 0)
+    B = h["blk_edge"]
+    four = h["ndim"] == 4
+    nc, pb = (5, 16) if four else (4, 8)
+    nb = [(d + B - 1) // B for d in (h["dims"] if four else h["dims"][1:])]
+    assert coding == 1 and sel_bits == 2 and nblocks == int(np.prod(nb))
+    sel_bytes = ((nblocks + 3) // 4 + 7) & ~7
+    packed = np.frombuffer(side, dtype=np.uint8, count=sel_bytes, offset=24)
+    sel = ((packed[:, None] >> (2 * np.arange(4))) & 3).reshape(-1)[:nblocks].astype(np.uint8)
+    p0 = 24 + sel_bytes
+    ks = list(side[p0:p0 + nc])
+    ngroups, = struct.unpack_from("<I", side, p0 + pb - 4)
+    assert ngroups == (nreg + 63) // 64 and max(ks, default=0) <= 56
+    goff = np.frombuffer(side, dtype=np.uint32, count=ngroups, offset=p0 + pb).astype(np.int64)
+    words = np.frombuffer(side, dtype=np.uint32, offset=p0 + pb + 4 * ngroups)
+    data = np.concatenate([words.astype(">u4").view(np.uint8), np.zeros(16, np.uint8)]).astype(np.uint64)  # MSB first
+
+    def window(p):  # the 64 bits from bit p on, left-aligned
+        by = (p >> 3).astype(np.int64)
+        sh = (p & 7).astype(np.uint64)
+        w = np.zeros(len(p), dtype=np.uint64)
+        for k in range(8):
+            w = (w << np.uint64(8)) | data[by + k]
+        return (w << sh) | (data[by + 8] >> (np.uint64(8) - sh))  # (a shift by 8 of a byte: 0)
+
+    deltas = np.zeros((ngroups * 64, nc), dtype=np.int64)
+    pos = goff.copy()
+    gbase = np.arange(ngroups, dtype=np.int64) * 64
+    for r in range(64):
+        act = np.flatnonzero(gbase + r < nreg)
+        if not act.size:
+            break
+        for i in range(nc):
+            p = pos[act]
+            inv = (~(window(p) >> np.uint64(40))) & np.uint64(0xFFFFFF)   # the first 24 bits, inverted: the unary part ends at its highest set bit
+            q = np.where(inv == 0, 24, 23 - np.floor(np.log2(np.maximum(inv, 1).astype(np.float64))).astype(np.int64))
+            esc = q == 24
+            p = p + q + np.where(esc, 0, 1)
+            w = window(p)
+            k = ks[i]
+            low = (w >> np.uint64(64 - k)) if k else np.zeros(len(p), dtype=np.uint64)
+            u = np.where(esc, w, (q.astype(np.uint64) << np.uint64(k)) | low)
+            pos[act] = p + np.where(esc, 64, k)
+            deltas[gbase[act] + r, i] = (u >> np.uint64(1)).astype(np.int64) ^ -((u & np.uint64(1)).astype(np.int64))
+    coef = np.cumsum(deltas[:nreg], axis=0)
+    assert int((sel == 2).sum()) == nreg
+    return sel.reshape(nb), coef

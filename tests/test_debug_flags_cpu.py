@@ -1,6 +1,7 @@
 """CPU tests (-m "not gpu") of the development switches' one list: enum sz3hip_dbg (include/sz3hip_debug.h) and sz3_amd.Dbg name the
 same switches with the same values, the bits that carry several meanings are exactly the known ones, the library's sources test the
-switches by name only, and sz3_amd.debug_flags sets the word for its body alone. No library and no device needed."""
+switches by name only, and sz3_amd.debug_flags sets the word for its body alone; the block decoder's read-out (enum sz3hip_blkdec_form /
+sz3hip_blkdec_word, sz3hip_debug_blkdec_last) is listed the same way in the header, in Python and in the library. No device needed."""
 import os
 import re
 
@@ -110,3 +111,24 @@ def test_debug_flags_context_manager(monkeypatch):
     with sz3_amd.debug_flags(0):
         assert stub.word == 0
     assert stub.word == 0
+
+
+def _header_enum(name, prefix):
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sz3hip_debug.h")).read(), flags=re.S)
+    body = re.search(r"enum\s+%s\s*\{(.*?)\}" % name, txt, flags=re.S).group(1)
+    return {m.group(1): int(m.group(2)) for m in re.finditer(prefix + r"([A-Z0-9_]+)\s*=\s*(\d+)", body)}
+
+
+def test_block_decoder_read_out_is_listed():
+    """the forms: header and sz3_amd.BlkDecForm agree, values 0 .. 11 once each; the words: the accessor's keys in the header's order;
+    the library exports the call, and before any block stream was decoded it reports nothing"""
+    forms = _header_enum("sz3hip_blkdec_form", "SZ3HIP_BLKDEC_FORM_")
+    assert forms == {name: int(v) for name, v in sz3_amd.BlkDecForm.__members__.items()}
+    assert sorted(forms.values()) == list(range(12)) and forms["NONE"] == 0
+    words = _header_enum("sz3hip_blkdec_word", "SZ3HIP_BLKDEC_WORD_")
+    assert sorted(words.values()) == list(range(7))
+    L = sz3_amd.lib()
+    assert hasattr(L, "sz3hip_debug_blkdec_last")
+    info = sz3_amd.debug_blkdec_last()
+    assert [k.upper() for k in info] == sorted(words, key=words.get)
+    assert info["form"] == sz3_amd.BlkDecForm.NONE and not any(info.values())

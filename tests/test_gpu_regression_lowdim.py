@@ -133,7 +133,7 @@ def test_grouped_and_per_block_2d_decoders_agree(shape, block, eb):
             with sz3_amd.debug_flags(flag):
                 dec, c2 = sz3_amd.decompress(blob, dtype, shape)
                 outs.append(dec)
-        assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2])
+        assert all(np.array_equal(outs[0], o) for o in outs[1:])
         assert float(np.max(np.abs(outs[0].astype(np.float64) - a.astype(np.float64)))) <= eb
         h, o, sec = szh_ref.parse(_payload_of(blob))
         if h["predictor"] == 2:  # (the selection may hand a field over to the plain path: nothing to compare then)
